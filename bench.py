@@ -9,7 +9,8 @@ One "step" = one batch of reads already in HBM through MapRead_lowacc (lra_map_r
 record buffer packed (lra_map_pack) and gathered to rank 0 (RCCL; the single exchange step), and on rank 0 the host tail (MAPQ, ordering, SAM
 text: lra_map_records_host) of every rank's reads in input order -- the host tail of batch i runs beside the device side of batch i + 1.
 
-Contract: python bench.py --gpus N --steps K --warmup W  -> rank 0 prints ONE JSON line.
+Contract: python bench.py --gpus N --steps K --warmup W  -> rank 0 prints ONE JSON line (ms_per_step: one timed step).  --dump-outputs DIR also writes
+what the last timed step computed, for a seeded sample of its reads, as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -19,6 +20,7 @@ import sys
 import contextlib
 import threading
 import time
+import zlib
 
 import numpy as np
 
@@ -108,6 +110,111 @@ def cpu_baseline(mapper, reads_h, off_h, args, last_res=None, opts=None, sample=
                       % (res["n_reads"], res["bases"], res["n_alignments"], n_threads, hw_threads, res["seconds"], fetch_s)}
 
 
+@contextlib.contextmanager
+def deterministic_inputs():
+    """The synthetic genome and reads bit for bit the same in every run with the same arguments: the repeat copies of synth_genome overlap, and the one
+    indexed write that places them lets an arbitrary one of the overlapping writes win under torch's default kernels; its deterministic kernel lets the
+    last one win, as the generator intends."""
+    import torch
+    prev, prev_warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        yield
+    finally:
+        torch.use_deterministic_algorithms(prev, warn_only=prev_warn)
+
+
+DUMP_READS = 256                 # --dump-outputs: reads in the sample (~90 kB each in float64: blocks + CIGAR runs of a 30 kb read)
+DUMP_SEED = 20250101             # the sample's seed: the same reads in every run with the same arguments
+DUMP_BUDGET = 64 << 20           # bytes in all
+
+
+def _ranges(lo, hi):
+    """the concatenation of arange(lo[i], hi[i]) over i"""
+    ln = (hi - lo).astype(np.int64)
+    return np.repeat(lo.astype(np.int64) - (np.cumsum(ln) - ln), ln) + np.arange(int(ln.sum()), dtype=np.int64)
+
+
+def _dump_arrays(idx, d, na, recs, reads_h, off_h, chrom_names):
+    """The sampled reads' share of the last step's outputs: per read, per job (primary chain), per alignment (SegAlignment), per refined block,
+    per CIGAR run, per SAM record line.  Integers as float64 (exact: none exceeds 2^53), the float32 fields as they are."""
+    f8 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    jobs = (idx[:, None] * na + np.arange(na)).reshape(-1)
+    jo = d["job_aln_off"].astype(np.int64)
+    A = _ranges(jo[idx * na], jo[idx * na + na])                           # the sampled reads' alignments (a read's jobs are consecutive)
+    bo, ro = d["block_off"].astype(np.int64), d["run_off"].astype(np.int64)
+    out = {"read_index": f8(idx),
+           "input_read_len": f8(off_h[idx + 1] - off_h[idx]),
+           "input_read_crc32": f8([zlib.crc32(reads_h[int(off_h[r]):int(off_h[r + 1])].tobytes()) for r in idx]),
+           "read_status": f8(d["read_status"][idx]),
+           "job_status": f8(d["job_status"][jobs].reshape(len(idx), na)),
+           "job_reached": f8(d["job_reached"][jobs].reshape(len(idx), na)),
+           "job_n_alignments": f8((jo[jobs + 1] - jo[jobs]).reshape(len(idx), na))}
+    out["aln_read"] = f8(d["aln_read"][A])
+    for k in ("strand", "supp", "secondary", "n0", "n1", "chrom", "refine_status"):
+        out["aln_" + k] = f8(d[k][A])
+    out["aln_first_sdp_value"] = np.ascontiguousarray(d["first_sdp_value"][A], dtype=np.float32)
+    out["aln_value"] = np.ascontiguousarray(d["value"][A], dtype=np.float32)
+    out["aln_counts"] = f8(d["counts"][A])
+    out["aln_n_blocks"] = f8(bo[A + 1] - bo[A])
+    out["blocks"] = f8(d["blocks"][_ranges(bo[A], bo[A + 1])]).reshape(-1, 3)
+    out["aln_n_runs"] = f8(ro[A + 1] - ro[A])
+    out["cigar_runs"] = f8(d["runs"][_ranges(ro[A], ro[A + 1])])
+    if recs is not None:
+        # one row per SAM line: read, FLAG, RNAME (index into the chromosome names, -1 = *), POS, MAPQ, crc32 of the CIGAR, length and crc32 of the whole line
+        chrom = {c: i for i, c in enumerate(chrom_names)}
+        rows, per_read = [], []
+        for r in idx:
+            lines = [ln for ln in recs[r].split(b"\n") if ln]
+            per_read.append(len(lines))
+            for ln in lines:
+                f = ln.split(b"\t")
+                sam = len(f) >= 11
+                rows.append([r, int(f[1]) if sam else -1, chrom.get(f[2], -1) if sam else -1, int(f[3]) if sam else -1, int(f[4]) if sam else -1,
+                             zlib.crc32(f[5]) if sam else -1, len(ln), zlib.crc32(ln)])
+        out["sam_lines_per_read"] = f8(per_read)
+        out["sam_records"] = f8(np.array(rows, dtype=np.int64).reshape(-1, 8))
+    return out
+
+
+def dump_outputs(out_dir, lane, sub, reads_h, off_h, n_threads):
+    """--dump-outputs: what the last timed step handed its caller, for a seeded sample of its reads -> a summary for the result line.  The alignments are the
+    step's lra_map_result (as the device left it); the SAM text is lra_map_records_host run again on the very packed buffer the step's host tail turned into text."""
+    mapper, res = lane["mapper"], lane["last_res"]
+    d = mapper.fetch(res)
+    n, na = int(res.n_reads), int(res.num_aln)
+    assert int(res.n_jobs) == n * na, (int(res.n_jobs), n, na)
+    recs = None
+    if lane.get("pin_n"):
+        hb = lane["pin"][:lane["pin_n"]].numpy()
+        snap = C.c_void_p()
+        rc = mapper.ctx.lib.lra_map_unpack_host(C.c_void_p(hb.ctypes.data), C.c_uint64(hb.nbytes), C.byref(snap))
+        assert rc == 0, rc
+        recs = mapper.records_host(snap, sub["rargs"], n_threads=n_threads)
+        assert len(recs) == n, (len(recs), n)
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.sort(rng.choice(n, min(n, DUMP_READS), replace=False)).astype(np.int64)
+    while True:                                                            # (over the cap: the first half of the sample, by read ordinal, and again)
+        arrays = _dump_arrays(idx, d, na, recs, reads_h, off_h, mapper.chrom_names)
+        total = sum(a.nbytes for a in arrays.values())
+        if total <= DUMP_BUDGET or len(idx) <= 1:
+            break
+        idx = idx[:len(idx) // 2]
+    # the genome the step mapped against: crc32 of 64 seeded windows of the copy in HBM (the reads' own bases: input_read_crc32)
+    ctx, G = mapper.ctx, int(mapper.G)
+    gptr = ctx.lib.lra_ctx_genome_ptr(ctx.h)
+    W = max(1, min(1 << 20, G // 64))
+    g0 = np.sort(rng.integers(0, G - W + 1, 64))
+    arrays["input_genome_window_start"] = g0.astype(np.float64)
+    arrays["input_genome_window_crc32"] = np.array([zlib.crc32(ctx.to_host(gptr + int(s), W, np.uint8).tobytes()) for s in g0], np.float64)
+    total += sum(arrays[k].nbytes for k in ("input_genome_window_start", "input_genome_window_crc32"))
+    assert total <= DUMP_BUDGET, total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "reads": int(len(idx)), "files": len(arrays), "bytes": int(total), "sam": recs is not None}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -152,7 +259,15 @@ def main():
     ap.add_argument("--lanes", type=int, default=int(os.environ.get("LRA_BENCH_LANES", 1)),
                     help="the batch is cut into this many sub-batches, each driven by its own context and HIP stream from its own host thread (ONE shared replica "
                          "of the reference), so that the serial tails of one sub-batch's kernels overlap the other's work")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller -- the alignments of lra_map_reads_lowacc and the SAM records of the "
+                         "host tail -- for a fixed, seeded sample of %d reads as DIR/<name>.npy (float64 / float32, at most 64 MB): two builds run with the same "
+                         "arguments see the same inputs and can be compared output for output (bench_outputs/<name> is git-ignored)" % DUMP_READS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.lanes != 1 or args.defer_seed):
+        ap.error("--dump-outputs needs one lane and no handed-back reads (--lanes 1 --defer-seed 0): the last step is then one batch")
 
     import torch
     import torch.distributed as dist
@@ -179,8 +294,10 @@ def main():
 
     # ---- reference side, once per process: genome, StoreIndex, LocalIndex (all on the device)
     t0 = time.time()
-    genome, chrom_pos, chrom_names = sg.make_grch38_like(dev, scale=args.genome_scale, seed=args.genome_seed, satellite_frac=args.satellite_frac)
+    with deterministic_inputs():
+        genome, chrom_pos, chrom_names = sg.make_grch38_like(dev, scale=args.genome_scale, seed=args.genome_seed, satellite_frac=args.satellite_frac)
     torch.cuda.synchronize()
+    torch.cuda.empty_cache()                                               # (the generator's scratch, the deterministic write's sort included, back before the index build)
     gen_s = time.time() - t0
     ctx = Context(dev_index)
     t0 = time.time()
@@ -190,7 +307,8 @@ def main():
     G = mapper.G
     # ---- this rank's reads (hash partition of the job's ordinals; weak scaling: args.reads per GPU), cut into args.lanes sub-batches
     t0 = time.time()
-    sim = sg.simulate_reads_sv(genome, chrom_pos, args.reads, args.read_len, args.read_len / 10, args.err, (30, 35, 35), 1000 + rank, sv_frac=args.sv_frac)
+    with deterministic_inputs():
+        sim = sg.simulate_reads_sv(genome, chrom_pos, args.reads, args.read_len, args.read_len / 10, args.err, (30, 35, 35), 1000 + rank, sv_frac=args.sv_frac)
     off_h = sim["off"].cpu().numpy()
     reads_h = sim["seq"][:int(off_h[-1])].cpu().numpy()
     n_sv = int((sim["sv"] > 0).sum())
@@ -390,6 +508,7 @@ def main():
                 if lane.get("pin") is None or lane["pin"].numel() < nb_:
                     lane["pin"] = torch.empty(int(nb_ * 1.25) + 4096, dtype=torch.uint8, pin_memory=True)
                 lane["pin"][:nb_].copy_(held, non_blocking=True)
+                lane["pin_n"] = nb_                                        # (--dump-outputs: the last step's packed records, kept for after the timed region)
                 copy_stream.synchronize()
                 hb = lane["pin"][:nb_].numpy()
                 tB = time.perf_counter()
@@ -605,6 +724,9 @@ def main():
     else:
         job_bases = total_bases
     nreads = args.reads * world
+    dumped = None
+    if args.dump_outputs and rank == 0:                                   # (untimed: the last step's results are still where it left them)
+        dumped = dump_outputs(args.dump_outputs, lanes[0], subs[0], reads_h, off_h, n_threads_rec)
 
     kernels = ["sketch_emit", "sketch_serial", "sketch_compact", "sort", "sort_fallback", "index_bounds", "compare", "strand",
                "aog_lds_tiny", "aog_lds_small", "aog_lds_medium", "aog_lds_large", "aog_lane", "aog_reg", "aog_hbm", "ir_segment", "ir_band", "ir_fill", "ir_trace", "ir_gather", "clean_sort", "clean", "linear_extend", "stats", "stats_cigar", "create_rc", "local_sketch", "local_sort_filter", "local_compare",
@@ -696,6 +818,8 @@ def main():
             "handed_back": {"defer_seed_matches": defer_T, "pool": args.heavy_pool, "reads_per_step": round(heavy["reads"] / max(args.steps, 1), 1), "batches": heavy["batches"]},
             "device_side_ms_per_step": round(t_dev / args.steps * 1e3, 1),
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             try:
                 if len(lanes) > 1 or defer_T:                              # (untimed: the sample is the head of sub-batch 0, whichever lane mapped it last -- and in ONE batch, nothing handed back)
