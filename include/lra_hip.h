@@ -750,6 +750,22 @@ int lra_calculate_statistics_batch(lra_ctx* ctx, int n_aln, const int32_t* d_blo
                                    const char* d_tseq, const uint64_t* d_t_off, const float* h_lookup, int n_lookup,
                                    lra_stats_result* out);
 
+/* ---- a17 (opts.printMD): the MD:Z value of every alignment, on the device --------------------------------------------
+ * Replaces  CreateAlignmentStrings (Alignment.h:247-331) + AlignmentStringsToMD (:204-245)  on the final blocks, byte for byte what
+ * lra_md_string(lra_alignment_strings(...)) gives: the columns compared as upper-cased characters (not seqMap: a read's N against a
+ * reference A is a mismatch), insertions consumed silently, '^' + the reference run for a deletion, no number behind a trailing mismatch
+ * or deletion, the empty string for an alignment without columns.  Arguments as lra_calculate_statistics_batch (d_q_len is not read).
+ * Output (context-owned, valid until the next call on the context): alignment a's text at d_md + d_md_off[a], d_md_off[a + 1] - d_md_off[a]
+ * bytes, no terminators; n_bytes = d_md_off[n_aln].  Synchronous.                                                                      */
+typedef struct lra_md_result {
+  int32_t n_aln;
+  uint64_t n_bytes;
+  const uint64_t* d_md_off;   /* [n_aln+1] */
+  const char* d_md;           /* [n_bytes] */
+} lra_md_result;
+int lra_md_strings_batch(lra_ctx* ctx, int n_aln, const int32_t* d_blocks, const uint64_t* d_block_off, const char* d_qseq, const uint64_t* d_q_off,
+                         const int32_t* d_q_len, const char* d_tseq, const uint64_t* d_t_off, lra_md_result* out);
+
 /* ---- a15: junctions of split alignments ---------------------------------------------------------------------
  * Replaces   RefineBreakpoint(read, genome, leftAln, rightAln, opts)   (RefineBreakpoint.h:210-466; Map_lowacc.h:592, Map_highacc.h:725)
  * for n junctions: if the read bases between the two segments (in forward read coordinates) number 1..499, both segments are extended into
@@ -773,8 +789,9 @@ int lra_refine_breakpoint_batch(lra_ctx* ctx, int n, const int32_t* d_read_len, 
  * Byte-for-byte the text of  Alignment::PrintSAM (Alignment.h:658-808), SimplePrintSAM (:811-905), PrintPAF (:600-656) and
  * PrintBed (:591-598) for alignments described by plain records (the fields those functions read).  Tags in the reference's order:
  * SAM  NM MM NX ND TD NI TI NV AS AO N0 RT TP SD ME LD SI MI LI [SA];  simple SAM  RT NM NX ND TD NI TI N0 NV AS AO;
- * PAF  OR NM NX ND TD NI TI SD ME LD SI MI LI N0 NV AS TP [NA] [RT] [CG].  opts.printMD is not supported (the MD string needs the
- * alignment strings).  n_blocks == 0 prints the unaligned record.  lra_format_sam prints segment `as` of the group and lists the other
+ * PAF  OR NM NX ND TD NI TI SD ME LD SI MI LI N0 NV AS TP [NA] [RT] [CG].  opts.printMD: rec.md (NULL: no tag) is printed as MD:Z after LI by
+ * lra_format_sam only, as the reference does (SimplePrintSAM, PrintPAF and PrintBed print no MD); lra_map_records_host fills it from a
+ * snapshot packed with LRA_PACK_MD.  n_blocks == 0 prints the unaligned record.  lra_format_sam prints segment `as` of the group and lists the other
  * segments, last to first, in SA:Z.  passthrough: the text appended when opts.passthroughtag is set (NULL otherwise).
  * Output: at most cap bytes into out (no terminator); *len = bytes needed.  Returns LRA_ERR_INVALID if cap < *len.            */
 typedef struct lra_aln_record {
@@ -1013,7 +1030,9 @@ typedef struct lra_map_result {
   const int32_t* d_chrom; const float* d_first_sdp_value;
   const uint64_t* d_block_off; const int32_t* d_blocks; const int32_t* d_refine_status;
   const int32_t* d_counts; const float* d_value; const uint64_t* d_run_off; const uint32_t* d_runs;
-  const char* d_strands; uint64_t rc_base;                 /* the reads forward, then (at rc_base) reverse complemented */
+  const char* d_strands; uint64_t rc_base;                 /* the reads forward, then (at rc_base) reverse complemented; the drivers leave the batch's read
+                                                            * offsets [n_reads + 1] behind them, at byte (2 * rc_base + 64 + 7) & ~7 (what LRA_PACK_MD addresses
+                                                            * the reads with: the caller's d_read_off may be reused by then) */
   lra_map_counters counters;
 } lra_map_result;
 void lra_map_opts_preset_ont(lra_map_opts* opts);          /* -ONT: lra.cpp:386-431 over Options.h:127-230 */
@@ -1106,14 +1125,17 @@ int lra_map_records(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts*
                     uint64_t* len, uint64_t* rec_off);
 /* lra_map_records in two halves, so that the host tail of batch i runs beside the device side of batch i + 1 (the reference interleaves them per
  * thread, lra.cpp:117-158):
- *   lra_map_snapshot      copies what the records need (per-alignment fields, counters, CIGAR runs, block ends; with_blocks != 0 also every block
- *                         and the chromosome text under it, needed by print format 'a' only) from the context's result buffers to a host object;
- *                         after it returns the context may run the next batch.
+ *   lra_map_snapshot      copies what the records need (per-alignment fields, counters, CIGAR runs, block ends; with_blocks & LRA_PACK_BLOCKS also
+ *                         every block and the chromosome text under it, needed by print format 'a' only; with_blocks & LRA_PACK_MD the MD:Z value
+ *                         of every alignment, lra_md_strings_batch on the result's own arrays, which format 's' then prints -- opts.printMD) from
+ *                         the context's result buffers to a host object; after it returns the context may run the next batch.
  *   lra_map_records_host  SetFromSegAlignment / AlignmentsOrder::Update / SimpleMapQV / OUTPUT for every read on n_threads host threads (0: up to
  *                         16); touches neither the context nor the device.  *text (owned by the snapshot, valid until it is freed or reused),
  *                         *len bytes, (*rec_off)[n_reads + 1] record boundaries; a read with a non-zero status word has an empty record.
  *   lra_map_host_free     releases the snapshot.                                                                                              */
 typedef struct lra_map_host lra_map_host;
+#define LRA_PACK_BLOCKS 1   /* the flag word of lra_map_snapshot / lra_map_pack (0 / 1 as before): the blocks (print format 'a') */
+#define LRA_PACK_MD 2       /* the MD:Z strings (opts.printMD): launches lra_md_strings_batch; the pack's header word 10 = their bytes, word 11 = 1 */
 int lra_map_snapshot(lra_ctx* ctx, const lra_map_result* res, int with_blocks, lra_map_host** out);
 int lra_map_records_host(lra_map_host* snap, const lra_map_opts* opts, const char* const* names, const char* const* reads, const char* const* quals,
                          const int32_t* read_len, const char* const* chrom_names, const char* passthrough, int n_threads, const char** text, uint64_t* len,
@@ -1124,7 +1146,8 @@ uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status)
 /* The record buffer of a batch as ONE device buffer -- what a rank sends to rank 0 in the single exchange step of the multi-GPU path (the
  * reference's ordered output, lra.cpp:145-166): lra_map_pack lays the same arrays out behind a 128-byte header in a context-owned buffer
  * (valid until the next pack on this context); lra_map_unpack_host turns a host copy of such a buffer (from any rank) into a snapshot for
- * lra_map_records_host.  lra_map_snapshot = pack + copy to the host + unpack.                                                               */
+ * lra_map_records_host.  lra_map_snapshot = pack + copy to the host + unpack.  with_blocks: the flag word above; LRA_PACK_MD appends
+ * md_off u64[nA + 1] | md u8[bytes] behind the blocks (a pack whose header words 10 and 11 are 0 has none: records without MD:Z).            */
 int lra_map_pack(lra_ctx* ctx, const lra_map_result* res, int with_blocks, const void** d_buf, uint64_t* bytes);
 int lra_map_unpack_host(const void* h_buf, uint64_t bytes, lra_map_host** out);
 

@@ -60,3 +60,9 @@ int lra_map_check_shared(lra_ctx* ctx);   // mapread.hip: borrowed reference dat
 // RefineBreakpoint over the consecutive SegAlignments of every job (Map_lowacc.h:586-596, Map_highacc.h:723-727); mapread.hip
 int lra_refine_breakpoints(lra_ctx* ctx, uint64_t nJ, uint64_t nA, const uint64_t* d_job_aln_off, const int32_t* d_strand, const uint64_t* q_off, const int32_t* q_len,
                            const uint64_t* t_off, const int64_t* t_len, const char* strands, const char* genome, lra_refine_result* fres);
+
+// The strands buffer of a batch (lra_map_result::d_strands: the reads forward, then at rc_base reverse complemented, 64 bytes of zeros) carries
+// the batch's read offsets [n_reads + 1] behind it at this byte: what the record stage (LRA_PACK_MD) addresses the reads with once the caller's
+// d_read_off may have been reused -- they travel with the strands through the two-stage handover and the passes' merges.  One copy per batch.
+inline size_t lra_strands_ro_at(uint64_t rc_base) { return (size_t)((2 * rc_base + 64 + 7) & ~(uint64_t)7); }
+inline size_t lra_strands_bytes(uint64_t rc_base, int n_reads) { return lra_strands_ro_at(rc_base) + ((size_t)n_reads + 1) * 8; }

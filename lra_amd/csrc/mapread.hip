@@ -635,11 +635,12 @@ static int lowacc_core(lra_ctx* ctx, int n_reads, const char* d_seq, const uint6
   stage("split_chains");
   hipLaunchKernelGGL(k_or_status_div, grid(n_slots), dim3(256), 0, st, n_slots, spres.d_status, num_aln, read_status);
   // a10: the reads forward, then reverse complemented, in one buffer + its local index (Map_lowacc.h:246-250)
-  char* both = (char*)lra_ensure(ctx, 57, 2 * tot + 64);
+  char* both = (char*)lra_ensure(ctx, 57, lra_strands_bytes(tot, n_reads));
   uint64_t* off2 = (uint64_t*)lra_ensure(ctx, 58, (2 * (size_t)n_reads + 2) * 8);
   if (!both || !off2) return LRA_ERR_NOMEM;
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(both, d_seq, tot, hipMemcpyDeviceToDevice, st));
   LRA_HIP_CHECK(ctx, hipMemsetAsync(both + 2 * tot, 0, 64, st));
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(both + lra_strands_ro_at(tot), d_read_off, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToDevice, st));
   if ((rc = lra_create_rc_batch(ctx, n_reads, d_seq, d_read_off, both + tot))) return rc;
   hipLaunchKernelGGL(k_add_off, dim3((n_reads + 256) / 256), dim3(256), 0, st, n_reads, d_read_off, tot, off2);
   // the reference indexes both strands of every read; only the strands with a split chain are ever looked up, so only those get tuples
@@ -1139,6 +1140,7 @@ struct lra_map_host {
   std::vector<uint8_t> reached;
   std::vector<uint64_t> chrom_pos;
   std::vector<std::string> segText; std::vector<uint32_t> segStart;   // print format 'a' only
+  bool has_md = false; std::vector<uint64_t> md_off; std::string md;  // LRA_PACK_MD: alignment a's MD:Z value is md[md_off[a], md_off[a + 1])
   lra_text_buf text; std::vector<uint64_t> rec_off;        // what lra_map_records_host produced last
 };
 
@@ -1155,6 +1157,15 @@ __global__ void k_block_ends(uint64_t nA, const uint64_t* __restrict__ boff, con
   const uint64_t b0 = boff[a], b1 = boff[a + 1];
   ends[2 * a] = b1 > b0 ? (uint32_t)blocks[3 * b0] : 0;
   ends[2 * a + 1] = b1 > b0 ? (uint32_t)(blocks[3 * (b1 - 1)] + blocks[3 * (b1 - 1) + 2]) : 0;
+}
+// LRA_PACK_MD: alignment a's read strand and chromosome in the result's own arrays (k_aln_address's offsets, from the read offsets the strands carry)
+__global__ void k_md_address(uint64_t nA, const uint32_t* __restrict__ aln_read, const int32_t* __restrict__ strand, const int32_t* __restrict__ chrom,
+                             const uint64_t* __restrict__ read_off, uint64_t rc_base, const uint64_t* __restrict__ chrom_pos, uint64_t* __restrict__ q_off,
+                             uint64_t* __restrict__ t_off) {
+  const uint64_t a = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= nA) return;
+  q_off[a] = read_off[aln_read[a]] + (strand[a] ? rc_base : 0);
+  t_off[a] = chrom_pos[chrom[a]];
 }
 }  // namespace
 
@@ -1246,20 +1257,23 @@ void lra_host_pool_put(void* p, size_t cap) {
 //   int64 header[16] = {magic, n_reads, num_aln, nJ, nA, n_blocks (0 unless with_blocks), n_runs, n_chrom, has_reached, has_rstat, ...}
 //   then, each padded to 8 bytes:  chrom_pos u64[n_chrom+1] | reached u8[nJ] | rstat u32[n_reads] | jo u64[nJ+1] | strand, supp, sec, n0, n1, chrom
 //   i32[nA] each | fval f32[nA] | counts i32[18 nA] | boff u64[nA+1] | ends u32[2 nA] | roff u64[nA+1] | runs u32[n_runs] | blocks i32[3 n_blocks]
+//   | (LRA_PACK_MD: header[10] = MD bytes, header[11] = 1) md_off u64[nA+1] | md u8[header[10]]
 namespace {
 constexpr int64_t PACK_MAGIC = 0x4c52414d41503031LL;   // "LRAMAP01"
 inline size_t pad8(size_t n) { return (n + 7) & ~(size_t)7; }
 struct PackLayout {
   size_t off[17]; size_t total;
-  PackLayout(uint64_t n_reads, uint64_t nJ, uint64_t nA, uint64_t n_blocks, uint64_t n_runs, uint64_t n_chrom) {
+  PackLayout(uint64_t n_reads, uint64_t nJ, uint64_t nA, uint64_t n_blocks, uint64_t n_runs, uint64_t n_chrom, bool md = false, uint64_t md_bytes = 0) {
     const size_t sz[17] = {16 * 8, (n_chrom + 1) * 8, nJ, n_reads * 4, (nJ + 1) * 8, nA * 4, nA * 4, nA * 4, nA * 4, nA * 4, nA * 4, nA * 4, 18 * nA * 4, (nA + 1) * 8,
                            2 * nA * 4, (nA + 1) * 8, n_runs * 4};
     size_t at = 0;
     for (int i = 0; i < 17; i++) { off[i] = at; at += pad8(sz[i]); }
     blocks_off = at; at += pad8(3 * n_blocks * 4);
+    md_off = at; if (md) at += pad8((nA + 1) * 8);
+    md_text = at; if (md) at += pad8(md_bytes);
     total = at;
   }
-  size_t blocks_off;
+  size_t blocks_off, md_off, md_text;
 };
 }  // namespace
 
@@ -1269,13 +1283,29 @@ extern "C" int lra_map_pack(lra_ctx* ctx, const lra_map_result* res, int with_bl
   if (!m) return LRA_ERR_INVALID;
   LRA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const uint64_t nR = (uint64_t)res->n_reads, nJ = res->n_jobs, nA = res->n_alignments, nB = with_blocks ? res->n_blocks : 0, nRuns = res->n_runs;
+  if (with_blocks & ~(LRA_PACK_BLOCKS | LRA_PACK_MD)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_pack: unknown flags 0x%x", with_blocks);
+  const bool withMd = (with_blocks & LRA_PACK_MD) != 0;
+  const uint64_t nR = (uint64_t)res->n_reads, nJ = res->n_jobs, nA = res->n_alignments, nB = (with_blocks & LRA_PACK_BLOCKS) ? res->n_blocks : 0, nRuns = res->n_runs;
   const uint64_t nCh = m->chrom_pos.size() - 1;
-  const PackLayout L(nR, nJ, nA, nB, nRuns, nCh);
+  // opts.printMD: the MD strings of the result's final blocks, from the reads on their strands (res->d_strands, addressed by the read offsets behind them) and the genome
+  lra_md_result md; memset(&md, 0, sizeof md);
+  if (withMd && nA) {
+    if (!res->d_strands || !res->d_aln_read || !res->d_strand || !res->d_chrom || !res->d_blocks || !res->d_block_off)
+      return lra_set_err(ctx, LRA_ERR_INVALID, "LRA_PACK_MD: the result has no reads / blocks to take the MD strings from");
+    if (!ctx->seed || !ctx->seed->genome || !m->d_chrom_pos) return lra_set_err(ctx, LRA_ERR_INVALID, "LRA_PACK_MD: genome not loaded");
+    uint64_t* adr = (uint64_t*)lra_ensure(ctx, 187, 2 * (nA + 1) * 8);
+    if (!adr) return LRA_ERR_NOMEM;
+    const uint64_t* ro = (const uint64_t*)(res->d_strands + lra_strands_ro_at(res->rc_base));
+    hipLaunchKernelGGL(k_md_address, dim3((unsigned)((nA + 255) / 256)), dim3(256), 0, st, nA, res->d_aln_read, res->d_strand, res->d_chrom, ro, res->rc_base,
+                       (const uint64_t*)m->d_chrom_pos, adr, adr + nA + 1);
+    const int rcm = lra_md_strings_batch(ctx, (int)nA, res->d_blocks, res->d_block_off, res->d_strands, adr, nullptr, (const char*)ctx->seed->genome, adr + nA + 1, &md);
+    if (rcm) return rcm;
+  }
+  const PackLayout L(nR, nJ, nA, nB, nRuns, nCh, withMd, md.n_bytes);
   char* buf = (char*)lra_ensure(ctx, 84, L.total + 64);
   if (!buf) return LRA_ERR_NOMEM;
   const int64_t hdr[16] = {PACK_MAGIC, (int64_t)nR, std::max(res->num_aln, 1), (int64_t)nJ, (int64_t)nA, (int64_t)nB, (int64_t)nRuns, (int64_t)nCh,
-                           res->d_job_reached ? 1 : 0, res->d_read_status ? 1 : 0, 0, 0, 0, 0, 0, 0};
+                           res->d_job_reached ? 1 : 0, res->d_read_status ? 1 : 0, (int64_t)md.n_bytes, withMd ? 1 : 0, 0, 0, 0, 0};
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(buf + L.off[0], hdr, sizeof hdr, hipMemcpyHostToDevice, st));
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(buf + L.off[1], m->d_chrom_pos, (nCh + 1) * 8, hipMemcpyDeviceToDevice, st));
   auto put = [&](int slot, const void* src, size_t n) -> hipError_t { return (n && src) ? hipMemcpyAsync(buf + L.off[slot], src, n, hipMemcpyDeviceToDevice, st) : hipSuccess; };
@@ -1292,6 +1322,11 @@ extern "C" int lra_map_pack(lra_ctx* ctx, const lra_map_result* res, int with_bl
   LRA_HIP_CHECK(ctx, put(13, res->d_block_off, nA ? (nA + 1) * 8 : 0)); LRA_HIP_CHECK(ctx, put(15, res->d_run_off, nA ? (nA + 1) * 8 : 0));
   LRA_HIP_CHECK(ctx, put(16, res->d_runs, nRuns * 4));
   if (nB) LRA_HIP_CHECK(ctx, hipMemcpyAsync(buf + L.blocks_off, res->d_blocks, 3 * nB * 4, hipMemcpyDeviceToDevice, st));
+  if (withMd) {
+    if (nA) LRA_HIP_CHECK(ctx, hipMemcpyAsync(buf + L.md_off, md.d_md_off, (nA + 1) * 8, hipMemcpyDeviceToDevice, st));
+    else LRA_HIP_CHECK(ctx, hipMemsetAsync(buf + L.md_off, 0, 8, st));
+    if (md.n_bytes) LRA_HIP_CHECK(ctx, hipMemcpyAsync(buf + L.md_text, md.d_md, md.n_bytes, hipMemcpyDeviceToDevice, st));
+  }
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
   *d_buf = buf; *bytes = L.total;
   return LRA_OK;
@@ -1306,7 +1341,9 @@ extern "C" int lra_map_unpack_host(const void* h_buf, uint64_t bytes, lra_map_ho
   memcpy(hdr, b, sizeof hdr);
   if (hdr[0] != PACK_MAGIC) return LRA_ERR_INVALID;
   const uint64_t nR = (uint64_t)hdr[1], nJ = (uint64_t)hdr[3], nA = (uint64_t)hdr[4], nB = (uint64_t)hdr[5], nRuns = (uint64_t)hdr[6], nCh = (uint64_t)hdr[7];
-  const PackLayout L(nR, nJ, nA, nB, nRuns, nCh);
+  const bool hasMd = hdr[10] != 0 || hdr[11] != 0;                      // (packs written before LRA_PACK_MD have zeros there)
+  if (hdr[10] < 0) return LRA_ERR_INVALID;
+  const PackLayout L(nR, nJ, nA, nB, nRuns, nCh, hasMd, (uint64_t)hdr[10]);
   if (L.total > bytes) return LRA_ERR_INVALID;
   lra_map_host* h = new lra_map_host();
   h->n_reads = (int32_t)nR; h->num_aln = (int)hdr[2]; h->nJ = nJ; h->nA = nA;
@@ -1326,6 +1363,14 @@ extern "C" int lra_map_unpack_host(const void* h_buf, uint64_t bytes, lra_map_ho
     else { std::vector<std::thread> th; for (int t = 0; t < T; t++) th.emplace_back(cp, t); for (auto& x : th) x.join(); }
   }
   if (nB) { h->blocks.resize(3 * nB); memcpy(h->blocks.data(), b + L.blocks_off, 3 * nB * 4); }
+  if (hasMd) {
+    h->has_md = true;
+    h->md_off.resize(nA + 1);
+    memcpy(h->md_off.data(), b + L.md_off, (nA + 1) * 8);
+    for (uint64_t a = 0; a < nA; a++)
+      if (h->md_off[a] > h->md_off[a + 1] || h->md_off[a + 1] > (uint64_t)hdr[10]) { delete h; return LRA_ERR_INVALID; }
+    h->md.assign(b + L.md_text, (size_t)hdr[10]);
+  }
   *out = h;
   return LRA_OK;
 }
@@ -1342,7 +1387,7 @@ extern "C" int lra_map_snapshot(lra_ctx* ctx, const lra_map_result* res, int wit
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   lra_map_host* h = nullptr;
   if ((rc = lra_map_unpack_host(hb, bytes, &h))) return rc;
-  if (with_blocks) {
+  if (with_blocks & LRA_PACK_BLOCKS) {
     // print format 'a': the pairwise text needs the chromosome bases under every alignment (and the read on its strand)
     lra_map_state* m = ctx->map;
     if (!ctx->seed || !ctx->seed->genome) { delete h; return lra_set_err(ctx, LRA_ERR_INVALID, "genome not loaded"); }
@@ -1372,6 +1417,8 @@ extern "C" int lra_map_records_host(lra_map_host* h, const lra_map_opts* o, cons
   const std::vector<int32_t>&strand = h->strand, &supp = h->supp, &sec = h->sec, &n0 = h->n0, &n1 = h->n1, &chrom = h->chrom, &counts = h->counts, &blocks = h->blocks;
   const std::vector<float>& fval = h->fval; const lra_pod_buf<uint32_t>& runs = h->runs; const std::vector<uint32_t>&rstat = h->rstat, &ends = h->ends; const std::vector<uint8_t>& reached = h->reached;
   const bool pairwise = o->printFormat == 'a';
+  const bool withMd = h->has_md && o->printFormat == 's';                 // (only PrintSAM prints MD; SimplePrintSAM, PrintPAF, PrintBed do not)
+  if (withMd && h->md_off.size() != nA + 1) return LRA_ERR_INVALID;
   const bool hi = !o->bypassClustering;                                   // MapRead_highacc's tail (Map_highacc.h:733-789)
   if (pairwise && h->segText.size() != h->nA) return LRA_ERR_INVALID;
   // every read is independent: host threads take contiguous ranges of reads, each builds its own text; ranges are joined in read order
@@ -1391,7 +1438,7 @@ extern "C" int lra_map_records_host(lra_map_host* h, const lra_map_opts* o, cons
       if (nJ && jo.size() > (size_t)hi * na) { const uint64_t a0 = jo[(size_t)lo * na], a1 = jo[(size_t)hi * na]; if (a1 < roff.size() && a0 <= a1) want += (size_t)((roff[a1] - roff[a0]) * 7 / 2) + (size_t)(a1 - a0) * 600; }
       text = part_take(want + want / 16);
     }
-    std::vector<std::string> cigars;
+    std::vector<std::string> cigars, mds;
     std::vector<lra_aln_record> recs;
     std::vector<int32_t> seg_off, index;
     std::vector<lra_aln_group> groups;
@@ -1399,7 +1446,7 @@ extern "C" int lra_map_records_host(lra_map_host* h, const lra_map_opts* o, cons
     std::string rcRead;
     int rc = LRA_OK;
     for (int r = lo; r < hi; r++) {
-      recs.clear(); cigars.clear(); seg_off.assign(1, 0); rcRead.clear();
+      recs.clear(); cigars.clear(); mds.clear(); seg_off.assign(1, 0); rcRead.clear();
       const bool flagged = !rstat.empty() && rstat[r];
       if (flagged && (!o->flagged_unaligned || (rstat[r] & LRA_ST_DEFERRED))) { plen[tix].push_back(0); continue; }   // flagged read: no record (the caller routes it elsewhere; d_read_status, lra_map_host_flagged)
       // low-accuracy path: p == 0 left no SegAlignment (Map_lowacc.h:578-581); high-accuracy path: read.unaligned or alignments.size() == 0
@@ -1414,6 +1461,7 @@ extern "C" int lra_map_records_host(lra_map_host* h, const lra_map_opts* o, cons
         size_t total = 0;
         for (int p = 0; p < na; p++) total += (size_t)(jo[(size_t)r * na + p + 1] - jo[(size_t)r * na + p]);
         cigars.reserve(total);                                            // the records keep pointers into these strings
+        if (withMd) mds.reserve(total);
         for (int p = 0; p < na; p++) {
           const size_t j = (size_t)r * na + p;
           // a chain that never reaches :574 ends the loop over p (:267, :491); one that does keeps its (possibly empty) group (:574-600)
@@ -1461,6 +1509,10 @@ extern "C" int lra_map_records_host(lra_map_host* h, const lra_map_opts* o, cons
               }
             }
             if (strand[a]) rec.read = rcRead.c_str();
+            if (withMd) {                                                 // opts.printMD: PrintSAM's MD:Z (Alignment.h:763-767)
+              mds.emplace_back(h->md.data() + h->md_off[a], (size_t)(h->md_off[a + 1] - h->md_off[a]));
+              rec.md = mds.back().c_str();
+            }
             if (pairwise) {
               rec.blocks = &blocks[3 * b0];
               rec.strand_read = strand[a] ? rcRead.c_str() : reads[r];

@@ -252,10 +252,11 @@ static int highacc_core(lra_ctx* ctx, int n_reads, const char* d_seq, const uint
   if (nC == 0) { cl_moff.assign(1, 0); }
   for (int r = 0; r < R; r++) hstat[r] |= st32[r];
   // the reads forward, then reverse complemented (strands[2], MapRead.h:166-168)
-  char* both = (char*)lra_ensure(ctx, 57, 2 * tot + 64);
+  char* both = (char*)lra_ensure(ctx, 57, lra_strands_bytes(tot, R));
   if (!both) return LRA_ERR_NOMEM;
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(both, d_seq, tot, hipMemcpyDeviceToDevice, st));
   LRA_HIP_CHECK(ctx, hipMemsetAsync(both + 2 * tot, 0, 64, st));
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(both + lra_strands_ro_at(tot), d_read_off, ((size_t)R + 1) * 8, hipMemcpyDeviceToDevice, st));
   if ((rc = lra_create_rc_batch(ctx, R, d_seq, d_read_off, both + tot))) return rc;
   const int na = std::max(1, o->sdp.NumAln);
   const uint64_t S = (uint64_t)R * na;
@@ -715,12 +716,13 @@ static int highacc_batch_impl(lra_ctx* ctx, int n_reads, const char* d_seq, cons
   lra_map_result mo; memset(&mo, 0, sizeof mo);
   if ((rc = lra_merge::merge_passes(ctx, 171, S, na, d_src, A, B, nA, nBk, nRn, 0, nullptr, &mo))) return rc;
   // the batch's strands buffer again (the second pass overwrote it with its own reads)
-  char* both = (char*)lra_ensure(ctx, 57, 2 * total_bases + 64);
+  char* both = (char*)lra_ensure(ctx, 57, lra_strands_bytes(total_bases, R));
   uint8_t* job_reached = (uint8_t*)lra_ensure(ctx, 82, S + 64);
   uint32_t* read_status = (uint32_t*)lra_ensure(ctx, 81, ((size_t)R + 1) * 4);
   if (!both || !job_reached || !read_status) return LRA_ERR_NOMEM;
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(both, d_seq, total_bases, hipMemcpyDeviceToDevice, st));
   LRA_HIP_CHECK(ctx, hipMemsetAsync(both + 2 * total_bases, 0, 64, st));
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(both + lra_strands_ro_at(total_bases), d_read_off, ((size_t)R + 1) * 8, hipMemcpyDeviceToDevice, st));
   if ((rc = lra_create_rc_batch(ctx, R, d_seq, d_read_off, both + total_bases))) return rc;
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(job_reached, hrA.data(), S, hipMemcpyHostToDevice, st));
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(read_status, hsA.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));

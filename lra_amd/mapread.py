@@ -61,6 +61,7 @@ class LowAccOptions:
     hardClip: bool = True
     PrintNumAln: int = 1
     printFormat: str = "s"
+    printMD: bool = False              # --printMD (lra.cpp:71, :592): MD:Z in SAM records (format 's'), built on the device (LRA_PACK_MD)
     deferSeedMatches: int = 0          # lra_map_opts.defer_seed_matches (scheduling only: reads with more tier-1 matches are handed back unmapped; 0 = off)
     deferMatches: int = None           # lra_map_opts.defer_matches (scheduling only; None = the preset's value, 0 = one pass)
 
@@ -129,6 +130,8 @@ class MapResult(C.Structure):
                                            "d_strands")] +
                 [("rc_base", C.c_uint64), ("counters", MapCounters)])
 
+
+PACK_BLOCKS, PACK_MD = 1, 2       # the flag word of lra_map_snapshot / lra_map_pack (LRA_PACK_BLOCKS, LRA_PACK_MD)
 
 READ_TYPES = {"ont": 0, "clr": 1, "ccs": 2, "contig": 3}
 
@@ -302,10 +305,17 @@ class LowAccMapper:
         """The refined block triples of a batch as a device tensor (what a rank hands to the gather step)."""
         return self.ctx.to_tensor(res.d_blocks, 3 * int(res.n_blocks), torch.int32)
 
+    @property
+    def print_md(self):
+        return bool(getattr(self.opts, "printMD", False)) if hasattr(self, "opts") else bool(getattr(self, "printMD", False))
+
     def records(self, res: MapResult, names, reads, quals=None, passthrough=None):
-        """lra_map_records: one bytes object per read in opts.printFormat."""
+        """lra_map_records: one bytes object per read in opts.printFormat (with printMD: the snapshot form, packed with LRA_PACK_MD)."""
         ctx = self.ctx
         n = int(res.n_reads)
+        if self.print_md:
+            snap = self.snapshot(res, with_blocks=chr(self.copts.printFormat) == "a")
+            return self.records_host(snap, self.record_args(names, reads, quals), passthrough=passthrough)
         enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
         nm = [enc(x) for x in names]; rd = [bytes(x) for x in reads]
         a_names = (C.c_char_p * n)(*nm); a_reads = (C.c_char_p * n)(*rd)
@@ -321,11 +331,12 @@ class LowAccMapper:
         raw = buf.raw
         return [raw[roff[i]:roff[i + 1]] for i in range(n)]
 
-    def snapshot(self, res: MapResult, with_blocks=False):
-        """lra_map_snapshot: host copy of what the records need; afterwards the context may run the next batch."""
+    def snapshot(self, res: MapResult, with_blocks=False, md=None):
+        """lra_map_snapshot: host copy of what the records need; afterwards the context may run the next batch.  md (None: opts.printMD): pack the MD strings too."""
         ctx = self.ctx
         h = C.c_void_p()
-        ctx.check(ctx.lib.lra_map_snapshot(ctx.h, C.byref(res), 1 if with_blocks else 0, C.byref(h)))
+        flags = (PACK_BLOCKS if with_blocks else 0) | (PACK_MD if (self.print_md if md is None else md) else 0)
+        ctx.check(ctx.lib.lra_map_snapshot(ctx.h, C.byref(res), flags, C.byref(h)))
         return h
 
     def record_args(self, names, reads, quals=None):
@@ -448,6 +459,7 @@ class LowAccMapper:
         rblocks = ctx.to_host(res.refined.d_blocks, 3 * int(res.refined.n_blocks), np.int32).reshape(-1, 3) if nA else np.zeros((0, 3), np.int32)
         jo = al["job_aln_off"].astype(np.int64)
         ix = {n: i for i, n in enumerate(refine.STAT_NAMES)}
+        mds = refine.md_of_refined(ctx, res.refine_batch, res.refined) if (o.printMD and o.printFormat == "s" and nA) else None
         out = []
         for r in range(res.n_reads):
             name = names[r] if isinstance(names[r], bytes) else str(names[r]).encode()
@@ -485,6 +497,8 @@ class LowAccMapper:
                         rec.n_blocks = len(b)
                         rec.first_block_qpos = int(b[0, 0]) if len(b) else 0
                         rec.last_block_qend = int(b[-1, 0] + b[-1, 2]) if len(b) else 0
+                        if mds is not None:
+                            rec.md = mds[a]
                         recs.append(rec)
                     seg_off.append(len(recs))
             if unaligned or not recs:
@@ -516,6 +530,7 @@ class HighAccMapper:
         self.G = int(g.numel())
         self.chrom_pos = [int(x) for x in chrom_pos]
         self.chrom_names = [n if isinstance(n, bytes) else str(n).encode() for n in chrom_names]
+        self.printMD = bool(overrides.pop("printMD", False))            # --printMD: a record-stage choice, not a field of lra_map_opts
         m = MapOpts()
         (ctx.lib.lra_map_opts_preset_contig if preset == "contig" else ctx.lib.lra_map_opts_preset_ccs)(C.byref(m))
         if gli:
@@ -552,6 +567,7 @@ class HighAccMapper:
         return res
 
     fetch = LowAccMapper.fetch
+    print_md = LowAccMapper.print_md
     fetch_local_index = LowAccMapper.fetch_local_index
     records = LowAccMapper.records
     record_args = LowAccMapper.record_args

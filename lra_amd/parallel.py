@@ -48,9 +48,18 @@ def gather_records(local: torch.Tensor, dst=0):
     return None
 
 
+def pack_records(ctx, res, print_md=False, with_blocks=False) -> np.ndarray:
+    """lra_map_pack of a batch result (on the context that owns it) -> the rank's record buffer as host bytes, for gather_records /
+    records_from_packed.  print_md (--printMD): with the MD strings of the final blocks (LRA_PACK_MD), which format 's' then prints."""
+    d_buf = C.c_void_p(); nb = C.c_uint64(0)
+    flags = (1 if with_blocks else 0) | (2 if print_md else 0)
+    ctx.check(ctx.lib.lra_map_pack(ctx.h, C.byref(res), flags, C.byref(d_buf), C.byref(nb)))
+    return ctx.to_host(d_buf.value, nb.value, np.uint8)
+
+
 def records_from_packed(lib, copts, packed: np.ndarray, names, reads, chrom_names, quals=None, passthrough=None, n_threads=0):
     """One rank's record buffer (host bytes, the layout of lra_map_pack) -> one text record per read of that rank, in the rank's read order.
-    Host only: lra_map_unpack_host + lra_map_records_host."""
+    Host only: lra_map_unpack_host + lra_map_records_host.  A buffer packed with the MD strings (pack_records(print_md=True)) gives MD:Z in format 's'."""
     n = len(names)
     buf = np.ascontiguousarray(packed, dtype=np.uint8)
     snap = C.c_void_p()

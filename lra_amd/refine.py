@@ -68,6 +68,35 @@ class StatsResult(C.Structure):
                 ("d_run_off", C.c_void_p), ("d_runs", C.c_void_p)]
 
 
+class MdResult(C.Structure):
+    """lra_md_result (include/lra_hip.h)"""
+    _fields_ = [("n_aln", C.c_int32), ("n_bytes", C.c_uint64), ("d_md_off", C.c_void_p), ("d_md", C.c_void_p)]
+
+
+def md_strings_batch(ctx: Context, b: RefineBatch):
+    """lra_md_strings_batch: the MD:Z value (lra --printMD) of every alignment of a RefineBatch-shaped input, on the device -> one bytes object per alignment."""
+    res = MdResult()
+    ctx.check(ctx.lib.lra_md_strings_batch(ctx.h, b.n, ptr(b.blocks), ptr(b.block_off), ptr(b.q_seq), ptr(b.q_off), ptr(b.q_len), ptr(b.t_seq), ptr(b.t_off),
+                                           C.byref(res)))
+    return fetch_md(ctx, res)
+
+
+def fetch_md(ctx: Context, res: MdResult):
+    n = int(res.n_aln)
+    off = ctx.to_host(res.d_md_off, n + 1, np.uint64) if n else np.zeros(1, np.uint64)
+    raw = ctx.to_host(res.d_md, int(res.n_bytes), np.uint8).tobytes() if int(res.n_bytes) else b""
+    return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+
+def md_of_refined(ctx: Context, b: RefineBatch, rres: RefineResult):
+    """lra_md_strings_batch straight on the (context-owned) output of indel_refine_batch (the blocks CalculateStatistics saw)."""
+    v = RefineBatch.__new__(RefineBatch)
+    v.ctx, v.n, v.n_blocks_in = ctx, b.n, int(rres.n_blocks)
+    v.blocks, v.block_off = int(rres.d_blocks), int(rres.d_block_off)
+    v.q_seq, v.q_off, v.q_len, v.t_seq, v.t_off, v.t_len = b.q_seq, b.q_off, b.q_len, b.t_seq, b.t_off, b.t_len
+    return md_strings_batch(ctx, v)
+
+
 STAT_NAMES = ["nm", "nmm", "nins", "ndel", "tdel", "tins", "nSmallDel", "nMedDel", "nLargeDel", "nSmallIns", "nMedIns", "nLargeIns",
               "preClip", "sufClip", "qStart", "qEnd", "tStart", "tEnd"]
 
