@@ -707,11 +707,14 @@ int lra_local_refine_inputs_batch(lra_ctx* ctx, int num_aln, const uint32_t* d_s
  * int32 triples d_blocks_in[3*d_block_off[a] .. 3*d_block_off[a+1]) (absolute read / chromosome
  * coordinates); alignment.read = the read strand it is on = d_qseq + d_q_off[a] of length
  * d_q_len[a] (read.length); genome.seqs[alignment.chromIndex] = d_tseq + d_t_off[a] of length
- * d_t_len[a] (genome.lengths[chromIndex]).  refine_band = opts.refineBand (2..64), match /
+ * d_t_len[a] (genome.lengths[chromIndex]).  refine_band = opts.refineBand, match /
  * mismatch / indel = opts.localMatch / localMismatch / localIndel, end_align as the argument.
+ * refine_band must lie in 2..64 and indel must be negative; otherwise the call returns
+ * LRA_ERR_INVALID before it launches anything, and out is left as it was.
  * Output: the refined alignment.blocks of every alignment (CSR, device arrays owned by the
  * context, valid until the next call), a status word per alignment (bits above; LRA_ST_RANGE
- * also flags a row window wider than 64 cells, not supported yet).  Synchronous.            */
+ * also flags a segment whose row window is wider than 1024 cells, the widest row the fill
+ * kernels take).  Synchronous.                                                               */
 typedef struct lra_refine_result {
   int32_t n_aln;
   uint64_t n_blocks, n_segments, n_rows, n_cells, n_aog;

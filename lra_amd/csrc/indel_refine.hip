@@ -1380,9 +1380,10 @@ extern "C" int lra_indel_refine_batch(lra_ctx* ctx, int n_aln, const int32_t* d_
     F.list = fill_lists; F.cursor = fill_cursor;
     const unsigned cap_grid = (unsigned)ctx->num_cu * 32;
     if (getenv("LRA_IR_DBG")) {
-      const int hc[3] = {h_cursor[4] - h_cursor[0], h_cursor[5] - h_cursor[1], h_cursor[6] - h_cursor[2]};
-      fprintf(stderr, "[ir] n_seg %llu n_rows %llu n_cells %llu n_task %llu fill classes 16/32/64: %d %d %d\n", (unsigned long long)n_seg,
-              (unsigned long long)n_rows, (unsigned long long)n_cells, (unsigned long long)n_task, hc[0], hc[1], hc[2]);
+      const int hc[4] = {h_cursor[4] - h_cursor[0], h_cursor[5] - h_cursor[1], h_cursor[6] - h_cursor[2], h_cursor[7] - h_cursor[3]};
+      fprintf(stderr, "[ir] n_seg %llu n_rows %llu n_cells %llu n_task %llu n_item %llu fill classes 16/32/64/wide: %d %d %d %d\n",
+              (unsigned long long)n_seg, (unsigned long long)n_rows, (unsigned long long)n_cells, (unsigned long long)n_task,
+              (unsigned long long)n_item, hc[0], hc[1], hc[2], hc[3]);
     }
     lra_time_begin(ctx, "ir_fill");
     const uint64_t n16 = (uint64_t)(h_cursor[4] - h_cursor[0]), n32 = (uint64_t)(h_cursor[5] - h_cursor[1]), n64 = (uint64_t)(h_cursor[6] - h_cursor[2]);
