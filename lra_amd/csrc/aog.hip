@@ -450,7 +450,7 @@ __device__ __forceinline__ void solve(int wlane, const Problem& pr, const Geo& g
   // ---- prefix trace back (:589-629), lane 0 -- or, with the arrows in HBM only (rolling), all lanes in step on the same state over a window of rows staged in
   // LDS: the walk is a chain of dependent one-byte loads a row apart (a cache line each); a window serves at least as many steps as it has rows
   if (rolling) {
-    unsigned char* chunk = (unsigned char*)(roll + 768 + 1024);          // chunkBytes (LRA_AOG_CHUNK: 4 KB; what a wave asks for sets how many fit a CU)
+    unsigned char* chunk = (unsigned char*)(roll + 768 + 1024);          // chunkBytes (8 KB; what a wave asks for sets how many fit a CU)
     const int chRows = max(1, chunkBytes / R);
     int cLo = 1, cHi = 0;
     auto arrowAt = [&](int i, int j) -> int {
@@ -627,7 +627,8 @@ __device__ __forceinline__ void solve_reg(int wlane, const Problem& pr, const Ge
   }
 }
 __device__ __forceinline__ long need_bytes_reg(const Geo& g) { return align4(g.nUsed) + align4(g.qLen + 1) + align4(g.tLen + 1); }
-constexpr int REG_S_BYTES = 2048, REG_M_BYTES = 8192, REG_L_BYTES = 32768, REG_X_BYTES = 65536;   // classes 10 (16 lanes), 11 (32 lanes), 12, 13 (64 lanes)
+constexpr int REG_S_BYTES = 2048, REG_M_BYTES = 8192, REG_L_BYTES = 32768;   // classes 10 (16 lanes), 11 (32 lanes), 12 (64 lanes)
+constexpr int REG_L_USED = 16384;   // largest arrows + codes footprint of class 12 (above: the HBM class, whose sweep is in registers too)
 
 struct BatchArgs {
   int n;
@@ -642,9 +643,6 @@ struct BatchArgs {
   char* gscratch; long gslot_bytes; int gslots;       // class 2: HBM work slots
   char* gscratchB; long gslotB_bytes; int gslotsB;    // class 6: a few larger ones
   int chunk_bytes;                                    // classes 2 / 6: the trace-back window in LDS
-  int use_reg;                                        // classes 10-13 (solve_reg) in use
-  int use_lane;                                       // class 14 (aog_lane_kernel) in use
-  int regL, regX;                                     // largest arrows + codes footprint of classes 12 and 13 (above: the HBM class, whose sweep is in registers too)
 };
 
 __device__ __forceinline__ bool load_problem(const BatchArgs& a, int p, Problem& pr, Geo& g, int& range_ok) {
@@ -669,13 +667,12 @@ __device__ __forceinline__ int classify_one(const BatchArgs& a, int p) {
   if (need <= CLASS_S_BYTES && g.k + 1 <= 16) cls = 3;
   if (cls == 2 && need > a.gslot_bytes) cls = 6;
   if (cls == 6 && need > a.gslotB_bytes) { a.score[p] = 0; a.nblocks[p] = 0; a.status[p] = LRA_ST_RANGE; return -1; }
-  if (!g.top && a.use_reg) {                                               // prefix band only: scores in registers (solve_reg), arrows + codes in LDS
+  if (!g.top) {                                                     // prefix band only: scores in registers (solve_reg), arrows + codes in LDS
     const long nr = need_bytes_reg(g);
-    if (a.use_lane && g.qLen <= LN_MAX && g.tLen <= LN_MAX) { const int mx = max(g.qLen, g.tLen); cls = mx <= 3 ? 14 : mx <= 6 ? 15 : mx <= 10 ? 16 : mx <= 16 ? 17 : 18; }
+    if (g.qLen <= LN_MAX && g.tLen <= LN_MAX) { const int mx = max(g.qLen, g.tLen); cls = mx <= 3 ? 14 : mx <= 6 ? 15 : mx <= 10 ? 16 : mx <= 16 ? 17 : 18; }
     else if (g.k + 2 <= 16 && nr <= REG_S_BYTES) cls = 10;
     else if (g.k + 2 <= 32 && nr <= REG_M_BYTES) cls = 11;
-    else if (g.k + 2 <= 64 && nr <= a.regL) cls = 12;
-    else if (g.k + 2 <= 64 && nr <= a.regX) cls = 13;
+    else if (g.k + 2 <= 64 && nr <= REG_L_USED) cls = 12;
   }
   return cls;
 }
@@ -765,12 +762,12 @@ __global__ void __launch_bounds__((CLS == 0 || CLS == 3 || CLS == 7) ? 256 : 64)
   }
 }
 
-// classes 10-13: solve_reg.  10: 16 lanes per problem, 16 problems per 256-thread workgroup; 11: 32 lanes, 4 problems per 128 threads; 12, 13: a wave per problem
+// classes 10-12: solve_reg.  10: 16 lanes per problem, 16 problems per 256-thread workgroup; 11: 32 lanes, 4 problems per 128 threads; 12: a wave per problem
 template <int CLS>
 __global__ void __launch_bounds__(CLS == 10 ? 256 : CLS == 11 ? 128 : 64) aog_reg_kernel(BatchArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int G = CLS == 10 ? 16 : CLS == 11 ? 32 : 64;
-  constexpr int BYTES = CLS == 10 ? REG_S_BYTES : CLS == 11 ? REG_M_BYTES : CLS == 12 ? REG_L_BYTES : REG_X_BYTES;
+  constexpr int BYTES = CLS == 10 ? REG_S_BYTES : CLS == 11 ? REG_M_BYTES : REG_L_BYTES;
   constexpr int GPW = 64 / G;
   const int lane = threadIdx.x & 63;
   const int wave_in_wg = threadIdx.x >> 6;
@@ -926,11 +923,11 @@ int lra_aog_launch_device(lra_ctx* ctx, int n, const char* d_qseq, const char* d
   char* s0 = (char*)lra_scratch(ctx, 0, 384 + sizeof(int) * (size_t)n + (size_t)n + 64);
   if (!s0) return LRA_ERR_NOMEM;
   a.counts = (int*)s0; a.offs = a.counts + 32; a.cursor = a.counts + 64; a.list = (int*)(s0 + 384); a.cls8 = (unsigned char*)(a.list + n);
-  // class 2: 4 MiB slots, LRA_AOG_SLOTS (default 8) per CU -- with the scores of most of these problems in LDS (rolling, see solve) a wave's HBM traffic is its
+  // class 2: 4 MiB slots, 8 per CU (two-stage batches: 6 -- step 955 -> 939 ms) -- with the scores of most of these problems in LDS (rolling, see solve) a wave's HBM traffic is its
   // arrows, and a CU can keep more of them in flight; class 6: 8 MiB slots, one per CU, for the rare larger problem (1.5 kb x 1.5 kb at k = 60, 5 kb x 5 kb at k = 15)
-  const int perCu = std::max(1, getenv("LRA_AOG_SLOTS") ? atoi(getenv("LRA_AOG_SLOTS")) : ctx->pipelined ? 6 : 8);   // (a zero or non-numeric value would leave the HBM class without a slot; two-stage batches: 6 -- step 955 -> 939 ms)
+  const int perCu = ctx->pipelined ? 6 : 8;
   a.gslots = ctx->num_cu * perCu; a.gslot_bytes = 4L << 20;
-  a.chunk_bytes = std::min(8192, std::max(1024, getenv("LRA_AOG_CHUNK") ? atoi(getenv("LRA_AOG_CHUNK")) : 8192)) & ~255;
+  a.chunk_bytes = 8192;
   a.gslotsB = ctx->num_cu; a.gslotB_bytes = 8L << 20;
   a.gscratch = (char*)lra_scratch(ctx, 1, (size_t)a.gslots * a.gslot_bytes + (size_t)a.gslotsB * a.gslotB_bytes);
   if (!a.gscratch) return LRA_ERR_NOMEM;
@@ -955,11 +952,6 @@ int lra_aog_launch_device(lra_ctx* ctx, int n, const char* d_qseq, const char* d
             n, nTop, nBigK, byNeed[0], byNeed[1], byNeed[2], byNeed[3], byNeed[4], byNeed[5], byNeed[6], byNeed[7], cellsBy[0] / 1e6, cellsBy[1] / 1e6, cellsBy[2] / 1e6, cellsBy[3] / 1e6,
             cellsBy[4] / 1e6, cellsBy[5] / 1e6, cellsBy[6] / 1e6, cellsBy[7] / 1e6, byK[0], byK[1], byK[2], steps / 1e6);
   }
-  a.use_reg = getenv("LRA_AOG_NOREG") ? 0 : 1;
-  a.use_lane = (a.use_reg && !getenv("LRA_AOG_NOLANE")) ? 1 : 0;
-  a.regL = getenv("LRA_AOG_REG_L") ? std::min(atoi(getenv("LRA_AOG_REG_L")), REG_L_BYTES) : 16384;
-  a.regX = getenv("LRA_AOG_REG_X") ? std::min(atoi(getenv("LRA_AOG_REG_X")), REG_X_BYTES) : 0;
-  if (a.use_reg) LRA_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)aog_reg_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, REG_X_BYTES));
   LRA_HIP_CHECK(ctx, hipMemsetAsync(a.counts, 0, 384, ctx->stream));
   const int cblocks = (int)(((long)n + CLS_ITEMS * 1024 - 1) / (CLS_ITEMS * 1024));
   hipLaunchKernelGGL(aog_classify, dim3(cblocks), dim3(1024), 0, ctx->stream, a);
@@ -972,10 +964,9 @@ int lra_aog_launch_device(lra_ctx* ctx, int n, const char* d_qseq, const char* d
   LRA_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)aog_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, CLASS_B_BYTES));
   LRA_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)aog_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CLASS_M2_BYTES));
   // The classes are independent, and every class's launch ends with a few long problems on a few CUs: they run side by side on the context's side streams
-  // (the HBM class, the longest, on the context's own stream) instead of one after the other.  LRA_AOG_SERIAL=1: one stream (for comparisons).
-  static const bool serial = getenv("LRA_AOG_SERIAL") != nullptr;
+  // (the HBM class, the longest, on the context's own stream) instead of one after the other.
   const hipStream_t sm = ctx->stream;
-  const hipStream_t s1 = serial ? sm : lra_side_fork(ctx, 1), s2 = serial ? sm : lra_side_fork(ctx, 2), s3 = serial ? sm : lra_side_fork(ctx, 3);
+  const hipStream_t s1 = lra_side_fork(ctx, 1), s2 = lra_side_fork(ctx, 2), s3 = lra_side_fork(ctx, 3);
   lra_time_begin(ctx, "aog_lds_large", s1);
   hipLaunchKernelGGL(aog_kernel<1>, dim3(wgB), dim3(64), CLASS_B_BYTES, s1, a);
   lra_time_end(ctx, s1);
@@ -992,36 +983,29 @@ int lra_aog_launch_device(lra_ctx* ctx, int n, const char* d_qseq, const char* d
   hipLaunchKernelGGL(aog_kernel<4>, dim3(min(n, ctx->num_cu * 8)), dim3(64), CLASS_M1_BYTES, s3, a);
   hipLaunchKernelGGL(aog_kernel<5>, dim3(min(n, ctx->num_cu * 5)), dim3(64), CLASS_M2_BYTES, s3, a);
   lra_time_end(ctx, s3);
-  if (a.use_lane) {
-    lra_time_begin(ctx, "aog_lane");
-    const int nb64 = (n + 63) / 64;
-    hipLaunchKernelGGL(aog_lane_kernel<24>, dim3(min(nb64, ctx->num_cu * 7)), dim3(64), 0, sm, a, 18);
-    hipLaunchKernelGGL(aog_lane_kernel<16>, dim3(min(nb64, ctx->num_cu * 14)), dim3(64), 0, sm, a, 17);
-    hipLaunchKernelGGL(aog_lane_kernel<10>, dim3(min(nb64, ctx->num_cu * 22)), dim3(64), 0, sm, a, 16);
-    hipLaunchKernelGGL(aog_lane_kernel<6>, dim3(min(nb64, ctx->num_cu * 32)), dim3(64), 0, sm, a, 15);
-    hipLaunchKernelGGL(aog_lane_kernel<3>, dim3(min(nb64, ctx->num_cu * 32)), dim3(64), 0, sm, a, 14);
-    lra_time_end(ctx);
-  }
-  if (a.use_reg) {
-    lra_time_begin(ctx, "aog_reg");
-    // the three register classes side by side as well (each ends with a few long problems; one after the other they took 43 ms of the a13 call, LRA_AOG_SERIAL=1)
-    hipLaunchKernelGGL(aog_reg_kernel<10>, dim3(min((n + 15) / 16, ctx->num_cu * 10)), dim3(256), 16 * REG_S_BYTES, sm, a);
-    lra_time_end(ctx);
-    lra_time_begin(ctx, "aog_reg_medium", s2);
-    hipLaunchKernelGGL(aog_reg_kernel<11>, dim3(min((n + 3) / 4, ctx->num_cu * 10)), dim3(128), 4 * REG_M_BYTES, s2, a);
-    lra_time_end(ctx, s2);
-    lra_time_begin(ctx, "aog_reg_large", s3);
-    hipLaunchKernelGGL(aog_reg_kernel<12>, dim3(min(n, ctx->num_cu * 10)), dim3(64), a.regL, s3, a);
-    lra_time_end(ctx, s3);
-    lra_time_begin(ctx, "aog_reg");
-    if (a.regX) hipLaunchKernelGGL(aog_reg_kernel<13>, dim3(min(n, ctx->num_cu * 4)), dim3(64), a.regX, sm, a);
-    lra_time_end(ctx);
-  }
+  lra_time_begin(ctx, "aog_lane");
+  const int nb64 = (n + 63) / 64;
+  hipLaunchKernelGGL(aog_lane_kernel<24>, dim3(min(nb64, ctx->num_cu * 7)), dim3(64), 0, sm, a, 18);
+  hipLaunchKernelGGL(aog_lane_kernel<16>, dim3(min(nb64, ctx->num_cu * 14)), dim3(64), 0, sm, a, 17);
+  hipLaunchKernelGGL(aog_lane_kernel<10>, dim3(min(nb64, ctx->num_cu * 22)), dim3(64), 0, sm, a, 16);
+  hipLaunchKernelGGL(aog_lane_kernel<6>, dim3(min(nb64, ctx->num_cu * 32)), dim3(64), 0, sm, a, 15);
+  hipLaunchKernelGGL(aog_lane_kernel<3>, dim3(min(nb64, ctx->num_cu * 32)), dim3(64), 0, sm, a, 14);
+  lra_time_end(ctx);
+  lra_time_begin(ctx, "aog_reg");
+  // the three register classes side by side as well (each ends with a few long problems; one after the other they took 43 ms of the a13 call)
+  hipLaunchKernelGGL(aog_reg_kernel<10>, dim3(min((n + 15) / 16, ctx->num_cu * 10)), dim3(256), 16 * REG_S_BYTES, sm, a);
+  lra_time_end(ctx);
+  lra_time_begin(ctx, "aog_reg_medium", s2);
+  hipLaunchKernelGGL(aog_reg_kernel<11>, dim3(min((n + 3) / 4, ctx->num_cu * 10)), dim3(128), 4 * REG_M_BYTES, s2, a);
+  lra_time_end(ctx, s2);
+  lra_time_begin(ctx, "aog_reg_large", s3);
+  hipLaunchKernelGGL(aog_reg_kernel<12>, dim3(min(n, ctx->num_cu * 10)), dim3(64), REG_L_USED, s3, a);
+  lra_time_end(ctx, s3);
   lra_time_begin(ctx, "aog_hbm");
   hipLaunchKernelGGL(aog_kernel<2>, dim3(wgC), dim3(64), (3 * 256 + 1024) * 4 + a.chunk_bytes, sm, a);
   hipLaunchKernelGGL(aog_kernel<6>, dim3(min(n, a.gslotsB)), dim3(64), (3 * 256 + 1024) * 4 + a.chunk_bytes, sm, a);
   lra_time_end(ctx);
-  if (!serial) { lra_side_join(ctx, 1); lra_side_join(ctx, 2); lra_side_join(ctx, 3); }
+  lra_side_join(ctx, 1); lra_side_join(ctx, 2); lra_side_join(ctx, 3);
   LRA_HIP_CHECK(ctx, hipGetLastError());
   return LRA_OK;
 }

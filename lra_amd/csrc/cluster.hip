@@ -28,8 +28,8 @@ struct CleanArgs {
   const uint64_t* match_off; const uint32_t* n_forward;
   const uint32_t* sq; const uint32_t* st; const uint64_t* sk;       // sorted matches (q, t, read key)
   uint32_t* cl_q; uint32_t* cl_t;                                   // cleaned matches (capacity layout)
-  unsigned char* onDiag; unsigned char* second; unsigned char* fw; unsigned char* rv; int* count; float* freq;
-  uint64_t* tab_key; uint32_t* tab_tag;
+  unsigned char* second; int* count; float* freq;
+  uint64_t* tab_key;
   const uint64_t* chrom_pos; int n_chrom;
   // clusters at capacity offsets (segment base), per-segment count
   uint64_t* c_start; uint64_t* c_end; uint32_t* c_qs; uint32_t* c_qe; uint32_t* c_ts; uint32_t* c_te; int* c_strand; int* c_chrom; float* c_freq;
@@ -74,160 +74,7 @@ __device__ int header_find(const uint64_t* pos, int npos, uint64_t query) {   //
   return lo - 1;
 }
 
-// SecondRoundCleanOffDiagonal (:802-868) on [os, oe)
-__device__ void second_round(const CleanArgs& A, uint64_t base, const uint32_t* q, const uint32_t* t, int out_counter, int MinDiagCluster, int os, int oe, int strand) {
-  unsigned char* second = A.second + base; unsigned char* fw = A.fw + base; unsigned char* rv = A.rv + base; int* count = A.count + base;
-  if (MinDiagCluster >= oe - os) return;
-  if (MinDiagCluster <= 0) { for (int i = os; i < oe; i++) { second[i] = 1; count[i] = out_counter; } return; }
-  if (oe - os <= 1) return;
-  const int cmd = A.o.SecondCleanMaxDiag;
-  for (int i = os; i < oe; i++) { fw[i] = 0; rv[i] = 0; }
-  for (int i = os + 1; i < oe; i++) if (labs(diag_diff(q[i], t[i], q[i - 1], t[i - 1], strand)) < cmd) fw[i - 1] = 1;
-  bool prev = false; int ds = 0;
-  for (int i = os; i < oe; i++) {
-    if (!prev && fw[i]) ds = i;
-    if (prev && !fw[i]) {
-      if (i - ds + 1 < MinDiagCluster) { for (int j = ds; j <= i; j++) fw[j] = 0; }
-      else fw[i] = 1;
-    }
-    prev = fw[i];
-  }
-  for (int i = oe - 2; i >= os; i--) if (labs(diag_diff(q[i], t[i], q[i + 1], t[i + 1], strand)) < cmd) rv[i + 1] = 1;
-  prev = false;
-  for (int i = oe - 1; i >= os; i--) {
-    if (!prev && rv[i]) ds = i;
-    if (prev && !rv[i]) {
-      if (ds - i + 1 < MinDiagCluster) { for (int j = i; j <= ds; j++) rv[j] = 0; }
-      else rv[i] = 1;
-    }
-    prev = rv[i];
-  }
-  for (int i = os; i < oe; i++) {
-    if (fw[i] && rv[i]) { second[i] = 1; count[i] = out_counter; }
-    else second[i] = 0;
-  }
-}
-
-constexpr int CLEAN_LANES = 16;
-__global__ void __launch_bounds__(64) clean_kernel(CleanArgs A) {
-  if (threadIdx.x >= CLEAN_LANES) return;                                // serial scans with dependent loads: fewer lanes per wave, more waves
-  const long seg = (long)blockIdx.x * CLEAN_LANES + threadIdx.x;
-  if (seg >= 2L * A.n_reads) return;
-  const int r = (int)(seg >> 1), strand = (int)(seg & 1);
-  const uint64_t m0 = A.match_off[r], mf = m0 + A.n_forward[r], m1 = A.match_off[r + 1];
-  const uint64_t base = strand ? mf : m0;
-  const int n = (int)((strand ? m1 : mf) - base);
-  A.seg_ncl[seg] = 0;
-  if (n == 0) return;                                                    // :568-570
-  const uint32_t* q = A.sq + base; const uint32_t* t = A.st + base; const uint64_t* key = A.sk + base;
-  unsigned char* onDiag = A.onDiag + base; unsigned char* second = A.second + base;
-  int* count = A.count + base; float* freq = A.freq + base;
-  const lra_clean_opts& o = A.o;
-  for (int i = 0; i < n; i++) { onDiag[i] = 0; second[i] = 0; count[i] = -1; freq[i] = 1.0f; }
-  if (n > 1 && labs(diag_diff(q[0], t[0], q[1], t[1], strand)) < o.cleanMaxDiag) onDiag[0] = 1;              // :573-576
-  for (int i = 1; i < n; i++) if (labs(diag_diff(q[i], t[i], q[i - 1], t[i - 1], strand)) < o.cleanMaxDiag) onDiag[i - 1] = 1;   // :578-584
-  bool prev = false, startSet = false;
-  int diagStart = 0, largest = 0;
-  for (int i = 0; i < n; i++) {                                          // :589-598
-    const bool od = onDiag[i];
-    if (!prev && od) { diagStart = i; startSet = true; }
-    if (prev && !od) largest = max(largest, i - diagStart + 1);
-    prev = od;
-  }
-  if (!startSet) return;                                                 // :600-603
-  largest = max(largest, n - diagStart);
-  int minDiagCluster = largest / 10;                                     // :608-609
-  if (minDiagCluster >= o.minDiagCluster) minDiagCluster = o.minDiagCluster;
-  // AVGfreq table: power of two >= 2n slots at 4*base
-  uint32_t tsz = 1; while (tsz < 2u * (uint32_t)n) tsz <<= 1;
-  uint64_t* tk = A.tab_key + 4 * base; uint32_t* tg = A.tab_tag + 4 * base;
-  int counter = 0;
-  prev = false;
-  if (minDiagCluster >= 0) {
-    for (int i = 0; i < n; i++) {                                        // :620-722
-      const bool od = onDiag[i];
-      if (!prev && od) diagStart = i;
-      if (prev && !od) {
-        const int len = i - diagStart + 1;
-        if (len >= minDiagCluster) {
-          int distinct = 0;                                              // AVGfreq :550-564
-          const uint32_t tag = (uint32_t)counter + 1;
-          for (int x = diagStart; x <= i; x++) {
-            const uint64_t kk = key[x];
-            uint32_t h = (uint32_t)((kk * 0x9E3779B97F4A7C15ULL) >> 40) & (tsz - 1);
-            while (true) {
-              if (tg[h] != tag) { tg[h] = tag; tk[h] = kk; distinct++; break; }
-              if (tk[h] == kk) break;
-              h = (h + 1) & (tsz - 1);
-            }
-          }
-          const float avgfreq = (float)len / (float)distinct;
-          for (int j = diagStart; j <= i; j++) freq[j] = avgfreq;
-          const int cc = o.cleanClustersize;
-          int MinDiagCluster = 0;
-          bool keepAll = false;
-          if (o.bypassClustering) {                                      // :635-657
-            if (avgfreq >= 3.0f && len < 10) {}
-            else if (avgfreq >= 2.0f && len >= cc) {
-              MinDiagCluster = (int)((float)o.SecondCleanMinDiagCluster + floorf((avgfreq - 1.5f) / 1.0f) * (float)o.punish_anchorfreq + (float)(((len - cc) / cc) * o.anchorPerlength));
-              second_round(A, base, q, t, counter, MinDiagCluster, diagStart, i + 1, strand);
-            } else if (avgfreq >= 1.5f && len >= cc) {
-              MinDiagCluster = (int)((float)o.SecondCleanMinDiagCluster + floorf((avgfreq - 1.5f) / 1.5f) * (float)o.punish_anchorfreq + (float)(((len - cc) / cc) * o.anchorPerlength));
-              second_round(A, base, q, t, counter, MinDiagCluster, diagStart, i + 1, strand);
-            } else keepAll = true;
-          } else {                                                       // :659-693
-            if (avgfreq >= 3.0f && len < 10) {}
-            else if (avgfreq >= 4.0f && len >= cc) {
-              MinDiagCluster = (int)((float)o.SecondCleanMinDiagCluster + floorf((avgfreq - 1.5f) / 1.0f) * (float)o.punish_anchorfreq + (float)(((len - cc) / cc) * o.anchorPerlength));
-              second_round(A, base, q, t, counter, MinDiagCluster, diagStart, i + 1, strand);
-            } else if (avgfreq >= 1.5f && len >= cc) {
-              MinDiagCluster = (int)((float)o.SecondCleanMinDiagCluster + floorf((avgfreq - 1.5f) / 1.5f) * (float)o.punish_anchorfreq + (float)(((len - cc) / cc) * o.anchorPerlength));
-              second_round(A, base, q, t, counter, MinDiagCluster, diagStart, i + 1, strand);
-            } else if (avgfreq > 1.0f && len >= cc) {
-              MinDiagCluster = (int)((float)o.SecondCleanMinDiagCluster - (5.0f - floorf((avgfreq - 1.0f) / 0.1f)) * (float)(o.punish_anchorfreq / 2) + (float)(((len - cc) / cc) * (o.anchorPerlength / 2)));
-              second_round(A, base, q, t, counter, MinDiagCluster, diagStart, i + 1, strand);
-            } else if (avgfreq > 1.0f) {
-              MinDiagCluster = (int)((float)o.SecondCleanMinDiagCluster - (5.0f - floorf((avgfreq - 1.0f) / 0.1f)) * (float)(o.punish_anchorfreq / 2) - (float)(((cc - i + diagStart - 1) / 15) * (o.anchorPerlength / 2)));
-              second_round(A, base, q, t, counter, MinDiagCluster, diagStart, i + 1, strand);
-            } else keepAll = true;
-          }
-          if (keepAll) for (int j = diagStart; j <= i; j++) { second[j] = 1; count[j] = counter; }
-        }
-        counter++;
-      }
-      prev = od;
-    }
-  }
-  // compaction (:728-738) and clusters (:740-797)
-  uint32_t* oq = A.cl_q + base; uint32_t* ot = A.cl_t + base;
-  int c = 0;
-  for (int i = 0; i < n; i++)
-    if (second[i]) { oq[c] = q[i]; ot[c] = t[i]; freq[c] = freq[i]; count[c] = count[i]; c++; }
-  uint32_t ncl = 0;
-  auto emit = [&](int s, int e) {
-    uint32_t qS = oq[s], qE = oq[s] + (uint32_t)o.globalK, tS = ot[s], tE = ot[s] + (uint32_t)o.globalK;
-    for (int b = s; b < e; b++) {
-      qS = min(qS, oq[b]); qE = max(qE, oq[b] + (uint32_t)o.globalK);
-      tS = min(tS, ot[b]); tE = max(tE, ot[b] + (uint32_t)o.globalK);
-    }
-    const uint64_t x = base + ncl;
-    A.c_start[x] = base + s; A.c_end[x] = base + e; A.c_qs[x] = qS; A.c_qe[x] = qE; A.c_ts[x] = tS; A.c_te[x] = tE;
-    A.c_strand[x] = strand; A.c_freq[x] = freq[s];
-    A.c_chrom[x] = header_find(A.chrom_pos, A.n_chrom + 1, tS);
-    ncl++;
-  };
-  int count_s = 0, cc2 = 1;
-  while (cc2 < c) {
-    if (count[cc2] == count[cc2 - 1]) { cc2++; continue; }
-    emit(count_s, cc2);
-    count_s = cc2;
-    cc2++;
-  }
-  if (cc2 == c && count_s < cc2) emit(count_s, cc2);
-  A.seg_ncl[seg] = ncl;
-}
-
-// ---- the same stage with a WAVE per (read, strand) segment.  clean_kernel walks a segment with one lane: every pass over its matches is a chain of dependent loads, and a
+// ---- CleanOffDiagonal (:568-797) with a WAVE per (read, strand) segment.  With one lane per segment every pass over its matches is a chain of dependent loads, and a
 // read out of a satellite array has tens of thousands of matches -- the launch lasted as long as its largest segment.  Every pass is a map, a scan or a reduction:
 //   * the diagonal runs (:589-722): from the ballots of the neighbour flags, 64 matches per step (runs(): calls back once per run, wave-uniformly, in order);
 //   * AVGfreq (:550-564): the run's distinct read k-mers through a compare-and-swap hash table (the run's own region of tab_key: cleared, then one CAS per probe);
@@ -455,7 +302,7 @@ extern "C" int lra_clean_matches_batch(lra_ctx* ctx, const lra_clean_opts* opts,
     (void)lra_segsort_pairs(ctx, nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, (unsigned int)nm, (unsigned int)(2 * n_reads), nullptr, nullptr, 0, 64, st);
   }
   auto sz = [](size_t n, size_t e) { return (n * e + 255) & ~(size_t)255; };
-  size_t needW = sz(N, 8) * 2 + sz(N, 4) * 2 + sz(NS, 8) + sz(N, 4) * 2 + sz(N, 8) + sz(N, 1) * 4 + sz(N, 4) * 2 + sz(4 * N, 8) + sz(4 * N, 4) +
+  size_t needW = sz(N, 8) * 2 + sz(N, 4) * 2 + sz(NS, 8) + sz(N, 4) * 2 + sz(N, 8) + sz(N, 1) + sz(N, 4) * 2 + sz(4 * N, 8) +
                  sz(n_chrom + 2, 8) + sz(N, 8) * 2 + sz(N, 4) * 6 + sz(N, 4) + sz(NS, 4) + sz(NS, 8) + temp_bytes + 4096;
   char* w = (char*)lra_ensure(ctx, 3, needW);
   if (!w) return LRA_ERR_NOMEM;
@@ -466,9 +313,9 @@ extern "C" int lra_clean_matches_batch(lra_ctx* ctx, const lra_clean_opts* opts,
   A.n_reads = n_reads; A.o = *opts; A.match_off = s->match_off; A.n_forward = s->n_forward;
   uint32_t* sq = carve<uint32_t>(w, N); uint32_t* stt = carve<uint32_t>(w, N); uint64_t* sk = carve<uint64_t>(w, N);
   A.sq = sq; A.st = stt; A.sk = sk;
-  A.onDiag = carve<unsigned char>(w, N); A.second = carve<unsigned char>(w, N); A.fw = carve<unsigned char>(w, N); A.rv = carve<unsigned char>(w, N);
+  A.second = carve<unsigned char>(w, N);
   A.count = carve<int>(w, N); A.freq = carve<float>(w, N);
-  A.tab_key = carve<uint64_t>(w, 4 * N); A.tab_tag = carve<uint32_t>(w, 4 * N);
+  A.tab_key = carve<uint64_t>(w, 4 * N);
   uint64_t* d_chrom = carve<uint64_t>(w, n_chrom + 2);
   A.chrom_pos = d_chrom; A.n_chrom = n_chrom;
   A.c_start = carve<uint64_t>(w, N); A.c_end = carve<uint64_t>(w, N);
@@ -478,8 +325,6 @@ extern "C" int lra_clean_matches_batch(lra_ctx* ctx, const lra_clean_opts* opts,
   uint64_t* seg_coff = carve<uint64_t>(w, NS);
   void* temp = (void*)w;
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(d_chrom, h_chrom_pos, (size_t)(n_chrom + 1) * 8, hipMemcpyHostToDevice, st));
-  static const bool cleanSerial = getenv("LRA_CLEAN_SERIAL") != nullptr;   // the one-lane-per-segment walk (kept for comparison)
-  if (cleanSerial) LRA_HIP_CHECK(ctx, hipMemsetAsync(A.tab_tag, 0, 4 * N * 4, st));   // (its hash table's tags; clean_wave_kernel clears what it uses)
   // results: cleaned matches
   char* rbuf = (char*)lra_ensure(ctx, 4, sz(N, 4) * 2 + 4096);
   if (!rbuf) return LRA_ERR_NOMEM;
@@ -495,8 +340,7 @@ extern "C" int lra_clean_matches_batch(lra_ctx* ctx, const lra_clean_opts* opts,
   lra_time_end(ctx);
   // ---- clean
   lra_time_begin(ctx, "clean");
-  if (cleanSerial) hipLaunchKernelGGL(clean_kernel, dim3((2 * n_reads + CLEAN_LANES - 1) / CLEAN_LANES), dim3(64), 0, st, A);
-  else hipLaunchKernelGGL(clean_wave_kernel, dim3(2 * n_reads), dim3(64), 0, st, A);
+  hipLaunchKernelGGL(clean_wave_kernel, dim3(2 * n_reads), dim3(64), 0, st, A);
   lra_time_end(ctx);
   if (lra_exclusive_scan<uint32_t>(ctx, 2L * n_reads, A.seg_ncl, seg_coff)) return LRA_ERR_HIP;
   uint64_t ncl = 0;

@@ -571,11 +571,10 @@ constexpr int CMP_CAP = 128;                    // pairs per task kept by the on
 // or one that no longer fits, is walked in HBM): a typical task has ~180 words, so 40 KB hold a block and four blocks fit a CU (fixed 257-word rows: two).
 constexpr int CMP_WORDS = 10240, CMP_TASK_MAX = 512;
 constexpr int CW_ROW = 512;                     // pairs per task kept by the one-walk form for large tasks (packed qi << 16 | ti; a task with more is walked again)
-// MODE 0: count; 1: write the pairs at out_off (after a scan of the counts: the walk runs twice); 2: count AND keep the pairs, packed, in a fixed row per task --
-// local_compact_pairs then lays them out by the scan of the counts.  A task with a list of more than 255 tuples or more than CMP_CAP pairs sends the batch
-// through modes 0 + 1 (nOver).
-// BIG: the batch's tasks are beyond the staging (windows of 2048 bases -- the .gli file `lra index` writes -- hold ~700 tuples a list): a lane per task walks its lists
-// where they lie, every lane of the block (the 16-lanes-per-wave form exists for the LDS rows).  Its two searches start where the walk stands: lower_bound from ts
+// MODE 2: count AND keep the pairs, packed, in a fixed row per task -- local_compact_pairs then lays them out by the scan of the counts.  A task with a list of more
+// than 255 tuples or more than CMP_CAP pairs sends the batch through mode 1 (nOver): write the pairs at out_off (after a scan of the counts: the walk runs twice).
+// BIG (mode 1 only: the re-walk of a large-task batch with more outgrown tasks than local_compare_cached's list holds): the batch's tasks are beyond the staging
+// (windows of 2048 bases -- the .gli file `lra index` writes -- hold ~700 tuples a list): a lane per task walks its lists where they lie, every lane of the block (the 16-lanes-per-wave form exists for the LDS rows).  Its two searches start where the walk stands: lower_bound from ts
 // upwards and upper_bound from te downwards by doubling steps, then by halving inside the bracket -- the bound of a sorted range does not depend on the probes that
 // find it, and the two lists interleave, so it is one or two elements away (the literal halving of [ts, te) is ten scattered probes).
 template <int MODE, bool BIG = false>
@@ -627,7 +626,6 @@ __global__ void __launch_bounds__(STAGE_NT) local_compare(CmpArgs A, uint32_t* _
   const long maxFreq = A.maxFreq;
   uint32_t* oq = EMIT ? A.out_qi + A.out_off[x] : nullptr; uint32_t* ot = EMIT ? A.out_ti + A.out_off[x] : nullptr;
   uint16_t* cp = (MODE == 2 && !BIG) ? A.capped + x * (uint64_t)CMP_CAP : nullptr;
-  uint32_t* row = (MODE == 2 && BIG) ? rows + x * (uint64_t)CW_ROW : nullptr;
   uint32_t n = 0;
   auto emit = [&](long qi, long ti) {                                    // :87-97
     if (maxDiag != 0 && minDiag != 0) {
@@ -636,7 +634,6 @@ __global__ void __launch_bounds__(STAGE_NT) local_compare(CmpArgs A, uint32_t* _
     }
     if (EMIT) { oq[n] = (uint32_t)(A.q_lo[x] + qi); ot[n] = (uint32_t)(A.t_lo[x] + ti); }
     if (MODE == 2 && !BIG && n < (uint32_t)CMP_CAP) cp[n] = (uint16_t)((qi << 8) | ti);
-    if (MODE == 2 && BIG && n < (uint32_t)CW_ROW) row[n] = ((uint32_t)qi << 16) | (uint32_t)ti;
     n++;
   };
 #define Q(i) T_(q[(i)])
@@ -692,123 +689,16 @@ __global__ void __launch_bounds__(STAGE_NT) local_compare(CmpArgs A, uint32_t* _
 #undef TT
   if (!EMIT) A.counts[x] = n;
   if (MODE == 2 && !BIG && (n > (uint32_t)CMP_CAP || nq > 255 || nt > 255)) atomicAdd(A.nOver, 1);
-  if (MODE == 2 && BIG && n > (uint32_t)CW_ROW) atomicAdd(A.nOver, 1);
 }
 
 
-// ---- CompareLists for batches of LARGE tasks (two lists of ~700 tuples: the 2048-base windows of a .gli file): the walk is a chain of dependent reads, one lane per
-// task, and with the lists where they lie every step of a wave is 64 scattered lines (142 ms per batch: each line fetched for one word and gone again before the next).
-// Here a wave takes CW_TPB tasks at a time: all its lanes copy the tasks' lists into LDS (every byte read once, coalesced), then CW_TPB lanes walk them -- the walk's
-// round trips are LDS round trips.  One walk per task: its pairs go to a row of CW_ROW packed pairs (qi << 16 | ti), local_compact_rows lays them out by the scan of
-// the counts; a task with more pairs is walked again, alone with its likes, writing at its offset (MODE 1).
-constexpr int CW_TPB = 4, CW_SLOT = 1536;
-template <int MODE>
-__global__ void __launch_bounds__(64) local_compare_wave(CmpArgs A, uint32_t* __restrict__ rows) {
-  __shared__ uint32_t stage[CW_TPB * CW_SLOT];
-  const int lane = threadIdx.x;
-  for (uint64_t g0 = (uint64_t)blockIdx.x * CW_TPB; g0 < A.n_tasks; g0 += (uint64_t)gridDim.x * CW_TPB) {
-    const uint64_t xl = g0 + (uint64_t)(lane & (CW_TPB - 1));             // lane i (and i + CW_TPB, ..) looks at task g0 + i
-    bool live = xl < A.n_tasks;
-    if (MODE == 1 && live) live = A.counts[xl] > (uint32_t)CW_ROW;
-    const uint64_t myQa = live ? A.q_lo[xl] : 0, myTa = live ? A.t_lo[xl] : 0;
-    const int myQn = live ? (int)(A.q_hi[xl] - myQa) : 0, myTn = live ? (int)(A.t_hi[xl] - myTa) : 0;
-    const bool myFits = myQn + myTn <= CW_SLOT;
-#pragma unroll
-    for (int i = 0; i < CW_TPB; i++) {
-      const uint64_t qa = __shfl(myQa, i), ta = __shfl(myTa, i);
-      const int qn = __shfl(myQn, i), tn = __shfl(myTn, i);
-      if (!__shfl((int)myFits, i)) continue;
-      uint32_t* d = stage + i * CW_SLOT;
-      for (int p = lane; p < qn; p += 64) d[p] = A.q[qa + p];
-      for (int p = lane; p < tn; p += 64) d[qn + p] = A.t[ta + p];
-    }
-    __syncthreads();
-    if (lane < CW_TPB && live) {
-      const uint64_t x = xl;
-      const int nq = myQn, nt = myTn;
-      const uint32_t* q = myFits ? stage + lane * CW_SLOT : A.q + myQa;
-      const uint32_t* t = myFits ? stage + lane * CW_SLOT + nq : A.t + myTa;
-      const int64_t maxDiag = A.maxDiag ? A.maxDiag[x] : 0, minDiag = A.minDiag ? A.minDiag[x] : 0;
-      const bool banded = maxDiag != 0 && minDiag != 0;
-      const int maxFreq = (int)A.maxFreq;
-      uint32_t* oq = MODE == 1 ? A.out_qi + A.out_off[x] : nullptr; uint32_t* ot = MODE == 1 ? A.out_ti + A.out_off[x] : nullptr;
-      uint32_t* row = rows + x * (uint64_t)CW_ROW;
-      const uint32_t qb = (uint32_t)myQa, tb = (uint32_t)myTa;
-      uint32_t n = 0;
-      auto emit = [&](int qi, int ti) {                                    // :87-97
-        if (banded) {
-          const int64_t d = (int64_t)P_(t[ti]) - (int64_t)P_(q[qi]);
-          if (!(d <= maxDiag && d >= minDiag)) return;
-        }
-        if (MODE == 1) { oq[n] = qb + (uint32_t)qi; ot[n] = tb + (uint32_t)ti; }
-        else if (n < (uint32_t)CW_ROW) row[n] = ((uint32_t)qi << 16) | (uint32_t)ti;
-        n++;
-      };
-#define Q(i) T_(q[(i)])
-#define TT(i) T_(t[(i)])
-      if (nq != 0 && nt != 0) {
-        int qs = 0, qe = nq - 1, ts = 0, te = nt;
-        do {
-          { const uint32_t k0 = TT(ts); while (qs <= qe && Q(qs) < k0) qs++; }
-          if (qs >= qe) break;
-          const uint32_t kq = Q(qs);
-          const uint32_t startGap = (kq - TT(ts)) & TMASK;
-          { const uint32_t k1 = TT(te - 1); while (qe > qs && te > ts && Q(qe) > k1) qe--; }
-          const uint32_t ke = Q(qe);
-          const uint32_t endGap = (TT(te - 1) - ke) & TMASK;
-          if (startGap == 0 || startGap > endGap) {
-            const int tsOrig = ts;
-            int lo = ts, hi = te;                                              // lower_bound(T[ts, te), Q[qs]) from ts upwards (see local_compare<.., BIG>)
-            for (int s_ = 1; lo < hi; s_ <<= 1) { const int p = lo + s_ - 1; if (p >= hi) break; if (TT(p) < kq) lo = p + 1; else { hi = p; break; } }
-            while (lo < hi) { const int mid = lo + (hi - lo) / 2; if (TT(mid) < kq) lo = mid + 1; else hi = mid; }
-            ts = lo;
-            if (ts < te && TT(ts) == kq) {
-              int tsi = ts;
-              while (tsi != te && kq == TT(tsi)) tsi++;
-              const int qsStart = qs;
-              while (qs < qe && Q(qs + 1) == kq) qs++;
-              if (qs - qsStart < maxFreq)
-                for (int ti = ts; ti != tsi; ti++)
-                  for (int qi = qsStart; qi <= qs; qi++) emit(qi, ti);
-            }
-            { const uint32_t raw = TT(tsOrig); while (ts < te && TT(ts) == raw) ts++; }
-            while (qs < qe && Q(qs) == kq) qs++;
-          } else {
-            if (te != nt && TT(te - 1) == ke) {
-            } else {
-              int lo = ts, hi = te;                                            // upper_bound(T[ts, te), Q[qe]) from te downwards
-              for (int s_ = 1; lo < hi; s_ <<= 1) { const int p = hi - s_; if (p < lo) break; if (!(ke < TT(p))) { lo = p + 1; break; } else hi = p; }
-              while (lo < hi) { const int mid = lo + (hi - lo) / 2; if (!(ke < TT(mid))) lo = mid + 1; else hi = mid; }
-              te = lo;
-            }
-            const int teStart = te;
-            int tei = te;
-            while (tei > ts && TT(tei - 1) == ke) tei--;
-            if (tei < teStart && teStart > 0) {
-              const int qeStart = qe;
-              while (qe > qs && Q(qe - 1) == ke) qe--;
-              if (qeStart - qe < maxFreq)
-                for (int ti = tei; ti < teStart; ti++)
-                  for (int qi = qe; qi <= qeStart; qi++) emit(qi, ti);
-            }
-            te = tei;
-          }
-        } while (qs < qe && ts < te);
-      }
-#undef Q
-#undef TT
-      if (MODE != 1) { A.counts[x] = n; if (n > (uint32_t)CW_ROW) atomicAdd(A.nOver, 1); }
-    }
-    __syncthreads();
-  }
-}
 // the rows' pairs to their places: a wave per task
 __global__ void __launch_bounds__(256) local_compact_rows(CmpArgs A, const uint32_t* __restrict__ rows) {
   const uint64_t x = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (x >= A.n_tasks) return;
   const int l = threadIdx.x & 63;
   const uint32_t n = A.counts[x];
-  if (n > (uint32_t)CW_ROW) return;                                        // (walked again: local_compare_wave<1>)
+  if (n > (uint32_t)CW_ROW) return;                                        // (walked again: local_compare_cached<1> or local_compare<1, true>)
   const uint64_t o = A.out_off[x];
   const uint32_t ql = (uint32_t)A.q_lo[x], tl = (uint32_t)A.t_lo[x];
   const uint32_t* rw = rows + x * (uint64_t)CW_ROW;
@@ -999,9 +889,8 @@ extern "C" int lra_local_index_masked_batch(lra_ctx* ctx, int n_seqs, const char
     lra_time_begin(ctx, "local_sketch");
     hipLaunchKernelGGL(local_sketch, dim3(gw), dim3(64), (size_t)((WMAX / 16 + WMAX / 32 + w) * 64 * 4), st, n_win, seq, w_start, w_len, k, w, stride, raw, cnt);
     lra_time_end(ctx);
-    static const bool exactOnly = getenv("LRA_LOCAL_EXACT_SORT") != nullptr;   // every list through the exact sort (kept for comparison)
     lra_time_begin(ctx, "local_sort_filter");
-    if (exactOnly || max_freq < 2 || n_win >= (1ULL << 32)) hipLaunchKernelGGL(local_sort_filter, dim3(gw), dim3(STAGE_NT), 0, st, n_win, stride, raw, max_freq, cnt, (const uint32_t*)nullptr, (const uint64_t*)nullptr);
+    if (max_freq < 2 || n_win >= (1ULL << 32)) hipLaunchKernelGGL(local_sort_filter, dim3(gw), dim3(STAGE_NT), 0, st, n_win, stride, raw, max_freq, cnt, (const uint32_t*)nullptr, (const uint64_t*)nullptr);
     else {
       char* ws = (char*)lra_ensure(ctx, 96, sz(NW, 4) * 2 + sz(NW, 8) + 1024);
       if (!ws) return LRA_ERR_NOMEM;
@@ -1016,8 +905,7 @@ extern "C" int lra_local_index_masked_batch(lra_ctx* ctx, int n_seqs, const char
       }
       if (lra_exclusive_scan<uint32_t>(ctx, (long)n_win, flag, foff)) return LRA_ERR_HIP;
       hipLaunchKernelGGL(local_sel, dim3((unsigned)((n_win + 255) / 256)), dim3(256), 0, st, n_win, (const uint32_t*)flag, (const uint64_t*)foff, sel);
-      static const bool laneExact = getenv("LRA_LOCAL_EXACT_LANES") != nullptr;   // (the one-lane-per-list exact sort for the long lists as well: kept for comparison)
-      if (stride > (uint64_t)RANK_CAP && !laneExact) {
+      if (stride > (uint64_t)RANK_CAP) {
         const int capAll = (int)((stride + 63) & ~(uint64_t)63);
         const unsigned ge = (unsigned)std::min<uint64_t>(n_win, (uint64_t)ctx->num_cu * 32);
         int lo = 0;
@@ -1072,40 +960,28 @@ extern "C" int lra_local_compare_batch(lra_ctx* ctx, uint64_t n_tasks, const uin
   uint64_t* off = carve<uint64_t>(w, n_tasks + 1);
   A.out_off = off; A.out_qi = nullptr; A.out_ti = nullptr;
   const unsigned g = (unsigned)((n_tasks + 63) / 64);
-  static const bool twoPass = getenv("LRA_LOCAL_TWO_PASS") != nullptr;      // count, scan, walk again (kept for comparison; also what a batch with an oversized task falls back to)
   int* nOver = (int*)lra_ensure(ctx, 94, 64);
   if (!nOver) return LRA_ERR_NOMEM;
   A.nOver = nOver;
   LRA_HIP_CHECK(ctx, hipMemsetAsync(nOver, 0, 16, st));
   // the form of the walk: a batch whose tasks are mostly beyond the staged rows (the local index's windows are larger than 256 bases) is walked where its lists lie
-  static const int forceBig = getenv("LRA_LOCAL_BIG") ? atoi(getenv("LRA_LOCAL_BIG")) : -1;
   uint64_t h_big = 0;
   hipLaunchKernelGGL(k_big_tasks, dim3((unsigned)((n_tasks + 255) / 256)), dim3(256), 0, st, A, (unsigned long long*)(nOver + 2));
   if (d2h8(ctx, &h_big, (const uint64_t*)(nOver + 2))) return LRA_ERR_HIP;
-  const bool big = forceBig >= 0 ? forceBig != 0 : 2 * h_big > n_tasks;
+  const bool big = 2 * h_big > n_tasks;
   const unsigned gB = (unsigned)((n_tasks + STAGE_NT - 1) / STAGE_NT);
-  static const bool waveForm = getenv("LRA_LOCAL_BIG_WAVE") != nullptr;     // (the large tasks' lists staged in LDS, four walks per wave: measured slower -- 188 ms against 142 --, kept for comparison)
-  const bool waveBig = big && waveForm;
-  A.capped = (twoPass || big) ? nullptr : (uint16_t*)lra_ensure(ctx, 95, (size_t)n_tasks * CMP_CAP * 2 + 256);
-  if (!twoPass && !big && !A.capped) return LRA_ERR_NOMEM;
+  A.capped = big ? nullptr : (uint16_t*)lra_ensure(ctx, 95, (size_t)n_tasks * CMP_CAP * 2 + 256);
+  if (!big && !A.capped) return LRA_ERR_NOMEM;
   constexpr int OVER_CAP = 1 << 20;
   uint32_t* rows = big ? (uint32_t*)lra_ensure(ctx, 95, (size_t)n_tasks * CW_ROW * 4 + (size_t)OVER_CAP * 4 + 512) : nullptr;
   if (big && !rows) return LRA_ERR_NOMEM;
   uint32_t* overList = big ? rows + (((size_t)n_tasks * CW_ROW + 63) & ~(size_t)63) : nullptr;
-  const unsigned gW = (unsigned)std::min<uint64_t>((n_tasks + CW_TPB - 1) / CW_TPB, (uint64_t)ctx->num_cu * 24);
   // The lane-per-task walk of large tasks has four cursors a lane, a cache line each: with every wave slot of a CU taken (2048 walks) a line is fetched for one word and is
   // gone before the cursor needs its next word -- the launch moves 40 x its lists.  Dynamic LDS nobody uses keeps it to two blocks (8 waves, 512 walks) per CU, whose lines
   // stay in the CU's share of L2: 77.9 ms per batch -> 47.6 (four blocks: 55.8; one: 61.5).
-  static const bool cachedBig = !(getenv("LRA_LOCAL_BIG_CACHED") && getenv("LRA_LOCAL_BIG_CACHED")[0] == '0');   // (0: the lists read where they lie)
-  static const size_t bigPad = getenv("LRA_LOCAL_BIG_PAD") ? (size_t)atol(getenv("LRA_LOCAL_BIG_PAD")) : 64000;
+  constexpr size_t bigPad = 64000;
   lra_time_begin(ctx, "local_compare");
-  if (waveBig) hipLaunchKernelGGL(local_compare_wave<2>, dim3(gW), dim3(64), 0, st, A, rows);
-  else if (big && cachedBig) hipLaunchKernelGGL(local_compare_cached<2>, dim3((unsigned)((n_tasks + 63) / 64)), dim3(64), 0, st, A, rows, (const uint32_t*)overList, OVER_CAP);
-  else if (big) {
-    if (bigPad > 65536) LRA_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)local_compare<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bigPad));
-    hipLaunchKernelGGL((local_compare<2, true>), dim3(gB), dim3(STAGE_NT), bigPad, st, A, rows);
-  }
-  else if (twoPass) hipLaunchKernelGGL(local_compare<0>, dim3(g), dim3(STAGE_NT), 0, st, A);
+  if (big) hipLaunchKernelGGL(local_compare_cached<2>, dim3((unsigned)((n_tasks + 63) / 64)), dim3(64), 0, st, A, rows, (const uint32_t*)overList, OVER_CAP);
   else hipLaunchKernelGGL(local_compare<2>, dim3(g), dim3(STAGE_NT), 0, st, A);
   lra_time_end(ctx);
   if (lra_exclusive_scan<uint32_t>(ctx, (long)n_tasks, A.counts, off)) return LRA_ERR_HIP;
@@ -1122,16 +998,12 @@ extern "C" int lra_local_compare_batch(lra_ctx* ctx, uint64_t n_tasks, const uin
   if (!r) return LRA_ERR_NOMEM;
   A.out_qi = carve<uint32_t>(r, total + 1); A.out_ti = carve<uint32_t>(r, total + 1);
   lra_time_begin(ctx, "local_compare");
-  if (waveBig) {
+  if (big) {
     hipLaunchKernelGGL(local_compact_rows, dim3((unsigned)((n_tasks + 3) / 4)), dim3(256), 0, st, A, (const uint32_t*)rows);
-    if (h_over > 0) hipLaunchKernelGGL(local_compare_wave<1>, dim3(gW), dim3(64), 0, st, A, rows);
-  } else if (big) {
-    hipLaunchKernelGGL(local_compact_rows, dim3((unsigned)((n_tasks + 3) / 4)), dim3(256), 0, st, A, (const uint32_t*)rows);
-    if (h_over > 0 && cachedBig && h_over <= OVER_CAP) hipLaunchKernelGGL(local_compare_cached<1>, dim3((unsigned)((h_over + 63) / 64)), dim3(64), 0, st, A, rows, (const uint32_t*)overList, h_over);
-    else if (h_over > 0 && cachedBig) { hipLaunchKernelGGL((local_compare<1, true>), dim3(gB), dim3(STAGE_NT), std::min<size_t>(bigPad, 65536), st, A, rows); }   // (more such tasks than the list holds: every task looked at)
-    else if (h_over > 0) hipLaunchKernelGGL((local_compare<1, true>), dim3(gB), dim3(STAGE_NT), std::min<size_t>(bigPad, 65536), st, A, rows);
+    if (h_over > 0 && h_over <= OVER_CAP) hipLaunchKernelGGL(local_compare_cached<1>, dim3((unsigned)((h_over + 63) / 64)), dim3(64), 0, st, A, rows, (const uint32_t*)overList, h_over);
+    else if (h_over > 0) hipLaunchKernelGGL((local_compare<1, true>), dim3(gB), dim3(STAGE_NT), bigPad, st, A, rows);   // (more such tasks than the list holds: every task looked at)
   }
-  else if (twoPass || h_over > 0) hipLaunchKernelGGL(local_compare<1>, dim3(g), dim3(STAGE_NT), 0, st, A);
+  else if (h_over > 0) hipLaunchKernelGGL(local_compare<1>, dim3(g), dim3(STAGE_NT), 0, st, A);
   else hipLaunchKernelGGL(local_compact_pairs, dim3((unsigned)((n_tasks + 3) / 4)), dim3(64), 0, st, A);
   lra_time_end(ctx);
   LRA_HIP_CHECK(ctx, hipGetLastError());

@@ -949,8 +949,7 @@ static int lowacc_batch_impl(lra_ctx* ctx, int n_reads, const char* d_seq, const
   m->last_text.clear(); m->last_sig = lra_map_sig{};         // a sizing call of lra_map_records for an earlier batch is void now
   ctx->pipelined = false;                                    // (the one call: nothing runs beside it)
   if (n_reads == 0) return LRA_OK;
-  uint32_t threshold = o->defer_matches > 0 ? (uint32_t)o->defer_matches : 0;
-  if (const char* e = getenv("LRA_DEFER_MATCHES")) threshold = (uint32_t)std::max(0, atoi(e));
+  const uint32_t threshold = o->defer_matches > 0 ? (uint32_t)o->defer_matches : 0;
   const std::function<int()> none;
   if (!threshold) return lowacc_core(ctx, n_reads, d_seq, d_read_off, total_bases, o, out, 0, nullptr, nullptr, nullptr, none);
   { int rcc = ensure_child(ctx, true); if (rcc) return rcc; }
@@ -965,7 +964,6 @@ static int lowacc_batch_impl(lra_ctx* ctx, int n_reads, const char* d_seq, const
   double t_split = 0, t_second = 0;
   auto start_second = [&]() -> int {
     t_split = wall();
-    if (getenv("LRA_DEFER_DROP")) { picked.clear(); return LRA_OK; }      // (experiment: the first pass without the deferred reads, nothing else running)
     second = std::thread([&, c = ctx->child]() {
       rc2 = lowacc_tail(c, in2, o, &o2);
       t_second = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -1025,7 +1023,7 @@ static int front_checks(lra_ctx* ctx, int n_reads, const lra_map_opts* o) {
   if (m->gli_window != o->localIndexWindow || m->gli_k != o->localK || m->gli_w != o->localW)
     return lra_set_err(ctx, LRA_ERR_INVALID, "the genome's local index has k = %d, w = %d, windows of %d bases; the options say %d, %d, %d (lra_map_opts_apply_local_index: glIndex.Read overrides them)",
                        m->gli_k, m->gli_w, m->gli_window, o->localK, o->localW, o->localIndexWindow);
-  if (o->defer_matches > 0 || o->defer_seed_matches > 0 || getenv("LRA_DEFER_MATCHES")) return lra_set_err(ctx, LRA_ERR_INVALID, "two-stage batches do not combine with defer_matches / defer_seed_matches");
+  if (o->defer_matches > 0 || o->defer_seed_matches > 0) return lra_set_err(ctx, LRA_ERR_INVALID, "two-stage batches do not combine with defer_matches / defer_seed_matches");
   return lra_map_check_shared(ctx);
 }
 // A front half that fails still hands over a batch -- an error batch: the back call that takes it returns the front half's code and holds nothing, so the

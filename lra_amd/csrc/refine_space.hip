@@ -308,7 +308,9 @@ __global__ void __launch_bounds__(64) rs_compact(int nLists, const uint64_t* __r
 // searches and run scans of the walk never wait on HBM.  The walk runs once: every emission of the reference is a rectangle (a run of
 // equal target keys x a run of equal query keys, target-major); the walk records the rectangle and counts its cells that pass the
 // diagonal band with all lanes, rs_emit then writes the pairs of all rectangles in the same order.
-constexpr int CMP_LDS_KEYS = 7168;                                        // 56 KB of keys per workgroup
+// Keys staged per wave: 12 KB of LDS (measured, headline batch, lists of 2-4 k keys per gap: 7168 keys of LDS per wave 54 ms, 3072: 50, 1536: 49, 512: 52 -- the
+// waves per CU matter more than where the keys sit).
+constexpr int CMP_LDS_KEYS = 1536;
 struct RsBand { long long minDiag, maxDiag; };
 __device__ __forceinline__ RsBand rs_band(const RsArgs& a, uint32_t i) {
   const long long diag2 = (long long)a.t_span[i] - (long long)(uint32_t)a.q_len[i];
@@ -561,8 +563,7 @@ static int refine_space_impl(lra_ctx* ctx, int n, const char* d_qseq, const uint
     hipLaunchKernelGGL(rs_compact, dim3(2 * nLarge), dim3(64), 0, st, 2 * nLarge, capOff, loff, rawKey, rawPos, a.lkey, a.lpos);
     { int rc = lra_sort_minimizers_batch(ctx, 2 * nLarge, loff, a.lkey, a.lpos); if (rc) return rc; }   // sort(EndGenomeTup), sort(EndReadTup)  :306,:308
     lra_time_begin(ctx, "rs_long_compare");
-    static const int ldsKeys = getenv("LRA_RS_LDS_KEYS") ? std::max(0, std::min(CMP_LDS_KEYS, atoi(getenv("LRA_RS_LDS_KEYS")))) : 1536;   // (measured, headline batch, lists of 2-4 k keys per gap: 7168 keys of LDS per wave 54 ms, 3072: 50, 1536: 49, 512: 52 -- the waves per CU matter more than where the keys sit)
-    hipLaunchKernelGGL(rs_compare, dim3(nLarge), dim3(64), (size_t)ldsKeys * 8, st, a, nLarge, ldsKeys);
+    hipLaunchKernelGGL(rs_compare, dim3(nLarge), dim3(64), (size_t)CMP_LDS_KEYS * 8, st, a, nLarge, CMP_LDS_KEYS);
     lra_time_end(ctx);
   }
   // ---- pairs

@@ -1993,12 +1993,11 @@ inline size_t sz(size_t n, size_t elem) { return (n * elem + 255) / 256 * 256; }
 // The one-wave-per-read builds of a launch: reads [from, to) of `order` (largest first).  Those of at most 512 points keep their element arrays in LDS
 // (three sizes of LDS request, so that small reads do not pay for large ones' occupancy); the rest work from the scratch arena.
 // from how many points on a read gets a workgroup (the workgroup kernels' per-point latency is half the wave kernel's, at four times its wave slots): a launch is as long
-// as its largest reads' chains.  LRA_SDP_BIG_POINTS overrides all, LRA_SDP_BIG_POINTS_A the first sparse DP's (mode 0) alone
+// as its largest reads' chains.  LRA_SDP_BIG_POINTS overrides it
 static long sdp_big_points(const lra_ctx* ctx, int mode) {
   if (const char* e = getenv("LRA_SDP_BIG_POINTS")) return atol(e);
   if (ctx->sdp_inner) return 1500;
-  if (mode == 0) { if (const char* e = getenv("LRA_SDP_BIG_POINTS_A")) return atol(e); return 2500; }   // (its largest reads have ~5000 points: the top few hundred as workgroups, 93 -> 83 ms)
-  if (const char* e = getenv("LRA_SDP_BIG_POINTS_2")) return atol(e);
+  if (mode == 0) return 2500;   // (its largest reads have ~5000 points: the top few hundred as workgroups, 93 -> 83 ms)
   // Two-stage batches: the other half of another batch fills what a long tail leaves idle, and a wave per read costs a third of the device time per point that a
   // workgroup per read does -- so only the reads that would make the wave launch far longer than everything beside it stay workgroup jobs (measured, two-stage step:
   // 6000: 980 ms, 9000: 954, 12000: 943, 14000: 933, 16000+: up again; each with at most one job per CU, see maxBig)
@@ -2006,14 +2005,13 @@ static long sdp_big_points(const lra_ctx* ctx, int mode) {
 }
 template <bool EMIT>
 static void launch_small_builds(lra_ctx* ctx, const BuildArgs& ba, const uint32_t* d_order, const std::vector<uint32_t>& h_order, const uint64_t* h_pt, int from, int to) {
-  static const bool noLds = getenv("LRA_SDP_BUILD_NOLDS") != nullptr;
   hipStream_t st = ctx->stream;
   auto pts = [&](int i) { return (long)(h_pt[h_order[i] + 1] - h_pt[h_order[i]]); };
   int at = from;
   // (measured: at 28 KB -- up to 1024 points -- five waves per CU are slower from LDS than 32 from the arena; up to 768 points is a wash)
   const long caps[3] = {512, 256, 128};
   int cut[4];                                                            // [from, cut0): arena;  [cut0, cut1): <= 512;  [cut1, cut2): <= 256;  [cut2, to): <= 128
-  for (int c = 0; c < 3; c++) { while (at < to && (noLds || pts(at) > caps[c])) at++; cut[c] = at; }
+  for (int c = 0; c < 3; c++) { while (at < to && pts(at) > caps[c]) at++; cut[c] = at; }
   cut[3] = to;
   if (cut[0] > from) {                                                   // arena: 16-bit indices below 16384 points (2 x node index + side must fit)
     int mid = from;
@@ -2023,12 +2021,9 @@ static void launch_small_builds(lra_ctx* ctx, const BuildArgs& ba, const uint32_
       BuildArgs bb = ba; bb.order = d_order + mid;
       // waves per SIMD the register budget is set for: 8; beside another batch's half (two-stage batches) 6 -- fewer, fatter waves leave the other half's launches room
       // (two-stage step 952 -> 937 ms; in the one call 8 is the faster one)
-      static const int occEnv = getenv("LRA_SDP_BUILD_OCC") ? atoi(getenv("LRA_SDP_BUILD_OCC")) : 0;
-      const int occ = occEnv ? occEnv : ctx->pipelined ? 6 : 8;
-      if (bb.stat) { if (occ == 6) hipLaunchKernelGGL((sdp_build<EMIT, 1, 2, 6, true>), dim3(cut[0] - mid), dim3(64), 0, st, bb); else hipLaunchKernelGGL((sdp_build<EMIT, 1, 2, 8, true>), dim3(cut[0] - mid), dim3(64), 0, st, bb); }
-      else if (occ == 4) hipLaunchKernelGGL((sdp_build<EMIT, 1, 2, 4>), dim3(cut[0] - mid), dim3(64), 0, st, bb);
-      else if (occ == 5) hipLaunchKernelGGL((sdp_build<EMIT, 1, 2, 5>), dim3(cut[0] - mid), dim3(64), 0, st, bb);
-      else if (occ == 6) hipLaunchKernelGGL((sdp_build<EMIT, 1, 2, 6>), dim3(cut[0] - mid), dim3(64), 0, st, bb);
+      const bool occ6 = ctx->pipelined;
+      if (bb.stat) { if (occ6) hipLaunchKernelGGL((sdp_build<EMIT, 1, 2, 6, true>), dim3(cut[0] - mid), dim3(64), 0, st, bb); else hipLaunchKernelGGL((sdp_build<EMIT, 1, 2, 8, true>), dim3(cut[0] - mid), dim3(64), 0, st, bb); }
+      else if (occ6) hipLaunchKernelGGL((sdp_build<EMIT, 1, 2, 6>), dim3(cut[0] - mid), dim3(64), 0, st, bb);
       else hipLaunchKernelGGL((sdp_build<EMIT, 1, 2>), dim3(cut[0] - mid), dim3(64), 0, st, bb);
     }
   }
@@ -2213,8 +2208,7 @@ int sdp_run(lra_ctx* ctx, int n_reads, const uint64_t* d_cluster_off, const uint
   // ---- chunks of reads: decompositions, ProcessPoint, trace
   // one chunk if it fits: the kernels' duration is set by the longest read once the chip is no longer full, so few large launches
   // beat many small ones (32768 reads, sdp_process: 4 chunks 420 ms, 2 chunks 255 ms, 1 chunk 187 ms)
-  uint64_t chunkPts = 96ull << 20;            // ~75 GB of arenas per chunk: a 32768-read batch of 30 kb reads (80 M points) is one chunk
-  if (const char* e = getenv("LRA_SDP_CHUNK_MPOINTS")) { const long v = atol(e); if (v > 0) chunkPts = (uint64_t)v << 20; }   // tuning knob
+  constexpr uint64_t chunkPts = 96ull << 20;  // ~75 GB of arenas per chunk: a 32768-read batch of 30 kb reads (80 M points) is one chunk
   uint64_t totalEntries = 0;
   for (int r0 = 0; r0 < n_reads;) {
     int r1 = r0 + 1;
@@ -2319,11 +2313,9 @@ int sdp_run(lra_ctx* ctx, int n_reads, const uint64_t* d_cluster_off, const uint
         const long big_pts = sdp_big_points(ctx, opts->mode);   // (tests lower it to run small reads through the workgroup kernels)
         // ... but no more of them than the device runs side by side (a workgroup holds 16 wave slots for a per-point latency a third of the wave kernel's, at 3.5 times its
         // wave-time per point): beyond that the large reads queue up behind each other, and the ones further down the order are better off as one wave each
-        static const int maxBigEnv = getenv("LRA_SDP_MAX_BIG") ? std::max(0, atoi(getenv("LRA_SDP_MAX_BIG"))) : -1;
         // (two-stage batches: one round of workgroup jobs -- one per CU, all resident at once; 192: 1026 ms, 256: 933, 320: 955)
-        const int maxBigAll = maxBigEnv >= 0 ? maxBigEnv : ctx->pipelined ? ctx->num_cu : (1 << 30);
-        static const int maxBigA = getenv("LRA_SDP_MAX_BIG_A") ? std::max(0, atoi(getenv("LRA_SDP_MAX_BIG_A"))) : 512;
-        const int maxBig = (opts->mode == 0 && !ctx->sdp_inner) ? std::min(maxBigAll, maxBigA) : maxBigAll;
+        const int maxBigAll = ctx->pipelined ? ctx->num_cu : (1 << 30);
+        const int maxBig = (opts->mode == 0 && !ctx->sdp_inner) ? std::min(maxBigAll, 512) : maxBigAll;
         while (nbig < nsub && nbig < maxBig && (long)(h_pt[r0 + ordAtt[nbig] + 1] - h_pt[r0 + ordAtt[nbig]]) >= big_pts) nbig++;
       }
       const bool forked = nbig > 0 && nsub > nbig;

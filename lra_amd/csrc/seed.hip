@@ -1149,14 +1149,14 @@ static int launch_sort(lra_ctx* ctx, int n_reads, const uint64_t* mm_off, uint64
   lra_time_begin(ctx, ctx->sort_tag);
   // Lists of at most capS tuples first, 256 threads and ~36 KB of LDS each: four of them fit a CU where the 1024-thread / 156 KB launch holds one, and a short list's sort
   // is a chain of barriers either way (the sparse DP's value lists: hundreds of tuples, tens of thousands of lists).  Then the rest, as before.
-  static const int capS = getenv("LRA_SORT_SMALL_CAP") ? std::max(0, std::min(cap, atoi(getenv("LRA_SORT_SMALL_CAP")))) : 2048;
-  if (capS >= 64 && ctx->sort_short) {
+  constexpr int capS = 2048;
+  if (ctx->sort_short) {
     const int maxsegS = (capS / 16 + 8 + 1) & ~1;
     const size_t ldsS = (size_t)capS * 16 + (size_t)maxsegS * 20 + 8 + (size_t)(capS / 32 + 2) * 4;
     const int gridS = std::min(n_reads, std::min(ctx->num_cu * 4, (int)(((size_t)grid * (cap + 64)) / (size_t)(capS + 64))));
     hipLaunchKernelGGL(sort_wg_kernel<0>, dim3(gridS), dim3(256), ldsS, st, n_reads, mm_off, mm_key, mm_pos, (void*)tscr, capS, (int*)nullptr, only, (char*)nullptr, (int*)nullptr, 0);
   }
-  hipLaunchKernelGGL(sort_wg_kernel<0>, dim3(grid), dim3(SORT_NT), lds, st, n_reads, mm_off, mm_key, mm_pos, (void*)tscr, cap, flags, only, (char*)nullptr, stat, (capS >= 64 && ctx->sort_short) ? capS + 1 : 0);
+  hipLaunchKernelGGL(sort_wg_kernel<0>, dim3(grid), dim3(SORT_NT), lds, st, n_reads, mm_off, mm_key, mm_pos, (void*)tscr, cap, flags, only, (char*)nullptr, stat, ctx->sort_short ? capS + 1 : 0);
   lra_time_end(ctx);
   // the launch for lists beyond the LDS capacity (1024-thread workgroups again, 64 of them, each waiting for room beside another batch's half) only when the LDS launch left
   // a list behind: it says how many, and the round trip that asks takes the place of the one behind the large-list launch
@@ -1310,8 +1310,7 @@ extern "C" int lra_seed_batch(lra_ctx* ctx, int n_reads, const char* d_seq, cons
   lra_time_end(ctx);
   // ---- a2: a read outside the repeats has no k-mer twice among its minimizers, and a list without equal keys has one sorted order only: the radix path takes nearly
   // all reads, the exact (libstdc++-identical) sort the ones with a repeated k-mer.  The temporaries are a3's outputs, not written yet.
-  static const bool exactOnly = getenv("LRA_SEED_EXACT_SORT") != nullptr;
-  if (exactOnly || total_mm == 0) { int rc = launch_sort(ctx, n_reads, s->mm_off, s->mm_key, s->mm_pos); if (rc) return rc; }
+  if (total_mm == 0) { int rc = launch_sort(ctx, n_reads, s->mm_off, s->mm_key, s->mm_pos); if (rc) return rc; }
   else { int rc = lra_sort_mostly_unique_batch(ctx, n_reads, s->mm_off, total_mm, s->mm_key, s->mm_pos, s->tk_lb, s->lb, std::min(2 * k, 63)); if (rc) return rc; }
   // ---- a3
   if (total_mm) {
@@ -1332,8 +1331,7 @@ extern "C" int lra_seed_batch(lra_ctx* ctx, int n_reads, const char* d_seq, cons
   }
   // reads per wave of the walk (a lane per read): 32 for a full batch (1024 waves; more waves cost more rounds than the divergence of 32 walks costs), fewer for a small one --
   // a batch of 256 contigs as 256 one-lane waves walks 9 % faster than as 8 waves of 32 diverging lanes (-CONTIG: 3787 -> 3461 ms per batch)
-  static const int lanesEnv = getenv("LRA_COMPARE_LANES") ? std::max(1, std::min(64, atoi(getenv("LRA_COMPARE_LANES")))) : 0;
-  const int FLAT_LANES = lanesEnv ? lanesEnv : std::max(1, std::min(32, n_reads / 1024));
+  const int FLAT_LANES = std::max(1, std::min(32, n_reads / 1024));
   lra_time_begin(ctx, "compare");
   hipLaunchKernelGGL(compare_kernel, dim3((n_reads + FLAT_LANES - 1) / FLAT_LANES), dim3(64), 0, st, FLAT_LANES, n_reads, s->mm_off, s->mm_key, s->lb, s->ub, s->tk_lb, s->tk_lbm1, s->tk_ubm1, s->idx_key,
                      (long)s->n_idx, (long)max_freq, s->cap_off, s->tmp_qi, s->tmp_ti, s->counts64);

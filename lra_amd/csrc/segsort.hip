@@ -7,7 +7,7 @@
 // same least-significant-digit radix sort -- stable, only the bits [begin_bit, end_bit) compared --, four size classes so that a short segment does not pay for a long one's
 // padding), stored once: 21-27 G pairs/s (tools/micro/segsort.hip: identical output on 32768 segments of 640 / 1760 / 3000 / 6000 pairs).  The segments outside that range --
 // the many tiny ones (a13's jobs: rocprim's warp sorts serve them well) and the rare ones beyond a workgroup's LDS -- stay with rocprim, which is called on a copy of the
-// offsets in which every other segment is empty.  LRA_SEGSORT=0: rocprim for everything (comparisons).
+// offsets in which every other segment is empty.
 #include "common.h"
 #include <cstring>
 #include <cstdlib>
@@ -58,7 +58,6 @@ __global__ void __launch_bounds__(NT) k_block_sort(unsigned nseg, const uint64_t
 // rejects in-place calls).
 hipError_t lra_segsort_pairs(lra_ctx* ctx, void* temp, size_t& temp_bytes, const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout, unsigned int total,
                              unsigned int nseg, const uint64_t* b, const uint64_t* e, int begin_bit, int end_bit, hipStream_t st) {
-  static const bool off = getenv("LRA_SEGSORT") && getenv("LRA_SEGSORT")[0] == '0';
   size_t rb = 0;
   hipError_t rc = rocprim::segmented_radix_sort_pairs(nullptr, rb, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, total, nseg, (uint64_t*)nullptr,
                                                       (uint64_t*)nullptr, begin_bit, end_bit, st);
@@ -66,7 +65,7 @@ hipError_t lra_segsort_pairs(lra_ctx* ctx, void* temp, size_t& temp_bytes, const
   const size_t rbA = (rb + 255) & ~(size_t)255, extra = 2 * ((size_t)nseg + 1) * 8 + 256 + 64;
   if (!temp) { temp_bytes = rbA + extra; return hipSuccess; }
   if (temp_bytes < rbA + extra) return hipErrorInvalidValue;
-  if (off || nseg == 0 || total == 0)
+  if (nseg == 0 || total == 0)
     return rocprim::segmented_radix_sort_pairs(temp, rb, kin, kout, vin, vout, total, nseg, b, e, begin_bit, end_bit, st);
   uint64_t* mb = (uint64_t*)((char*)temp + rbA); uint64_t* me = mb + nseg + 1;
   unsigned* cc = (unsigned*)(me + nseg + 1);

@@ -40,8 +40,7 @@ struct StatArgs {
 // term, :462/:491) has been added the float `value` is an exact integer, so those contributions can
 // be summed in any order (ival) -- whole 64-column chunks at a time.  From the first long gap on
 // every run is applied to the float in the reference's order.
-// GW lanes per alignment (64 / GW alignments per wave): a noisy read's blocks are ~16 columns, so a whole wave per alignment leaves three quarters of its lanes idle
-// on almost every block, and the kernel's time is (alignments / resident groups) x one alignment's chain of ~1800 dependent block steps.
+// GW lanes per alignment (64 / GW alignments per wave); launched with GW = 64 for the alignments stats_starts leaves to it (normally none).
 template <int GW>
 __global__ void __launch_bounds__(64) stats_kernel(StatArgs A) {
   const int lane = threadIdx.x & (GW - 1), gbase = threadIdx.x - lane;      // lane: inside the alignment's group
@@ -425,8 +424,6 @@ __global__ void stats_capacity(int n_aln, const int32_t* blocks, const uint64_t*
   cap[a] = (uint64_t)(max(qs, 0L) + max(ts, 0L) + 2);
 }
 
-__global__ void stats_fill(int n, int32_t* p, int v) { const int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) p[i] = v; }
-
 __global__ void __launch_bounds__(64) stats_compact(int n_aln, const uint64_t* cap_off, const uint64_t* run_off, const uint32_t* src, uint32_t* dst) {
   for (int a = blockIdx.x; a < n_aln; a += gridDim.x) {
     const uint64_t s = cap_off[a], d = run_off[a], n = run_off[a + 1] - d;
@@ -472,20 +469,10 @@ extern "C" int lra_calculate_statistics_batch(lra_ctx* ctx, int n_aln, const int
   if (!tmp) return LRA_ERR_NOMEM;
   A.runs = tmp;
   const int grid = n_aln < ctx->num_cu * 32 ? n_aln : ctx->num_cu * 32;
-  static const int statGw = getenv("LRA_STATS_GW") ? atoi(getenv("LRA_STATS_GW")) : 16;
-  static const bool serialOnly = getenv("LRA_STATS_SERIAL") != nullptr;     // the one-alignment-after-the-other walk for everything (kept for comparison)
-  A.only = nullptr;
   lra_time_begin(ctx, "stats");
-  if (serialOnly) {
-    if (statGw == 64) hipLaunchKernelGGL(stats_kernel<64>, dim3(grid), dim3(64), 0, st, A);
-    else if (statGw == 32) hipLaunchKernelGGL(stats_kernel<32>, dim3(std::min((n_aln + 1) / 2, ctx->num_cu * 32)), dim3(64), 0, st, A);
-    else hipLaunchKernelGGL(stats_kernel<16>, dim3(std::min((n_aln + 3) / 4, ctx->num_cu * 32)), dim3(64), 0, st, A);
-    hipLaunchKernelGGL(stats_fill, dim3((n_aln + 255) / 256), dim3(256), 0, st, n_aln, A.serial, 1);
-  } else {
-    hipLaunchKernelGGL(stats_starts, dim3(n_aln), dim3(64), 0, st, A);
-    A.only = A.serial;
-    hipLaunchKernelGGL(stats_kernel<64>, dim3(grid), dim3(64), 0, st, A);   // the alignments with overlapping / empty blocks (normally none)
-  }
+  hipLaunchKernelGGL(stats_starts, dim3(n_aln), dim3(64), 0, st, A);
+  A.only = A.serial;
+  hipLaunchKernelGGL(stats_kernel<64>, dim3(grid), dim3(64), 0, st, A);   // the alignments with overlapping / empty blocks (normally none)
   lra_time_end(ctx);
   if (getenv("LRA_STATS_DBG")) {
     std::vector<int32_t> h(nA); std::vector<uint64_t> bo(nA + 1);
