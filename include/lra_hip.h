@@ -74,9 +74,17 @@ int lra_ctx_release_buffers(lra_ctx* ctx, uint64_t* bytes);
 /* stream = a hipStream_t (NULL = the default stream).  All later calls launch on it. */
 int lra_ctx_set_stream(lra_ctx* ctx, void* stream);
 const char* lra_ctx_last_error(lra_ctx* ctx);
+/* lra align -a, "Query all positions in a read, not just minimizers" (lra.cpp:182-184, opts.storeAll): with the switch on, the drivers
+ * (lra_map_reads_lowacc_batch, lra_map_reads_lowacc_front, lra_map_reads_highacc_batch, lra_map_reads_host) sketch each read with w = 1 -- MapRead.h:172-176
+ * copies the options, sets allOpts.globalW = 1 on the copy and calls StoreMinimizers(read, globalK, 1) -- and keep opts.globalW for everything after the sketch
+ * (the high-accuracy RefineBtwnClusters_chain's W, Map_highacc.h:466-468).  A context setting rather than a field of lra_map_opts, which callers allocate and
+ * the presets write in full.  Off when the context is made.  on must be 0 or 1; a NULL ctx or another value is LRA_ERR_INVALID.
+ * lra_ctx_store_all returns the switch (0 / 1), or LRA_ERR_INVALID for a NULL ctx.                                                                                  */
+int lra_ctx_set_store_all(lra_ctx* ctx, int on);
+int lra_ctx_store_all(lra_ctx* ctx);
 /* ABI version of the loaded library (tests check it against this header). */
 int lra_abi_version(void);
-#define LRA_ABI_VERSION 9   /* 9: lra_ctx_release_buffers; 8: lra_map_opts_apply_local_index, lra_ctx_local_index_params, lra_ctx_load_local_index (the .gli file's k / w / window override the options', as glIndex.Read does); 7: lra_sort_pairs_batch;  2: lra_map_opts.defer_matches, lra_map_counters.n_deferred_reads; 3: lra_map_opts.flagged_unaligned, lra_map_counters.n_flagged_reads, lra_map_host_flagged; 4: lra_reads_last_error, a corrupt FASTQ record is LRA_ERR_INVALID; lra_map_opts.defer_seed_matches; 5: lra_seed_prefetch, lra_ctx_adopt_seed, lra_map_reads_lowacc_front / _back, lra_map_back_release; 6: a failed front half hands over an error batch (one back call per front call), separate n_handed_back_reads counter, lra_map_host_trim */
+#define LRA_ABI_VERSION 9   /* 9: lra_ctx_release_buffers; later, additively (no struct or signature changed): lra_ctx_set_store_all, lra_ctx_store_all; 8: lra_map_opts_apply_local_index, lra_ctx_local_index_params, lra_ctx_load_local_index (the .gli file's k / w / window override the options', as glIndex.Read does); 7: lra_sort_pairs_batch;  2: lra_map_opts.defer_matches, lra_map_counters.n_deferred_reads; 3: lra_map_opts.flagged_unaligned, lra_map_counters.n_flagged_reads, lra_map_host_flagged; 4: lra_reads_last_error, a corrupt FASTQ record is LRA_ERR_INVALID; lra_map_opts.defer_seed_matches; 5: lra_seed_prefetch, lra_ctx_adopt_seed, lra_map_reads_lowacc_front / _back, lra_map_back_release; 6: a failed front half hands over an error batch (one back call per front call), separate n_handed_back_reads counter, lra_map_host_trim */
 
 /* Convenience for hosts without their own HIP binding: synchronous device->host copy on the
  * context's stream (a C++ host would call hipMemcpy itself).                                */
@@ -144,8 +152,9 @@ int lra_read_gli(const char* path, int* k, int* w, int* window, uint64_t* n_wind
  *   CompareLists<GenomeTuple,Tuple>(readmm, genomemm, allMatches, opts, true)     CompareLists.h:9
  *   SeparateMatchesByStrand(read, genome, k, allMatches, forMatches, revMatches)  MapRead.h:109
  * Input: n_reads upper-case ASCII reads concatenated in d_seq, read r = bytes
- * [d_read_off[r], d_read_off[r+1]).  k = opts.globalK, w = opts.globalW,
- * max_freq = opts.globalMaxFreq.
+ * [d_read_off[r], d_read_off[r+1]).  k = opts.globalK, w = opts.globalW (1 for lra align -a,
+ * lra_ctx_set_store_all: every position whose k-mer is free of non-ACGT bytes, position-parallel
+ * over the batch), max_freq = opts.globalMaxFreq.
  * Output (device arrays owned by the context, valid until the next lra_seed_batch call on
  * it; CSR by read):
  *   d_mm_*     readmm after the sort (t with the strand flag in bit 63, pos)
@@ -181,8 +190,8 @@ int lra_seed_batch(lra_ctx* ctx, int n_reads, const char* d_seq, const uint64_t*
  * device has room, and a1-a4 of the batch after it fit there.  `side` is a second context of the same device that shares the mapping context's reference data
  * (lra_ctx_share_reference), driven by a host thread of its own on its own (low-priority) stream: lra_seed_prefetch is lra_seed_batch on it, synchronous, the result
  * kept by `side`.  lra_ctx_adopt_seed(ctx, side) then hands that result to the mapping context (the two contexts exchange their seed-stage batch buffers; no copy);
- * the next lra_map_reads_lowacc_batch / lra_map_reads_highacc_batch on `ctx` with the same n_reads, d_seq, d_read_off and the same globalK / globalW / globalMaxFreq
- * starts from it instead of seeding -- with any other arguments it seeds as usual and the adopted result is dropped.  Same alignments either way: scheduling only.
+ * the next lra_map_reads_lowacc_batch / lra_map_reads_highacc_batch on `ctx` with the same n_reads, d_seq, d_read_off and the same globalK / globalMaxFreq and the
+ * w the batch sketches with (opts.globalW, or 1 on a context with lra_ctx_set_store_all on: prefetch with that w) starts from it instead of seeding -- with any other arguments it seeds as usual and the adopted result is dropped.  Same alignments either way: scheduling only.
  * The reads (d_seq, d_read_off) must stay untouched from the prefetch to the batch call.  Not combined with opts.defer_seed_matches (LRA_ERR_INVALID).
  * Replaces nothing in the reference: lra's worker threads (lra.cpp:678-714) each run MapRead start to end; this is the device's way of having two reads in flight. */
 int lra_seed_prefetch(lra_ctx* side, int n_reads, const char* d_seq, const uint64_t* d_read_off, int k, int w, int max_freq);

@@ -25,6 +25,8 @@ SYMBOLS = {
     "lra_ctx_destroy": (None, [_vp]),
     "lra_ctx_release_buffers": (C.c_int, [_vp, _u64p]),
     "lra_ctx_set_stream": (C.c_int, [_vp, _vp]),
+    "lra_ctx_set_store_all": (C.c_int, [_vp, C.c_int]),
+    "lra_ctx_store_all": (C.c_int, [_vp]),
     "lra_ctx_last_error": (C.c_char_p, [_vp]),
     "lra_copy_to_host": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
     "lra_copy_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),

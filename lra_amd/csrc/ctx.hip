@@ -176,6 +176,13 @@ void lra_side_join(lra_ctx* ctx, int i) {
 
 // The context's side streams run at the priority of the stream it is bound to: a host that maps several sub-batches at once gives each context a stream of
 // its own priority (the high one runs as if alone, the others fill what it leaves idle), and a stage's forked kernels must not jump that order.
+extern "C" int lra_ctx_set_store_all(lra_ctx* ctx, int on) {
+  if (!ctx || (on != 0 && on != 1)) return LRA_ERR_INVALID;
+  ctx->store_all = on == 1;
+  return LRA_OK;
+}
+extern "C" int lra_ctx_store_all(lra_ctx* ctx) { return ctx ? (ctx->store_all ? 1 : 0) : LRA_ERR_INVALID; }
+
 extern "C" int lra_ctx_set_stream(lra_ctx* ctx, void* stream) {
   if (!ctx) return LRA_ERR_INVALID;
   ctx->stream = (hipStream_t)stream;

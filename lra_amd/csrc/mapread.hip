@@ -584,15 +584,17 @@ static int lowacc_core(lra_ctx* ctx, int n_reads, const char* d_seq, const uint6
   // opts.defer_seed_matches: the reads with more tier-1 matches than that are handed back (the seed stage empties their match lists: no later stage sees them)
   const uint32_t seedT = o->defer_seed_matches > 0 ? (uint32_t)o->defer_seed_matches : 0;
   // (a result made ahead of the call -- lra_seed_prefetch on a side context, lra_ctx_adopt_seed -- from these reads with these parameters is what lra_seed_batch would make)
+  // (lra align -a, lra_ctx_set_store_all: the sketch takes w = 1, MapRead.h:172-176; nothing on this path reads opts.globalW after it)
+  const int seedW = ctx->store_all ? 1 : o->globalW;
   const bool ahead = ctx->ahead.valid && ctx->ahead.n_reads == n_reads && ctx->ahead.d_seq == d_seq && ctx->ahead.d_read_off == d_read_off &&
-                     ctx->ahead.k == o->globalK && ctx->ahead.w == o->globalW && ctx->ahead.max_freq == o->globalMaxFreq;
+                     ctx->ahead.k == o->globalK && ctx->ahead.w == seedW && ctx->ahead.max_freq == o->globalMaxFreq;
   ctx->ahead.valid = false;
   if (ahead) {
     if (seedT) return lra_set_err(ctx, LRA_ERR_INVALID, "defer_seed_matches and a seed result adopted ahead of the call do not combine");
     sres = ctx->ahead.res;
   } else {
     ctx->seed->defer_T = seedT;
-    rc = lra_seed_batch(ctx, n_reads, d_seq, d_read_off, o->globalK, o->globalW, o->globalMaxFreq, &sres);
+    rc = lra_seed_batch(ctx, n_reads, d_seq, d_read_off, o->globalK, seedW, o->globalMaxFreq, &sres);
     ctx->seed->defer_T = 0;
     if (rc) return rc;
   }

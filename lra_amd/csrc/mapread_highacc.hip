@@ -234,11 +234,13 @@ static int highacc_core(lra_ctx* ctx, int n_reads, const char* d_seq, const uint
   // ---- a1-a4 (MapRead.h:169-203), a5 (Map_highacc.h:41-42)
   lra_seed_result sres;
   {
+    // (lra align -a, lra_ctx_set_store_all: the sketch alone takes w = 1, MapRead.h:172-176; W -- and Wt below -- stay opts.globalW)
+    const int seedW = ctx->store_all ? 1 : W;
     const bool ahead = ctx->ahead.valid && ctx->ahead.n_reads == R && ctx->ahead.d_seq == d_seq && ctx->ahead.d_read_off == d_read_off &&
-                       ctx->ahead.k == K && ctx->ahead.w == W && ctx->ahead.max_freq == o->globalMaxFreq;   // (lra_seed_prefetch + lra_ctx_adopt_seed)
+                       ctx->ahead.k == K && ctx->ahead.w == seedW && ctx->ahead.max_freq == o->globalMaxFreq;   // (lra_seed_prefetch + lra_ctx_adopt_seed)
     ctx->ahead.valid = false;
     if (ahead) sres = ctx->ahead.res;
-    else if ((rc = lra_seed_batch(ctx, R, d_seq, d_read_off, K, W, o->globalMaxFreq, &sres))) return rc;
+    else if ((rc = lra_seed_batch(ctx, R, d_seq, d_read_off, K, seedW, o->globalMaxFreq, &sres))) return rc;
   }
   lra_cluster_result cres;
   if ((rc = lra_clean_matches_batch(ctx, &o->clean, CH, nChr, &cres))) return rc;

@@ -309,6 +309,84 @@ __global__ void __launch_bounds__(256) sketch_compact(int n_reads, const uint64_
   }
 }
 
+// ---- a1 at w = 1 (lra align -a: StoreMinimizers(read, globalK, 1), MapRead.h:172-183).  With a window of one k-mer there is no window machine: MinCount.h:8-179
+// emits, for a read of L > k bases, every position p < L - k whose k-mer holds no non-ACGT byte, and p = L - k only when that k-mer is clean AND seq[L - k - 1]
+// is ACGT (both N searches, :27 and :115, stop before a window that starts at L - k, so the last k-mer is reached only by continuity); nothing when L <= k.
+// Whether p is emitted depends on the bytes near p alone, so the stage is position-parallel over the batch's bases: tile t = positions
+// [base + 64 t, base + 64 t + 64) of the concatenated reads (base = read_off[0]), reads of any length and reads with N alike.  Each wave takes a run of
+// consecutive tiles and keeps the read it is in from one tile to the next; lanes of a tile that crosses a read boundary look their read up themselves.
+// COUNT: tile_cnt[t] = emitted positions in tile t, tile_mask[t] = which.  EMIT: keys and positions straight to their final places, tile_pre[t] (the exclusive
+// scan of tile_cnt) + the emitted lanes below.
+__device__ __forceinline__ int read_at(const uint64_t* __restrict__ off, int lo, int hi, uint64_t g) {   // the last r in [lo, hi) with off[r] <= g (off[lo] <= g)
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (off[mid] <= g) lo = mid; else hi = mid; }
+  return lo;
+}
+constexpr int SKA_NT = 256;          // 4 waves per workgroup, each with its own run of tiles
+template <bool EMIT>
+__global__ void __launch_bounds__(SKA_NT) sketch_all_kernel(uint64_t n_tiles, uint64_t tiles_per_wave, int n_reads, const unsigned char* __restrict__ seq,
+                                                            const uint64_t* __restrict__ read_off, int k, uint32_t* __restrict__ tile_cnt,
+                                                            uint64_t* __restrict__ tile_mask, const uint64_t* __restrict__ tile_pre,
+                                                            uint64_t* __restrict__ mm_key, uint32_t* __restrict__ mm_pos) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t wave = (uint64_t)blockIdx.x * (SKA_NT / 64) + (threadIdx.x >> 6);
+  const uint64_t t0 = wave * tiles_per_wave;
+  if (t0 >= n_tiles) return;
+  const uint64_t t1 = min(n_tiles, t0 + tiles_per_wave);
+  const uint64_t base = read_off[0], end = read_off[n_reads];
+  const uint64_t kbits = (k >= 32) ? 0xFFFFFFFFULL : ((1ULL << k) - 1);
+  const uint64_t mask2k = (k >= 32) ? ~0ULL : ((1ULL << (2 * k)) - 1);
+  const unsigned long long below = (lane == 0) ? 0ULL : (~0ULL >> (64 - lane));
+  int r0 = read_at(read_off, 0, n_reads, base + t0 * 64);          // the read of the tile's first position (wave-uniform)
+  uint64_t r0_end = read_off[r0 + 1];
+  for (uint64_t t = t0; t < t1; t++) {
+    const uint64_t G = base + t * 64, g = G + lane;
+    if (G >= r0_end) { r0 = read_at(read_off, r0, n_reads, G); r0_end = read_off[r0 + 1]; }
+    int r = r0; uint64_t rs = read_off[r0], re = r0_end;
+    if (g >= r0_end && g < end) { r = read_at(read_off, r0, n_reads, g); rs = read_off[r]; re = read_off[r + 1]; }
+    // this lane's byte and, for lanes below k - 1, one of the k - 1 bytes behind the tile (bytes past the batch read as 'A': no position there is emitted)
+    const int cA = g < end ? code_n(seq[g]) : 0;
+    const int cB = (lane < k - 1 && G + 64 + lane < end) ? code_n(seq[G + 64 + lane]) : 0;
+    const unsigned long long nA = __ballot(cA > 3), nB = __ballot(cB > 3);
+    uint64_t xn = nA >> lane;
+    if (lane) xn |= nB << (64 - lane);
+    const uint64_t L = re - rs, p = g - rs;
+    bool em = g < end && L > (uint64_t)k && p <= L - k && (xn & kbits) == 0;
+    if (em && p == L - k) em = code_n(seq[g - 1]) <= 3;              // the last k-mer: only after an ACGT byte (see above)
+    const unsigned long long me = __ballot(em);
+    if (!EMIT) {
+      if (lane == 0) { tile_cnt[t] = (uint32_t)__popcll(me); tile_mask[t] = me; }
+      continue;
+    }
+    if (!me) continue;
+    // 2-bit codes packed by ballot, every lane cuts its own k-mer out (as sketch_wave_kernel; an N's code there is 0, it is never in an emitted k-mer)
+    const int c0 = cA & 3, c1 = cB > 3 ? 0 : cB;
+    const unsigned long long b0 = __ballot(c0 & 1), b1 = __ballot(c0 & 2), u0 = __ballot(c1 & 1), u1 = __ballot(c1 & 2);
+    uint64_t x0 = b0 >> lane, x1 = b1 >> lane;
+    if (lane) { x0 |= u0 << (64 - lane); x1 |= u1 << (64 - lane); }
+    x0 &= kbits; x1 &= kbits;
+    const uint64_t LE = spread32(x0) | (spread32(x1) << 1);
+    const uint64_t rc = (~LE) & mask2k;
+    uint64_t v = __brevll(LE);
+    v = ((v >> 1) & 0x5555555555555555ULL) | ((v & 0x5555555555555555ULL) << 1);
+    const uint64_t fwd = (k >= 32) ? v : (v >> (64 - 2 * k));
+    if (em) {
+      const uint64_t o = tile_pre[t] + (uint64_t)__popcll(me & below);
+      mm_key[o] = ((fwd & FOR_MASK) < (rc & FOR_MASK)) ? (fwd & FOR_MASK) : (rc | REV_MASK);   // MinCount.h:60-61
+      mm_pos[o] = (uint32_t)p;
+    }
+  }
+}
+
+// mm_off[r] = the emitted positions in front of read r's first base: tile_pre of its tile + the emitted lanes of that tile below it
+__global__ void __launch_bounds__(256) sketch_all_offsets(int n_reads, const uint64_t* __restrict__ read_off, uint64_t n_tiles, const uint64_t* __restrict__ tile_pre,
+                                                          const uint64_t* __restrict__ tile_mask, uint64_t* __restrict__ mm_off) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r > n_reads) return;
+  const uint64_t d = read_off[r] - read_off[0], t = d >> 6;
+  const int l = (int)(d & 63);
+  mm_off[r] = t >= n_tiles ? tile_pre[n_tiles] : tile_pre[t] + (uint64_t)__popcll(tile_mask[t] & (l ? (~0ULL >> (64 - l)) : 0ULL));
+}
+
 // ------------------------------------------------------------------------------------ a2
 // libstdc++ std::sort (bits/stl_algo.h: __introsort_loop + __final_insertion_sort, threshold
 // 16, median-of-three to first, unguarded Hoare partition, heap-sort fall-back) restated on
@@ -1246,6 +1324,102 @@ extern "C" int lra_sort_minimizers_batch(lra_ctx* ctx, int n_lists, const uint64
   return LRA_OK;
 }
 
+// the minimizer arrays (and a3's per-minimizer arrays) for total_mm tuples
+static int grow_mm(lra_ctx* ctx, lra_seed_state* s, uint64_t total_mm) {
+  if (total_mm >= (1ULL << 32)) return lra_set_err(ctx, LRA_ERR_INVALID, "batch too large: %llu minimizers", (unsigned long long)total_mm);
+  if (total_mm > s->cap_mm) {
+    size_t c = total_mm + total_mm / 4 + 1024;
+    if (!regrow(s->mm_key, c) || !regrow(s->mm_pos, c) || !regrow(s->lb, c) || !regrow(s->ub, c) || !regrow(s->tk_lb, c) ||
+        !regrow(s->tk_lbm1, c) || !regrow(s->tk_ubm1, c))
+      { s->cap_mm = 0; return lra_set_err(ctx, LRA_ERR_NOMEM, "minimizer arrays"); }
+    s->cap_mm = c;
+  }
+  return LRA_OK;
+}
+
+// a1 for w > 1: the window machine, a wave per read (sketch_wave_kernel), the reads with a non-ACGT byte a lane per read (sketch_kernel)
+static int sketch_windows(lra_ctx* ctx, lra_seed_state* s, int n_reads, const unsigned char* seq, const uint64_t* d_read_off, int k, int w, uint64_t& total_mm) {
+  hipStream_t st = ctx->stream;
+  const int nb = (n_reads + 63) / 64;
+  // ---- a1: count, scan, emit
+  const int gridW = n_reads < ctx->num_cu * 32 ? n_reads : ctx->num_cu * 32;
+  int* flagN = (int*)s->n_forward;   // reused before a4 writes it
+  uint64_t total_bases = 0;
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&total_bases, d_read_off + n_reads, 8, hipMemcpyDeviceToHost, st));
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  // (the staging arrays -- 12 bytes per base of the batch -- live in the sparse DP's arena, slot 12: the seed stage comes first in a batch, the arena is dead until the
+  // first sparse DP, and what the batch before left there -- IndelRefine's and CalculateStatistics' arrays -- belonged to a result that ends with this call)
+  char* stg = (char*)lra_ensure(ctx, 12, (size_t)total_bases * 12 + 1024);
+  if (!stg) return LRA_ERR_NOMEM;
+  uint64_t* wkey = (uint64_t*)stg;
+  uint32_t* wpos = (uint32_t*)(stg + (((size_t)total_bases * 8 + 255) & ~(size_t)255));
+  lra_time_begin(ctx, "sketch_emit");
+  hipLaunchKernelGGL(sketch_wave_kernel<true>, dim3(gridW), dim3(64), 0, st, n_reads, seq, d_read_off, k, w, d_read_off, wkey, wpos, s->counts32, flagN);
+  lra_time_end(ctx);
+  lra_time_begin(ctx, "sketch_serial");
+  hipLaunchKernelGGL(sketch_kernel<false>, dim3(nb), dim3(64), 0, st, n_reads, seq, d_read_off, k, w, (const uint64_t*)nullptr,
+                     (uint64_t*)nullptr, (uint32_t*)nullptr, s->counts32, (const int*)flagN);
+  lra_time_end(ctx);
+  if (lra_exclusive_scan<uint32_t>(ctx, (long)n_reads, s->counts32, s->mm_off)) return LRA_ERR_HIP;
+  total_mm = 0;
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&total_mm, s->mm_off + n_reads, 8, hipMemcpyDeviceToHost, st));
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  { int rc = grow_mm(ctx, s, total_mm); if (rc) return rc; }
+  lra_time_begin(ctx, "sketch_compact");
+  hipLaunchKernelGGL(sketch_compact, dim3(std::min((n_reads + 3) / 4, ctx->num_cu * 32)), dim3(256), 0, st, n_reads, d_read_off, (const uint64_t*)s->mm_off, (const int*)flagN,
+                     (const uint64_t*)wkey, (const uint32_t*)wpos, s->mm_key, s->mm_pos);
+  lra_time_end(ctx);
+  lra_time_begin(ctx, "sketch_serial");
+  hipLaunchKernelGGL(sketch_kernel<true>, dim3(nb), dim3(64), 0, st, n_reads, seq, d_read_off, k, w, s->mm_off, s->mm_key, s->mm_pos,
+                     (uint32_t*)nullptr, (const int*)flagN);
+  lra_time_end(ctx);
+  return LRA_OK;
+}
+
+// a1 for w = 1 (sketch_all_kernel): count per tile, scan, the reads' offsets, emit.  No staging copy and no compaction: the emit pass writes the final places.
+static int sketch_store_all(lra_ctx* ctx, lra_seed_state* s, int n_reads, const unsigned char* seq, const uint64_t* d_read_off, int k, uint64_t& total_mm) {
+  hipStream_t st = ctx->stream;
+  uint64_t ends[2] = {0, 0};
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&ends[0], d_read_off, 8, hipMemcpyDeviceToHost, st));
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&ends[1], d_read_off + n_reads, 8, hipMemcpyDeviceToHost, st));
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  if (ends[1] < ends[0]) return lra_set_err(ctx, LRA_ERR_INVALID, "read offsets decrease");
+  const uint64_t n_tiles = (ends[1] - ends[0] + 63) / 64;
+  // (tile counts, masks and their scan -- 20 bytes per 64 bases -- in slot 12, where the window machine stages its lists: dead until the first sparse DP)
+  const size_t cnt_b = ((n_tiles + 1) * 4 + 255) & ~(size_t)255, msk_b = ((n_tiles + 1) * 8 + 255) & ~(size_t)255;
+  char* tb = (char*)lra_ensure(ctx, 12, cnt_b + msk_b + (n_tiles + 1) * 8 + 1024);
+  if (!tb) return LRA_ERR_NOMEM;
+  uint32_t* tile_cnt = (uint32_t*)tb;
+  uint64_t* tile_mask = (uint64_t*)(tb + cnt_b);
+  uint64_t* tile_pre = (uint64_t*)(tb + cnt_b + msk_b);
+  // a run of consecutive tiles per wave: waves for twice what the device holds at once (8 per SIMD), and no more (each starts with a search of the read offsets)
+  const uint64_t max_waves = (uint64_t)ctx->num_cu * 64;
+  const uint64_t tpw = std::max<uint64_t>(1, (n_tiles + max_waves - 1) / max_waves);
+  const uint64_t n_waves = (n_tiles + tpw - 1) / tpw;
+  const dim3 grid((unsigned)((n_waves + SKA_NT / 64 - 1) / (SKA_NT / 64)));
+  if (n_tiles) {
+    lra_time_begin(ctx, "sketch_all_count");
+    hipLaunchKernelGGL(sketch_all_kernel<false>, grid, dim3(SKA_NT), 0, st, n_tiles, tpw, n_reads, seq, d_read_off, k, tile_cnt, tile_mask, (const uint64_t*)nullptr,
+                       (uint64_t*)nullptr, (uint32_t*)nullptr);
+    lra_time_end(ctx);
+  }
+  LRA_HIP_CHECK(ctx, hipMemsetAsync(tile_mask + n_tiles, 0, 8, st));
+  if (lra_exclusive_scan<uint32_t>(ctx, (long)n_tiles, tile_cnt, tile_pre)) return LRA_ERR_HIP;
+  hipLaunchKernelGGL(sketch_all_offsets, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256), 0, st, n_reads, d_read_off, n_tiles, (const uint64_t*)tile_pre,
+                     (const uint64_t*)tile_mask, s->mm_off);
+  total_mm = 0;
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&total_mm, tile_pre + n_tiles, 8, hipMemcpyDeviceToHost, st));
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  { int rc = grow_mm(ctx, s, total_mm); if (rc) return rc; }
+  if (total_mm) {
+    lra_time_begin(ctx, "sketch_all_emit");
+    hipLaunchKernelGGL(sketch_all_kernel<true>, grid, dim3(SKA_NT), 0, st, n_tiles, tpw, n_reads, seq, d_read_off, k, (uint32_t*)nullptr, (uint64_t*)nullptr,
+                       (const uint64_t*)tile_pre, s->mm_key, s->mm_pos);
+    lra_time_end(ctx);
+  }
+  return LRA_OK;
+}
+
 extern "C" int lra_seed_batch(lra_ctx* ctx, int n_reads, const char* d_seq, const uint64_t* d_read_off, int k, int w,
                               int max_freq, lra_seed_result* out) {
   if (!ctx || !out || n_reads < 0) return LRA_ERR_INVALID;
@@ -1268,46 +1442,10 @@ extern "C" int lra_seed_batch(lra_ctx* ctx, int n_reads, const char* d_seq, cons
     s->cap_reads = c;
   }
   const unsigned char* seq = (const unsigned char*)d_seq;
-  const int nb = (n_reads + 63) / 64;
-  // ---- a1: count, scan, emit
   const int gridW = n_reads < ctx->num_cu * 32 ? n_reads : ctx->num_cu * 32;
-  int* flagN = (int*)s->n_forward;   // reused before a4 writes it
-  uint64_t total_bases = 0;
-  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&total_bases, d_read_off + n_reads, 8, hipMemcpyDeviceToHost, st));
-  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  // (the staging arrays -- 12 bytes per base of the batch -- live in the sparse DP's arena, slot 12: the seed stage comes first in a batch, the arena is dead until the
-  // first sparse DP, and what the batch before left there -- IndelRefine's and CalculateStatistics' arrays -- belonged to a result that ends with this call)
-  char* stg = (char*)lra_ensure(ctx, 12, (size_t)total_bases * 12 + 1024);
-  if (!stg) return LRA_ERR_NOMEM;
-  uint64_t* wkey = (uint64_t*)stg;
-  uint32_t* wpos = (uint32_t*)(stg + (((size_t)total_bases * 8 + 255) & ~(size_t)255));
-  lra_time_begin(ctx, "sketch_emit");
-  hipLaunchKernelGGL(sketch_wave_kernel<true>, dim3(gridW), dim3(64), 0, st, n_reads, seq, d_read_off, k, w, d_read_off, wkey, wpos, s->counts32, flagN);
-  lra_time_end(ctx);
-  lra_time_begin(ctx, "sketch_serial");
-  hipLaunchKernelGGL(sketch_kernel<false>, dim3(nb), dim3(64), 0, st, n_reads, seq, d_read_off, k, w, (const uint64_t*)nullptr,
-                     (uint64_t*)nullptr, (uint32_t*)nullptr, s->counts32, (const int*)flagN);
-  lra_time_end(ctx);
-  if (lra_exclusive_scan<uint32_t>(ctx, (long)n_reads, s->counts32, s->mm_off)) return LRA_ERR_HIP;
+  // ---- a1
   uint64_t total_mm = 0;
-  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&total_mm, s->mm_off + n_reads, 8, hipMemcpyDeviceToHost, st));
-  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  if (total_mm >= (1ULL << 32)) return lra_set_err(ctx, LRA_ERR_INVALID, "batch too large: %llu minimizers", (unsigned long long)total_mm);
-  if (total_mm > s->cap_mm) {
-    size_t c = total_mm + total_mm / 4 + 1024;
-    if (!regrow(s->mm_key, c) || !regrow(s->mm_pos, c) || !regrow(s->lb, c) || !regrow(s->ub, c) || !regrow(s->tk_lb, c) ||
-        !regrow(s->tk_lbm1, c) || !regrow(s->tk_ubm1, c))
-      { s->cap_mm = 0; return lra_set_err(ctx, LRA_ERR_NOMEM, "minimizer arrays"); }
-    s->cap_mm = c;
-  }
-  lra_time_begin(ctx, "sketch_compact");
-  hipLaunchKernelGGL(sketch_compact, dim3(std::min((n_reads + 3) / 4, ctx->num_cu * 32)), dim3(256), 0, st, n_reads, d_read_off, (const uint64_t*)s->mm_off, (const int*)flagN,
-                     (const uint64_t*)wkey, (const uint32_t*)wpos, s->mm_key, s->mm_pos);
-  lra_time_end(ctx);
-  lra_time_begin(ctx, "sketch_serial");
-  hipLaunchKernelGGL(sketch_kernel<true>, dim3(nb), dim3(64), 0, st, n_reads, seq, d_read_off, k, w, s->mm_off, s->mm_key, s->mm_pos,
-                     (uint32_t*)nullptr, (const int*)flagN);
-  lra_time_end(ctx);
+  { int rc = w == 1 ? sketch_store_all(ctx, s, n_reads, seq, d_read_off, k, total_mm) : sketch_windows(ctx, s, n_reads, seq, d_read_off, k, w, total_mm); if (rc) return rc; }
   // ---- a2: a read outside the repeats has no k-mer twice among its minimizers, and a list without equal keys has one sorted order only: the radix path takes nearly
   // all reads, the exact (libstdc++-identical) sort the ones with a repeated k-mer.  The temporaries are a3's outputs, not written yet.
   if (total_mm == 0) { int rc = launch_sort(ctx, n_reads, s->mm_off, s->mm_key, s->mm_pos); if (rc) return rc; }

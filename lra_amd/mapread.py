@@ -62,6 +62,7 @@ class LowAccOptions:
     PrintNumAln: int = 1
     printFormat: str = "s"
     printMD: bool = False              # --printMD (lra.cpp:71, :592): MD:Z in SAM records (format 's'), built on the device (LRA_PACK_MD)
+    storeAll: bool = False             # -a (lra.cpp:182-184): sketch every position of a read, w = 1 (lra_ctx_set_store_all); globalW stays for the rest
     deferSeedMatches: int = 0          # lra_map_opts.defer_seed_matches (scheduling only: reads with more tier-1 matches are handed back unmapped; 0 = off)
     deferMatches: int = None           # lra_map_opts.defer_matches (scheduling only; None = the preset's value, 0 = one pass)
 
@@ -84,6 +85,11 @@ def clr_options(**kw):
              read_type="clr")
     d.update(kw)
     return LowAccOptions(**d)
+
+
+def set_store_all(ctx: Context, on):
+    """lra_ctx_set_store_all: the drivers on this context sketch with w = 1 (lra align -a)."""
+    ctx.check(ctx.lib.lra_ctx_set_store_all(ctx.h, 1 if on else 0))
 
 
 def seq_offsets(chrom_pos, window):
@@ -180,6 +186,7 @@ class LowAccMapper:
         ctx.check(ctx.lib.lra_ctx_load_chromosomes(ctx.h, cp, len(self.chrom_pos) - 1))
         ctx.check(ctx.lib.lra_ctx_build_local_index(ctx.h, o.localK, o.localW, o.localIndexWindow, o.localMaxFreq))
         self.copts = self._c_opts()
+        set_store_all(ctx, o.storeAll)
         self.gdev = torch.cat([g.to(dev), torch.zeros(64, dtype=torch.uint8, device=dev)]) if staged else None
         self.g_off = torch.tensor(self.chrom_pos, dtype=torch.int64, device=dev)
         self._gli = None
@@ -207,10 +214,20 @@ class LowAccMapper:
         m = cls.__new__(cls)
         m.ctx = ctx; m.opts = other.opts; m.G = other.G; m.chrom_pos = other.chrom_pos; m.chrom_names = other.chrom_names; m.index_stats = other.index_stats
         ctx.check(ctx.lib.lra_ctx_share_reference(ctx.h, other.ctx.h))
+        set_store_all(ctx, m.opts.storeAll)
         m.copts = other.copts; m.gdev = None; m.g_off = other.g_off; m._gli = None; m.gso = None; m.lut = other.lut
         m.sdp_opts, m.sdp2_opts, m.clean_opts = other.sdp_opts, other.sdp2_opts, other.clean_opts
         m.stats = {}
         return m
+
+    @property
+    def seed_w(self):
+        """The w the drivers sketch with: what a caller of seed.seed_prefetch passes for a result these mappers adopt (1 with -a, else globalW)."""
+        return 1 if self.store_all else int(self.copts.globalW)
+
+    @property
+    def store_all(self):
+        return bool(self.opts.storeAll)
 
     def fetch_local_index(self):
         """The genome's local index as the context holds it (what lra_ctx_build_local_index built): host arrays (seqOffsets, tupleBoundaries, tuples)."""
@@ -241,6 +258,7 @@ class LowAccMapper:
         """lra_map_reads_lowacc_batch: the whole device side in one library call."""
         ctx = self.ctx
         res = MapResult()
+        set_store_all(ctx, self.store_all)
         ctx.check(ctx.lib.lra_map_reads_lowacc_batch(ctx.h, rbatch.n, C.c_void_p(rbatch.seq.data_ptr()), C.c_void_p(rbatch.off.data_ptr()),
                                                      C.c_uint64(int(rbatch.total_bases)), C.byref(self.copts), C.byref(res)))
         c = res.counters
@@ -252,6 +270,7 @@ class LowAccMapper:
     # ---- two-stage batches (include/lra_hip.h: lra_map_reads_lowacc_front / _back): front(i + 1) on one host thread beside back(i) on another
     def front(self, rbatch):
         ctx = self.ctx
+        set_store_all(ctx, self.store_all)
         ctx.check(ctx.lib.lra_map_reads_lowacc_front(ctx.h, rbatch.n, C.c_void_p(rbatch.seq.data_ptr()), C.c_void_p(rbatch.off.data_ptr()),
                                                      C.c_uint64(int(rbatch.total_bases)), C.byref(self.copts)))
 
@@ -280,6 +299,7 @@ class LowAccMapper:
         import copy
         m = copy.copy(self)
         m.ctx = ctx
+        set_store_all(ctx, self.store_all)
         return m
 
     def fetch(self, res: MapResult):
@@ -373,7 +393,7 @@ class LowAccMapper:
         nR = rbatch.n
         tot = int(rbatch.total_bases)
         lens = rbatch.off[1:] - rbatch.off[:-1]
-        sres = seed.seed_batch(ctx, rbatch, o.globalK, o.globalW, o.globalMaxFreq)
+        sres = seed.seed_batch(ctx, rbatch, o.globalK, self.seed_w, o.globalMaxFreq)
         cres = cluster.clean_matches_batch(ctx, self.clean_opts, CH)
         eres = cluster.linear_extend_batch(ctx, o.globalK, rbatch)
         # match_rate = 3 for a read with a repetitive cluster (Map_lowacc.h:86-89, :184-185)
@@ -531,6 +551,7 @@ class HighAccMapper:
         self.chrom_pos = [int(x) for x in chrom_pos]
         self.chrom_names = [n if isinstance(n, bytes) else str(n).encode() for n in chrom_names]
         self.printMD = bool(overrides.pop("printMD", False))            # --printMD: a record-stage choice, not a field of lra_map_opts
+        self.storeAll = bool(overrides.pop("storeAll", False))          # -a: a context setting (lra_ctx_set_store_all), not a field of lra_map_opts
         m = MapOpts()
         (ctx.lib.lra_map_opts_preset_contig if preset == "contig" else ctx.lib.lra_map_opts_preset_ccs)(C.byref(m))
         if gli:
@@ -554,11 +575,19 @@ class HighAccMapper:
         cp = (C.c_uint64 * len(self.chrom_pos))(*self.chrom_pos)
         ctx.check(ctx.lib.lra_ctx_load_chromosomes(ctx.h, cp, len(self.chrom_pos) - 1))
         ctx.check(ctx.lib.lra_ctx_build_local_index(ctx.h, m.localK, m.localW, m.localIndexWindow, m.localMaxFreq))     # glIndex: only the REFINEclusters branch reads it
+        set_store_all(ctx, self.storeAll)
         self.stats = {}
+
+    @property
+    def store_all(self):
+        return self.storeAll
+
+    seed_w = LowAccMapper.seed_w
 
     def align(self, rbatch) -> MapResult:
         ctx = self.ctx
         res = MapResult()
+        set_store_all(ctx, self.storeAll)
         ctx.check(ctx.lib.lra_map_reads_highacc_batch(ctx.h, rbatch.n, C.c_void_p(rbatch.seq.data_ptr()), C.c_void_p(rbatch.off.data_ptr()),
                                                       C.c_uint64(int(rbatch.total_bases)), C.byref(self.copts), C.byref(res)))
         c = res.counters
