@@ -1131,6 +1131,16 @@ uint64_t lra_map_host_trim(uint64_t keep_bytes);   /* (ABI 6) the record stage k
                                                      * host memory; a fresh 100 MB part is 25 000 page faults): release them down to keep_bytes (0 = all); returns the bytes still held */
 int lra_host_thread_budget(void);   /* host threads lra_map_records* use when asked for 0: hardware threads, capped by the container's CPU quota (cgroup cpu.max) less four */
 void lra_reads_close(lra_reads* r);
+/* lra_reads_next_batch with the parsing on ctx's device: the SAME batch (reads, cut, names, quals, errors) in *batch (host arrays, as lra_reads_next_batch
+ * returns them), and the batch's bases / offsets on the device: *d_seq = the upper-cased bases back to back + 64 zero bytes, *d_off[n_reads + 1] with
+ * d_off[0] = 0 -- what lra_map_reads_lowacc_batch / _highacc_batch / _lowacc_front take.  Device arrays are owned by the reader, work is enqueued on ctx's
+ * stream and complete at return; both stay valid until the next call on r or lra_reads_close.  A reader uses one form: lra_reads_next_batch on a reader
+ * that has used this one, or this one on a reader that has used lra_reads_next_batch, returns LRA_ERR_INVALID (this form reads ahead of its batches).
+ * The reader's device buffers live on the device of its first call (another device: LRA_ERR_INVALID). */
+int lra_reads_next_batch_device(lra_reads* r, lra_ctx* ctx, uint64_t max_bases, lra_read_batch* batch, const char** d_seq, const uint64_t** d_off);
+/* bytes of a file the device form reads and parses per step (default 256 MiB; minimum 4096).  A step holds at least one whole record: one longer than
+ * the step makes that step read on.  LRA_ERR_INVALID on a reader that has used lra_reads_next_batch. */
+int lra_reads_set_device_chunk(lra_reads* r, uint64_t bytes);
 int lra_map_reads_host(lra_ctx* ctx, int n_reads, const char* h_seq, const uint64_t* h_off, const lra_map_opts* opts, lra_map_result* out);
 int lra_map_records(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* opts, const char* const* names, const char* const* reads,
                     const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* passthrough, char* out, uint64_t cap,

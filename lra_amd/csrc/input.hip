@@ -9,24 +9,11 @@
 // BAM / SAM / CRAM input (Input.h:284-390) goes through htslib in the reference and is not built.
 #include "common.h"
 #include "map_state.h"
+#include "reads_state.h"
 #include <fstream>
 #include <sstream>
 #include <string>
 #include <vector>
-
-struct lra_reads {
-  std::vector<std::string> files;
-  size_t cur = 0;
-  std::ifstream strm;
-  int type = -1;                                   // 0 FASTA, 1 FASTQ
-  bool open_ok = false;
-  std::string error;                               // a record the reference would abort on: lra_reads_next_batch returns LRA_ERR_INVALID from then on
-  // the current batch
-  std::string seq, names, quals;
-  std::vector<uint64_t> off, name_off, qual_off;
-  std::vector<const char*> name_ptr, seq_ptr, qual_ptr;
-  std::vector<int32_t> len;
-};
 
 namespace {
 
@@ -117,11 +104,16 @@ extern "C" int lra_reads_open(const char* const* files, int n_files, lra_reads**
   return LRA_OK;
 }
 
-extern "C" void lra_reads_close(lra_reads* r) { delete r; }
+extern "C" void lra_reads_close(lra_reads* r) {
+  if (r && r->dev) lra_reads_dev_free(r->dev);
+  delete r;
+}
 
 extern "C" int lra_reads_next_batch(lra_reads* r, uint64_t max_bases, lra_read_batch* b) {
   if (!r || !b) return LRA_ERR_INVALID;
   memset(b, 0, sizeof *b);
+  if (r->form == LRA_READS_DEVICE_FORM) return LRA_ERR_INVALID;          // the device form has read ahead of its batches: the two forms share no file position
+  r->form = LRA_READS_HOST_FORM;
   r->seq.clear(); r->names.clear(); r->quals.clear(); r->off.assign(1, 0); r->name_off.assign(1, 0); r->qual_off.assign(1, 0); r->len.clear();
   std::string name, seq, qual;
   uint64_t total = 0;

@@ -1,0 +1,612 @@
+// lra_amd/csrc/input_device.hip -- lra_reads_next_batch with the parsing on the device (lra_reads_next_batch_device).
+//
+// The batches are those of lra_reads_next_batch (input.hip: Input::Initialize / GetNext / BufferedRead, quirks included); only where the bytes are parsed
+// differs.  Split:
+//   host    opens and sniffs the files in order, reads a file a step at a time (lra_reads_set_device_chunk bytes) into a page-locked buffer, keeps the
+//           bytes of a record the step cut (they start the next step; a record longer than a step makes the step grow until it holds one whole record),
+//           and walks GetNext's state machine over the step's record table (one entry per record: counts and offsets, no bytes).
+//   device  byte-stream passes over the step, 4 KiB per workgroup, 16 bytes per lane:
+//             rd_count_lines   per tile: '\n' count, FASTA header starts ('>' at a line start)                        -> exclusive scans
+//             rd_emit_lines    every '\n' at its line index
+//             rd_count_kept    per tile: the bytes that stay (sequence lines: all but ' ' and '\n'; FASTQ quality lines the same) -> exclusive scans
+//             rd_emit          the sequence bytes upper-cased at their final offsets, the quality bytes behind them (one NUL slot per record), and per
+//                              record its start and its offsets; a FASTQ line that is empty marks its record
+//             rd_name_len      per record: the name token (`ss >> c >> name` on the header line)                        -> exclusive scan
+//             rd_name_emit     the names, NUL-terminated, back to back
+//           FASTQ records are framed by line index mod 4 from the step's start (a step starts at a record); FASTA records by their header lines.
+//   batch   the records a batch takes are contiguous runs of a step's records: their bases are copied device to device into the reader's d_seq (64 zero
+//           bytes behind the last), their names / qualities / bases once to page-locked host arrays.
+#include "common.h"
+#include "reads_state.h"
+#include "scan.h"
+#include <fcntl.h>
+#include <unistd.h>
+#include <algorithm>
+
+namespace {
+
+constexpr int RD_NT = 256, RD_BPT = 16, RD_TILE = RD_NT * RD_BPT;   // a workgroup per 4 KiB tile, 16 bytes per lane (one 128-bit load)
+
+struct RecInfo {            // one per record of a step (device-written, copied back whole)
+  uint64_t start;           // byte of the header line's start in the step
+  uint64_t seq;             // kept sequence bytes of the step in front of the record
+  uint64_t qual;            // kept quality bytes in front of the record (its qualities sit at qual + record index: one NUL slot per record)
+  uint64_t name;            // offset of its name in the step's name buffer
+  uint64_t tok;             // byte of the name token's start
+  uint32_t tok_len;
+  uint32_t flags;           // FASTQ: bit i = line i of the record is empty
+};
+
+__device__ inline void load16(const unsigned char* __restrict__ raw, uint64_t p, unsigned char b[RD_BPT]) {
+  const uint4 v = *reinterpret_cast<const uint4*>(raw + p);
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int j = 0; j < RD_BPT; j++) b[j] = (unsigned char)(w[j >> 2] >> (8 * (j & 3)));
+}
+
+// exclusive prefix over the workgroup of one 32-bit count per lane; *tot = the workgroup's sum
+__device__ inline uint32_t block_excl(uint32_t v, uint32_t* sh, uint32_t* tot) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d); if (lane >= d) inc += o; }
+  if (lane == 63) sh[wave] = inc;
+  __syncthreads();
+  uint32_t wb = 0, t = 0;
+#pragma unroll
+  for (int w = 0; w < RD_NT / 64; w++) { const uint32_t x = sh[w]; wb += (w < wave) ? x : 0; t += x; }
+  __syncthreads();
+  *tot = t;
+  return wb + inc - v;
+}
+
+__device__ inline unsigned char prev_byte(const unsigned char* raw, uint64_t p) { return p ? raw[p - 1] : (unsigned char)'\n'; }
+
+__global__ void __launch_bounds__(RD_NT) rd_count_lines(const unsigned char* __restrict__ raw, int fasta, uint32_t* __restrict__ cnt_nl,
+                                                        uint32_t* __restrict__ cnt_hdr) {
+  __shared__ uint32_t sh[RD_NT / 64];
+  const uint64_t p0 = (uint64_t)blockIdx.x * RD_TILE + threadIdx.x * RD_BPT;
+  unsigned char b[RD_BPT];
+  load16(raw, p0, b);
+  unsigned char prev = prev_byte(raw, p0);
+  uint32_t nl = 0, hdr = 0;
+#pragma unroll
+  for (int j = 0; j < RD_BPT; j++) { nl += b[j] == '\n'; hdr += fasta && b[j] == '>' && prev == '\n'; prev = b[j]; }   // the zero padding matches neither
+  uint32_t t;
+  block_excl(nl | (hdr << 16), sh, &t);                    // <= 4096 of each per tile: both halves in one word
+  if (threadIdx.x == 0) { cnt_nl[blockIdx.x] = t & 0xffff; cnt_hdr[blockIdx.x] = t >> 16; }
+}
+
+__global__ void __launch_bounds__(RD_NT) rd_emit_lines(const unsigned char* __restrict__ raw, const uint64_t* __restrict__ nl_base, uint64_t* __restrict__ nl_pos) {
+  __shared__ uint32_t sh[RD_NT / 64];
+  const uint64_t p0 = (uint64_t)blockIdx.x * RD_TILE + threadIdx.x * RD_BPT;
+  unsigned char b[RD_BPT];
+  load16(raw, p0, b);
+  uint32_t nl = 0;
+#pragma unroll
+  for (int j = 0; j < RD_BPT; j++) nl += b[j] == '\n';
+  uint32_t t;
+  uint64_t L = nl_base[blockIdx.x] + block_excl(nl, sh, &t);
+  for (int j = 0; j < RD_BPT; j++)
+    if (b[j] == '\n') nl_pos[L++] = p0 + j;
+}
+
+// The state of a lane's first byte: its line index, and whether that line is a FASTA header (the line's first byte, found through nl_pos)
+struct LaneState { uint64_t line; bool hdr; bool at_ls; };
+__device__ inline LaneState lane_state(const unsigned char* raw, const uint64_t* nl_pos, uint64_t line, uint64_t p0, int fasta) {
+  LaneState s;
+  s.line = line;
+  s.at_ls = prev_byte(raw, p0) == '\n';
+  s.hdr = false;
+  if (fasta && !s.at_ls) s.hdr = raw[line ? nl_pos[line - 1] + 1 : 0] == '>';
+  return s;
+}
+
+// counts of a lane's 16 bytes that stay: sequence bytes (FASTA: lines that are not headers; FASTQ: line 1 of 4) and quality bytes (FASTQ: line 3 of 4)
+__device__ inline void lane_kept(const unsigned char b[RD_BPT], uint64_t p0, uint64_t len, LaneState s, int fasta, uint32_t* ns, uint32_t* nq) {
+  uint32_t a = 0, q = 0;
+  for (int j = 0; j < RD_BPT && p0 + j < len; j++) {
+    const unsigned char c = b[j];
+    if (s.at_ls) s.hdr = c == '>';
+    const bool keep = c != '\n' && c != ' ';
+    const int field = (int)(s.line & 3);
+    a += keep && (fasta ? !s.hdr : field == 1);
+    q += keep && !fasta && field == 3;
+    s.at_ls = c == '\n';
+    s.line += c == '\n';
+  }
+  *ns = a; *nq = q;
+}
+
+__global__ void __launch_bounds__(RD_NT) rd_count_kept(const unsigned char* __restrict__ raw, uint64_t len, int fasta, const uint64_t* __restrict__ nl_base,
+                                                       const uint64_t* __restrict__ nl_pos, uint32_t* __restrict__ cnt_seq, uint32_t* __restrict__ cnt_qual) {
+  __shared__ uint32_t sh[RD_NT / 64];
+  const uint64_t p0 = (uint64_t)blockIdx.x * RD_TILE + threadIdx.x * RD_BPT;
+  unsigned char b[RD_BPT];
+  load16(raw, p0, b);
+  uint32_t nl = 0;
+#pragma unroll
+  for (int j = 0; j < RD_BPT; j++) nl += b[j] == '\n';
+  uint32_t t;
+  const uint64_t line = nl_base[blockIdx.x] + block_excl(nl, sh, &t);
+  uint32_t ns, nq;
+  lane_kept(b, p0, len, lane_state(raw, nl_pos, line, p0, fasta), fasta, &ns, &nq);
+  uint32_t ts, tq;
+  block_excl(ns, sh, &ts);
+  block_excl(nq, sh, &tq);
+  if (threadIdx.x == 0) { cnt_seq[blockIdx.x] = ts; cnt_qual[blockIdx.x] = tq; }
+}
+
+__global__ void __launch_bounds__(RD_NT) rd_emit(const unsigned char* __restrict__ raw, uint64_t len, int fasta, const uint64_t* __restrict__ nl_base,
+                                                 const uint64_t* __restrict__ hdr_base, const uint64_t* __restrict__ nl_pos, const uint64_t* __restrict__ seq_base,
+                                                 const uint64_t* __restrict__ qual_base, char* __restrict__ c_seq, char* __restrict__ c_qual,
+                                                 RecInfo* __restrict__ rec) {
+  __shared__ uint32_t sh[RD_NT / 64];
+  const uint64_t p0 = (uint64_t)blockIdx.x * RD_TILE + threadIdx.x * RD_BPT;
+  unsigned char b[RD_BPT];
+  load16(raw, p0, b);
+  unsigned char prev = prev_byte(raw, p0);
+  uint32_t nl = 0, hdr = 0;
+#pragma unroll
+  for (int j = 0; j < RD_BPT; j++) { nl += b[j] == '\n'; hdr += fasta && b[j] == '>' && prev == '\n'; prev = b[j]; }
+  uint32_t t;
+  const uint32_t ex = block_excl(nl | (hdr << 16), sh, &t);
+  LaneState s = lane_state(raw, nl_pos, nl_base[blockIdx.x] + (ex & 0xffff), p0, fasta);
+  uint64_t h = hdr_base[blockIdx.x] + (ex >> 16);                      // FASTA: header starts in front of this lane = the index of the next record
+  uint32_t ns, nq;
+  lane_kept(b, p0, len, s, fasta, &ns, &nq);
+  uint64_t sp = seq_base[blockIdx.x] + block_excl(ns, sh, &t);
+  uint64_t qp = qual_base[blockIdx.x] + block_excl(nq, sh, &t);
+  for (int j = 0; j < RD_BPT && p0 + j < len; j++) {
+    const unsigned char c = b[j];
+    const uint64_t p = p0 + j;
+    const int field = (int)(s.line & 3);
+    if (s.at_ls) {
+      s.hdr = c == '>';
+      if (fasta ? s.hdr : field == 0) {
+        RecInfo& r = rec[fasta ? h++ : s.line >> 2];
+        r.start = p; r.seq = sp; r.qual = qp;
+      }
+      if (!fasta && c == '\n') atomicOr(&rec[s.line >> 2].flags, 1u << field);   // an empty line: the reader's "this file is over"
+    }
+    const bool keep = c != '\n' && c != ' ';
+    if (keep && (fasta ? !s.hdr : field == 1)) c_seq[sp++] = (char)((c >= 'a' && c <= 'z') ? c - 32 : c);   // C-locale toupper
+    if (keep && !fasta && field == 3) c_qual[qp++ + (s.line >> 2)] = (char)c;
+    s.at_ls = c == '\n';
+    s.line += c == '\n';
+  }
+}
+
+// C-locale isspace: what `std::stringstream >>` skips
+__device__ inline bool is_ws(unsigned char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
+
+// per record: the name token of its header line (`nameStrm >> c >> read.name`: blanks, one character, blanks, then the token up to the next blank);
+// FASTQ: the NUL behind the record's qualities
+__global__ void rd_name_len(const unsigned char* __restrict__ raw, uint64_t len, int fasta, uint64_t n_rec, const uint64_t* __restrict__ qual_total,
+                            RecInfo* __restrict__ rec, uint32_t* __restrict__ name_len, char* __restrict__ c_qual) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rec) return;
+  uint64_t p = rec[r].start;
+  while (p < len && raw[p] != '\n' && is_ws(raw[p])) p++;
+  if (p < len && raw[p] != '\n') {
+    p++;
+    while (p < len && raw[p] != '\n' && is_ws(raw[p])) p++;
+  }
+  uint64_t e = p;
+  while (e < len && raw[e] != '\n' && !is_ws(raw[e])) e++;
+  rec[r].tok = p; rec[r].tok_len = (uint32_t)(e - p);
+  name_len[r] = (uint32_t)(e - p) + 1;
+  if (!fasta) c_qual[(r + 1 < n_rec ? rec[r + 1].qual : *qual_total) + r] = 0;
+}
+
+__global__ void rd_name_emit(const unsigned char* __restrict__ raw, uint64_t n_rec, const uint64_t* __restrict__ name_off, RecInfo* __restrict__ rec,
+                             char* __restrict__ c_names) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rec) return;
+  const uint64_t o = name_off[r], a = rec[r].tok;
+  const uint32_t n = rec[r].tok_len;
+  for (uint32_t i = 0; i < n; i++) c_names[o + i] = (char)raw[a + i];
+  c_names[o + n] = 0;
+  rec[r].name = o;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------------
+// host side
+
+namespace {
+
+template <typename T> struct DevBuf {
+  T* p = nullptr; size_t n = 0;
+  bool ensure(size_t want) {                                       // contents NOT kept
+    if (want <= n) return true;
+    if (p) (void)hipFree(p);
+    p = nullptr; n = 0;
+    const size_t m = std::max(want, (size_t)4096);
+    if (hipMalloc((void**)&p, m * sizeof(T)) != hipSuccess) return false;
+    n = m;
+    return true;
+  }
+  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+};
+template <typename T> struct PinBuf {
+  T* p = nullptr; size_t n = 0;
+  bool ensure(size_t want, size_t keep, hipStream_t st) {   // the first `keep` items are kept: the copies into them queued on `st` land first
+    if (want <= n) return true;
+    if (hipStreamSynchronize(st) != hipSuccess) return false;   // (st may be the null stream)
+    const size_t m = std::max({want, n + n / 2, (size_t)(1 << 20) / sizeof(T)});
+    T* q = nullptr;
+    if (hipHostMalloc((void**)&q, m * sizeof(T), hipHostMallocDefault) != hipSuccess) return false;
+    if (keep) memcpy(q, p, keep * sizeof(T));
+    if (p) (void)hipHostFree(p);
+    p = q; n = m;
+    return true;
+  }
+  void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
+};
+
+struct Unit {               // a record of the step as GetNext sees it
+  uint64_t idx;             // index in the step's record table
+  bool ok;                  // FASTQ: none of its 4 lines is empty
+  bool eof_after;           // FASTQ: reading it set the stream's eof bit
+};
+
+}  // namespace
+
+struct lra_reads_dev {
+  int device = -1;
+  uint64_t chunk = 256ull << 20;
+  // the current file
+  int fd = -1;
+  int type = -1;
+  bool file_at_eof = false;                        // every byte of the file is in the step buffer
+  bool fq_eof = false;                             // FASTQ: the stream's eof bit (GetNext returns false from then on)
+  bool started = false;
+  // the step: raw bytes on the host (the carry of the last step in front), the parsed record table
+  PinBuf<char> h_raw; uint64_t len = 0, consumed = 0;
+  std::vector<RecInfo> rec;                        // n_started records + 1 sentinel (the step's totals)
+  uint64_t n_avail = 0, next = 0;                  // records GetNext may take from this step, the next one
+  bool step_ends_file = false;
+  uint64_t n_nl = 0, n_started = 0;
+  // device buffers of the step
+  DevBuf<unsigned char> d_raw; DevBuf<uint32_t> cnt[4]; DevBuf<uint64_t> base[4]; DevBuf<uint64_t> nl_pos; DevBuf<RecInfo> d_rec;
+  DevBuf<uint32_t> name_len; DevBuf<uint64_t> name_off; DevBuf<char> c_seq, c_qual, c_names;
+  // the batch
+  DevBuf<char> d_seq; DevBuf<uint64_t> d_off;
+  PinBuf<char> h_seq, h_names, h_quals;
+  std::vector<uint64_t> off, name_off_h, qual_off_h;
+  std::vector<int32_t> len_h;
+  std::vector<uint8_t> hasq;
+  std::vector<const char*> name_ptr, seq_ptr, qual_ptr;
+  uint64_t seg_a = 0, seg_b = 0;                   // the pending run of this step's records [seg_a, seg_b) not yet copied to the batch
+  uint64_t b_seq = 0, b_names = 0, b_quals = 0;    // the batch's bytes so far
+  ~lra_reads_dev() {
+    if (fd >= 0) close(fd);
+    h_raw.release(); d_raw.release(); nl_pos.release(); d_rec.release(); name_len.release(); name_off.release();
+    for (int i = 0; i < 4; i++) { cnt[i].release(); base[i].release(); }
+    c_seq.release(); c_qual.release(); c_names.release(); d_seq.release(); d_off.release(); h_seq.release(); h_names.release(); h_quals.release();
+  }
+};
+
+void lra_reads_dev_free(lra_reads_dev* d) { delete d; }
+
+namespace {
+
+// Input::Initialize's sniffing (input.hip open_file: '>' first = FASTA; '@' first and '+' opening the third line = FASTQ) on the file's first bytes
+int sniff(int fd) {
+  std::string head;
+  char buf[65536];
+  for (;;) {
+    const ssize_t k = read(fd, buf, sizeof buf);
+    if (k <= 0) break;
+    head.append(buf, (size_t)k);
+    const size_t a = head.find('\n');
+    if (a != std::string::npos && head.find('\n', a + 1) != std::string::npos && head.size() > head.find('\n', a + 1) + 1) break;
+    if (head[0] != '@') break;
+  }
+  if (lseek(fd, 0, SEEK_SET) != 0 || head.empty()) return -1;
+  if (head[0] == '>') return 0;
+  if (head[0] != '@') return -1;
+  const size_t a = head.find('\n');
+  if (a == std::string::npos) return -1;
+  const size_t b = head.find('\n', a + 1);
+  if (b == std::string::npos || b + 1 >= head.size()) return -1;
+  return head[b + 1] == '+' ? 1 : -1;
+}
+
+bool open_dev_file(lra_reads* r) {
+  lra_reads_dev* d = r->dev;
+  if (d->fd >= 0) close(d->fd);
+  d->fd = open(r->files[r->cur].c_str(), O_RDONLY);
+  d->type = d->fd >= 0 ? sniff(d->fd) : -1;
+  d->len = d->consumed = 0; d->file_at_eof = false; d->fq_eof = false;
+  d->rec.clear(); d->n_avail = d->next = 0; d->step_ends_file = false;
+  d->seg_a = d->seg_b = 0;
+  return d->type >= 0;
+}
+
+int grow_batch_seq(lra_ctx* ctx, lra_reads_dev* d, uint64_t want) {
+  if (want <= d->d_seq.n) return LRA_OK;
+  const size_t m = std::max((size_t)want, d->d_seq.n * 2);
+  char* q = nullptr;
+  if (hipMalloc((void**)&q, m) != hipSuccess) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc(%zu) failed", m);
+  if (d->b_seq) LRA_HIP_CHECK(ctx, hipMemcpyAsync(q, d->d_seq.p, d->b_seq, hipMemcpyDeviceToDevice, ctx->stream));
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (d->d_seq.p) (void)hipFree(d->d_seq.p);
+  d->d_seq.p = q; d->d_seq.n = m;
+  return LRA_OK;
+}
+
+// the pending run of the step's records to the batch: bases device to device, names and qualities to the host arrays (asynchronous)
+int flush_segment(lra_ctx* ctx, lra_reads_dev* d) {
+  const uint64_t a = d->seg_a, b = d->seg_b;
+  d->seg_a = d->seg_b = d->next;
+  if (a == b) return LRA_OK;
+  const RecInfo& A = d->rec[a]; const RecInfo& B = d->rec[b];
+  const uint64_t ns = B.seq - A.seq, nn = B.name - A.name;
+  if (int rc = grow_batch_seq(ctx, d, d->b_seq + ns + 64)) return rc;
+  if (!d->h_names.ensure(d->b_names + nn, d->b_names, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc failed");
+  if (ns) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_seq.p + d->b_seq, d->c_seq.p + A.seq, ns, hipMemcpyDeviceToDevice, ctx->stream));
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->h_names.p + d->b_names, d->c_names.p + A.name, nn, hipMemcpyDeviceToHost, ctx->stream));
+  d->b_seq += ns; d->b_names += nn;
+  if (d->type == 1) {
+    const uint64_t nq = (B.qual + b) - (A.qual + a);
+    if (!d->h_quals.ensure(d->b_quals + nq, d->b_quals, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc failed");
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->h_quals.p + d->b_quals, d->c_qual.p + A.qual + a, nq, hipMemcpyDeviceToHost, ctx->stream));
+    d->b_quals += nq;
+  } else {
+    if (!d->h_quals.ensure(d->b_quals + (b - a), d->b_quals, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc failed");
+    memset(d->h_quals.p + d->b_quals, 0, b - a);                   // a FASTA read's quality string: empty (its pointer is NULL)
+    d->b_quals += b - a;
+  }
+  return LRA_OK;
+}
+
+// the device passes over h_raw[0, len): the record table of the step
+int parse(lra_ctx* ctx, lra_reads_dev* d) {
+  const int fasta = d->type == 0;
+  const uint64_t len = d->len, nt = std::max<uint64_t>(1, (len + RD_TILE - 1) / RD_TILE), padded = nt * RD_TILE;
+  hipStream_t st = ctx->stream;
+  if (!d->d_raw.ensure(padded)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc(%zu) failed", (size_t)padded);
+  for (int i = 0; i < 4; i++)
+    if (!d->cnt[i].ensure(nt) || !d->base[i].ensure(nt + 1)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
+  lra_time_begin(ctx, "input_h2d");
+  if (len) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_raw.p, d->h_raw.p, len, hipMemcpyHostToDevice, st));
+  LRA_HIP_CHECK(ctx, hipMemsetAsync(d->d_raw.p + len, 0, padded - len, st));
+  lra_time_end(ctx);
+  lra_time_begin(ctx, "input_parse");
+  hipLaunchKernelGGL(rd_count_lines, dim3((unsigned)nt), dim3(RD_NT), 0, st, d->d_raw.p, fasta, d->cnt[0].p, d->cnt[1].p);
+  if (int rc = lra_exclusive_scan(ctx, (long)nt, d->cnt[0].p, d->base[0].p)) return rc;
+  if (int rc = lra_exclusive_scan(ctx, (long)nt, d->cnt[1].p, d->base[1].p)) return rc;
+  lra_time_end(ctx);
+  uint64_t tot[2];
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&tot[0], d->base[0].p + nt, 8, hipMemcpyDeviceToHost, st));
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&tot[1], d->base[1].p + nt, 8, hipMemcpyDeviceToHost, st));
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  d->n_nl = tot[0];
+  const uint64_t lines_in = d->n_nl + (len && d->h_raw.p[len - 1] != '\n');
+  d->n_started = fasta ? tot[1] : (lines_in + 3) / 4;
+  const uint64_t n = d->n_started;
+  if (!d->nl_pos.ensure(d->n_nl + 1) || !d->d_rec.ensure(n + 1) || !d->name_len.ensure(n + 1) || !d->name_off.ensure(n + 2) || !d->c_seq.ensure(len + 1) ||
+      !d->c_qual.ensure(len + n + 1))
+    return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
+  lra_time_begin(ctx, "input_parse");
+  LRA_HIP_CHECK(ctx, hipMemsetAsync(d->d_rec.p, 0, (n + 1) * sizeof(RecInfo), st));
+  hipLaunchKernelGGL(rd_emit_lines, dim3((unsigned)nt), dim3(RD_NT), 0, st, d->d_raw.p, d->base[0].p, d->nl_pos.p);
+  hipLaunchKernelGGL(rd_count_kept, dim3((unsigned)nt), dim3(RD_NT), 0, st, d->d_raw.p, len, fasta, d->base[0].p, d->nl_pos.p, d->cnt[2].p, d->cnt[3].p);
+  if (int rc = lra_exclusive_scan(ctx, (long)nt, d->cnt[2].p, d->base[2].p)) return rc;
+  if (int rc = lra_exclusive_scan(ctx, (long)nt, d->cnt[3].p, d->base[3].p)) return rc;
+  hipLaunchKernelGGL(rd_emit, dim3((unsigned)nt), dim3(RD_NT), 0, st, d->d_raw.p, len, fasta, d->base[0].p, d->base[1].p, d->nl_pos.p, d->base[2].p, d->base[3].p,
+                     d->c_seq.p, d->c_qual.p, d->d_rec.p);
+  if (n) {
+    const unsigned g = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(rd_name_len, dim3(g), dim3(256), 0, st, d->d_raw.p, len, fasta, n, d->base[3].p + nt, d->d_rec.p, d->name_len.p, d->c_qual.p);
+    if (int rc = lra_exclusive_scan(ctx, (long)n, d->name_len.p, d->name_off.p)) return rc;
+    uint64_t name_bytes = 0;
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&name_bytes, d->name_off.p + n, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (!d->c_names.ensure(name_bytes + 1)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
+    hipLaunchKernelGGL(rd_name_emit, dim3(g), dim3(256), 0, st, d->d_raw.p, n, d->name_off.p, d->d_rec.p, d->c_names.p);
+  }
+  LRA_HIP_CHECK(ctx, hipGetLastError());
+  lra_time_end(ctx);
+  d->rec.resize(n + 1);
+  if (n) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->rec.data(), d->d_rec.p, n * sizeof(RecInfo), hipMemcpyDeviceToHost, st));
+  uint64_t sent[3] = {0, 0, 0};
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&sent[0], d->base[2].p + nt, 8, hipMemcpyDeviceToHost, st));
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&sent[1], d->base[3].p + nt, 8, hipMemcpyDeviceToHost, st));
+  if (n) LRA_HIP_CHECK(ctx, hipMemcpyAsync(&sent[2], d->name_off.p + n, 8, hipMemcpyDeviceToHost, st));
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  RecInfo& s = d->rec[n];
+  memset(&s, 0, sizeof s);
+  s.start = len; s.seq = sent[0]; s.qual = sent[1]; s.name = sent[2];
+  return LRA_OK;
+}
+
+// the next step of the current file: the carry of the last step, then up to `chunk` more bytes; a step that holds no whole record (and is not the file's
+// end) reads on, twice as much each time
+int next_step(lra_ctx* ctx, lra_reads* r) {
+  lra_reads_dev* d = r->dev;
+  if (int rc = flush_segment(ctx, d)) return rc;
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));           // the step's buffers are reused below
+  if (d->consumed) { memmove(d->h_raw.p, d->h_raw.p + d->consumed, d->len - d->consumed); d->len -= d->consumed; d->consumed = 0; }
+  uint64_t want = d->chunk;
+  for (;;) {
+    if (!d->file_at_eof) {
+      if (!d->h_raw.ensure(d->len + want + 1, d->len, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc(%zu) failed", (size_t)(d->len + want));
+      uint64_t got = 0;
+      while (got < want) {
+        const ssize_t k = read(d->fd, d->h_raw.p + d->len + got, (size_t)std::min<uint64_t>(want - got, 1ull << 30));
+        if (k < 0) return lra_set_err(ctx, LRA_ERR_INVALID, "device reader: read of %s failed", r->files[r->cur].c_str());
+        if (k == 0) { d->file_at_eof = true; break; }
+        got += (uint64_t)k;
+      }
+      d->len += got;
+    }
+    if (int rc = parse(ctx, d)) return rc;
+    const uint64_t n = d->n_started;
+    uint64_t complete;
+    if (d->type == 0) complete = d->file_at_eof ? n : (n ? n - 1 : 0);
+    else if (d->file_at_eof) complete = d->n_nl / 4 + 1;           // through the first unit whose 4th getline meets the end of the file (4u + 3 >= n_nl)
+    else complete = d->n_nl / 4;
+    if (complete == 0 && !d->file_at_eof) { want = std::max(want, d->len) * 2; continue; }
+    d->n_avail = complete;
+    d->step_ends_file = d->file_at_eof;
+    d->consumed = d->file_at_eof ? d->len : (complete < n ? d->rec[complete].start : d->len);
+    d->next = d->seg_a = d->seg_b = 0;
+    if (d->type == 1 && d->rec.size() < complete + 1) {            // units behind the end of the file: no bytes, their lines are empty
+      const RecInfo s = d->rec.back();
+      d->rec.resize(complete + 1, s);
+    }
+    return LRA_OK;
+  }
+}
+
+// the next record (FASTA) or 4-line unit (FASTQ) of the current file; false: a FASTA file is over
+int next_unit(lra_ctx* ctx, lra_reads* r, Unit* u, bool* have) {
+  lra_reads_dev* d = r->dev;
+  *have = false;
+  while (d->next >= d->n_avail) {
+    if (d->step_ends_file && d->started) {
+      if (d->type == 1) { *u = Unit{d->next, false, true}; *have = true; d->fq_eof = true; }   // (not reached: the unit at the end carries the eof bit)
+      return LRA_OK;
+    }
+    d->started = true;
+    if (int rc = next_step(ctx, r)) return rc;
+  }
+  const uint64_t i = d->next++;
+  u->idx = i;
+  if (d->type == 0) { u->ok = true; u->eof_after = false; *have = true; return LRA_OK; }
+  const uint64_t lines_in = d->n_nl + (d->len && d->h_raw.p[d->len - 1] != '\n');
+  const uint64_t last = 4 * i + 3;
+  bool ok = last < lines_in && (i >= d->n_started ? false : (d->rec[i].flags & 15) == 0);
+  u->ok = ok;
+  u->eof_after = d->step_ends_file && last >= d->n_nl;
+  d->fq_eof = u->eof_after;
+  *have = true;
+  return LRA_OK;
+}
+
+bool fasta_dry(lra_reads_dev* d) { return d->type == 0 && d->started && d->step_ends_file && d->next >= d->n_avail; }
+
+int open_next_file(lra_reads* r, bool* ok) {
+  lra_reads_dev* d = r->dev;
+  ++r->cur;
+  *ok = r->cur < r->files.size() && open_dev_file(r);
+  d->started = false;
+  return LRA_OK;
+}
+
+// Input::GetNext (input.hip get_next) over the step's record table; *got: a record was taken (its index in d->rec)
+int get_next_dev(lra_ctx* ctx, lra_reads* r, bool* got, uint64_t* idx) {
+  lra_reads_dev* d = r->dev;
+  *got = false;
+  if (!r->open_ok) return LRA_OK;
+  if (d->type == 0 && fasta_dry(d)) {
+    if (int rc = flush_segment(ctx, d)) return rc;
+    bool ok;
+    open_next_file(r, &ok);
+    if (!ok) { r->open_ok = false; return LRA_OK; }
+  }
+  if (d->type == 1 && d->fq_eof) return LRA_OK;
+  Unit u; bool have;
+  if (d->type == 0) {
+    if (int rc = next_unit(ctx, r, &u, &have)) return rc;
+    if (!have) return LRA_OK;                                      // (a FASTA file holds at least the record its first byte opens)
+    *got = true; *idx = u.idx;
+    return LRA_OK;
+  }
+  if (int rc = next_unit(ctx, r, &u, &have)) return rc;
+  if (!have) return LRA_OK;
+  if (!u.ok) {                                                     // this file is over: the next one
+    if (int rc = flush_segment(ctx, d)) return rc;
+    bool ok;
+    open_next_file(r, &ok);
+    if (!ok) { r->open_ok = false; return LRA_OK; }
+    if (d->type == 1) {
+      if (int rc = next_unit(ctx, r, &u, &have)) return rc;
+      if (!have) return LRA_OK;
+    }
+  }
+  if (!u.ok) { d->seg_a = d->seg_b = d->next; return LRA_OK; }    // (a unit taken and dropped: the batch's run restarts behind it)
+  const RecInfo& a = d->rec[u.idx]; const RecInfo& b = d->rec[u.idx + 1];
+  const uint64_t sl = b.seq - a.seq, ql = b.qual - a.qual;
+  if (sl != ql) {
+    std::string name(a.tok_len, '\0');
+    if (a.tok_len) memcpy(&name[0], d->h_raw.p + a.tok, a.tok_len);
+    r->open_ok = false;
+    r->error = "FASTQ record '" + name + "' of " + r->files[r->cur] + ": quality string of " + std::to_string(ql) + " characters for a read of " +
+               std::to_string(sl) + " bases";
+    return LRA_OK;
+  }
+  *got = true; *idx = u.idx;
+  return LRA_OK;
+}
+
+}  // namespace
+
+extern "C" int lra_reads_set_device_chunk(lra_reads* r, uint64_t bytes) {
+  if (!r || bytes < 4096 || bytes > (1ull << 40)) return LRA_ERR_INVALID;
+  if (r->form == LRA_READS_HOST_FORM) return LRA_ERR_INVALID;
+  if (!r->dev) r->dev = new lra_reads_dev();
+  r->dev->chunk = bytes;
+  return LRA_OK;
+}
+
+extern "C" int lra_reads_next_batch_device(lra_reads* r, lra_ctx* ctx, uint64_t max_bases, lra_read_batch* b, const char** d_seq, const uint64_t** d_off) {
+  if (!r || !ctx || !b || !d_seq || !d_off) return LRA_ERR_INVALID;
+  memset(b, 0, sizeof *b);
+  *d_seq = nullptr; *d_off = nullptr;
+  if (r->form == LRA_READS_HOST_FORM) return LRA_ERR_INVALID;       // the host form reads the file where this one would have read ahead of it
+  if (!r->dev) r->dev = new lra_reads_dev();
+  lra_reads_dev* d = r->dev;
+  if (d->device >= 0 && d->device != ctx->device) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_reads_next_batch_device: the reader's buffers are on device %d", d->device);
+  LRA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (r->form == LRA_READS_NO_FORM) {                              // the first call: the device form's own handle on the first file (lra_reads_open sniffed it already)
+    r->form = LRA_READS_DEVICE_FORM;
+    d->device = ctx->device;
+    r->cur = 0;
+    r->strm.close();
+    r->open_ok = open_dev_file(r);
+  }
+  d->b_seq = d->b_names = d->b_quals = 0;
+  d->seg_a = d->seg_b = d->next;
+  d->off.assign(1, 0); d->name_off_h.assign(1, 0); d->qual_off_h.assign(1, 0); d->len_h.clear(); d->hasq.clear();
+  uint64_t total = 0;
+  while (total < max_bases) {                                      // BufferedRead
+    bool got = false; uint64_t i = 0;
+    if (int rc = get_next_dev(ctx, r, &got, &i)) return rc;
+    if (!got) break;
+    if (i != d->seg_b) { if (int rc = flush_segment(ctx, d)) return rc; d->seg_a = i; }
+    d->seg_b = i + 1;
+    const RecInfo& a = d->rec[i]; const RecInfo& c = d->rec[i + 1];
+    const uint64_t sl = c.seq - a.seq;
+    total += sl;
+    d->off.push_back(d->off.back() + sl);
+    d->name_off_h.push_back(d->name_off_h.back() + (c.name - a.name));
+    d->qual_off_h.push_back(d->qual_off_h.back() + (d->type == 1 ? (c.qual - a.qual) + 1 : 1));
+    d->len_h.push_back((int32_t)sl);
+    d->hasq.push_back(d->type == 1);
+  }
+  if (int rc = flush_segment(ctx, d)) return rc;
+  const size_t n = d->len_h.size();
+  if (int rc = grow_batch_seq(ctx, d, total + 64)) return rc;
+  if (!d->d_off.ensure(n + 1) || !d->h_seq.ensure(total + 64, 0, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: allocation failed");
+  if (!d->h_names.ensure(d->b_names + 1, d->b_names, ctx->stream) || !d->h_quals.ensure(d->b_quals + 1, d->b_quals, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: allocation failed");
+  LRA_HIP_CHECK(ctx, hipMemsetAsync(d->d_seq.p + total, 0, 64, ctx->stream));
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_off.p, d->off.data(), (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  lra_time_begin(ctx, "input_d2h");
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->h_seq.p, d->d_seq.p, total + 64, hipMemcpyDeviceToHost, ctx->stream));
+  lra_time_end(ctx);
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  d->name_ptr.resize(n); d->seq_ptr.resize(n); d->qual_ptr.resize(n);
+  for (size_t k = 0; k < n; k++) {
+    d->name_ptr[k] = d->h_names.p + d->name_off_h[k]; d->seq_ptr[k] = d->h_seq.p + d->off[k];
+    d->qual_ptr[k] = d->hasq[k] ? d->h_quals.p + d->qual_off_h[k] : nullptr;
+  }
+  b->n_reads = (int32_t)n; b->total_bases = total; b->seq = d->h_seq.p; b->off = d->off.data(); b->read_len = d->len_h.data();
+  b->names = d->name_ptr.data(); b->reads = d->seq_ptr.data(); b->quals = d->qual_ptr.data();
+  *d_seq = d->d_seq.p; *d_off = d->d_off.p;
+  return r->error.empty() ? LRA_OK : LRA_ERR_INVALID;
+}

@@ -12,27 +12,49 @@ class ReadBatchC(C.Structure):
 
 
 class ReadsFile:
-    def __init__(self, files):
+    """ctx=None: lra_reads_next_batch (host parsing).  With a Context: lra_reads_next_batch_device (the parsing on that context's GPU; chunk = the bytes
+    of a file it reads and parses per step, lra_reads_set_device_chunk; None keeps the library's default)."""
+
+    def __init__(self, files, ctx=None, chunk=None):
         self.lib = load_library()
+        self.ctx = ctx
         arr = (C.c_char_p * len(files))(*[f.encode() if isinstance(f, str) else f for f in files])
         self.h = C.c_void_p()
         rc = self.lib.lra_reads_open(arr, len(files), C.byref(self.h))
         if rc != 0:
             raise IOError("cannot determine the format of the input reads (%d)" % rc)
+        if chunk is not None:
+            rc = self.lib.lra_reads_set_device_chunk(self.h, C.c_uint64(int(chunk)))
+            if rc != 0:
+                self.close()
+                raise ValueError("lra_reads_set_device_chunk(%d) failed (%d)" % (int(chunk), rc))
 
     def next_batch(self, max_bases):
-        """-> None at the end, else dict(names, seqs, quals (None for FASTA reads), off, raw=(ReadBatchC kept alive until the next call))"""
+        """-> None at the end, else dict(names, seqs, quals (None for FASTA reads), off, raw=(ReadBatchC kept alive until the next call)); the device form
+        adds d_seq / d_off (device pointers, valid until the next call) and n / total_bases"""
         b = ReadBatchC()
-        rc = self.lib.lra_reads_next_batch(self.h, C.c_uint64(int(max_bases)), C.byref(b))
+        if self.ctx is None:
+            rc = self.lib.lra_reads_next_batch(self.h, C.c_uint64(int(max_bases)), C.byref(b))
+            dev = None
+        else:
+            d_seq, d_off = C.c_void_p(), C.c_void_p()
+            rc = self.lib.lra_reads_next_batch_device(self.h, self.ctx.h, C.c_uint64(int(max_bases)), C.byref(b), C.byref(d_seq), C.byref(d_off))
+            dev = (d_seq.value, d_off.value)
         n = b.n_reads
         out = None
         if n:
             off = np.ctypeslib.as_array(b.off, shape=(n + 1,)).copy()
             seq = C.string_at(b.seq, int(b.total_bases))
             out = dict(names=[b.names[i] for i in range(n)], seqs=[seq[int(off[i]):int(off[i + 1])] for i in range(n)], quals=[b.quals[i] for i in range(n)], off=off, raw=b)
+            if dev is not None:
+                out.update(d_seq=dev[0], d_off=dev[1], n=n, total_bases=int(b.total_bases))
         if rc != 0:
-            e = IOError("lra_reads_next_batch failed (%d): %s" % (rc, (self.lib.lra_reads_last_error(self.h) or b"").decode()))
+            err = self.lib.lra_reads_last_error(self.h) or b""
+            if not err and self.ctx is not None:
+                err = self.lib.lra_ctx_last_error(self.ctx.h) or b""
+            e = IOError("%s failed (%d): %s" % ("lra_reads_next_batch" if self.ctx is None else "lra_reads_next_batch_device", rc, err.decode()))
             e.partial = out                     # the reads in front of the bad record
+            e.rc = rc
             raise e
         return out
 
@@ -48,4 +70,16 @@ def map_reads_host(mapper, raw_batch):
     ctx = mapper.ctx
     res = MapResult()
     ctx.check(ctx.lib.lra_map_reads_host(ctx.h, raw_batch.n_reads, C.c_void_p(raw_batch.seq), raw_batch.off, C.byref(mapper.copts), C.byref(res)))
+    return res
+
+
+def map_reads_device(mapper, batch):
+    """The driver the options select (bypassClustering: lra_map_reads_lowacc_batch, else lra_map_reads_highacc_batch, as lra_map_reads_host does) on a
+    device-form batch of ReadsFile.next_batch, straight from the reader's device arrays (mapper: LowAccMapper / HighAccMapper) -> MapResult"""
+    from .mapread import MapResult, set_store_all
+    ctx = mapper.ctx
+    res = MapResult()
+    set_store_all(ctx, mapper.store_all)
+    drv = ctx.lib.lra_map_reads_lowacc_batch if mapper.copts.bypassClustering else ctx.lib.lra_map_reads_highacc_batch
+    ctx.check(drv(ctx.h, batch["n"], C.c_void_p(batch["d_seq"]), C.c_void_p(batch["d_off"]), C.c_uint64(batch["total_bases"]), C.byref(mapper.copts), C.byref(res)))
     return res

@@ -1,0 +1,134 @@
+"""Map read files against a genome FASTA and print the records as `lra align` would (needs the GPU):
+
+    python tools/map_files.py -ONT genome.fa reads.fq [more.fa ...] [-p s|p|pc|b|a] [-H] [--printMD] [-a] [--PrintNumAln N] [--refineBreakpoints] [-o out.sam]
+
+The reads are parsed on the device (lra_reads_next_batch_device) and mapped from the reader's device arrays; --host-input parses them on the host
+(lra_reads_next_batch) and maps through lra_map_reads_host, the same records.  The index: genome.fa.mms / genome.fa.gli when both exist (lra_read_mms /
+lra_read_gli), else built on the device with the preset's `lra index` parameters.  The genome itself is read on the host.  Per-stage times go to stderr."""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+from lra_amd import index, mapread, reads_io
+from lra_amd.context import Context
+
+INDEX_PARAMS = {"ONT": (17, 10, 150, 15, 1), "CLR": (15, 10, 250, 12, 1), "CCS": (17, 10, 150, 15, 1), "CONTIG": (19, 10, 30, 20, 1)}   # `lra index -<preset>`
+PRESET_BATCH = 500_000_000                                                        # bases per batch: about the bench batch's device footprint
+
+
+def read_genome(path):
+    """-> (names, chrom_pos, upper-case bases back to back) of a FASTA file (Genome::Read: the name is the header's first token)"""
+    names, parts, pos = [], [], [0]
+    cur = []
+    with open(path, "rb") as f:
+        for line in f:
+            line = line.rstrip(b"\r\n")
+            if line.startswith(b">"):
+                if names:
+                    s = b"".join(cur).upper(); parts.append(s); pos.append(pos[-1] + len(s)); cur = []
+                tok = line[1:].split()
+                names.append(tok[0] if tok else b"")
+            elif line:
+                cur.append(line)
+    if names:
+        s = b"".join(cur).upper(); parts.append(s); pos.append(pos[-1] + len(s))
+    if not names:
+        raise SystemExit("%s: no FASTA records" % path)
+    return names, pos, np.frombuffer(b"".join(parts), np.uint8).copy()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    pre = ap.add_mutually_exclusive_group(required=True)
+    for p in ("ONT", "CLR", "CCS", "CONTIG"):
+        pre.add_argument("-" + p, dest="preset", action="store_const", const=p)
+    ap.add_argument("genome")
+    ap.add_argument("reads", nargs="+")
+    ap.add_argument("-p", dest="fmt", default="s", choices=["s", "p", "pc", "b", "a"], help="print format: SAM, PAF, PAF with cigar, BED, pairwise")
+    ap.add_argument("-H", dest="hard_clip", action="store_true", help="hard-clip SAM records")
+    ap.add_argument("--printMD", action="store_true", help="MD:Z in SAM records")
+    ap.add_argument("-a", dest="store_all", action="store_true", help="seed from every k-mer of a read")
+    ap.add_argument("--PrintNumAln", type=int, default=1)
+    ap.add_argument("--refineBreakpoints", action="store_true")
+    ap.add_argument("-o", dest="out", default=None, help="output file (default stdout)")
+    ap.add_argument("--host-input", action="store_true", help="parse the read files on the host (lra_reads_next_batch)")
+    ap.add_argument("--batch-bases", type=int, default=PRESET_BATCH, help="bases per batch (a batch ends with the read that crosses this)")
+    ap.add_argument("--chunk", type=int, default=None, help="bytes the device reader reads and parses per step (default: the library's)")
+    args = ap.parse_args()
+    P = args.preset
+    t0 = time.perf_counter()
+    names, chrom_pos, genome = read_genome(args.genome)
+    ctx = Context(0)
+    mms, gli = args.genome + ".mms", args.genome + ".gli"
+    ik = ipos = None
+    gli_params = None
+    if os.path.exists(mms) and os.path.exists(gli):
+        m = index.read_mms(mms)
+        assert [int(x) for x in m["chrom_pos"]] == chrom_pos, "the .mms file is of another genome"
+        ik, ipos = m["key"], m["pos"]
+        g = index.read_gli(gli)
+        gli_params = (g["k"], g["w"], g["window"])
+    fmt = {"s": "s", "p": "p", "pc": "c", "b": "b", "a": "a"}[args.fmt]
+    if P in ("ONT", "CLR"):
+        o = mapread.LowAccOptions() if P == "ONT" else mapread.clr_options()
+        if gli_params:
+            o = mapread.with_gli(o, *gli_params)
+        o.printFormat = fmt; o.PrintNumAln = args.PrintNumAln; o.printMD = args.printMD; o.storeAll = args.store_all
+        o.refineBreakpoint = args.refineBreakpoints
+        if args.hard_clip:
+            o.hardClip = True
+        mapper = mapread.LowAccMapper(ctx, genome, ik, ipos, names, chrom_pos, o, index_params=INDEX_PARAMS[P], staged=False)
+    else:
+        ov = dict(printFormat=ord(fmt), PrintNumAln=args.PrintNumAln, refineBreakpoint=int(args.refineBreakpoints), printMD=args.printMD, storeAll=args.store_all)
+        if args.hard_clip:
+            ov["hardClip"] = 1
+        mapper = mapread.HighAccMapper(ctx, genome, ik, ipos, names, chrom_pos, preset=P.lower(), index_params=INDEX_PARAMS[P], gli=gli_params, **ov)
+    t_index = time.perf_counter() - t0
+    out = open(args.out, "wb") if args.out else sys.stdout.buffer
+    if fmt == "s":
+        cl = ["lra", "align", "-" + P, args.genome, *args.reads, "-p", args.fmt] + (["-H"] if args.hard_clip else []) + (["--printMD"] if args.printMD else []) + \
+             (["-a"] if args.store_all else []) + ["--PrintNumAln", str(args.PrintNumAln)] + (["--refineBreakpoints"] if args.refineBreakpoints else [])
+        out.write(mapread.LowAccMapper.sam_header(mapper, b"lra_amd", " ".join(cl).encode()))   # the lra command line: the same for either reader
+    rf = reads_io.ReadsFile(args.reads, ctx=None if args.host_input else ctx, chunk=None if args.host_input else args.chunk)
+    t_read = t_map = t_rec = 0.0
+    n_reads = n_bases = n_batches = 0
+    failed = None
+    while True:
+        t = time.perf_counter()
+        try:
+            b = rf.next_batch(args.batch_bases)
+        except IOError as e:                                                # a corrupt FASTQ record: map the reads in front of it, then fail
+            b, failed = e.partial, e
+        t_read += time.perf_counter() - t
+        if b is None:
+            break
+        t = time.perf_counter()
+        res = reads_io.map_reads_host(mapper, b["raw"]) if args.host_input else reads_io.map_reads_device(mapper, b)
+        t_map += time.perf_counter() - t
+        t = time.perf_counter()
+        for txt in mapper.records(res, b["names"], b["seqs"], quals=b["quals"]):
+            out.write(txt)
+        t_rec += time.perf_counter() - t
+        n_reads += len(b["names"]); n_bases += int(b["off"][-1]); n_batches += 1
+        if failed:
+            break
+    rf.close()
+    if args.out:
+        out.close()
+    else:
+        out.flush()
+    sys.stderr.write("map_files: %d reads, %d bases, %d batches; genome + index %.2f s, %s %.2f s (%.1f Mbases/s), map %.2f s, records %.2f s\n"
+                     % (n_reads, n_bases, n_batches, t_index, "read+parse (host)" if args.host_input else "read+parse (device)", t_read,
+                        n_bases / max(t_read, 1e-9) / 1e6, t_map, t_rec))
+    ctx.close()
+    if failed:
+        sys.stderr.write("map_files: %s\n" % failed)
+        sys.exit(1)
+
+
+if __name__ == "__main__":
+    main()
