@@ -15,9 +15,10 @@
 //               k look-ahead / look-back updates of one event are done by k lanes; a
 //               128-row ring in LDS holds the rows still being modified), then suffix-min /
 //               prefix-max / prefix-sum scans over the rows (:318-328)
-//   ir_fill     one wave per segment   : rows are swept top to bottom, ONE LANE PER CELL OF
-//               THE ROW; the previous row stays in registers (cross-lane permutes line the
-//               two windows up); the in-row insertion recurrence is solved in closed form with
+//   ir_fill     16 / 64 lanes per segment: rows are swept top to bottom, ONE LANE PER CELL OF
+//               THE ROW; the previous row stays in registers (on 16 lanes the lanes are laid out
+//               by query column, so the cell above is the lane's own register and the cell to the
+//               left one DPP rotation away); the in-row insertion recurrence is solved in closed form with
 //               one prefix-max scan (see "row recurrence" below), so a row costs O(log width)
 //               dependent steps; one byte of trace-back state per cell goes to HBM
 //               (coalesced, the only HBM traffic that scales with cells)
@@ -505,7 +506,8 @@ __device__ __forceinline__ int scan_max(int w) {
   return w;
 }
 
-// G lanes per segment (G = 16 or 64 by the segment's widest row; rows of 17 .. 32 cells go to ir_fill_16x2), 64/G segments per wave.
+// G lanes per segment, 64/G segments per wave; launched with G = 64 for segments whose widest row has 33 .. 64 cells (rows of at most 32 cells go to
+// ir_fill_cols, wider ones to ir_fill_wide).
 // Each group sweeps its own segment row by row: one lane per cell, previous row in registers.
 // The query bases of the rows come from a sliding register window (2G bases + G prefetched), the
 // row descriptors from a register chunk of G rows; the only per-row memory traffic is the row of
@@ -695,29 +697,56 @@ __global__ void __launch_bounds__(64) ir_fill_wide(FillArgs F) {
   }
 }
 
-// ---------------------------------------------------------------------------------- trace
-// Segments whose widest row has 17 .. 32 cells, on 16 lanes (four segments per wave instead of two): a read's rows are 15 cells wide (2 refineBand + 1) except around
-// its indels, so with 32 lanes per segment half of them idle on almost every row.  A row of more than 16 cells is done in two pieces of 16, the second one taking over
-// the first's running prefix maximum and its last cell's V / M (what the shifts by one cell read); the previous row's M and D are two registers per lane.
-__global__ void __launch_bounds__(64) ir_fill_16x2(FillArgs F) {
+// Segments whose widest row has at most 16 (NP = 1, class 0) or 17 .. 32 cells (NP = 2, class 1): 16 lanes per segment, four segments per wave.  The lanes are laid
+// out by QUERY COLUMN: lane c of a group holds the row's cell whose query position is == c (mod 16) -- piece 0 the one in [S, S + 15], piece 1 the one 16 further
+// (a read's rows are 15 cells wide (2 refineBand + 1) except around its indels, so piece 1 runs on few rows).  A row's cell d of piece 0 is in lane (S + d) mod 16:
+// the window is a rotating range of the 16-lane ring.  Then every neighbour of the recurrence is in the lane or one lane to the left:
+//   the cell above (same q, previous row) is the lane's own register (pM[0] or pM[1] by the previous row's piece);
+//   the diagonal (q - 1 above), the cell to the left (V, W, M at q - 1) are DPP row_ror:1 of the same values (a DPP row is exactly one group), the head lane of
+//   piece 1 (cell 16) takes piece 0's cell 15 the same way;
+//   the prefix maximum of V is a max-scan over the ring that starts at the head lane (d = 0) and does not wrap past it;
+//   the query base of the lane's cell: the lane keeps the bases 16 K0 + c + {0, 16, 32, 48} (K0 = S / 16), refilled as the window slides;
+//   the row descriptors: the group's lanes load the next 16 rows' descriptors one per lane, 16 rows ahead, and put them in LDS when their turn comes;
+//   a row reads its own with one 16-byte LDS read (a global load per row would have to wait for the row's byte stores before it: one memory counter).
+// No cross-lane permute in the row loop.  The arithmetic and the equality cascade are those of ir_fill; cc is the cell's position in the row.
+// row_ror:N: lane i takes lane i - N of its 16-lane row.  Every source lane exists, so bound_ctrl changes nothing; set, it lets the compiler fold the move into
+// the instruction that uses it.  A DPP read returns the source lane's value only if that lane is on, so a rotation must not end up under a test that switches
+// lanes of its row off: pin() makes a value be computed where it stands, on every lane, before the selects that use it.
+template <int N>
+__device__ __forceinline__ int ror(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x120 + N, 0xf, 0xf, true); }
+__device__ __forceinline__ int pin(int x) { asm volatile("" : "+v"(x)); return x; }
+// Inclusive max-scan over a 16-lane ring from the lane with d = 0 on, not wrapping past it (d = lane - head mod 16).
+__device__ __forceinline__ int ring_scan_max(int w, int d) {
+  { const int t = pin(max(w, ror<1>(w))); w = (d >= 1) ? t : w; }
+  { const int t = pin(max(w, ror<2>(w))); w = (d >= 2) ? t : w; }
+  { const int t = pin(max(w, ror<4>(w))); w = (d >= 4) ? t : w; }
+  { const int t = pin(max(w, ror<8>(w))); w = (d >= 8) ? t : w; }
+  return w;
+}
+template <int NP>
+__global__ void __launch_bounds__(64) ir_fill_cols(FillArgs F) {
   constexpr int G = 16;
+  constexpr int CLS = NP - 1;
   const int lane = threadIdx.x;
   const int c = lane % G, gbase = lane - c;
   const int g = F.g, go = 2 * F.g + 1;
-  const long listEnd = F.cursor[4 + 1];
+  const long listEnd = F.cursor[4 + CLS];
   const uint32_t* list = F.list;
   long ti = -1, tLen = 0;
   const Row* rows = nullptr; const unsigned char* qb = nullptr; unsigned char* P = nullptr;
-  long chunkBase = 0, qLast = 0;
-  Row chunk; chunk.S = chunk.E = chunk.T = 0; chunk.C = 0;
-  int W0 = 0, q0 = 0, q1 = 0, q2 = 0, q3 = 0;                               // query bases W0 + c, + 16, + 32, + 48
-  int pM[2] = {BAD, BAD}, pD[2] = {BAD, BAD}, prevS = 0, prevLen = 0;
+  long qLast = 0;
+  __shared__ Row s_chunk[64];                                               // the group's current 16 rows: s_chunk[gbase + (ti - chunkBase)]
+  long chunkBase = 0;
+  Row chunk; chunk.S = chunk.E = chunk.T = 0; chunk.C = 0;                  // lane c: row chunkBase + 16 + c (the next chunk)
+  int K0 = 0, q0 = 0, q1 = 0, q2 = 0, q3 = 0;                               // query bases 16 K0 + c, + 16, + 32, + 48
+  int pM[NP], pD[NP], prevS = 0, prevLen = 0;                               // the previous row, by column
+  for (int p = 0; p < NP; p++) { pM[p] = BAD; pD[p] = BAD; }
   bool done = false;
   auto ldq = [&](long idx) -> int { return qb[idx < qLast ? idx : qLast]; };
   while (true) {
     if (!done && ti < 0) {
       long x = 0;
-      if (c == 0) x = atomicAdd(&F.cursor[1], 1);
+      if (c == 0) x = atomicAdd(&F.cursor[CLS], 1);
       x = __shfl(x, gbase);
       if (x < listEnd) {
         const uint64_t s = list[x];
@@ -727,40 +756,51 @@ __global__ void __launch_bounds__(64) ir_fill_16x2(FillArgs F) {
         qb = (const unsigned char*)F.qseq + F.q_off[a];
         qLast = (long)F.q_len[a] - 1;
         P = F.path + F.s_cell_off[s];
-        ti = 0; chunkBase = 0;
+        ti = 0; chunkBase = -G;                                             // (the first row loads its chunk below)
         if (c < tLen) chunk = rows[c];
-        W0 = rows[0].S;
-        q0 = ldq((long)W0 + c); q1 = ldq((long)W0 + G + c); q2 = ldq((long)W0 + 2 * G + c); q3 = ldq((long)W0 + 3 * G + c);
+        K0 = rows[0].S >> 4;
+        const long b = 16L * K0 + c;
+        q0 = ldq(b); q1 = ldq(b + G); q2 = ldq(b + 2 * G); q3 = ldq(b + 3 * G);
       } else done = true;
     }
     if (__ballot(!done) == 0ULL) break;
-    if (!done && ti - chunkBase == G) { chunkBase = ti; if (ti + c < tLen) chunk = rows[ti + c]; }
-    const int src = gbase + (int)((ti - chunkBase) & (G - 1));
-    const int S = __shfl(chunk.S, src), E = __shfl(chunk.E, src), tch = __shfl(chunk.T, src);
-    const unsigned int C = __shfl(chunk.C, src);
-    while (!done && S - W0 >= G) { W0 += G; q0 = q1; q1 = q2; q2 = q3; q3 = ldq((long)W0 + 3 * G + c); }
+    if (!done && ti - chunkBase == G) {
+      chunkBase = ti;
+      s_chunk[lane] = chunk;
+      wave_sync_lds();
+      if (ti + G + c < tLen) chunk = rows[ti + G + c];
+    }
+    const Row rw = s_chunk[gbase + (int)((ti - chunkBase) & (G - 1))];
+    const int S = rw.S, E = rw.E, tch = rw.T;
+    const unsigned int C = rw.C;
+    if (!done && (S >> 4) != K0) {                                          // the window slides (S never decreases)
+      const int adv = (S >> 4) - K0;
+      K0 = S >> 4;
+      const long b = 16L * K0 + c;
+      if (adv == 1) { q0 = q1; q1 = q2; q2 = q3; }                           // (moves of bases that came in 16 or more rows ago, then the new load)
+      else { q0 = ldq(b); q1 = ldq(b + G); q2 = ldq(b + 2 * G); }
+      q3 = ldq(b + 3 * G);
+    }
     const int len = E - S + 1;
     const bool lastRow = (ti == tLen - 1);
     const int off = S - prevS;
-    int nM[2] = {BAD, BAD}, nD[2] = {BAD, BAD};
-    int carryW = NEG, carryV = NEG, carryM = BAD;
-    const int np = (!done && len > G) ? 2 : 1;
-    for (int p = 0; p < np; p++) {
-      const int cc = c + G * p;
-      // the query base of cell cc: position S + cc = W0 + j, j in [0, 4 G)
-      const int j = S - W0 + cc;
-      const int l = gbase + (j & (G - 1));
-      const int qa = __shfl(q0, l), qbb = __shfl(q1, l), qc = __shfl(q2, l), qd = __shfl(q3, l);
-      const int qch = (j < G) ? qa : (j < 2 * G) ? qbb : (j < 3 * G) ? qc : qd;
+    const int d = (c - S) & (G - 1);                                        // this lane's cell of piece 0
+    const bool head = (d == 0);
+    const bool lo = c >= (S & (G - 1));                                     // piece 0's cell is in block K0 (else K0 + 1)
+    int nM[NP], nD[NP];
+    for (int p = 0; p < NP; p++) { nM[p] = BAD; nD[p] = BAD; }
+    int cW = NEG, cV = NEG, cM = BAD, cA = BAD;                             // piece 0 one lane to the left: cell 15 at the head lane (what piece 1's cell 16 reads)
+    for (int p = 0; p < NP; p++) {
+      if (p == 1 && len <= G) break;                                        // (uniform in a group)
+      const int cc = d + G * p;
+      const int qch = (p == 0) ? (lo ? q0 : q1) : (lo ? q1 : q2);
       const bool interior = cc >= 1 && (lastRow ? cc <= len - 1 : cc <= len - 2);
       const int srcA = cc + off, srcD = srcA - 1;
       const bool aboveIn = srcA <= prevLen - 1;                            // qE[ti-1] >= q   (:491,:548,:567)
-      // the previous row's cells srcA and srcA - 1 (pieces 0 / 1 of it)
-      const int la = gbase + (srcA & (G - 1)), ld = gbase + (srcD & (G - 1));
-      const int a0 = __shfl(pM[0], la), a1 = __shfl(pM[1], la), b0 = __shfl(pD[0], la), b1 = __shfl(pD[1], la);
-      const int d0 = __shfl(pM[0], ld), d1 = __shfl(pM[1], ld);
-      const int aM = (srcA & G) ? a1 : a0, aD = (srcA & G) ? b1 : b0;
-      const int dM = (srcD & G) ? d1 : d0;
+      const int aM = (NP > 1 && srcA >= G) ? pM[NP - 1] : pM[0];           // the previous row's cell srcA: same column
+      const int aD = (NP > 1 && srcA >= G) ? pD[NP - 1] : pD[0];
+      const int rA = pin(ror<1>(aM));                                      // its cell srcA - 1: lane c - 1's cell srcA (piece 0's at piece 1's head)
+      const int dM = (p == 1 && head) ? cA : rA;                           // (only read by interior cells, cc >= 1)
       const bool okA = aboveIn && !is_bound(ti - 1, srcA, prevLen);
       const bool okD = aboveIn && srcD >= 0 && !is_bound(ti - 1, srcD, prevLen);
       const int dOpen = okA ? aM + go : BAD, dExt = okA ? aD : BAD;        // :491-502 (gapExtend = 0)
@@ -769,14 +809,14 @@ __global__ void __launch_bounds__(64) ir_fill_16x2(FillArgs F) {
       const int mS = okD ? dM + (tch == qch ? F.match : F.mismatch) : BAD; // :548-563
       const int dS = okA ? aM + g : BAD;                                   // :567-574
       const int V = interior ? max(mS, max(dS, Dv)) : NEG;
-      const int W = max(scan_max<G>(V), carryW);                           // inclusive prefix max of V over the row so far
-      int Wm1 = shr1(W, NEG), Vm1 = shr1(V, NEG);
-      if (c == 0) { Wm1 = carryW; Vm1 = carryV; }                          // (piece 0: NEG, NEG)
+      const int W = ring_scan_max((p == 1 && head) ? max(V, cW) : V, d);   // inclusive prefix max of V over the row so far (piece 0's maximum enters at piece 1's head)
+      const int rW = pin(ror<1>(W)), rV = pin(ror<1>(V));
+      const int Wm1 = head ? cW : rW, Vm1 = head ? cV : rV;                // (piece 0: NEG, NEG at the head)
       const int Iv = max(BAD, go + Wm1);
       int M = max(max(BAD, V), max(Vm1 + g, go + Wm1));
       if (!interior) M = BAD;
-      int Mleft = shr1(M, BAD);
-      if (c == 0) Mleft = carryM;
+      const int rM = pin(ror<1>(M));
+      int Mleft = head ? cM : rM;
       if (cc <= 1) Mleft = BAD;                                            // the row's left boundary cell (:413-418)
       const int iOpen = Mleft + go;                                        // :523
       const int insOpen = (Iv == iOpen) ? 1 : 0;                           // :528-540
@@ -798,16 +838,18 @@ __global__ void __launch_bounds__(64) ir_fill_16x2(FillArgs F) {
       }
       if (!done && cc < len) P[C + cc] = outB;
       nM[p] = outM; nD[p] = outD;
-      carryW = __shfl(W, gbase + G - 1); carryV = __shfl(V, gbase + G - 1); carryM = __shfl(M, gbase + G - 1);
+      if (NP > 1 && p == 0) { cW = rW; cV = rV; cM = rM; cA = rA; }     // (at the head lane: piece 0's cell 15)
     }
     if (!done) {
-      pM[0] = nM[0]; pM[1] = nM[1]; pD[0] = nD[0]; pD[1] = nD[1]; prevS = S; prevLen = len;
+      for (int p = 0; p < NP; p++) { pM[p] = nM[p]; pD[p] = nD[p]; }
+      prevS = S; prevLen = len;
       ti++;
       if (ti == tLen) ti = -1;
     }
   }
 }
 
+// ---------------------------------------------------------------------------------- trace
 struct TraceArgs {
   uint64_t n_seg;
   const int32_t* s_kind; const int32_t* s_tStart; const uint64_t* s_rows; const uint64_t* s_row_off;
@@ -1217,10 +1259,10 @@ extern "C" int lra_indel_refine_batch(lra_ctx* ctx, int n_aln, const int32_t* d_
     const uint64_t n16 = (uint64_t)(h_cursor[4] - h_cursor[0]), n32 = (uint64_t)(h_cursor[5] - h_cursor[1]), n64 = (uint64_t)(h_cursor[6] - h_cursor[2]);
     // a kernel's time is its longest segment's row chain, whatever the class: the classes side by side (the widest class of segments, usually the bulk, on the context's stream)
     const uint64_t nWide = (uint64_t)(h_cursor[7] - h_cursor[3]);
-    if (n16) hipLaunchKernelGGL(ir_fill<16>, dim3((unsigned)std::min<uint64_t>((n16 + 3) / 4, cap_grid)), dim3(64), 0, lra_side_fork(ctx, 1), F);
+    if (n16) hipLaunchKernelGGL(ir_fill_cols<1>, dim3((unsigned)std::min<uint64_t>((n16 + 3) / 4, cap_grid)), dim3(64), 0, lra_side_fork(ctx, 1), F);
     if (n64) hipLaunchKernelGGL(ir_fill<64>, dim3((unsigned)std::min<uint64_t>(n64, cap_grid)), dim3(64), 0, lra_side_fork(ctx, 2), F);
     if (nWide) hipLaunchKernelGGL(ir_fill_wide, dim3((unsigned)std::min<uint64_t>(nWide, cap_grid)), dim3(64), 0, lra_side_fork(ctx, 3), F);
-    if (n32) hipLaunchKernelGGL(ir_fill_16x2, dim3((unsigned)std::min<uint64_t>((n32 + 3) / 4, cap_grid)), dim3(64), 0, st, F);
+    if (n32) hipLaunchKernelGGL(ir_fill_cols<2>, dim3((unsigned)std::min<uint64_t>((n32 + 3) / 4, cap_grid)), dim3(64), 0, st, F);
     if (n16) lra_side_join(ctx, 1);
     if (n64) lra_side_join(ctx, 2);
     if (nWide) lra_side_join(ctx, 3);
