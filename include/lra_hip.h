@@ -84,7 +84,7 @@ int lra_ctx_set_store_all(lra_ctx* ctx, int on);
 int lra_ctx_store_all(lra_ctx* ctx);
 /* ABI version of the loaded library (tests check it against this header). */
 int lra_abi_version(void);
-#define LRA_ABI_VERSION 9   /* 9: lra_ctx_release_buffers; later, additively (no struct or signature changed): lra_ctx_set_store_all, lra_ctx_store_all; 8: lra_map_opts_apply_local_index, lra_ctx_local_index_params, lra_ctx_load_local_index (the .gli file's k / w / window override the options', as glIndex.Read does); 7: lra_sort_pairs_batch;  2: lra_map_opts.defer_matches, lra_map_counters.n_deferred_reads; 3: lra_map_opts.flagged_unaligned, lra_map_counters.n_flagged_reads, lra_map_host_flagged; 4: lra_reads_last_error, a corrupt FASTQ record is LRA_ERR_INVALID; lra_map_opts.defer_seed_matches; 5: lra_seed_prefetch, lra_ctx_adopt_seed, lra_map_reads_lowacc_front / _back, lra_map_back_release; 6: a failed front half hands over an error batch (one back call per front call), separate n_handed_back_reads counter, lra_map_host_trim */
+#define LRA_ABI_VERSION 9   /* 9: lra_ctx_release_buffers; later, additively (no struct or signature changed): lra_ctx_set_store_all, lra_ctx_store_all; SAM / BAM input: lra_reads_set_flag_remove, lra_reads_set_passthrough, lra_reads_batch_tags, lra_map_records_tags, lra_map_records_host_tags, lra_bgzf_inflate_batch, lra_bgzf_inflate_host; 8: lra_map_opts_apply_local_index, lra_ctx_local_index_params, lra_ctx_load_local_index (the .gli file's k / w / window override the options', as glIndex.Read does); 7: lra_sort_pairs_batch;  2: lra_map_opts.defer_matches, lra_map_counters.n_deferred_reads; 3: lra_map_opts.flagged_unaligned, lra_map_counters.n_flagged_reads, lra_map_host_flagged; 4: lra_reads_last_error, a corrupt FASTQ record is LRA_ERR_INVALID; lra_map_opts.defer_seed_matches; 5: lra_seed_prefetch, lra_ctx_adopt_seed, lra_map_reads_lowacc_front / _back, lra_map_back_release; 6: a failed front half hands over an error batch (one back call per front call), separate n_handed_back_reads counter, lra_map_host_trim */
 
 /* Convenience for hosts without their own HIP binding: synchronous device->host copy on the
  * context's stream (a C++ host would call hipMemcpy itself).                                */
@@ -1117,7 +1117,14 @@ int lra_map_reads_highacc_batch(lra_ctx* ctx, int n_reads, const char* d_seq, co
  * A FASTQ record whose quality string has another length than its read (the reference asserts, Input.h:287) makes lra_reads_next_batch return LRA_ERR_INVALID
  * on that call and on every later one: the batch of that call holds the reads in front of the record, lra_reads_last_error names the record.
  * lra_map_reads_host is the boundary with host buffers: it copies the batch to the device and calls the driver opts->bypassClustering selects.
- * Not supported: streamed input ("-", "stdin", "/dev/stdin": the format sniffing seeks; the reference reads those through htslib) and BAM input (htslib).  */
+ * SAM (plain or BGZF-compressed) and BAM files are read as GetNext's HTS branch reads them (Input.h:296-393), without htslib: records whose flag meets
+ * lra_reads_set_flag_remove's mask are skipped (-Flag), the bases are the 4-bit codes through "=ACMGRSVTWYHKDBN", the qualities +33; a record without
+ * qualities has quals[i] == NULL.  Where the reference's input stops without a word -- a truncated file, a bad BGZF block, a bad record, a SAM SEQ / QUAL
+ * length mismatch, a file behind a SAM / BAM file (never read), a SAM / BAM file behind a FASTQ file that an empty batch would meet -- the call returns
+ * LRA_ERR_INVALID as for a corrupt FASTQ record: lra_reads_last_error names the file and the reason (a block by its compressed offset, a record by its
+ * index), the batch holds the reads in front of it, and the error is sticky.
+ * Not supported: streamed input ("-", "stdin", "/dev/stdin": the format sniffing seeks; the reference refuses to stream SAM / BAM), CRAM, fastq.gz and
+ * other gzip that is not BGZF (the reference refuses these too).  */
 typedef struct lra_reads lra_reads;
 typedef struct lra_read_batch {
   int32_t n_reads; uint64_t total_bases;
@@ -1141,6 +1148,22 @@ int lra_reads_next_batch_device(lra_reads* r, lra_ctx* ctx, uint64_t max_bases, 
 /* bytes of a file the device form reads and parses per step (default 256 MiB; minimum 4096).  A step holds at least one whole record: one longer than
  * the step makes that step read on.  LRA_ERR_INVALID on a reader that has used lra_reads_next_batch. */
 int lra_reads_set_device_chunk(lra_reads* r, uint64_t bytes);
+/* -Flag and --passthrough of SAM / BAM input (lra.cpp:194, :246): both only before the first batch (after it: LRA_ERR_INVALID).  flags: records with
+ * flag & flags != 0 are skipped.  on (0 / 1): lra_reads_batch_tags gives each SAM / BAM read of the last batch its aux fields as sam_format1 prints them
+ * (the text behind its 11th tab: A as XX:A:c, every integer type as XX:i:<decimal>, f as XX:f:%g, Z and H as written, B as XX:B:<t>,v1,v2...; fields
+ * joined by tabs), NULL for a read without aux fields.  *tags[n_reads] is owned by the reader, valid until the next call; every entry is NULL for
+ * FASTA / FASTQ reads and when passthrough is off. */
+int lra_reads_set_flag_remove(lra_reads* r, uint32_t flags);
+int lra_reads_set_passthrough(lra_reads* r, int on);
+int lra_reads_batch_tags(const lra_reads* r, const char* const** tags);
+/* BGZF inflate (the SAM/BAM spec's section 4.1; RFC 1951 / 1952), the stage the BAM reader runs: member i is in[in_off[i], in_off[i + 1]) -- a gzip
+ * member with a 'BC' field whose BSIZE + 1 is its length --, its data goes to out[out_off[i], out_off[i + 1]), which must be its ISIZE (<= 65536).
+ * status[i]: 0, or the reason the member is bad (1 header, 2 data ends early, 3 more than ISIZE, 4 invalid code, 5 distance before the block, 6 stored
+ * LEN / NLEN, 7 less than ISIZE, 8 CRC-32, 9 ISIZE): nothing outside a member's ranges is read or written.  _batch: device arrays, on ctx's device and
+ * stream, complete at return (one wave per member); _host: host arrays, the same decoder. */
+int lra_bgzf_inflate_batch(lra_ctx* ctx, int n_blocks, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_out_off, uint8_t* d_out,
+                           int32_t* d_status);
+int lra_bgzf_inflate_host(int n_blocks, const uint8_t* in, const uint64_t* in_off, const uint64_t* out_off, uint8_t* out, int32_t* status);
 int lra_map_reads_host(lra_ctx* ctx, int n_reads, const char* h_seq, const uint64_t* h_off, const lra_map_opts* opts, lra_map_result* out);
 int lra_map_records(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* opts, const char* const* names, const char* const* reads,
                     const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* passthrough, char* out, uint64_t cap,
@@ -1163,6 +1186,14 @@ int lra_map_records_host(lra_map_host* snap, const lra_map_opts* opts, const cha
                          const int32_t* read_len, const char* const* chrom_names, const char* passthrough, int n_threads, const char** text, uint64_t* len,
                          const uint64_t** rec_off);
 void lra_map_host_free(lra_map_host* snap);
+/* lra_map_records / lra_map_records_host with one passthrough text per read (NULL: none), as lra_reads_batch_tags gives them: --passthrough of SAM /
+ * BAM input (Alignment.h:797, :900).  The text of a read is that of the functions above with passthrough = passthrough[i]. */
+int lra_map_records_tags(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* opts, const char* const* names, const char* const* reads,
+                         const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough, char* out,
+                         uint64_t cap, uint64_t* len, uint64_t* rec_off);
+int lra_map_records_host_tags(lra_map_host* snap, const lra_map_opts* opts, const char* const* names, const char* const* reads, const char* const* quals,
+                              const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough, int n_threads, const char** text,
+                              uint64_t* len, const uint64_t** rec_off);
 /* the reads of a snapshot whose status word is non-zero: their number; *status (optional) = the snapshot's status array [n_reads], owned by the snapshot */
 uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status);
 /* The record buffer of a batch as ONE device buffer -- what a rank sends to rank 0 in the single exchange step of the multi-GPU path (the

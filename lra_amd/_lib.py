@@ -66,6 +66,11 @@ SYMBOLS = {
     "lra_reads_last_error": (C.c_char_p, [_vp]),
     "lra_reads_next_batch_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "lra_reads_set_device_chunk": (C.c_int, [_vp, C.c_uint64]),
+    "lra_reads_set_flag_remove": (C.c_int, [_vp, C.c_uint32]),
+    "lra_reads_set_passthrough": (C.c_int, [_vp, C.c_int]),
+    "lra_reads_batch_tags": (C.c_int, [_vp, _vp]),
+    "lra_bgzf_inflate_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "lra_bgzf_inflate_host": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lra_host_thread_budget": (C.c_int, []),
     "lra_map_host_trim": (C.c_uint64, [C.c_uint64]),
     "lra_map_reads_host": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
@@ -127,6 +132,8 @@ SYMBOLS = {
     "lra_map_pack": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "lra_map_unpack_host": (C.c_int, [_vp, C.c_uint64, _vp]),
     "lra_map_records": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_char_p, _vp, C.c_uint64, _vp, _vp]),
+    "lra_map_records_tags": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp]),
+    "lra_map_records_host_tags": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "lra_filter_chains_batch": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "lra_filter_chains_ex_batch": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "lra_calculate_statistics_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),

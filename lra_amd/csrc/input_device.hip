@@ -1,4 +1,4 @@
-// lra_amd/csrc/input_device.hip -- lra_reads_next_batch with the parsing on the device (lra_reads_next_batch_device).
+// lra_amd/csrc/input_device.hip -- lra_reads_next_batch with the parsing on the device (lra_reads_next_batch_device); BAM steps with input_bam.hip.
 //
 // The batches are those of lra_reads_next_batch (input.hip: Input::Initialize / GetNext / BufferedRead, quirks included); only where the bytes are parsed
 // differs.  Split:
@@ -19,6 +19,8 @@
 #include "common.h"
 #include "reads_state.h"
 #include "scan.h"
+#include "bam_kernels.h"
+#include "bgzf.h"
 #include <fcntl.h>
 #include <unistd.h>
 #include <algorithm>
@@ -27,15 +29,6 @@ namespace {
 
 constexpr int RD_NT = 256, RD_BPT = 16, RD_TILE = RD_NT * RD_BPT;   // a workgroup per 4 KiB tile, 16 bytes per lane (one 128-bit load)
 
-struct RecInfo {            // one per record of a step (device-written, copied back whole)
-  uint64_t start;           // byte of the header line's start in the step
-  uint64_t seq;             // kept sequence bytes of the step in front of the record
-  uint64_t qual;            // kept quality bytes in front of the record (its qualities sit at qual + record index: one NUL slot per record)
-  uint64_t name;            // offset of its name in the step's name buffer
-  uint64_t tok;             // byte of the name token's start
-  uint32_t tok_len;
-  uint32_t flags;           // FASTQ: bit i = line i of the record is empty
-};
 
 __device__ inline void load16(const unsigned char* __restrict__ raw, uint64_t p, unsigned char b[RD_BPT]) {
   const uint4 v = *reinterpret_cast<const uint4*>(raw + p);
@@ -281,11 +274,25 @@ struct lra_reads_dev {
   std::vector<const char*> name_ptr, seq_ptr, qual_ptr;
   uint64_t seg_a = 0, seg_b = 0;                   // the pending run of this step's records [seg_a, seg_b) not yet copied to the batch
   uint64_t b_seq = 0, b_names = 0, b_quals = 0;    // the batch's bytes so far
+  // BAM (input_bam.hip's kernels): h_raw holds compressed bytes; a step inflates its whole members behind the carried tail of the last step's data
+  uint64_t bam_skip = 0;                           // header bytes still to skip in the decompressed stream
+  uint64_t comp_file_off = 0;                      // file offset of h_raw[0]
+  uint64_t bam_rec_base = 0;                       // records framed by the file's earlier steps
+  DevBuf<uint8_t> d_comp, d_dec[2]; int dec_cur = 0; uint64_t dec_len = 0, dec_used = 0;
+  DevBuf<uint64_t> d_boff, rec_pos, bam_out; DevBuf<int32_t> d_bstat; DevBuf<uint32_t> bcnt[5]; DevBuf<uint64_t> boffs[5];
+  DevBuf<unsigned long long> first_bad; DevBuf<uint8_t> c_aux;
+  std::vector<uint8_t> h_aux;                      // the step's aux bytes (passthrough on)
+  std::string pending_error;                       // the step stops at a problem: the error once its records are taken
+  // records parsed on the host (SAM text) in the device form's batch: their bases go up at the batch's end
+  std::string h_pend; std::vector<uint64_t> pend_at;
   ~lra_reads_dev() {
     if (fd >= 0) close(fd);
     h_raw.release(); d_raw.release(); nl_pos.release(); d_rec.release(); name_len.release(); name_off.release();
     for (int i = 0; i < 4; i++) { cnt[i].release(); base[i].release(); }
     c_seq.release(); c_qual.release(); c_names.release(); d_seq.release(); d_off.release(); h_seq.release(); h_names.release(); h_quals.release();
+    d_comp.release(); d_dec[0].release(); d_dec[1].release(); d_boff.release(); rec_pos.release(); bam_out.release(); d_bstat.release();
+    for (int i = 0; i < 5; i++) { bcnt[i].release(); boffs[i].release(); }
+    first_bad.release(); c_aux.release();
   }
 };
 
@@ -323,6 +330,19 @@ bool open_dev_file(lra_reads* r) {
   d->len = d->consumed = 0; d->file_at_eof = false; d->fq_eof = false;
   d->rec.clear(); d->n_avail = d->next = 0; d->step_ends_file = false;
   d->seg_a = d->seg_b = 0;
+  r->hts.reset();
+  if (d->fd >= 0 && d->type < 0) {                                 // SAM / BAM (input.hip's sniffing)
+    uint64_t header = 0;
+    d->type = lra_hts_sniff(r->files[r->cur], &header);
+    if (d->type == LRA_IN_BAM) {
+      d->bam_skip = header; d->comp_file_off = 0; d->bam_rec_base = 0; d->dec_len = d->dec_used = 0; d->pending_error.clear();
+    } else if (d->type == LRA_IN_SAM) {                            // parsed on the host: the compatibility path
+      std::string err;
+      r->hts.reset(lra_hts_open(r->files[r->cur], LRA_IN_SAM, &err));
+      if (!r->hts) d->type = -1;
+    }
+  }
+  r->type = d->type;
   return d->type >= 0;
 }
 
@@ -350,7 +370,7 @@ int flush_segment(lra_ctx* ctx, lra_reads_dev* d) {
   if (ns) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_seq.p + d->b_seq, d->c_seq.p + A.seq, ns, hipMemcpyDeviceToDevice, ctx->stream));
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->h_names.p + d->b_names, d->c_names.p + A.name, nn, hipMemcpyDeviceToHost, ctx->stream));
   d->b_seq += ns; d->b_names += nn;
-  if (d->type == 1) {
+  if (d->type == LRA_IN_FASTQ || d->type == LRA_IN_BAM) {
     const uint64_t nq = (B.qual + b) - (A.qual + a);
     if (!d->h_quals.ensure(d->b_quals + nq, d->b_quals, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc failed");
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->h_quals.p + d->b_quals, d->c_qual.p + A.qual + a, nq, hipMemcpyDeviceToHost, ctx->stream));
@@ -463,6 +483,160 @@ int next_step(lra_ctx* ctx, lra_reads* r) {
   }
 }
 
+// the next step of a BAM file: whole BGZF members of up to `chunk` compressed bytes (a member the step cut stays on the host for the next one) inflated
+// behind the undecoded tail of the last step's data (a record the step cut, carried device to device), framed and decoded into the step's record
+// table.  A step that holds no whole record (and is not the file's end) reads on, twice as much each time.
+int next_step_bam(lra_ctx* ctx, lra_reads* r) {
+  lra_reads_dev* d = r->dev;
+  if (int rc = flush_segment(ctx, d)) return rc;
+  hipStream_t st = ctx->stream;
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  if (d->consumed) {
+    memmove(d->h_raw.p, d->h_raw.p + d->consumed, d->len - d->consumed);
+    d->len -= d->consumed; d->comp_file_off += d->consumed; d->consumed = 0;
+  }
+  const int src = d->dec_cur, dst = d->dec_cur ^ 1;
+  const uint64_t carry = d->dec_len - d->dec_used;
+  uint64_t want = d->chunk;
+  for (;;) {
+    if (!d->file_at_eof) {
+      if (!d->h_raw.ensure(d->len + want + 1, d->len, st)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc(%zu) failed", (size_t)(d->len + want));
+      uint64_t got = 0;
+      while (got < want) {
+        const ssize_t k = read(d->fd, d->h_raw.p + d->len + got, (size_t)std::min<uint64_t>(want - got, 1ull << 30));
+        if (k < 0) return lra_set_err(ctx, LRA_ERR_INVALID, "device reader: read of %s failed", r->files[r->cur].c_str());
+        if (k == 0) { d->file_at_eof = true; break; }
+        got += (uint64_t)k;
+      }
+      d->len += got;
+    }
+    // the members: host walk of the BGZF headers, one hop per member
+    std::vector<uint64_t> in_off(1, 0), out_off(1, carry);
+    std::string block_err;
+    const uint8_t* h = (const uint8_t*)d->h_raw.p;
+    uint64_t p = 0;
+    while (p < d->len) {
+      uint32_t total = 0, cdata = 0;
+      const int m = lra_bgzf_member(h + p, d->len - p, &total, &cdata);
+      if (m < 0) { block_err = "not a BGZF block"; break; }
+      if (m == 0 || p + total > d->len) { if (d->file_at_eof) block_err = "the file ends inside it"; break; }
+      const uint32_t isize = lra_le32(h + p + total - 4);
+      if (isize > 65536) { block_err = "a bad ISIZE"; break; }
+      p += total;
+      in_off.push_back(p); out_off.push_back(out_off.back() + isize);
+    }
+    const int nb = (int)in_off.size() - 1;
+    if (nb == 0 && block_err.empty() && !d->file_at_eof) { want = std::max(want, d->len) * 2; continue; }
+    const uint64_t dlen_all = out_off.back();
+    if (!d->d_comp.ensure(p + 1) || !d->d_boff.ensure(2 * (size_t)(nb + 1)) || !d->d_bstat.ensure(nb + 1) || !d->d_dec[dst].ensure(dlen_all + 64))
+      return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
+    lra_time_begin(ctx, "input_h2d");
+    if (p) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_comp.p, h, p, hipMemcpyHostToDevice, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_boff.p, in_off.data(), (nb + 1) * 8, hipMemcpyHostToDevice, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_boff.p + nb + 1, out_off.data(), (nb + 1) * 8, hipMemcpyHostToDevice, st));
+    lra_time_end(ctx);
+    if (carry) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_dec[dst].p, d->d_dec[src].p + d->dec_used, carry, hipMemcpyDeviceToDevice, st));
+    lra_time_begin(ctx, "input_inflate");
+    lra_bgzf_launch_inflate(st, nb, d->d_comp.p, d->d_boff.p, d->d_boff.p + nb + 1, d->d_dec[dst].p, d->d_bstat.p);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    lra_time_end(ctx);
+    std::vector<int32_t> bst((size_t)nb);
+    if (nb) LRA_HIP_CHECK(ctx, hipMemcpyAsync(bst.data(), d->d_bstat.p, nb * 4, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    int good = nb;
+    for (int b = 0; b < nb; b++) if (bst[b]) { good = b; break; }
+    std::string err;
+    if (good < nb) err = r->files[r->cur] + ": a bad BGZF block at compressed offset " + std::to_string(d->comp_file_off + in_off[good]) + " (" + lra_bgzf_reason(bst[good]) + ")";
+    else if (!block_err.empty()) err = r->files[r->cur] + ": a bad BGZF block at compressed offset " + std::to_string(d->comp_file_off + p) + " (" + block_err + ")";
+    const uint64_t dlen = out_off[good];
+    const bool at_end = !err.empty() || (d->file_at_eof && p == d->len);   // no byte of the file behind this step's data
+    // the header, then the chain of block_size fields
+    const uint64_t start = std::min(d->bam_skip, dlen);
+    const uint64_t cap = (dlen - start) / 36 + 1;
+    if (!d->rec_pos.ensure(cap) || !d->bam_out.ensure(4)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
+    uint64_t fr[4] = {0, start, 0, 0};
+    lra_time_begin(ctx, "input_frame");
+    if (dlen > start) {
+      lra_bam_launch_frame(st, d->d_dec[dst].p, start, dlen, d->rec_pos.p, cap, d->bam_out.p);
+      LRA_HIP_CHECK(ctx, hipMemcpyAsync(fr, d->bam_out.p, 32, hipMemcpyDeviceToHost, st));
+      LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    }
+    lra_time_end(ctx);
+    const uint64_t n = fr[0];
+    if (n == 0 && !at_end && fr[2] == 0 && dlen > start) { want = std::max(want, d->len) * 2; continue; }   // one record longer than the step
+    // the records: validate, flagRemove, counts -> scans -> emit
+    for (int i = 0; i < 5; i++)
+      if (!d->bcnt[i].ensure(n + 1) || !d->boffs[i].ensure(n + 2)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
+    if (!d->first_bad.ensure(1) || !d->d_rec.ensure(n + 1)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
+    lra_time_begin(ctx, "input_decode");
+    const unsigned long long none = ~0ull;
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->first_bad.p, &none, 8, hipMemcpyHostToDevice, st));
+    uint32_t* cnt[5]; uint64_t* offs[5];
+    for (int i = 0; i < 5; i++) { cnt[i] = d->bcnt[i].p; offs[i] = d->boffs[i].p; }
+    lra_bam_launch_count(st, d->d_dec[dst].p, d->rec_pos.p, n, r->flag_remove, cnt, d->first_bad.p);
+    for (int i = 0; i < 5; i++) if (int rc = lra_exclusive_scan(ctx, (long)n, cnt[i], offs[i])) return rc;
+    uint64_t tot[5];
+    for (int i = 0; i < 5; i++) LRA_HIP_CHECK(ctx, hipMemcpyAsync(&tot[i], offs[i] + n, 8, hipMemcpyDeviceToHost, st));
+    unsigned long long fb = none;
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&fb, d->first_bad.p, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    const uint64_t n_kept = tot[0];
+    if (!d->c_seq.ensure(tot[1] + 1) || !d->c_qual.ensure(tot[2] + n_kept + 1) || !d->c_names.ensure(tot[3] + 1) || !d->c_aux.ensure(tot[4] + 1))
+      return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
+    lra_bam_launch_emit(st, d->d_dec[dst].p, d->rec_pos.p, n, d->bcnt[0].p, offs, d->c_seq.p, d->c_qual.p, d->c_names.p, d->c_aux.p, d->d_rec.p);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    lra_time_end(ctx);
+    d->rec.resize(n_kept + 1);
+    lra_time_begin(ctx, "input_d2h");
+    if (n_kept) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->rec.data(), d->d_rec.p, n_kept * sizeof(RecInfo), hipMemcpyDeviceToHost, st));
+    d->h_aux.resize(r->passthrough ? tot[4] : 0);
+    if (r->passthrough && tot[4]) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->h_aux.data(), d->c_aux.p, tot[4], hipMemcpyDeviceToHost, st));
+    uint64_t kept_before_bad = n_kept;
+    if (fb < n) LRA_HIP_CHECK(ctx, hipMemcpyAsync(&kept_before_bad, offs[0] + fb, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    lra_time_end(ctx);
+    RecInfo& sent = d->rec[n_kept];
+    memset(&sent, 0, sizeof sent);
+    sent.start = n; sent.seq = tot[1]; sent.qual = tot[2]; sent.name = tot[3]; sent.tok = tot[4];
+    // where the step stops: a bad record, a bad block, the end of the file inside a record
+    const std::string where = "record " + std::to_string(d->bam_rec_base + std::min<uint64_t>(fb, n)) + " of " + r->files[r->cur];
+    d->pending_error.clear();
+    if (fb < n) d->pending_error = where + ": a bad record";         // (the messages of input.hip's lra_hts_next: both forms say the same)
+    else if (fr[2]) d->pending_error = where + ": a bad record (block_size " + std::to_string(fr[3]) + ")";
+    else if (!err.empty()) d->pending_error = err;
+    else if (at_end && fr[1] < dlen) d->pending_error = where + ": cut by the end of the file";
+    d->n_avail = fb < n ? kept_before_bad : n_kept;
+    d->next = d->seg_a = d->seg_b = 0;
+    d->step_ends_file = at_end || !d->pending_error.empty();
+    d->bam_skip -= start;
+    d->bam_rec_base += n;
+    d->consumed = p;
+    d->dec_cur = dst; d->dec_len = dlen; d->dec_used = fr[1];
+    return LRA_OK;
+  }
+}
+
+// GetNext's HTS branch over the BAM steps (both forms share input.hip's rules: flagRemove, the errors, no file read behind a SAM / BAM file)
+int get_next_bam_dev(lra_ctx* ctx, lra_reads* r, bool* got, uint64_t* idx) {
+  lra_reads_dev* d = r->dev;
+  *got = false;
+  while (!d->started || d->next >= d->n_avail) {
+    if (d->started && d->step_ends_file) {
+      if (int rc = flush_segment(ctx, d)) return rc;
+      r->open_ok = false;
+      if (!d->pending_error.empty()) r->error = d->pending_error;
+      else if (r->cur + 1 < r->files.size())
+        r->error = r->files[r->cur + 1] + ": not read: the reference reads no file behind a SAM / BAM file (" + r->files[r->cur] + ")";
+      return LRA_OK;
+    }
+    d->started = true;
+    if (int rc = next_step_bam(ctx, r)) return rc;
+  }
+  r->hts_unread = false;
+  *got = true; *idx = d->next++;
+  return LRA_OK;
+}
+
 // the next record (FASTA) or 4-line unit (FASTQ) of the current file; false: a FASTA file is over
 int next_unit(lra_ctx* ctx, lra_reads* r, Unit* u, bool* have) {
   lra_reads_dev* d = r->dev;
@@ -499,15 +673,22 @@ int open_next_file(lra_reads* r, bool* ok) {
 }
 
 // Input::GetNext (input.hip get_next) over the step's record table; *got: a record was taken (its index in d->rec)
-int get_next_dev(lra_ctx* ctx, lra_reads* r, bool* got, uint64_t* idx) {
+// SAM / BAM: a BAM record is an entry of the step's table; a SAM record is parsed on the host (*host, in *hrec)
+int get_next_dev(lra_ctx* ctx, lra_reads* r, bool* got, uint64_t* idx, lra_hts_rec* hrec, bool* host) {
   lra_reads_dev* d = r->dev;
-  *got = false;
+  *got = false; *host = false;
   if (!r->open_ok) return LRA_OK;
   if (d->type == 0 && fasta_dry(d)) {
     if (int rc = flush_segment(ctx, d)) return rc;
     bool ok;
     open_next_file(r, &ok);
     if (!ok) { r->open_ok = false; return LRA_OK; }
+  }
+  if (d->type == LRA_IN_BAM) return get_next_bam_dev(ctx, r, got, idx);
+  if (d->type == LRA_IN_SAM) {
+    if (int rc = flush_segment(ctx, d)) return rc;
+    *got = *host = lra_hts_get_next(r, hrec);
+    return LRA_OK;
   }
   if (d->type == 1 && d->fq_eof) return LRA_OK;
   Unit u; bool have;
@@ -524,6 +705,7 @@ int get_next_dev(lra_ctx* ctx, lra_reads* r, bool* got, uint64_t* idx) {
     bool ok;
     open_next_file(r, &ok);
     if (!ok) { r->open_ok = false; return LRA_OK; }
+    if (d->type >= LRA_IN_BAM) { r->hts_unread = true; return LRA_OK; }   // Input.h:242-266: re-initialized, returns 0
     if (d->type == 1) {
       if (int rc = next_unit(ctx, r, &u, &have)) return rc;
       if (!have) return LRA_OK;
@@ -573,11 +755,38 @@ extern "C" int lra_reads_next_batch_device(lra_reads* r, lra_ctx* ctx, uint64_t 
   d->b_seq = d->b_names = d->b_quals = 0;
   d->seg_a = d->seg_b = d->next;
   d->off.assign(1, 0); d->name_off_h.assign(1, 0); d->qual_off_h.assign(1, 0); d->len_h.clear(); d->hasq.clear();
+  d->h_pend.clear(); d->pend_at.clear();
+  r->tags.clear(); r->tag_ptr.clear();
+  std::vector<uint8_t> hast;
   uint64_t total = 0;
+  lra_hts_rec hrec;
   while (total < max_bases) {                                      // BufferedRead
-    bool got = false; uint64_t i = 0;
-    if (int rc = get_next_dev(ctx, r, &got, &i)) return rc;
+    bool got = false, host = false; uint64_t i = 0;
+    if (int rc = get_next_dev(ctx, r, &got, &i, &hrec, &host)) return rc;
     if (!got) break;
+    std::string tag;
+    if (host) {                                                    // a SAM record: its bytes straight into the batch's arrays
+      const uint64_t sl = hrec.seq.size(), nn = hrec.name.size() + 1, nq = hrec.qual.size() + 1;
+      if (int rc = grow_batch_seq(ctx, d, d->b_seq + sl + 64)) return rc;
+      if (!d->h_names.ensure(d->b_names + nn, d->b_names, ctx->stream) || !d->h_quals.ensure(d->b_quals + nq, d->b_quals, ctx->stream))
+        return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc failed");
+      memcpy(d->h_names.p + d->b_names, hrec.name.c_str(), nn);
+      memcpy(d->h_quals.p + d->b_quals, hrec.qual.c_str(), nq);
+      d->pend_at.push_back(d->b_seq); d->pend_at.push_back(d->h_pend.size()); d->pend_at.push_back(sl);
+      d->h_pend += hrec.seq;
+      d->b_seq += sl; d->b_names += nn; d->b_quals += nq;
+      total += sl;
+      d->off.push_back(d->off.back() + sl);
+      d->name_off_h.push_back(d->name_off_h.back() + nn);
+      d->qual_off_h.push_back(d->qual_off_h.back() + nq);
+      d->len_h.push_back((int32_t)sl);
+      d->hasq.push_back(hrec.has_qual);
+      const bool t = r->passthrough && lra_format_aux((const uint8_t*)hrec.aux.data(), hrec.aux.size(), &tag);
+      hast.push_back(t); r->tags.push_back(t ? tag : std::string());
+      continue;
+    }
+    const bool t = d->type == LRA_IN_BAM && r->passthrough && d->rec[i].tok_len && lra_format_aux(d->h_aux.data() + d->rec[i].tok, d->rec[i].tok_len, &tag);
+    hast.push_back(t); r->tags.push_back(t ? tag : std::string());
     if (i != d->seg_b) { if (int rc = flush_segment(ctx, d)) return rc; d->seg_a = i; }
     d->seg_b = i + 1;
     const RecInfo& a = d->rec[i]; const RecInfo& c = d->rec[i + 1];
@@ -585,13 +794,16 @@ extern "C" int lra_reads_next_batch_device(lra_reads* r, lra_ctx* ctx, uint64_t 
     total += sl;
     d->off.push_back(d->off.back() + sl);
     d->name_off_h.push_back(d->name_off_h.back() + (c.name - a.name));
-    d->qual_off_h.push_back(d->qual_off_h.back() + (d->type == 1 ? (c.qual - a.qual) + 1 : 1));
+    d->qual_off_h.push_back(d->qual_off_h.back() + (d->type != LRA_IN_FASTA ? (c.qual - a.qual) + 1 : 1));
     d->len_h.push_back((int32_t)sl);
-    d->hasq.push_back(d->type == 1);
+    d->hasq.push_back(d->type == LRA_IN_FASTQ || (d->type == LRA_IN_BAM && (a.flags & 1)));
   }
   if (int rc = flush_segment(ctx, d)) return rc;
   const size_t n = d->len_h.size();
+  lra_reads_check_unread(r, n);
   if (int rc = grow_batch_seq(ctx, d, total + 64)) return rc;
+  for (size_t k = 0; k < d->pend_at.size(); k += 3)               // the SAM records' bases
+    if (d->pend_at[k + 2]) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_seq.p + d->pend_at[k], d->h_pend.data() + d->pend_at[k + 1], d->pend_at[k + 2], hipMemcpyHostToDevice, ctx->stream));
   if (!d->d_off.ensure(n + 1) || !d->h_seq.ensure(total + 64, 0, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: allocation failed");
   if (!d->h_names.ensure(d->b_names + 1, d->b_names, ctx->stream) || !d->h_quals.ensure(d->b_quals + 1, d->b_quals, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: allocation failed");
   LRA_HIP_CHECK(ctx, hipMemsetAsync(d->d_seq.p + total, 0, 64, ctx->stream));
@@ -605,6 +817,8 @@ extern "C" int lra_reads_next_batch_device(lra_reads* r, lra_ctx* ctx, uint64_t 
     d->name_ptr[k] = d->h_names.p + d->name_off_h[k]; d->seq_ptr[k] = d->h_seq.p + d->off[k];
     d->qual_ptr[k] = d->hasq[k] ? d->h_quals.p + d->qual_off_h[k] : nullptr;
   }
+  r->tag_ptr.resize(n);
+  for (size_t k = 0; k < n; k++) r->tag_ptr[k] = hast[k] ? r->tags[k].c_str() : nullptr;
   b->n_reads = (int32_t)n; b->total_bases = total; b->seq = d->h_seq.p; b->off = d->off.data(); b->read_len = d->len_h.data();
   b->names = d->name_ptr.data(); b->reads = d->seq_ptr.data(); b->quals = d->qual_ptr.data();
   *d_seq = d->d_seq.p; *d_off = d->d_off.p;

@@ -1406,9 +1406,10 @@ extern "C" int lra_map_snapshot(lra_ctx* ctx, const lra_map_result* res, int wit
   return LRA_OK;
 }
 
-extern "C" int lra_map_records_host(lra_map_host* h, const lra_map_opts* o, const char* const* names, const char* const* reads, const char* const* quals,
-                                    const int32_t* read_len, const char* const* chrom_names, const char* passthrough, int n_threads, const char** text,
-                                    uint64_t* len, const uint64_t** rec_off) {
+// passthrough: the text behind every read's records; tags (when not NULL) instead: one per read, NULL = none (--passthrough of SAM / BAM input)
+static int records_host(lra_map_host* h, const lra_map_opts* o, const char* const* names, const char* const* reads, const char* const* quals,
+                        const int32_t* read_len, const char* const* chrom_names, const char* passthrough, const char* const* tags, int n_threads,
+                        const char** text, uint64_t* len, const uint64_t** rec_off) {
   if (!h || !o || !names || !reads || !read_len || !chrom_names || !len) return LRA_ERR_INVALID;
   const size_t nA = h->nA, nJ = h->nJ;
   (void)nA;
@@ -1529,7 +1530,7 @@ extern "C" int lra_map_records_host(lra_map_host* h, const lra_map_opts* o, cons
         lra_aln_record un; memset(&un, 0, sizeof un);
         un.read_name = names[r]; un.read = reads[r]; un.qual = quals ? quals[r] : nullptr; un.read_len = read_len[r];
         const size_t before = text.size();
-        if ((rc = lra_output_read_str(nullptr, nullptr, 0, nullptr, o->PrintNumAln, (char)o->printFormat, o->hardClip, passthrough, 1, &un, text))) break;
+        if ((rc = lra_output_read_str(nullptr, nullptr, 0, nullptr, o->PrintNumAln, (char)o->printFormat, o->hardClip, tags ? tags[r] : passthrough, 1, &un, text))) break;
         need = text.size() - before;
       } else {
         const int n = (int)seg_off.size() - 1;
@@ -1540,7 +1541,7 @@ extern "C" int lra_map_records_host(lra_map_host* h, const lra_map_opts* o, cons
           break;
         // (the records' text goes straight into the thread's part, written once: the sizing-then-filling calls of the C entry points formatted every record four times)
         const size_t before = text.size();
-        if ((rc = lra_output_read_str(groups.data(), index.data(), n, recs.data(), o->PrintNumAln, (char)o->printFormat, o->hardClip, passthrough, 0, nullptr, text))) break;
+        if ((rc = lra_output_read_str(groups.data(), index.data(), n, recs.data(), o->PrintNumAln, (char)o->printFormat, o->hardClip, tags ? tags[r] : passthrough, 0, nullptr, text))) break;
         need = text.size() - before;
       }
       plen[tix].push_back(need);
@@ -1580,14 +1581,29 @@ extern "C" int lra_map_records_host(lra_map_host* h, const lra_map_opts* o, cons
   return LRA_OK;
 }
 
-extern "C" int lra_map_records(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
-                               const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* passthrough, char* out,
-                               uint64_t cap, uint64_t* len, uint64_t* rec_off) {
+extern "C" int lra_map_records_host(lra_map_host* h, const lra_map_opts* o, const char* const* names, const char* const* reads, const char* const* quals,
+                                    const int32_t* read_len, const char* const* chrom_names, const char* passthrough, int n_threads, const char** text,
+                                    uint64_t* len, const uint64_t** rec_off) {
+  return records_host(h, o, names, reads, quals, read_len, chrom_names, passthrough, nullptr, n_threads, text, len, rec_off);
+}
+
+extern "C" int lra_map_records_host_tags(lra_map_host* h, const lra_map_opts* o, const char* const* names, const char* const* reads, const char* const* quals,
+                                         const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough, int n_threads,
+                                         const char** text, uint64_t* len, const uint64_t** rec_off) {
+  if (!passthrough) return LRA_ERR_INVALID;
+  return records_host(h, o, names, reads, quals, read_len, chrom_names, nullptr, passthrough, n_threads, text, len, rec_off);
+}
+
+static int map_records(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
+                       const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* passthrough, const char* const* tags,
+                       char* out, uint64_t cap, uint64_t* len, uint64_t* rec_off) {
   if (!ctx || !res || !o || !names || !reads || !read_len || !chrom_names || !len) return LRA_ERR_INVALID;
   lra_map_state* m = ctx->map;
   if (!m) return LRA_ERR_INVALID;
-  // two-call convention: the sizing call keeps its text, the filling call for the same result and format hands it over
-  const lra_map_sig sig{res->d_blocks, res->d_runs, res->n_reads, res->n_alignments, o->printFormat, o->PrintNumAln, o->hardClip, passthrough, o->flagged_unaligned, res->d_read_status};
+  // two-call convention: the sizing call keeps its text, the filling call for the same result and format hands it over (per-read tags: their array
+  // stands where the one passthrough text does)
+  const lra_map_sig sig{res->d_blocks, res->d_runs, res->n_reads, res->n_alignments, o->printFormat, o->PrintNumAln, o->hardClip,
+                        tags ? (const char*)tags : passthrough, o->flagged_unaligned, res->d_read_status};
   if (out && m->last_sig == sig && !m->last_text.empty() && cap >= m->last_text.size()) {
     memcpy(out, m->last_text.data(), m->last_text.size());
     *len = m->last_text.size();
@@ -1599,7 +1615,7 @@ extern "C" int lra_map_records(lra_ctx* ctx, const lra_map_result* res, const lr
   int rc = lra_map_snapshot(ctx, res, o->printFormat == 'a', &h);
   if (rc) return rc;
   const char* text = nullptr; const uint64_t* ro = nullptr;
-  rc = lra_map_records_host(h, o, names, reads, quals, read_len, chrom_names, passthrough, 0, &text, len, &ro);
+  rc = records_host(h, o, names, reads, quals, read_len, chrom_names, passthrough, tags, 0, &text, len, &ro);
   if (rc) { lra_map_host_free(h); return rc; }
   if (rec_off) memcpy(rec_off, ro, ((size_t)res->n_reads + 1) * 8);
   if (!out) {                                                            // sizing call: remember text and offsets
@@ -1612,4 +1628,17 @@ extern "C" int lra_map_records(lra_ctx* ctx, const lra_map_result* res, const lr
   memcpy(out, text, *len);
   lra_map_host_free(h);
   return LRA_OK;
+}
+
+extern "C" int lra_map_records(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
+                               const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* passthrough, char* out,
+                               uint64_t cap, uint64_t* len, uint64_t* rec_off) {
+  return map_records(ctx, res, o, names, reads, quals, read_len, chrom_names, passthrough, nullptr, out, cap, len, rec_off);
+}
+
+extern "C" int lra_map_records_tags(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
+                                    const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough,
+                                    char* out, uint64_t cap, uint64_t* len, uint64_t* rec_off) {
+  if (!passthrough) return LRA_ERR_INVALID;
+  return map_records(ctx, res, o, names, reads, quals, read_len, chrom_names, nullptr, passthrough, out, cap, len, rec_off);
 }

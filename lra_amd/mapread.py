@@ -330,12 +330,16 @@ class LowAccMapper:
         return bool(getattr(self.opts, "printMD", False)) if hasattr(self, "opts") else bool(getattr(self, "printMD", False))
 
     def records(self, res: MapResult, names, reads, quals=None, passthrough=None):
-        """lra_map_records: one bytes object per read in opts.printFormat (with printMD: the snapshot form, packed with LRA_PACK_MD)."""
+        """lra_map_records: one bytes object per read in opts.printFormat (with printMD: the snapshot form, packed with LRA_PACK_MD).  passthrough: one
+        text for every read, or a list with one per read (None: no tags; lra_map_records_tags, --passthrough of SAM / BAM input)."""
         ctx = self.ctx
         n = int(res.n_reads)
         if self.print_md:
             snap = self.snapshot(res, with_blocks=chr(self.copts.printFormat) == "a")
             return self.records_host(snap, self.record_args(names, reads, quals), passthrough=passthrough)
+        per_read = isinstance(passthrough, (list, tuple))
+        if per_read:
+            passthrough = (C.c_char_p * n)(*[None if t is None else bytes(t) for t in passthrough])
         enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
         nm = [enc(x) for x in names]; rd = [bytes(x) for x in reads]
         a_names = (C.c_char_p * n)(*nm); a_reads = (C.c_char_p * n)(*rd)
@@ -345,9 +349,10 @@ class LowAccMapper:
         ln = C.c_uint64(0)
         roff = (C.c_uint64 * (n + 1))()
         args = (ctx.h, C.byref(res), C.byref(self.copts), a_names, a_reads, a_quals, a_len, a_chr, passthrough)
-        ctx.check(ctx.lib.lra_map_records(*args, None, C.c_uint64(0), C.byref(ln), roff))
+        fn = ctx.lib.lra_map_records_tags if per_read else ctx.lib.lra_map_records
+        ctx.check(fn(*args, None, C.c_uint64(0), C.byref(ln), roff))
         buf = C.create_string_buffer(ln.value + 1)
-        ctx.check(ctx.lib.lra_map_records(*args, buf, C.c_uint64(ln.value), C.byref(ln), roff))
+        ctx.check(fn(*args, buf, C.c_uint64(ln.value), C.byref(ln), roff))
         raw = buf.raw
         return [raw[roff[i]:roff[i + 1]] for i in range(n)]
 
@@ -373,8 +378,12 @@ class LowAccMapper:
         ctypes releases the GIL).  -> list of per-read bytes, or the total number of bytes when as_list is False."""
         lib = self.ctx.lib
         text = C.c_char_p(); ln = C.c_uint64(0); roff = C.POINTER(C.c_uint64)()
-        rc = lib.lra_map_records_host(snap, C.byref(self.copts), args["names"], args["reads"], args["quals"], args["lens"], args["chroms"], passthrough,
-                                      int(n_threads), C.byref(text), C.byref(ln), C.byref(roff))
+        fn = lib.lra_map_records_host
+        if isinstance(passthrough, (list, tuple)):
+            fn = lib.lra_map_records_host_tags
+            passthrough = (C.c_char_p * args["n"])(*[None if t is None else bytes(t) for t in passthrough])
+        rc = fn(snap, C.byref(self.copts), args["names"], args["reads"], args["quals"], args["lens"], args["chroms"], passthrough,
+                int(n_threads), C.byref(text), C.byref(ln), C.byref(roff))
         if rc != 0:
             lib.lra_map_host_free(snap)
             raise RuntimeError("lra_map_records_host failed (%d)" % rc)

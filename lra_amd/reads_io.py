@@ -1,4 +1,4 @@
-"""ctypes mirror of the input side (lra_amd/csrc/input.hip): FASTA / FASTQ batches and the host-buffer boundary.  Tests and tools only."""
+"""ctypes mirror of the input side (lra_amd/csrc/input.hip): FASTA / FASTQ / SAM / BAM batches and the host-buffer boundary.  Tests and tools only."""
 import ctypes as C
 
 import numpy as np
@@ -13,9 +13,10 @@ class ReadBatchC(C.Structure):
 
 class ReadsFile:
     """ctx=None: lra_reads_next_batch (host parsing).  With a Context: lra_reads_next_batch_device (the parsing on that context's GPU; chunk = the bytes
-    of a file it reads and parses per step, lra_reads_set_device_chunk; None keeps the library's default)."""
+    of a file it reads and parses per step, lra_reads_set_device_chunk; None keeps the library's default).  flag_remove: SAM / BAM records whose flag
+    meets it are skipped (-Flag); passthrough: each SAM / BAM read's aux fields in the batch's "tags" (--passthrough)."""
 
-    def __init__(self, files, ctx=None, chunk=None):
+    def __init__(self, files, ctx=None, chunk=None, flag_remove=0, passthrough=False):
         self.lib = load_library()
         self.ctx = ctx
         arr = (C.c_char_p * len(files))(*[f.encode() if isinstance(f, str) else f for f in files])
@@ -28,6 +29,10 @@ class ReadsFile:
             if rc != 0:
                 self.close()
                 raise ValueError("lra_reads_set_device_chunk(%d) failed (%d)" % (int(chunk), rc))
+        if flag_remove or passthrough:
+            if self.lib.lra_reads_set_flag_remove(self.h, int(flag_remove)) != 0 or self.lib.lra_reads_set_passthrough(self.h, int(bool(passthrough))) != 0:
+                self.close()
+                raise ValueError("lra_reads_set_flag_remove / lra_reads_set_passthrough failed")
 
     def next_batch(self, max_bases):
         """-> None at the end, else dict(names, seqs, quals (None for FASTA reads), off, raw=(ReadBatchC kept alive until the next call)); the device form
@@ -45,7 +50,10 @@ class ReadsFile:
         if n:
             off = np.ctypeslib.as_array(b.off, shape=(n + 1,)).copy()
             seq = C.string_at(b.seq, int(b.total_bases))
-            out = dict(names=[b.names[i] for i in range(n)], seqs=[seq[int(off[i]):int(off[i + 1])] for i in range(n)], quals=[b.quals[i] for i in range(n)], off=off, raw=b)
+            tags = C.POINTER(C.c_char_p)()
+            self.lib.lra_reads_batch_tags(self.h, C.byref(tags))
+            out = dict(names=[b.names[i] for i in range(n)], seqs=[seq[int(off[i]):int(off[i + 1])] for i in range(n)], quals=[b.quals[i] for i in range(n)], off=off, raw=b,
+                       tags=[tags[i] for i in range(n)] if tags else [None] * n)
             if dev is not None:
                 out.update(d_seq=dev[0], d_off=dev[1], n=n, total_bases=int(b.total_bases))
         if rc != 0:

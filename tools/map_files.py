@@ -58,6 +58,8 @@ def main():
     ap.add_argument("--host-input", action="store_true", help="parse the read files on the host (lra_reads_next_batch)")
     ap.add_argument("--batch-bases", type=int, default=PRESET_BATCH, help="bases per batch (a batch ends with the read that crosses this)")
     ap.add_argument("--chunk", type=int, default=None, help="bytes the device reader reads and parses per step (default: the library's)")
+    ap.add_argument("-Flag", dest="flag", type=int, default=0, help="SAM / BAM input: skip records whose flag meets this mask")
+    ap.add_argument("--passthrough", action="store_true", help="SAM / BAM input: append each read's aux fields to its SAM records")
     args = ap.parse_args()
     P = args.preset
     t0 = time.perf_counter()
@@ -91,9 +93,11 @@ def main():
     out = open(args.out, "wb") if args.out else sys.stdout.buffer
     if fmt == "s":
         cl = ["lra", "align", "-" + P, args.genome, *args.reads, "-p", args.fmt] + (["-H"] if args.hard_clip else []) + (["--printMD"] if args.printMD else []) + \
-             (["-a"] if args.store_all else []) + ["--PrintNumAln", str(args.PrintNumAln)] + (["--refineBreakpoints"] if args.refineBreakpoints else [])
+             (["-a"] if args.store_all else []) + ["--PrintNumAln", str(args.PrintNumAln)] + (["--refineBreakpoints"] if args.refineBreakpoints else []) + \
+             (["-Flag", str(args.flag)] if args.flag else []) + (["--passthrough"] if args.passthrough else [])
         out.write(mapread.LowAccMapper.sam_header(mapper, b"lra_amd", " ".join(cl).encode()))   # the lra command line: the same for either reader
-    rf = reads_io.ReadsFile(args.reads, ctx=None if args.host_input else ctx, chunk=None if args.host_input else args.chunk)
+    rf = reads_io.ReadsFile(args.reads, ctx=None if args.host_input else ctx, chunk=None if args.host_input else args.chunk, flag_remove=args.flag,
+                            passthrough=args.passthrough)
     t_read = t_map = t_rec = 0.0
     n_reads = n_bases = n_batches = 0
     failed = None
@@ -101,7 +105,7 @@ def main():
         t = time.perf_counter()
         try:
             b = rf.next_batch(args.batch_bases)
-        except IOError as e:                                                # a corrupt FASTQ record: map the reads in front of it, then fail
+        except IOError as e:                                                # a corrupt record or file: map the reads in front of it, then fail
             b, failed = e.partial, e
         t_read += time.perf_counter() - t
         if b is None:
@@ -110,7 +114,7 @@ def main():
         res = reads_io.map_reads_host(mapper, b["raw"]) if args.host_input else reads_io.map_reads_device(mapper, b)
         t_map += time.perf_counter() - t
         t = time.perf_counter()
-        for txt in mapper.records(res, b["names"], b["seqs"], quals=b["quals"]):
+        for txt in mapper.records(res, b["names"], b["seqs"], quals=b["quals"], passthrough=b["tags"] if args.passthrough else None):
             out.write(txt)
         t_rec += time.perf_counter() - t
         n_reads += len(b["names"]); n_bases += int(b["off"][-1]); n_batches += 1
