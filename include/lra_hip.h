@@ -84,7 +84,7 @@ int lra_ctx_set_store_all(lra_ctx* ctx, int on);
 int lra_ctx_store_all(lra_ctx* ctx);
 /* ABI version of the loaded library (tests check it against this header). */
 int lra_abi_version(void);
-#define LRA_ABI_VERSION 9   /* 9: lra_ctx_release_buffers; later, additively (no struct or signature changed): lra_ctx_set_store_all, lra_ctx_store_all; SAM / BAM input: lra_reads_set_flag_remove, lra_reads_set_passthrough, lra_reads_batch_tags, lra_map_records_tags, lra_map_records_host_tags, lra_bgzf_inflate_batch, lra_bgzf_inflate_host; 8: lra_map_opts_apply_local_index, lra_ctx_local_index_params, lra_ctx_load_local_index (the .gli file's k / w / window override the options', as glIndex.Read does); 7: lra_sort_pairs_batch;  2: lra_map_opts.defer_matches, lra_map_counters.n_deferred_reads; 3: lra_map_opts.flagged_unaligned, lra_map_counters.n_flagged_reads, lra_map_host_flagged; 4: lra_reads_last_error, a corrupt FASTQ record is LRA_ERR_INVALID; lra_map_opts.defer_seed_matches; 5: lra_seed_prefetch, lra_ctx_adopt_seed, lra_map_reads_lowacc_front / _back, lra_map_back_release; 6: a failed front half hands over an error batch (one back call per front call), separate n_handed_back_reads counter, lra_map_host_trim */
+#define LRA_ABI_VERSION 9   /* 9: lra_ctx_release_buffers; later, additively (no struct or signature changed): lra_ctx_set_store_all, lra_ctx_store_all; SAM / BAM input: lra_reads_set_flag_remove, lra_reads_set_passthrough, lra_reads_batch_tags, lra_map_records_tags, lra_map_records_host_tags, lra_bgzf_inflate_batch, lra_bgzf_inflate_host; the genome reader: lra_genome_open, _read_host, _read_device, _info, _names, _host_seq, _device_seq, _install, _last_error, _set_device_chunk, _close; 8: lra_map_opts_apply_local_index, lra_ctx_local_index_params, lra_ctx_load_local_index (the .gli file's k / w / window override the options', as glIndex.Read does); 7: lra_sort_pairs_batch;  2: lra_map_opts.defer_matches, lra_map_counters.n_deferred_reads; 3: lra_map_opts.flagged_unaligned, lra_map_counters.n_flagged_reads, lra_map_host_flagged; 4: lra_reads_last_error, a corrupt FASTQ record is LRA_ERR_INVALID; lra_map_opts.defer_seed_matches; 5: lra_seed_prefetch, lra_ctx_adopt_seed, lra_map_reads_lowacc_front / _back, lra_map_back_release; 6: a failed front half hands over an error batch (one back call per front call), separate n_handed_back_reads counter, lra_map_host_trim */
 
 /* Convenience for hosts without their own HIP binding: synchronous device->host copy on the
  * context's stream (a C++ host would call hipMemcpy itself).                                */
@@ -1164,6 +1164,40 @@ int lra_reads_batch_tags(const lra_reads* r, const char* const** tags);
 int lra_bgzf_inflate_batch(lra_ctx* ctx, int n_blocks, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_out_off, uint8_t* d_out,
                            int32_t* d_status);
 int lra_bgzf_inflate_host(int n_blocks, const uint8_t* in, const uint64_t* in_off, const uint64_t* out_off, uint8_t* out, int32_t* status);
+/* ---- the genome (Genome::Read, Genome.h:115-138) -------------------------------------------------------------------------------------------------
+ * A genome FASTA file -- plain text, gzip or BGZF, as gzopen takes them -- into what lra_ctx_load_genome[_device] and lra_ctx_load_chromosomes take: the
+ * bases of all records back to back, upper-cased, and header.pos.  The parsing rules are kseq_read's FASTA branch; lra_amd/csrc/genome.hip states them.
+ * In short: bytes in front of the first '>' or '@' are dropped; a record starts at a line whose first byte is '>' or '@'; its name runs to the first
+ * isspace byte (it may be empty); of a sequence line every byte is a base (blanks, tabs and digits too) but one '\r' in front of the '\n'; empty lines
+ * are skipped; a record without bases is kept; a file without records gives n_chrom = 0 and LRA_OK.
+ *   lra_genome_open          opens and sniffs the file: BGZF (a 'BC' field), other gzip (1f 8b 08), else plain text.  LRA_ERR_INVALID: no such file.
+ *   lra_genome_read_host     parses everything on the host.
+ *   lra_genome_read_device   parses on ctx's device, on ctx's stream, complete at return: the file is read in steps into page-locked memory and
+ *                            parsed by byte-stream kernels; BGZF members are inflated on the device, other gzip on the host (one serial bit stream).
+ *                            A reader uses one form (the other one afterwards: LRA_ERR_INVALID); a second call of the same form returns the first's code.
+ *   lra_genome_info          after a read: the number of records, the bytes of their names (with the NULs), the number of bases.
+ *   lra_genome_names         names[names_len]: the names NUL-terminated, back to back; pos[n_chrom + 1] = header.pos (either may be NULL).
+ *   lra_genome_host_seq / lra_genome_device_seq   the bases, owned by the reader, + 64 zero bytes; NULL for the other form.
+ *   lra_genome_install       lra_ctx_load_genome[_device] + lra_ctx_load_chromosomes from what the reader holds (device form: device to device, on
+ *                            the reader's device).  A genome without records is LRA_ERR_INVALID here.
+ *   lra_genome_set_device_chunk   bytes of the file's data per step (default 256 MiB, minimum 4096; before the read).  The host form decodes
+ *                            compressed input in steps of the same size.
+ * LRA_ERR_INVALID from a read, with lra_genome_last_error naming the place, and sticky: a line that starts with '+' inside a record (a FASTQ genome
+ * is not read; the text names the record); a record whose first sequence line is "\r" alone (kseq would keep that '\r' as a base; refused); a bad
+ * compressed member (named by its compressed offset: truncated, a bad code, CRC-32, ISIZE, bytes that start no member); 2^32 bases or more.  Of several
+ * faults the first in file order is reported, by both forms alike.                                                                              */
+typedef struct lra_genome lra_genome;
+int lra_genome_open(const char* path, lra_genome** out);
+int lra_genome_read_host(lra_genome* g);
+int lra_genome_read_device(lra_genome* g, lra_ctx* ctx);
+int lra_genome_info(const lra_genome* g, int32_t* n_chrom, uint64_t* names_len, uint64_t* total);
+int lra_genome_names(const lra_genome* g, char* names, uint64_t* pos);
+const char* lra_genome_host_seq(const lra_genome* g);
+const char* lra_genome_device_seq(const lra_genome* g);
+int lra_genome_install(const lra_genome* g, lra_ctx* ctx);
+const char* lra_genome_last_error(const lra_genome* g);
+int lra_genome_set_device_chunk(lra_genome* g, uint64_t bytes);
+void lra_genome_close(lra_genome* g);
 int lra_map_reads_host(lra_ctx* ctx, int n_reads, const char* h_seq, const uint64_t* h_off, const lra_map_opts* opts, lra_map_result* out);
 int lra_map_records(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* opts, const char* const* names, const char* const* reads,
                     const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* passthrough, char* out, uint64_t cap,

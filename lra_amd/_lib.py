@@ -71,6 +71,17 @@ SYMBOLS = {
     "lra_reads_batch_tags": (C.c_int, [_vp, _vp]),
     "lra_bgzf_inflate_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lra_bgzf_inflate_host": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "lra_genome_open": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),
+    "lra_genome_read_host": (C.c_int, [_vp]),
+    "lra_genome_read_device": (C.c_int, [_vp, _vp]),
+    "lra_genome_info": (C.c_int, [_vp, _i32p, _u64p, _u64p]),
+    "lra_genome_names": (C.c_int, [_vp, _vp, _vp]),
+    "lra_genome_host_seq": (_vp, [_vp]),
+    "lra_genome_device_seq": (_vp, [_vp]),
+    "lra_genome_install": (C.c_int, [_vp, _vp]),
+    "lra_genome_last_error": (C.c_char_p, [_vp]),
+    "lra_genome_set_device_chunk": (C.c_int, [_vp, C.c_uint64]),
+    "lra_genome_close": (None, [_vp]),
     "lra_host_thread_budget": (C.c_int, []),
     "lra_map_host_trim": (C.c_uint64, [C.c_uint64]),
     "lra_map_reads_host": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),

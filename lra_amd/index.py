@@ -1,5 +1,5 @@
-"""`lra index` on the device and the index files: ctypes mirror of lra_ctx_build_global_index / lra_write_mms / lra_read_mms / lra_write_gli /
-lra_read_gli (include/lra_hip.h; reference MMIndex.h:286-424, :138-173).  No algorithmic code here."""
+"""`lra index` on the device and the index files: ctypes mirror of lra_ctx_build_global_index / lra_ctx_local_index / lra_write_mms / lra_read_mms /
+lra_write_gli / lra_read_gli (include/lra_hip.h; reference MMIndex.h:286-424, :138-173).  No algorithmic code here."""
 import ctypes as C
 
 import numpy as np
@@ -40,6 +40,19 @@ def global_index(ctx: Context):
     if n.value == 0:
         return np.zeros(0, np.uint64), np.zeros(0, np.uint32)
     return ctx.to_host(dk.value, n.value, np.uint64), ctx.to_host(dp.value, n.value, np.uint32)
+
+
+def local_index(ctx: Context):
+    """The context's local index (lra_ctx_build_local_index / lra_ctx_load_local_index) as the .gli payload: dict(k, w, window, seq_offsets, tuple_bnd,
+    tuples), host arrays -- what write_gli takes."""
+    from .local import LocalIndexResult
+    res = LocalIndexResult(); gso = C.c_void_p()
+    k, w, win = C.c_int(0), C.c_int(0), C.c_int(0)
+    ctx.check(ctx.lib.lra_ctx_local_index(ctx.h, C.byref(res), C.byref(gso)))
+    ctx.check(ctx.lib.lra_ctx_local_index_params(ctx.h, C.byref(k), C.byref(w), C.byref(win)))
+    nw, nt = int(res.n_windows), int(res.n_tuples)
+    return dict(k=k.value, w=w.value, window=win.value, seq_offsets=ctx.to_host(gso.value, nw + 1, np.uint64),
+                tuple_bnd=ctx.to_host(res.d_tuple_bnd, nw + 1, np.uint64), tuples=ctx.to_host(res.d_tuples, nt, np.uint32))
 
 
 def _chk(rc, what):

@@ -4,7 +4,8 @@
 
 The reads are parsed on the device (lra_reads_next_batch_device) and mapped from the reader's device arrays; --host-input parses them on the host
 (lra_reads_next_batch) and maps through lra_map_reads_host, the same records.  The index: genome.fa.mms / genome.fa.gli when both exist (lra_read_mms /
-lra_read_gli), else built on the device with the preset's `lra index` parameters.  The genome itself is read on the host.  Per-stage times go to stderr."""
+lra_read_gli), else built on the device with the preset's `lra index` parameters.  The genome (plain text, gzip or BGZF) is parsed on the device too
+(lra_genome_read_device); --host-genome parses it on the host (lra_genome_read_host).  Per-stage times go to stderr."""
 import argparse
 import os
 import sys
@@ -13,7 +14,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
-from lra_amd import index, mapread, reads_io
+from lra_amd import genome_io, index, mapread, reads_io
 from lra_amd.context import Context
 
 INDEX_PARAMS = {"ONT": (17, 10, 150, 15, 1), "CLR": (15, 10, 250, 12, 1), "CCS": (17, 10, 150, 15, 1), "CONTIG": (19, 10, 30, 20, 1)}   # `lra index -<preset>`
@@ -21,7 +22,8 @@ PRESET_BATCH = 500_000_000                                                      
 
 
 def read_genome(path):
-    """-> (names, chrom_pos, upper-case bases back to back) of a FASTA file (Genome::Read: the name is the header's first token)"""
+    """-> (names, chrom_pos, upper-case bases back to back) of a plain FASTA file (Genome::Read: the name is the header's first token).  main reads the
+    genome through lra_amd.genome_io; this stays as the tests' independent yardstick."""
     names, parts, pos = [], [], [0]
     cur = []
     with open(path, "rb") as f:
@@ -57,14 +59,23 @@ def main():
     ap.add_argument("-o", dest="out", default=None, help="output file (default stdout)")
     ap.add_argument("--host-input", action="store_true", help="parse the read files on the host (lra_reads_next_batch)")
     ap.add_argument("--batch-bases", type=int, default=PRESET_BATCH, help="bases per batch (a batch ends with the read that crosses this)")
+    ap.add_argument("--host-genome", action="store_true", help="parse the genome file on the host (lra_genome_read_host)")
     ap.add_argument("--chunk", type=int, default=None, help="bytes the device reader reads and parses per step (default: the library's)")
     ap.add_argument("-Flag", dest="flag", type=int, default=0, help="SAM / BAM input: skip records whose flag meets this mask")
     ap.add_argument("--passthrough", action="store_true", help="SAM / BAM input: append each read's aux fields to its SAM records")
     args = ap.parse_args()
     P = args.preset
     t0 = time.perf_counter()
-    names, chrom_pos, genome = read_genome(args.genome)
     ctx = Context(0)
+    gf = genome_io.GenomeFile(args.genome, ctx=None if args.host_genome else ctx)
+    try:
+        gf.read()
+    except IOError as e:
+        raise SystemExit("map_files: %s" % e)
+    if not gf.names:
+        raise SystemExit("%s: no FASTA records" % args.genome)
+    names, chrom_pos, genome = gf.names, gf.chrom_pos, gf.seq
+    gf.close()                                                                   # (the bases are a copy: a numpy array or a device tensor)
     mms, gli = args.genome + ".mms", args.genome + ".gli"
     ik = ipos = None
     gli_params = None
