@@ -82,9 +82,14 @@ const char* lra_ctx_last_error(lra_ctx* ctx);
  * lra_ctx_store_all returns the switch (0 / 1), or LRA_ERR_INVALID for a NULL ctx.                                                                                  */
 int lra_ctx_set_store_all(lra_ctx* ctx, int on);
 int lra_ctx_store_all(lra_ctx* ctx);
+/* opts.svsigLen (Options.h:70; `-SV LEN PATH`, lra.cpp:64): the net gap length above which the record stage (LRA_PACK_SVSIG) emits an SV signature.
+ * A context setting, like the one above: lra_map_opts and lra_map_result stay as they are.  Default 25; a negative len is LRA_ERR_INVALID.
+ * lra_ctx_svsig_len returns the value, or LRA_ERR_INVALID for a NULL ctx.                                                                     */
+int lra_ctx_set_svsig_len(lra_ctx* ctx, int len);
+int lra_ctx_svsig_len(lra_ctx* ctx);
 /* ABI version of the loaded library (tests check it against this header). */
 int lra_abi_version(void);
-#define LRA_ABI_VERSION 9   /* 9: lra_ctx_release_buffers; later, additively (no struct or signature changed): lra_ctx_set_store_all, lra_ctx_store_all; SAM / BAM input: lra_reads_set_flag_remove, lra_reads_set_passthrough, lra_reads_batch_tags, lra_map_records_tags, lra_map_records_host_tags, lra_bgzf_inflate_batch, lra_bgzf_inflate_host; the genome reader: lra_genome_open, _read_host, _read_device, _info, _names, _host_seq, _device_seq, _install, _last_error, _set_device_chunk, _close; 8: lra_map_opts_apply_local_index, lra_ctx_local_index_params, lra_ctx_load_local_index (the .gli file's k / w / window override the options', as glIndex.Read does); 7: lra_sort_pairs_batch;  2: lra_map_opts.defer_matches, lra_map_counters.n_deferred_reads; 3: lra_map_opts.flagged_unaligned, lra_map_counters.n_flagged_reads, lra_map_host_flagged; 4: lra_reads_last_error, a corrupt FASTQ record is LRA_ERR_INVALID; lra_map_opts.defer_seed_matches; 5: lra_seed_prefetch, lra_ctx_adopt_seed, lra_map_reads_lowacc_front / _back, lra_map_back_release; 6: a failed front half hands over an error batch (one back call per front call), separate n_handed_back_reads counter, lra_map_host_trim */
+#define LRA_ABI_VERSION 9   /* 9: lra_ctx_release_buffers; later, additively (no struct or signature changed): lra_ctx_set_store_all, lra_ctx_store_all; SV signatures: lra_sv_signatures_batch, lra_ctx_set_svsig_len, lra_ctx_svsig_len, lra_map_svsig_host, lra_map_svsig; SAM / BAM input: lra_reads_set_flag_remove, lra_reads_set_passthrough, lra_reads_batch_tags, lra_map_records_tags, lra_map_records_host_tags, lra_bgzf_inflate_batch, lra_bgzf_inflate_host; the genome reader: lra_genome_open, _read_host, _read_device, _info, _names, _host_seq, _device_seq, _install, _last_error, _set_device_chunk, _close; 8: lra_map_opts_apply_local_index, lra_ctx_local_index_params, lra_ctx_load_local_index (the .gli file's k / w / window override the options', as glIndex.Read does); 7: lra_sort_pairs_batch;  2: lra_map_opts.defer_matches, lra_map_counters.n_deferred_reads; 3: lra_map_opts.flagged_unaligned, lra_map_counters.n_flagged_reads, lra_map_host_flagged; 4: lra_reads_last_error, a corrupt FASTQ record is LRA_ERR_INVALID; lra_map_opts.defer_seed_matches; 5: lra_seed_prefetch, lra_ctx_adopt_seed, lra_map_reads_lowacc_front / _back, lra_map_back_release; 6: a failed front half hands over an error batch (one back call per front call), separate n_handed_back_reads counter, lra_map_host_trim */
 
 /* Convenience for hosts without their own HIP binding: synchronous device->host copy on the
  * context's stream (a C++ host would call hipMemcpy itself).                                */
@@ -778,6 +783,34 @@ typedef struct lra_md_result {
 int lra_md_strings_batch(lra_ctx* ctx, int n_aln, const int32_t* d_blocks, const uint64_t* d_block_off, const char* d_qseq, const uint64_t* d_q_off,
                          const int32_t* d_q_len, const char* d_tseq, const uint64_t* d_t_off, lra_md_result* out);
 
+/* ---- opts.Printsvsig / opts.svsigLen: the SV signatures of every alignment, on the device -----------------------------
+ * Replaces  Alignment::Printsvsig (Alignment.h:336-411), which CalculateStatistics calls (:518) to fill MapRead's svsigstrm.  For every block b
+ * of an alignment but the last: q / t = the block's end in the read / the chromosome, qg / tg = the bases from there to block b + 1, less their
+ * common part min(qg, tg).  qg > min_len is one INS signature {t, t, qg, read[q, q + qg)}; otherwise tg > min_len is one DEL signature
+ * {t, t + tg - 1, tg, text[t, t + tg)} -- the gap sits in front of the common columns.  read = d_qseq + d_q_off[a] (the strand the alignment lies
+ * on), text = d_tseq + d_t_off[a] (its chromosome); positions are 0-based in the chromosome, bytes are copied as stored.  A pair with a negative
+ * gap gives nothing (the reference asserts; the pipeline produces none).  Arguments as lra_md_strings_batch (d_q_len is not read), min_len >= 0.
+ * Output (context-owned, valid until the next call on the context): alignment a's signatures are d_sig[d_sig_off[a] .. d_sig_off[a + 1]), in
+ * block order; a signature's bases are d_seq[seq_off, seq_off + len), the sequences back to back in signature order.  Synchronous.            */
+#define LRA_SV_INS 0
+#define LRA_SV_DEL 1
+typedef struct lra_svsig_rec {
+  uint64_t seq_off;           /* of its bases in d_seq */
+  uint32_t t_start;           /* t: the end of block `block` in the chromosome (INS: start = end = t; DEL: end = t + len - 1) */
+  uint32_t len;               /* the net gap = the number of bases */
+  uint32_t kind;              /* LRA_SV_INS / LRA_SV_DEL */
+  uint32_t block;             /* the gap is behind this block of the alignment */
+} lra_svsig_rec;
+typedef struct lra_svsig_result {
+  int32_t n_aln;
+  uint64_t n_sig, n_seq_bytes;
+  const uint64_t* d_sig_off;        /* [n_aln+1] */
+  const lra_svsig_rec* d_sig;       /* [n_sig] */
+  const char* d_seq;                /* [n_seq_bytes] */
+} lra_svsig_result;
+int lra_sv_signatures_batch(lra_ctx* ctx, int n_aln, const int32_t* d_blocks, const uint64_t* d_block_off, const char* d_qseq, const uint64_t* d_q_off,
+                            const int32_t* d_q_len, const char* d_tseq, const uint64_t* d_t_off, int32_t min_len, lra_svsig_result* out);
+
 /* ---- a15: junctions of split alignments ---------------------------------------------------------------------
  * Replaces   RefineBreakpoint(read, genome, leftAln, rightAln, opts)   (RefineBreakpoint.h:210-466; Map_lowacc.h:592, Map_highacc.h:725)
  * for n junctions: if the read bases between the two segments (in forward read coordinates) number 1..499, both segments are extended into
@@ -1206,7 +1239,8 @@ int lra_map_records(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts*
  * thread, lra.cpp:117-158):
  *   lra_map_snapshot      copies what the records need (per-alignment fields, counters, CIGAR runs, block ends; with_blocks & LRA_PACK_BLOCKS also
  *                         every block and the chromosome text under it, needed by print format 'a' only; with_blocks & LRA_PACK_MD the MD:Z value
- *                         of every alignment, lra_md_strings_batch on the result's own arrays, which format 's' then prints -- opts.printMD) from
+ *                         of every alignment, lra_md_strings_batch on the result's own arrays, which format 's' then prints -- opts.printMD;
+ *                         with_blocks & LRA_PACK_SVSIG the SV signatures of every alignment, which lra_map_svsig_host prints -- opts.Printsvsig) from
  *                         the context's result buffers to a host object; after it returns the context may run the next batch.
  *   lra_map_records_host  SetFromSegAlignment / AlignmentsOrder::Update / SimpleMapQV / OUTPUT for every read on n_threads host threads (0: up to
  *                         16); touches neither the context nor the device.  *text (owned by the snapshot, valid until it is freed or reused),
@@ -1215,6 +1249,8 @@ int lra_map_records(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts*
 typedef struct lra_map_host lra_map_host;
 #define LRA_PACK_BLOCKS 1   /* the flag word of lra_map_snapshot / lra_map_pack (0 / 1 as before): the blocks (print format 'a') */
 #define LRA_PACK_MD 2       /* the MD:Z strings (opts.printMD): launches lra_md_strings_batch; the pack's header word 10 = their bytes, word 11 = 1 */
+#define LRA_PACK_SVSIG 4    /* the SV signatures (opts.Printsvsig): launches lra_sv_signatures_batch with the context's svsig length
+                             * (lra_ctx_set_svsig_len); the pack's header word 12 = the section's bytes, word 13 = 1.  The record text is unchanged */
 int lra_map_snapshot(lra_ctx* ctx, const lra_map_result* res, int with_blocks, lra_map_host** out);
 int lra_map_records_host(lra_map_host* snap, const lra_map_opts* opts, const char* const* names, const char* const* reads, const char* const* quals,
                          const int32_t* read_len, const char* const* chrom_names, const char* passthrough, int n_threads, const char** text, uint64_t* len,
@@ -1234,9 +1270,25 @@ uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status)
  * reference's ordered output, lra.cpp:145-166): lra_map_pack lays the same arrays out behind a 128-byte header in a context-owned buffer
  * (valid until the next pack on this context); lra_map_unpack_host turns a host copy of such a buffer (from any rank) into a snapshot for
  * lra_map_records_host.  lra_map_snapshot = pack + copy to the host + unpack.  with_blocks: the flag word above; LRA_PACK_MD appends
- * md_off u64[nA + 1] | md u8[bytes] behind the blocks (a pack whose header words 10 and 11 are 0 has none: records without MD:Z).            */
+ * md_off u64[nA + 1] | md u8[bytes] behind the blocks (a pack whose header words 10 and 11 are 0 has none: records without MD:Z).
+ * LRA_PACK_SVSIG appends, behind the MD section, sig_off u64[nA + 1] | lra_svsig_rec[sig_off[nA]] | the sequences u8[], each padded to 8 bytes,
+ * header word 12 = the three parts' bytes, word 13 = 1 (both 0: no section).  lra_map_unpack_host refuses a section that is cut short or
+ * inconsistent (sig_off not monotone from 0, a record's kind, block or sequence range outside its alignment / the bytes) with LRA_ERR_INVALID. */
 int lra_map_pack(lra_ctx* ctx, const lra_map_result* res, int with_blocks, const void** d_buf, uint64_t* bytes);
 int lra_map_unpack_host(const void* h_buf, uint64_t bytes, lra_map_host** out);
+/* MapRead's second stream, svsigstrm (what Alignment::Printsvsig writes under opts.Printsvsig, Alignment.h:374-399), from a snapshot packed with
+ * LRA_PACK_SVSIG: one line per signature,  chrom \t readName \t start \t end \t length \t INS|DEL \t sequence \n.  A read's lines are those of its
+ * alignments in result order (job, then segment: the order of the reference's CalculateStatistics calls), an alignment's in block order;
+ * (*rec_off)[n_reads + 1] gives every read's range of *text (*len bytes; both owned by the snapshot and apart from the record text, valid until
+ * the snapshot is freed or the call repeated).  A read with a non-zero status word (flagged or handed back) has no lines.  n_threads as
+ * lra_map_records_host; touches neither the context nor the device.  LRA_ERR_INVALID for a snapshot packed without the flag.
+ * lra_map_svsig = snapshot with LRA_PACK_SVSIG, print, free; its text is owned by the context (valid until the next lra_map_svsig on it).
+ * One deviation: on -CCS / -CONTIG the reference calls CalculateStatistics twice per alignment (Map_highacc.h:721, :731), so it would print every
+ * signature twice, the first time from the blocks before RefineBreakpoint; here each is printed once, from the final blocks.                    */
+int lra_map_svsig_host(lra_map_host* snap, const char* const* names, const char* const* chrom_names, int n_threads, const char** text, uint64_t* len,
+                       const uint64_t** rec_off);
+int lra_map_svsig(lra_ctx* ctx, const lra_map_result* res, const char* const* names, const char* const* chrom_names, const char** text, uint64_t* len,
+                  const uint64_t** rec_off);
 
 #ifdef __cplusplus
 }

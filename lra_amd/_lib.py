@@ -27,6 +27,8 @@ SYMBOLS = {
     "lra_ctx_set_stream": (C.c_int, [_vp, _vp]),
     "lra_ctx_set_store_all": (C.c_int, [_vp, C.c_int]),
     "lra_ctx_store_all": (C.c_int, [_vp]),
+    "lra_ctx_set_svsig_len": (C.c_int, [_vp, C.c_int]),
+    "lra_ctx_svsig_len": (C.c_int, [_vp]),
     "lra_ctx_last_error": (C.c_char_p, [_vp]),
     "lra_copy_to_host": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
     "lra_copy_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
@@ -142,6 +144,8 @@ SYMBOLS = {
     "lra_map_host_flagged": (C.c_uint64, [_vp, _vp]),
     "lra_map_pack": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
     "lra_map_unpack_host": (C.c_int, [_vp, C.c_uint64, _vp]),
+    "lra_map_svsig_host": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "lra_map_svsig": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lra_map_records": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_char_p, _vp, C.c_uint64, _vp, _vp]),
     "lra_map_records_tags": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp]),
     "lra_map_records_host_tags": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
@@ -149,6 +153,7 @@ SYMBOLS = {
     "lra_filter_chains_ex_batch": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "lra_calculate_statistics_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "lra_md_strings_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lra_sv_signatures_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp]),
     "lra_local_index_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "lra_local_index_masked_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "lra_local_compare_batch": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),

@@ -56,6 +56,7 @@ struct lra_ctx {
   // one it adopted and lra_map_reads_lowacc_batch / lra_map_reads_highacc_batch will use instead of seeding when they are called with the same reads
   struct { bool valid = false; int n_reads = 0; const char* d_seq = nullptr; const uint64_t* d_read_off = nullptr; int k = 0, w = 0, max_freq = 0; lra_seed_result res; } ahead;
   bool store_all = false;                    // lra_ctx_set_store_all (lra align -a): the drivers sketch with w = 1
+  int svsig_len = 25;                        // lra_ctx_set_svsig_len (opts.svsigLen, Options.h:70): the record stage's SV signatures are the net gaps above it
   bool low_priority = false; int prio = 0;   // the second pass's streams (its side streams too) are created with the device's lowest priority
 };
 

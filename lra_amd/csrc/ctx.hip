@@ -182,6 +182,12 @@ extern "C" int lra_ctx_set_store_all(lra_ctx* ctx, int on) {
   return LRA_OK;
 }
 extern "C" int lra_ctx_store_all(lra_ctx* ctx) { return ctx ? (ctx->store_all ? 1 : 0) : LRA_ERR_INVALID; }
+extern "C" int lra_ctx_set_svsig_len(lra_ctx* ctx, int len) {
+  if (!ctx || len < 0) return LRA_ERR_INVALID;
+  ctx->svsig_len = len;
+  return LRA_OK;
+}
+extern "C" int lra_ctx_svsig_len(lra_ctx* ctx) { return ctx ? ctx->svsig_len : LRA_ERR_INVALID; }
 
 extern "C" int lra_ctx_set_stream(lra_ctx* ctx, void* stream) {
   if (!ctx) return LRA_ERR_INVALID;

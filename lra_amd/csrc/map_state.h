@@ -53,6 +53,7 @@ struct lra_map_state {
   std::shared_ptr<lra_gen_cell> owner_cell; uint64_t owner_generation = 0;  // a borrower: whose data, at which generation (see seed_state.h)
   std::vector<float> lut;                          // LogLookUpTable.h:9-15
   lra_text_buf last_text; std::vector<uint64_t> last_off; lra_map_sig last_sig;   // lra_map_records: sizing call -> filling call
+  lra_text_buf sv_text; std::vector<uint64_t> sv_off;                             // lra_map_svsig: the text and read ranges of its last call
 };
 
 int lra_map_count_flagged(lra_ctx* ctx, lra_map_result* out);   // mapread.hip: counters.n_flagged_reads of a finished batch
@@ -62,7 +63,7 @@ int lra_refine_breakpoints(lra_ctx* ctx, uint64_t nJ, uint64_t nA, const uint64_
                            const uint64_t* t_off, const int64_t* t_len, const char* strands, const char* genome, lra_refine_result* fres);
 
 // The strands buffer of a batch (lra_map_result::d_strands: the reads forward, then at rc_base reverse complemented, 64 bytes of zeros) carries
-// the batch's read offsets [n_reads + 1] behind it at this byte: what the record stage (LRA_PACK_MD) addresses the reads with once the caller's
+// the batch's read offsets [n_reads + 1] behind it at this byte: what the record stage (LRA_PACK_MD, LRA_PACK_SVSIG) addresses the reads with once the caller's
 // d_read_off may have been reused -- they travel with the strands through the two-stage handover and the passes' merges.  One copy per batch.
 inline size_t lra_strands_ro_at(uint64_t rc_base) { return (size_t)((2 * rc_base + 64 + 7) & ~(uint64_t)7); }
 inline size_t lra_strands_bytes(uint64_t rc_base, int n_reads) { return lra_strands_ro_at(rc_base) + ((size_t)n_reads + 1) * 8; }

@@ -1141,6 +1141,8 @@ struct lra_map_host {
   std::vector<uint64_t> chrom_pos;
   std::vector<std::string> segText; std::vector<uint32_t> segStart;   // print format 'a' only
   bool has_md = false; std::vector<uint64_t> md_off; std::string md;  // LRA_PACK_MD: alignment a's MD:Z value is md[md_off[a], md_off[a + 1])
+  bool has_sv = false; std::vector<uint64_t> sv_off; std::vector<lra_svsig_rec> sv_rec; std::string sv_seq;   // LRA_PACK_SVSIG: alignment a's signatures are sv_rec[sv_off[a], sv_off[a + 1])
+  lra_text_buf sv_text; std::vector<uint64_t> sv_rec_off;  // what lra_map_svsig_host produced last
   lra_text_buf text; std::vector<uint64_t> rec_off;        // what lra_map_records_host produced last
 };
 
@@ -1158,7 +1160,7 @@ __global__ void k_block_ends(uint64_t nA, const uint64_t* __restrict__ boff, con
   ends[2 * a] = b1 > b0 ? (uint32_t)blocks[3 * b0] : 0;
   ends[2 * a + 1] = b1 > b0 ? (uint32_t)(blocks[3 * (b1 - 1)] + blocks[3 * (b1 - 1) + 2]) : 0;
 }
-// LRA_PACK_MD: alignment a's read strand and chromosome in the result's own arrays (k_aln_address's offsets, from the read offsets the strands carry)
+// LRA_PACK_MD / LRA_PACK_SVSIG: alignment a's read strand and chromosome in the result's own arrays (k_aln_address's offsets, from the read offsets the strands carry)
 __global__ void k_md_address(uint64_t nA, const uint32_t* __restrict__ aln_read, const int32_t* __restrict__ strand, const int32_t* __restrict__ chrom,
                              const uint64_t* __restrict__ read_off, uint64_t rc_base, const uint64_t* __restrict__ chrom_pos, uint64_t* __restrict__ q_off,
                              uint64_t* __restrict__ t_off) {
@@ -1258,12 +1260,14 @@ void lra_host_pool_put(void* p, size_t cap) {
 //   then, each padded to 8 bytes:  chrom_pos u64[n_chrom+1] | reached u8[nJ] | rstat u32[n_reads] | jo u64[nJ+1] | strand, supp, sec, n0, n1, chrom
 //   i32[nA] each | fval f32[nA] | counts i32[18 nA] | boff u64[nA+1] | ends u32[2 nA] | roff u64[nA+1] | runs u32[n_runs] | blocks i32[3 n_blocks]
 //   | (LRA_PACK_MD: header[10] = MD bytes, header[11] = 1) md_off u64[nA+1] | md u8[header[10]]
+//   | (LRA_PACK_SVSIG: header[12] = the section's bytes, header[13] = 1) sig_off u64[nA+1] | lra_svsig_rec[sig_off[nA]] | the sequences u8[]
 namespace {
 constexpr int64_t PACK_MAGIC = 0x4c52414d41503031LL;   // "LRAMAP01"
 inline size_t pad8(size_t n) { return (n + 7) & ~(size_t)7; }
 struct PackLayout {
   size_t off[17]; size_t total;
-  PackLayout(uint64_t n_reads, uint64_t nJ, uint64_t nA, uint64_t n_blocks, uint64_t n_runs, uint64_t n_chrom, bool md = false, uint64_t md_bytes = 0) {
+  PackLayout(uint64_t n_reads, uint64_t nJ, uint64_t nA, uint64_t n_blocks, uint64_t n_runs, uint64_t n_chrom, bool md = false, uint64_t md_bytes = 0,
+             uint64_t sv_bytes = 0) {
     const size_t sz[17] = {16 * 8, (n_chrom + 1) * 8, nJ, n_reads * 4, (nJ + 1) * 8, nA * 4, nA * 4, nA * 4, nA * 4, nA * 4, nA * 4, nA * 4, 18 * nA * 4, (nA + 1) * 8,
                            2 * nA * 4, (nA + 1) * 8, n_runs * 4};
     size_t at = 0;
@@ -1271,10 +1275,14 @@ struct PackLayout {
     blocks_off = at; at += pad8(3 * n_blocks * 4);
     md_off = at; if (md) at += pad8((nA + 1) * 8);
     md_text = at; if (md) at += pad8(md_bytes);
+    sv_off = at; at += sv_bytes;
     total = at;
   }
-  size_t blocks_off, md_off, md_text;
+  size_t blocks_off, md_off, md_text, sv_off;
 };
+// the SV section: sig_off, the records, the sequences
+inline size_t sv_section_bytes(uint64_t nA, uint64_t n_sig, uint64_t n_seq) { return (nA + 1) * 8 + n_sig * sizeof(lra_svsig_rec) + pad8(n_seq); }
+static_assert(sizeof(lra_svsig_rec) == 24, "lra_svsig_rec is part of the pack's layout");
 }  // namespace
 
 extern "C" int lra_map_pack(lra_ctx* ctx, const lra_map_result* res, int with_blocks, const void** d_buf, uint64_t* bytes) {
@@ -1283,29 +1291,36 @@ extern "C" int lra_map_pack(lra_ctx* ctx, const lra_map_result* res, int with_bl
   if (!m) return LRA_ERR_INVALID;
   LRA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  if (with_blocks & ~(LRA_PACK_BLOCKS | LRA_PACK_MD)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_pack: unknown flags 0x%x", with_blocks);
-  const bool withMd = (with_blocks & LRA_PACK_MD) != 0;
+  if (with_blocks & ~(LRA_PACK_BLOCKS | LRA_PACK_MD | LRA_PACK_SVSIG)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_pack: unknown flags 0x%x", with_blocks);
+  const bool withMd = (with_blocks & LRA_PACK_MD) != 0, withSv = (with_blocks & LRA_PACK_SVSIG) != 0;
   const uint64_t nR = (uint64_t)res->n_reads, nJ = res->n_jobs, nA = res->n_alignments, nB = (with_blocks & LRA_PACK_BLOCKS) ? res->n_blocks : 0, nRuns = res->n_runs;
   const uint64_t nCh = m->chrom_pos.size() - 1;
-  // opts.printMD: the MD strings of the result's final blocks, from the reads on their strands (res->d_strands, addressed by the read offsets behind them) and the genome
+  // opts.printMD, opts.Printsvsig: the MD strings / SV signatures of the result's final blocks, from the reads on their strands (res->d_strands, addressed by the
+  // read offsets behind them) and the genome
   lra_md_result md; memset(&md, 0, sizeof md);
-  if (withMd && nA) {
+  lra_svsig_result sv; memset(&sv, 0, sizeof sv);
+  if ((withMd || withSv) && nA) {
     if (!res->d_strands || !res->d_aln_read || !res->d_strand || !res->d_chrom || !res->d_blocks || !res->d_block_off)
-      return lra_set_err(ctx, LRA_ERR_INVALID, "LRA_PACK_MD: the result has no reads / blocks to take the MD strings from");
-    if (!ctx->seed || !ctx->seed->genome || !m->d_chrom_pos) return lra_set_err(ctx, LRA_ERR_INVALID, "LRA_PACK_MD: genome not loaded");
+      return lra_set_err(ctx, LRA_ERR_INVALID, "LRA_PACK_MD / LRA_PACK_SVSIG: the result has no reads / blocks to work on");
+    if (!ctx->seed || !ctx->seed->genome || !m->d_chrom_pos) return lra_set_err(ctx, LRA_ERR_INVALID, "LRA_PACK_MD / LRA_PACK_SVSIG: genome not loaded");
     uint64_t* adr = (uint64_t*)lra_ensure(ctx, 187, 2 * (nA + 1) * 8);
     if (!adr) return LRA_ERR_NOMEM;
     const uint64_t* ro = (const uint64_t*)(res->d_strands + lra_strands_ro_at(res->rc_base));
     hipLaunchKernelGGL(k_md_address, dim3((unsigned)((nA + 255) / 256)), dim3(256), 0, st, nA, res->d_aln_read, res->d_strand, res->d_chrom, ro, res->rc_base,
                        (const uint64_t*)m->d_chrom_pos, adr, adr + nA + 1);
-    const int rcm = lra_md_strings_batch(ctx, (int)nA, res->d_blocks, res->d_block_off, res->d_strands, adr, nullptr, (const char*)ctx->seed->genome, adr + nA + 1, &md);
+    int rcm = LRA_OK;
+    if (withMd) rcm = lra_md_strings_batch(ctx, (int)nA, res->d_blocks, res->d_block_off, res->d_strands, adr, nullptr, (const char*)ctx->seed->genome, adr + nA + 1, &md);
+    if (!rcm && withSv)
+      rcm = lra_sv_signatures_batch(ctx, (int)nA, res->d_blocks, res->d_block_off, res->d_strands, adr, nullptr, (const char*)ctx->seed->genome, adr + nA + 1,
+                                    ctx->svsig_len, &sv);
     if (rcm) return rcm;
   }
-  const PackLayout L(nR, nJ, nA, nB, nRuns, nCh, withMd, md.n_bytes);
+  const uint64_t svBytes = withSv ? sv_section_bytes(nA, sv.n_sig, sv.n_seq_bytes) : 0;
+  const PackLayout L(nR, nJ, nA, nB, nRuns, nCh, withMd, md.n_bytes, svBytes);
   char* buf = (char*)lra_ensure(ctx, 84, L.total + 64);
   if (!buf) return LRA_ERR_NOMEM;
   const int64_t hdr[16] = {PACK_MAGIC, (int64_t)nR, std::max(res->num_aln, 1), (int64_t)nJ, (int64_t)nA, (int64_t)nB, (int64_t)nRuns, (int64_t)nCh,
-                           res->d_job_reached ? 1 : 0, res->d_read_status ? 1 : 0, (int64_t)md.n_bytes, withMd ? 1 : 0, 0, 0, 0, 0};
+                           res->d_job_reached ? 1 : 0, res->d_read_status ? 1 : 0, (int64_t)md.n_bytes, withMd ? 1 : 0, (int64_t)svBytes, withSv ? 1 : 0, 0, 0};
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(buf + L.off[0], hdr, sizeof hdr, hipMemcpyHostToDevice, st));
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(buf + L.off[1], m->d_chrom_pos, (nCh + 1) * 8, hipMemcpyDeviceToDevice, st));
   auto put = [&](int slot, const void* src, size_t n) -> hipError_t { return (n && src) ? hipMemcpyAsync(buf + L.off[slot], src, n, hipMemcpyDeviceToDevice, st) : hipSuccess; };
@@ -1327,6 +1342,18 @@ extern "C" int lra_map_pack(lra_ctx* ctx, const lra_map_result* res, int with_bl
     else LRA_HIP_CHECK(ctx, hipMemsetAsync(buf + L.md_off, 0, 8, st));
     if (md.n_bytes) LRA_HIP_CHECK(ctx, hipMemcpyAsync(buf + L.md_text, md.d_md, md.n_bytes, hipMemcpyDeviceToDevice, st));
   }
+  if (withSv) {
+    char* w = buf + L.sv_off;
+    if (nA) LRA_HIP_CHECK(ctx, hipMemcpyAsync(w, sv.d_sig_off, (nA + 1) * 8, hipMemcpyDeviceToDevice, st));
+    else LRA_HIP_CHECK(ctx, hipMemsetAsync(w, 0, 8, st));
+    w += (nA + 1) * 8;
+    if (sv.n_sig) LRA_HIP_CHECK(ctx, hipMemcpyAsync(w, sv.d_sig, sv.n_sig * sizeof(lra_svsig_rec), hipMemcpyDeviceToDevice, st));
+    w += sv.n_sig * sizeof(lra_svsig_rec);
+    if (sv.n_seq_bytes) {
+      LRA_HIP_CHECK(ctx, hipMemsetAsync(w + (pad8(sv.n_seq_bytes) - 8), 0, 8, st));                     // (the padding is part of the pack)
+      LRA_HIP_CHECK(ctx, hipMemcpyAsync(w, sv.d_seq, sv.n_seq_bytes, hipMemcpyDeviceToDevice, st));
+    }
+  }
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
   *d_buf = buf; *bytes = L.total;
   return LRA_OK;
@@ -1343,7 +1370,9 @@ extern "C" int lra_map_unpack_host(const void* h_buf, uint64_t bytes, lra_map_ho
   const uint64_t nR = (uint64_t)hdr[1], nJ = (uint64_t)hdr[3], nA = (uint64_t)hdr[4], nB = (uint64_t)hdr[5], nRuns = (uint64_t)hdr[6], nCh = (uint64_t)hdr[7];
   const bool hasMd = hdr[10] != 0 || hdr[11] != 0;                      // (packs written before LRA_PACK_MD have zeros there)
   if (hdr[10] < 0) return LRA_ERR_INVALID;
-  const PackLayout L(nR, nJ, nA, nB, nRuns, nCh, hasMd, (uint64_t)hdr[10]);
+  const bool hasSv = hdr[12] != 0 || hdr[13] != 0;                      // (packs written before LRA_PACK_SVSIG have zeros there)
+  if (hasSv && (hdr[12] < (int64_t)((nA + 1) * 8) || (hdr[12] & 7))) return LRA_ERR_INVALID;
+  const PackLayout L(nR, nJ, nA, nB, nRuns, nCh, hasMd, (uint64_t)hdr[10], hasSv ? (uint64_t)hdr[12] : 0);
   if (L.total > bytes) return LRA_ERR_INVALID;
   lra_map_host* h = new lra_map_host();
   h->n_reads = (int32_t)nR; h->num_aln = (int)hdr[2]; h->nJ = nJ; h->nA = nA;
@@ -1370,6 +1399,33 @@ extern "C" int lra_map_unpack_host(const void* h_buf, uint64_t bytes, lra_map_ho
     for (uint64_t a = 0; a < nA; a++)
       if (h->md_off[a] > h->md_off[a + 1] || h->md_off[a + 1] > (uint64_t)hdr[10]) { delete h; return LRA_ERR_INVALID; }
     h->md.assign(b + L.md_text, (size_t)hdr[10]);
+  }
+  if (hasSv) {
+    // sig_off runs from 0 without a step back; the records and the sequences fill what the section has behind it (the sequences padded to 8 bytes); every
+    // record names a gap of its own alignment and bases inside the sequences
+    h->has_sv = true;
+    const char* w = b + L.sv_off;
+    size_t left = (size_t)hdr[12] - (nA + 1) * 8;
+    h->sv_off.resize(nA + 1);
+    memcpy(h->sv_off.data(), w, (nA + 1) * 8); w += (nA + 1) * 8;
+    bool ok = h->sv_off[0] == 0 && (h->boff.size() == nA + 1 || nA == 0);
+    for (uint64_t a = 0; ok && a < nA; a++) ok = h->sv_off[a] <= h->sv_off[a + 1];
+    const uint64_t nS = h->sv_off[nA];
+    ok = ok && nS <= left / sizeof(lra_svsig_rec);
+    if (ok) {
+      h->sv_rec.resize(nS);
+      if (nS) memcpy(h->sv_rec.data(), w, nS * sizeof(lra_svsig_rec));
+      w += nS * sizeof(lra_svsig_rec); left -= nS * sizeof(lra_svsig_rec);
+      for (uint64_t a = 0; ok && a < nA; a++) {
+        const uint64_t nb = h->boff[a + 1] - h->boff[a];
+        for (uint64_t x = h->sv_off[a]; ok && x < h->sv_off[a + 1]; x++) {
+          const lra_svsig_rec& r = h->sv_rec[x];
+          ok = (r.kind == LRA_SV_INS || r.kind == LRA_SV_DEL) && r.len > 0 && (uint64_t)r.block + 1 < nb && r.seq_off <= left && r.len <= left - r.seq_off;
+        }
+      }
+    }
+    if (!ok) { delete h; return LRA_ERR_INVALID; }
+    h->sv_seq.assign(w, left);
   }
   *out = h;
   return LRA_OK;
@@ -1592,6 +1648,78 @@ extern "C" int lra_map_records_host_tags(lra_map_host* h, const lra_map_opts* o,
                                          const char** text, uint64_t* len, const uint64_t** rec_off) {
   if (!passthrough) return LRA_ERR_INVALID;
   return records_host(h, o, names, reads, quals, read_len, chrom_names, nullptr, passthrough, n_threads, text, len, rec_off);
+}
+
+// MapRead's svsigstrm: Printsvsig's lines (Alignment.h:374-399) of every read, from the signatures a snapshot packed with LRA_PACK_SVSIG holds.  Host threads
+// take contiguous ranges of reads, as in records_host; a read's alignments come in result order (job, then segment).
+extern "C" int lra_map_svsig_host(lra_map_host* h, const char* const* names, const char* const* chrom_names, int n_threads, const char** text, uint64_t* len,
+                                  const uint64_t** rec_off) {
+  if (!h || !names || !chrom_names || !len || !h->has_sv) return LRA_ERR_INVALID;
+  const int n_reads = h->n_reads, na = h->num_aln;
+  const size_t nJ = h->nJ;
+  if (nJ && (h->jo.size() != nJ + 1 || nJ != (size_t)n_reads * na || h->jo[nJ] > h->nA)) return LRA_ERR_INVALID;
+  int T = n_threads > 0 ? n_threads : lra_host_threads();
+  T = std::max(1, std::min(T, n_reads / 32 + 1));
+  std::vector<std::string> part(T);
+  std::vector<std::vector<uint64_t>> plen(T);
+  auto put_num = [](std::string& s, uint64_t v) { char tmp[24]; int k = 24; do { tmp[--k] = (char)('0' + v % 10); v /= 10; } while (v); s.append(tmp + k, (size_t)(24 - k)); };
+  auto work = [&](int tix) {
+    const int lo = (int)((long)n_reads * tix / T), hi = (int)((long)n_reads * (tix + 1) / T);
+    std::string& out = part[tix];
+    plen[tix].reserve((size_t)(hi - lo));
+    for (int r = lo; r < hi; r++) {
+      const size_t before = out.size();
+      const bool flagged = !h->rstat.empty() && h->rstat[r];                // flagged or handed back: no alignment of the read is output
+      if (!flagged && nJ) {
+        for (uint64_t a = h->jo[(size_t)r * na]; a < h->jo[(size_t)(r + 1) * na]; a++) {
+          for (uint64_t x = h->sv_off[a]; x < h->sv_off[a + 1]; x++) {
+            const lra_svsig_rec& g = h->sv_rec[x];
+            out += chrom_names[h->chrom[a]]; out += '\t'; out += names[r]; out += '\t';
+            put_num(out, g.t_start); out += '\t';
+            put_num(out, g.kind == LRA_SV_DEL ? (uint32_t)(g.t_start + g.len - 1) : g.t_start); out += '\t';
+            put_num(out, g.len);
+            out += g.kind == LRA_SV_DEL ? "\tDEL\t" : "\tINS\t";
+            out.append(h->sv_seq.data() + g.seq_off, g.len);
+            out += '\n';
+          }
+        }
+      }
+      plen[tix].push_back(out.size() - before);
+    }
+  };
+  if (T == 1) work(0);
+  else { std::vector<std::thread> th; for (int t = 0; t < T; t++) th.emplace_back(work, t); for (auto& x : th) x.join(); }
+  size_t total = 0;
+  for (int t = 0; t < T; t++) total += part[t].size();
+  h->sv_text.alloc(total);
+  if (total && !h->sv_text.data()) return LRA_ERR_NOMEM;
+  h->sv_rec_off.assign((size_t)n_reads + 1, 0);
+  uint64_t at = 0; size_t r = 0;
+  for (int t = 0; t < T; t++) {
+    if (!part[t].empty()) memcpy(h->sv_text.data() + at, part[t].data(), part[t].size());
+    for (uint64_t l : plen[t]) { h->sv_rec_off[r++] = at; at += l; }
+  }
+  h->sv_rec_off[n_reads] = at;
+  *len = total;
+  if (text) *text = h->sv_text.data();
+  if (rec_off) *rec_off = h->sv_rec_off.data();
+  return LRA_OK;
+}
+
+extern "C" int lra_map_svsig(lra_ctx* ctx, const lra_map_result* res, const char* const* names, const char* const* chrom_names, const char** text, uint64_t* len,
+                             const uint64_t** rec_off) {
+  if (!ctx || !res || !names || !chrom_names || !len || !ctx->map) return LRA_ERR_INVALID;
+  lra_map_host* h = nullptr;
+  int rc = lra_map_snapshot(ctx, res, LRA_PACK_SVSIG, &h);
+  if (rc) return rc;
+  if (!(rc = lra_map_svsig_host(h, names, chrom_names, 0, nullptr, len, nullptr))) {
+    lra_map_state* m = ctx->map;                                           // the text outlives the snapshot: the context keeps it until the next call
+    m->sv_text.swap(h->sv_text); m->sv_off.swap(h->sv_rec_off);
+    if (text) *text = m->sv_text.data();
+    if (rec_off) *rec_off = m->sv_off.data();
+  }
+  lra_map_host_free(h);
+  return rc;
 }
 
 static int map_records(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,

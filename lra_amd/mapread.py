@@ -62,6 +62,7 @@ class LowAccOptions:
     PrintNumAln: int = 1
     printFormat: str = "s"
     printMD: bool = False              # --printMD (lra.cpp:71, :592): MD:Z in SAM records (format 's'), built on the device (LRA_PACK_MD)
+    svsigLen: int = 25                 # opts.svsigLen (Options.h:70; -SV LEN PATH): net gaps above it are SV signatures (lra_ctx_set_svsig_len; the record stage's LRA_PACK_SVSIG)
     storeAll: bool = False             # -a (lra.cpp:182-184): sketch every position of a read, w = 1 (lra_ctx_set_store_all); globalW stays for the rest
     deferSeedMatches: int = 0          # lra_map_opts.defer_seed_matches (scheduling only: reads with more tier-1 matches are handed back unmapped; 0 = off)
     deferMatches: int = None           # lra_map_opts.defer_matches (scheduling only; None = the preset's value, 0 = one pass)
@@ -90,6 +91,11 @@ def clr_options(**kw):
 def set_store_all(ctx: Context, on):
     """lra_ctx_set_store_all: the drivers on this context sketch with w = 1 (lra align -a)."""
     ctx.check(ctx.lib.lra_ctx_set_store_all(ctx.h, 1 if on else 0))
+
+
+def set_svsig_len(ctx: Context, n):
+    """lra_ctx_set_svsig_len: the record stage on this context emits an SV signature for every net gap longer than n (opts.svsigLen)."""
+    ctx.check(ctx.lib.lra_ctx_set_svsig_len(ctx.h, int(n)))
 
 
 def seq_offsets(chrom_pos, window):
@@ -137,7 +143,7 @@ class MapResult(C.Structure):
                 [("rc_base", C.c_uint64), ("counters", MapCounters)])
 
 
-PACK_BLOCKS, PACK_MD = 1, 2       # the flag word of lra_map_snapshot / lra_map_pack (LRA_PACK_BLOCKS, LRA_PACK_MD)
+PACK_BLOCKS, PACK_MD, PACK_SVSIG = 1, 2, 4       # the flag word of lra_map_snapshot / lra_map_pack (LRA_PACK_BLOCKS, LRA_PACK_MD, LRA_PACK_SVSIG)
 
 READ_TYPES = {"ont": 0, "clr": 1, "ccs": 2, "contig": 3}
 
@@ -356,13 +362,49 @@ class LowAccMapper:
         raw = buf.raw
         return [raw[roff[i]:roff[i + 1]] for i in range(n)]
 
-    def snapshot(self, res: MapResult, with_blocks=False, md=None):
-        """lra_map_snapshot: host copy of what the records need; afterwards the context may run the next batch.  md (None: opts.printMD): pack the MD strings too."""
+    @property
+    def svsig_len(self):
+        return int(getattr(self.opts, "svsigLen", 25)) if hasattr(self, "opts") else int(getattr(self, "svsigLen", 25))
+
+    def snapshot(self, res: MapResult, with_blocks=False, md=None, svsig=False):
+        """lra_map_snapshot: host copy of what the records need; afterwards the context may run the next batch.  md (None: opts.printMD): pack the MD strings too.
+        svsig: pack the SV signatures too (LRA_PACK_SVSIG, net gaps above svsigLen), for svsig_host; the record text does not change."""
         ctx = self.ctx
         h = C.c_void_p()
-        flags = (PACK_BLOCKS if with_blocks else 0) | (PACK_MD if (self.print_md if md is None else md) else 0)
+        flags = (PACK_BLOCKS if with_blocks else 0) | (PACK_MD if (self.print_md if md is None else md) else 0) | (PACK_SVSIG if svsig else 0)
+        if svsig:
+            set_svsig_len(ctx, self.svsig_len)
         ctx.check(ctx.lib.lra_map_snapshot(ctx.h, C.byref(res), flags, C.byref(h)))
         return h
+
+    def svsig_host(self, snap, names, n_threads=0, free=True):
+        """lra_map_svsig_host on a snapshot taken with svsig=True (host threads only) -> per read the bytes of its SV signature lines."""
+        lib = self.ctx.lib
+        n = len(names)
+        nm = [x if isinstance(x, bytes) else str(x).encode() for x in names]
+        text = C.c_char_p(); ln = C.c_uint64(0); roff = C.POINTER(C.c_uint64)()
+        rc = lib.lra_map_svsig_host(snap, (C.c_char_p * n)(*nm), (C.c_char_p * len(self.chrom_names))(*self.chrom_names), int(n_threads), C.byref(text),
+                                    C.byref(ln), C.byref(roff))
+        if rc != 0:
+            lib.lra_map_host_free(snap)
+            raise RuntimeError("lra_map_svsig_host failed (%d)" % rc)
+        raw = C.string_at(text, ln.value)
+        out = [raw[roff[i]:roff[i + 1]] for i in range(n)]
+        if free:
+            lib.lra_map_host_free(snap)
+        return out
+
+    def sv_signatures(self, res: MapResult, names):
+        """lra_map_svsig: MapRead's svsigstrm for a batch -- per read the lines Alignment::Printsvsig writes for its alignments (net gaps above svsigLen)."""
+        ctx = self.ctx
+        n = int(res.n_reads)
+        nm = [x if isinstance(x, bytes) else str(x).encode() for x in names]
+        set_svsig_len(ctx, self.svsig_len)
+        text = C.c_char_p(); ln = C.c_uint64(0); roff = C.POINTER(C.c_uint64)()
+        ctx.check(ctx.lib.lra_map_svsig(ctx.h, C.byref(res), (C.c_char_p * n)(*nm), (C.c_char_p * len(self.chrom_names))(*self.chrom_names), C.byref(text),
+                                        C.byref(ln), C.byref(roff)))
+        raw = C.string_at(text, ln.value)
+        return [raw[roff[i]:roff[i + 1]] for i in range(n)]
 
     def record_args(self, names, reads, quals=None):
         """The per-read host arrays lra_map_records_host takes (built once per batch; keep the returned object alive during the call)."""
@@ -560,6 +602,7 @@ class HighAccMapper:
         self.chrom_pos = [int(x) for x in chrom_pos]
         self.chrom_names = [n if isinstance(n, bytes) else str(n).encode() for n in chrom_names]
         self.printMD = bool(overrides.pop("printMD", False))            # --printMD: a record-stage choice, not a field of lra_map_opts
+        self.svsigLen = int(overrides.pop("svsigLen", 25))              # opts.svsigLen: a context setting too (lra_ctx_set_svsig_len)
         self.storeAll = bool(overrides.pop("storeAll", False))          # -a: a context setting (lra_ctx_set_store_all), not a field of lra_map_opts
         m = MapOpts()
         (ctx.lib.lra_map_opts_preset_contig if preset == "contig" else ctx.lib.lra_map_opts_preset_ccs)(C.byref(m))
@@ -606,6 +649,9 @@ class HighAccMapper:
 
     fetch = LowAccMapper.fetch
     print_md = LowAccMapper.print_md
+    svsig_len = LowAccMapper.svsig_len
+    svsig_host = LowAccMapper.svsig_host
+    sv_signatures = LowAccMapper.sv_signatures
     fetch_local_index = LowAccMapper.fetch_local_index
     records = LowAccMapper.records
     record_args = LowAccMapper.record_args

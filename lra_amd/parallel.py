@@ -48,11 +48,15 @@ def gather_records(local: torch.Tensor, dst=0):
     return None
 
 
-def pack_records(ctx, res, print_md=False, with_blocks=False) -> np.ndarray:
+def pack_records(ctx, res, print_md=False, with_blocks=False, svsig=False, svsig_len=None) -> np.ndarray:
     """lra_map_pack of a batch result (on the context that owns it) -> the rank's record buffer as host bytes, for gather_records /
-    records_from_packed.  print_md (--printMD): with the MD strings of the final blocks (LRA_PACK_MD), which format 's' then prints."""
+    records_from_packed.  print_md (--printMD): with the MD strings of the final blocks (LRA_PACK_MD), which format 's' then prints.
+    svsig: with the SV signatures (LRA_PACK_SVSIG) for svsig_from_packed -- the net gaps above the context's svsig length, which svsig_len
+    (opts.svsigLen) sets first when given."""
     d_buf = C.c_void_p(); nb = C.c_uint64(0)
-    flags = (1 if with_blocks else 0) | (2 if print_md else 0)
+    flags = (1 if with_blocks else 0) | (2 if print_md else 0) | (4 if svsig else 0)
+    if svsig and svsig_len is not None:
+        ctx.check(ctx.lib.lra_ctx_set_svsig_len(ctx.h, int(svsig_len)))
     ctx.check(ctx.lib.lra_map_pack(ctx.h, C.byref(res), flags, C.byref(d_buf), C.byref(nb)))
     return ctx.to_host(d_buf.value, nb.value, np.uint8)
 
@@ -77,6 +81,28 @@ def records_from_packed(lib, copts, packed: np.ndarray, names, reads, chrom_name
     if rc != 0:
         lib.lra_map_host_free(snap)
         raise RuntimeError("lra_map_records_host failed (%d)" % rc)
+    raw = C.string_at(text, ln.value)
+    out = [raw[roff[i]:roff[i + 1]] for i in range(n)]
+    lib.lra_map_host_free(snap)
+    return out
+
+
+def svsig_from_packed(lib, packed: np.ndarray, names, chrom_names, n_threads=0):
+    """One rank's record buffer packed with svsig=True -> per read of that rank the bytes of its SV signature lines (MapRead's svsigstrm), in the
+    rank's read order.  Host only: lra_map_unpack_host + lra_map_svsig_host; merge_by_ordinal puts the ranks' lists in input order."""
+    n = len(names)
+    buf = np.ascontiguousarray(packed, dtype=np.uint8)
+    snap = C.c_void_p()
+    rc = lib.lra_map_unpack_host(C.c_void_p(buf.ctypes.data), C.c_uint64(buf.nbytes), C.byref(snap))
+    if rc != 0:
+        raise RuntimeError("lra_map_unpack_host failed (%d)" % rc)
+    nm = [x if isinstance(x, bytes) else str(x).encode() for x in names]
+    cn = [x if isinstance(x, bytes) else str(x).encode() for x in chrom_names]
+    text = C.c_char_p(); ln = C.c_uint64(0); roff = C.POINTER(C.c_uint64)()
+    rc = lib.lra_map_svsig_host(snap, (C.c_char_p * n)(*nm), (C.c_char_p * len(cn))(*cn), int(n_threads), C.byref(text), C.byref(ln), C.byref(roff))
+    if rc != 0:
+        lib.lra_map_host_free(snap)
+        raise RuntimeError("lra_map_svsig_host failed (%d)" % rc)
     raw = C.string_at(text, ln.value)
     out = [raw[roff[i]:roff[i + 1]] for i in range(n)]
     lib.lra_map_host_free(snap)

@@ -97,6 +97,35 @@ def md_of_refined(ctx: Context, b: RefineBatch, rres: RefineResult):
     return md_strings_batch(ctx, v)
 
 
+class SvSigRec(C.Structure):
+    """lra_svsig_rec (include/lra_hip.h)"""
+    _fields_ = [("seq_off", C.c_uint64), ("t_start", C.c_uint32), ("len", C.c_uint32), ("kind", C.c_uint32), ("block", C.c_uint32)]
+
+
+class SvSigResult(C.Structure):
+    """lra_svsig_result (include/lra_hip.h)"""
+    _fields_ = [("n_aln", C.c_int32), ("n_sig", C.c_uint64), ("n_seq_bytes", C.c_uint64), ("d_sig_off", C.c_void_p), ("d_sig", C.c_void_p), ("d_seq", C.c_void_p)]
+
+
+SV_INS, SV_DEL = 0, 1
+SVSIG_PIECE = 1024                  # svsig.hip's SV_PIECE: the output bytes one wave of the copy kernel moves (the tests place sequence lengths around it)
+SVSIG_REC = np.dtype([("seq_off", "<u8"), ("t_start", "<u4"), ("len", "<u4"), ("kind", "<u4"), ("block", "<u4")])
+
+
+def sv_signatures_batch(ctx: Context, b: RefineBatch, min_len=25):
+    """lra_sv_signatures_batch: the SV signatures (Alignment::Printsvsig) of every alignment of a RefineBatch-shaped input, on the device ->
+    (sig_off uint64[n + 1], records as a SVSIG_REC array [n_sig], the sequence bytes): alignment a's records are [sig_off[a], sig_off[a + 1]), record
+    x's bases are seq[seq_off, seq_off + len)."""
+    res = SvSigResult()
+    ctx.check(ctx.lib.lra_sv_signatures_batch(ctx.h, b.n, ptr(b.blocks), ptr(b.block_off), ptr(b.q_seq), ptr(b.q_off), ptr(b.q_len), ptr(b.t_seq), ptr(b.t_off),
+                                              C.c_int32(int(min_len)), C.byref(res)))
+    n, ns, nb = int(res.n_aln), int(res.n_sig), int(res.n_seq_bytes)
+    off = ctx.to_host(res.d_sig_off, n + 1, np.uint64)
+    recs = ctx.to_host(res.d_sig, ns * SVSIG_REC.itemsize, np.uint8).view(SVSIG_REC) if ns else np.zeros(0, SVSIG_REC)
+    seq = ctx.to_host(res.d_seq, nb, np.uint8).tobytes() if nb else b""
+    return off, recs, seq
+
+
 STAT_NAMES = ["nm", "nmm", "nins", "ndel", "tdel", "tins", "nSmallDel", "nMedDel", "nLargeDel", "nSmallIns", "nMedIns", "nLargeIns",
               "preClip", "sufClip", "qStart", "qEnd", "tStart", "tEnd"]
 

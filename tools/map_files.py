@@ -54,6 +54,8 @@ def main():
     ap.add_argument("-H", dest="hard_clip", action="store_true", help="hard-clip SAM records")
     ap.add_argument("--printMD", action="store_true", help="MD:Z in SAM records")
     ap.add_argument("-a", dest="store_all", action="store_true", help="seed from every k-mer of a read")
+    ap.add_argument("-SV", dest="sv", nargs=2, metavar=("LEN", "PATH"), default=None,
+                    help="write the SV signatures (net gaps inside an alignment longer than LEN) of every read to PATH")
     ap.add_argument("--PrintNumAln", type=int, default=1)
     ap.add_argument("--refineBreakpoints", action="store_true")
     ap.add_argument("-o", dest="out", default=None, help="output file (default stdout)")
@@ -92,6 +94,8 @@ def main():
             o = mapread.with_gli(o, *gli_params)
         o.printFormat = fmt; o.PrintNumAln = args.PrintNumAln; o.printMD = args.printMD; o.storeAll = args.store_all
         o.refineBreakpoint = args.refineBreakpoints
+        if args.sv:
+            o.svsigLen = int(args.sv[0])
         if args.hard_clip:
             o.hardClip = True
         mapper = mapread.LowAccMapper(ctx, genome, ik, ipos, names, chrom_pos, o, index_params=INDEX_PARAMS[P], staged=False)
@@ -99,16 +103,19 @@ def main():
         ov = dict(printFormat=ord(fmt), PrintNumAln=args.PrintNumAln, refineBreakpoint=int(args.refineBreakpoints), printMD=args.printMD, storeAll=args.store_all)
         if args.hard_clip:
             ov["hardClip"] = 1
+        if args.sv:
+            ov["svsigLen"] = int(args.sv[0])
         mapper = mapread.HighAccMapper(ctx, genome, ik, ipos, names, chrom_pos, preset=P.lower(), index_params=INDEX_PARAMS[P], gli=gli_params, **ov)
     t_index = time.perf_counter() - t0
     out = open(args.out, "wb") if args.out else sys.stdout.buffer
     if fmt == "s":
         cl = ["lra", "align", "-" + P, args.genome, *args.reads, "-p", args.fmt] + (["-H"] if args.hard_clip else []) + (["--printMD"] if args.printMD else []) + \
              (["-a"] if args.store_all else []) + ["--PrintNumAln", str(args.PrintNumAln)] + (["--refineBreakpoints"] if args.refineBreakpoints else []) + \
-             (["-Flag", str(args.flag)] if args.flag else []) + (["--passthrough"] if args.passthrough else [])
+             (["-Flag", str(args.flag)] if args.flag else []) + (["--passthrough"] if args.passthrough else []) + (["-SV", *args.sv] if args.sv else [])
         out.write(mapread.LowAccMapper.sam_header(mapper, b"lra_amd", " ".join(cl).encode()))   # the lra command line: the same for either reader
     rf = reads_io.ReadsFile(args.reads, ctx=None if args.host_input else ctx, chunk=None if args.host_input else args.chunk, flag_remove=args.flag,
                             passthrough=args.passthrough)
+    sv_out = open(args.sv[1], "wb") if args.sv else None
     t_read = t_map = t_rec = 0.0
     n_reads = n_bases = n_batches = 0
     failed = None
@@ -125,13 +132,23 @@ def main():
         res = reads_io.map_reads_host(mapper, b["raw"]) if args.host_input else reads_io.map_reads_device(mapper, b)
         t_map += time.perf_counter() - t
         t = time.perf_counter()
-        for txt in mapper.records(res, b["names"], b["seqs"], quals=b["quals"], passthrough=b["tags"] if args.passthrough else None):
+        tags = b["tags"] if args.passthrough else None
+        if sv_out:                                                          # one snapshot: the records and the signatures of the same batch, both in read order
+            snap = mapper.snapshot(res, with_blocks=fmt == "a", svsig=True)
+            texts = mapper.records_host(snap, mapper.record_args(b["names"], b["seqs"], b["quals"]), passthrough=tags, free=False)
+            for sig in mapper.svsig_host(snap, b["names"]):
+                sv_out.write(sig)
+        else:
+            texts = mapper.records(res, b["names"], b["seqs"], quals=b["quals"], passthrough=tags)
+        for txt in texts:
             out.write(txt)
         t_rec += time.perf_counter() - t
         n_reads += len(b["names"]); n_bases += int(b["off"][-1]); n_batches += 1
         if failed:
             break
     rf.close()
+    if sv_out:
+        sv_out.close()
     if args.out:
         out.close()
     else:
