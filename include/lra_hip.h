@@ -1156,8 +1156,17 @@ int lra_map_reads_highacc_batch(lra_ctx* ctx, int n_reads, const char* d_seq, co
  * length mismatch, a file behind a SAM / BAM file (never read), a SAM / BAM file behind a FASTQ file that an empty batch would meet -- the call returns
  * LRA_ERR_INVALID as for a corrupt FASTQ record: lra_reads_last_error names the file and the reason (a block by its compressed offset, a record by its
  * index), the batch holds the reads in front of it, and the error is sticky.
- * Not supported: streamed input ("-", "stdin", "/dev/stdin": the format sniffing seeks; the reference refuses to stream SAM / BAM), CRAM, fastq.gz and
- * other gzip that is not BGZF (the reference refuses these too).  */
+ * lra_reads_open refuses compressed FASTA / FASTQ as the reference does.  lra_reads_open_flags(files, n, LRA_READS_COMPRESSED_TEXT, &r) (additive to
+ * ABI 9; flags 0 = lra_reads_open) takes them, gzip and BGZF: a file that starts 1f 8b is sniffed by its inflated head with the FASTA / FASTQ rule, and a
+ * compressed file yields exactly the batches its decompressed bytes would yield as a plain file at the same place in the file list (names, bases,
+ * qualities, off, read_len, batch cuts, the FASTQ end-of-file rules, the quality-length error, what happens to the files behind it).  BGZF that holds BAM
+ * or SAM stays BAM / SAM; other gzip that holds neither FASTA nor FASTQ (gzip'd SAM, gzip'd BAM bytes) stays refused.  A compression fault (a truncated
+ * file, a bad code, a CRC-32 or ISIZE mismatch, bytes behind a member that start no member) follows the BAM reader's rule: LRA_ERR_INVALID, sticky, the
+ * file and the member's compressed offset in lra_reads_last_error; the batch holds the records that are whole in the bytes in front of the fault.
+ * The device form inflates BGZF members on the device (one wave per member) and parses where the data lies; gzip that is not BGZF is one serial bit
+ * stream, inflated by ONE host thread in both forms (about 0.16 GB/s of text): BGZF is the format to use at speed.
+ * Not supported: streamed input ("-", "stdin", "/dev/stdin": the format sniffing seeks; the reference refuses to stream SAM / BAM), CRAM, and gzip that is
+ * not BGZF around anything but FASTA / FASTQ.  */
 typedef struct lra_reads lra_reads;
 typedef struct lra_read_batch {
   int32_t n_reads; uint64_t total_bases;
@@ -1165,6 +1174,8 @@ typedef struct lra_read_batch {
   const char* const* names; const char* const* reads; const char* const* quals;
 } lra_read_batch;
 int lra_reads_open(const char* const* files, int n_files, lra_reads** out);
+#define LRA_READS_COMPRESSED_TEXT 1   /* lra_reads_open_flags: gzip / BGZF FASTA and FASTQ files are read */
+int lra_reads_open_flags(const char* const* files, int n_files, uint32_t flags, lra_reads** out);   /* flags outside the defined ones: LRA_ERR_INVALID */
 int lra_reads_next_batch(lra_reads* r, uint64_t max_bases, lra_read_batch* batch);
 const char* lra_reads_last_error(const lra_reads* r);
 uint64_t lra_map_host_trim(uint64_t keep_bytes);   /* (ABI 6) the record stage keeps its threads' text parts between batches (process-wide, at most LRA_PARTS_POOL_MB, default 4096, of
@@ -1193,9 +1204,12 @@ int lra_reads_batch_tags(const lra_reads* r, const char* const** tags);
  * member with a 'BC' field whose BSIZE + 1 is its length --, its data goes to out[out_off[i], out_off[i + 1]), which must be its ISIZE (<= 65536).
  * status[i]: 0, or the reason the member is bad (1 header, 2 data ends early, 3 more than ISIZE, 4 invalid code, 5 distance before the block, 6 stored
  * LEN / NLEN, 7 less than ISIZE, 8 CRC-32, 9 ISIZE): nothing outside a member's ranges is read or written.  _batch: device arrays, on ctx's device and
- * stream, complete at return (one wave per member); _host: host arrays, the same decoder. */
+ * stream, complete at return (one wave per member); _host: host arrays, the same decoder.  _lut_batch: the contract of _batch by the table-driven
+ * kernel (inflate_lut.hip: lookup tables and an output ring in LDS, the whole wave copies matches and writes dwords), the compressed text reader's. */
 int lra_bgzf_inflate_batch(lra_ctx* ctx, int n_blocks, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_out_off, uint8_t* d_out,
                            int32_t* d_status);
+int lra_bgzf_inflate_lut_batch(lra_ctx* ctx, int n_blocks, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_out_off, uint8_t* d_out,
+                               int32_t* d_status);
 int lra_bgzf_inflate_host(int n_blocks, const uint8_t* in, const uint64_t* in_off, const uint64_t* out_off, uint8_t* out, int32_t* status);
 /* ---- the genome (Genome::Read, Genome.h:115-138) -------------------------------------------------------------------------------------------------
  * A genome FASTA file -- plain text, gzip or BGZF, as gzopen takes them -- into what lra_ctx_load_genome[_device] and lra_ctx_load_chromosomes take: the

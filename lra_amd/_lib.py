@@ -63,6 +63,7 @@ SYMBOLS = {
     "lra_linear_extend_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "lra_sparse_dp_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lra_reads_open": (C.c_int, [_vp, C.c_int, _vp]),
+    "lra_reads_open_flags": (C.c_int, [_vp, C.c_int, C.c_uint32, _vp]),
     "lra_reads_next_batch": (C.c_int, [_vp, C.c_uint64, _vp]),
     "lra_reads_close": (None, [_vp]),
     "lra_reads_last_error": (C.c_char_p, [_vp]),
@@ -72,6 +73,7 @@ SYMBOLS = {
     "lra_reads_set_passthrough": (C.c_int, [_vp, C.c_int]),
     "lra_reads_batch_tags": (C.c_int, [_vp, _vp]),
     "lra_bgzf_inflate_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "lra_bgzf_inflate_lut_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lra_bgzf_inflate_host": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lra_genome_open": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),
     "lra_genome_read_host": (C.c_int, [_vp]),

@@ -1,6 +1,7 @@
 """BGZF, BAM and SAM writers for tests and tools (the SAM/BAM specification, sections 1 and 4), built on Python's zlib.
 
 bgzf_compress   BGZF members at any level and strategy, cut where the caller says, with or without the 28-byte EOF member
+gzip_compress   plain (non-BGZF) gzip of one or more members, with optional FNAME / FEXTRA / FHCRC header fields
 bam_bytes       an unaligned BAM (header + records with typed aux fields of every kind), uncompressed; write_bam compresses it
 sam_text        the same records as SAM text; write_sam writes it plain or BGZF-compressed
 
@@ -32,6 +33,27 @@ def bgzf_compress(data: bytes, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, cuts=N
     bounds = [0] + [c for c in cuts if 0 < c < len(data)] + [len(data)]
     out = [member(data[a:b], level, strategy) for a, b in zip(bounds, bounds[1:]) if b > a or len(data) == 0]
     return b"".join(out) + (EOF_BLOCK if eof else b"")
+
+
+def gzip_member(data: bytes, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, fname=None, fextra=None, fhcrc=False) -> bytes:
+    """one RFC 1952 member of data (any size) without a BGZF 'BC' field; fname (bytes), fextra (bytes, must not hold a BC subfield) and fhcrc set the
+    header's FNAME / FEXTRA / FHCRC fields"""
+    flg = (4 if fextra is not None else 0) | (8 if fname is not None else 0) | (2 if fhcrc else 0)
+    head = b"\x1f\x8b\x08" + bytes([flg]) + b"\0\0\0\0" + b"\0\xff"
+    if fextra is not None:
+        head += struct.pack("<H", len(fextra)) + fextra
+    if fname is not None:
+        head += fname + b"\0"
+    if fhcrc:
+        head += struct.pack("<H", zlib.crc32(head) & 0xffff)
+    c = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
+    return head + c.compress(data) + c.flush() + struct.pack("<II", zlib.crc32(data) & 0xffffffff, len(data) & 0xffffffff)
+
+
+def gzip_compress(data: bytes, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, cuts=(), **fields) -> bytes:
+    """data as concatenated gzip members cut at the offsets `cuts` (none: one member); fields: gzip_member's fname / fextra / fhcrc, on every member"""
+    bounds = [0] + [c for c in cuts if 0 < c < len(data)] + [len(data)]
+    return b"".join(gzip_member(data[a:b], level, strategy, **fields) for a, b in zip(bounds, bounds[1:]))
 
 
 def blocks(data: bytes):

@@ -19,7 +19,15 @@
 //      record by index), the batch of that call holds the reads in front of the problem, the error is sticky; every batch before it is the reference's;
 //   3. sniffing keeps FASTA and FASTQ first; then a gzip member with a BGZF 'BC' field is inflated (its data starts "BAM\1": BAM, else BGZF SAM); plain
 //      text whose first line is a SAM header line ('@', two letters, a tab) or has at least 11 tab-separated fields is SAM; everything else (CRAM,
-//      non-BGZF gzip, fastq.gz) is refused.
+//      non-BGZF gzip, fastq.gz) is refused.  lra_reads_open_flags with LRA_READS_COMPRESSED_TEXT adds one branch in front of the BGZF one: a file that
+//      starts 1f 8b is sniffed by its inflated head (the first members of BGZF; up to 64 KiB + 1 KiB of output of other gzip) with the FASTA / FASTQ rule
+//      above, and read as that: BGZF members through lra_bgzf_inflate_one, other gzip through lra_gz_stream in steps, both behind a std::streambuf that
+//      feeds the line parser below, so the batches are those of the decompressed bytes as a plain file.  BGZF that holds BAM or SAM stays BAM / SAM; other
+//      gzip that holds neither FASTA nor FASTQ stays refused;
+//   4. a compression fault in such a file (a truncated file, a bad code, a CRC-32 or ISIZE mismatch, bytes behind a member that start no member) follows
+//      decision 2: LRA_ERR_INVALID, sticky, the file and the member's compressed offset in lra_reads_last_error.  The reads in front of the fault are the
+//      records that are whole in the bytes in front of the faulty member (of all bytes decoded before the fault, for gzip): a record the fault cuts, or
+//      one whose end only the end of the file would show (the last FASTA record, a FASTQ record without its last newline), is not delivered.
 #include "common.h"
 #include "map_state.h"
 #include "reads_state.h"
@@ -239,6 +247,111 @@ lra_hts_in* lra_hts_open(const std::string& path, int type, std::string* err) {
   return h;
 }
 
+const char* lra_gz_reason(int st) {
+  switch (st) {
+    case LRA_GZ_ERR_HEADER: return "not a gzip member";
+    case LRA_GZ_ERR_TRUNCATED: return "the file ends inside it";
+    case LRA_BGZF_ERR_ISIZE: return "its ISIZE is not the size of its data";
+    default: return lra_bgzf_reason(st);
+  }
+}
+
+namespace {
+
+// compressed FASTA / FASTQ (decision 3): the inflated bytes as the stream the line parser reads
+struct ztext_bgzf : lra_ztext {
+  std::unique_ptr<lra_hts_in, lra_hts_deleter> h;
+  std::string path;
+  int_type underflow() override {
+    if (gptr() < egptr()) return traits_type::to_int_type(*gptr());
+    if (!fault.empty() || !h) return traits_type::eof();
+    h->pos = h->buf.size();
+    if (!h->next_block()) {
+      if (!h->err.empty()) fault = path + ": " + h->err;
+      return traits_type::eof();
+    }
+    char* b = (char*)h->buf.data();
+    setg(b + h->pos, b + h->pos, b + h->buf.size());
+    return traits_type::to_int_type(*gptr());
+  }
+};
+
+struct ztext_gzip : lra_ztext {
+  std::string path, next_fault;
+  std::vector<uint8_t> comp;
+  std::vector<char> out;
+  lra_gz_stream gz;
+  bool loaded = false, done = false;
+  int_type underflow() override {
+    if (gptr() < egptr()) return traits_type::to_int_type(*gptr());
+    if (!loaded) {                                 // the whole compressed file: lra_gz_stream walks one array
+      loaded = true;
+      const int fd = open(path.c_str(), O_RDONLY);
+      if (fd < 0) { done = true; next_fault = "cannot open " + path; }
+      else {
+        for (;;) {
+          const size_t at = comp.size();
+          comp.resize(at + (4u << 20));
+          const ssize_t k = read(fd, comp.data() + at, 4u << 20);
+          comp.resize(at + (k > 0 ? (size_t)k : 0));
+          if (k <= 0) break;
+        }
+        close(fd);
+        lra_gz_init(gz, comp.data(), comp.size());
+        out.resize(1u << 20);
+      }
+    }
+    if (done) { fault = next_fault; return traits_type::eof(); }
+    uint64_t got = 0;
+    const int st = lra_gz_step(gz, (uint8_t*)out.data(), out.size(), &got);
+    if (st) next_fault = path + ": a bad gzip member at compressed offset " + std::to_string(gz.member_at) + " (" + lra_gz_reason(st) + ")";
+    if (st || got < out.size()) done = true;
+    if (!got) { fault = next_fault; return traits_type::eof(); }
+    setg(out.data(), out.data(), out.data() + got);
+    return traits_type::to_int_type(*gptr());
+  }
+};
+
+int sniff_text_head(const uint8_t* p, size_t n) {   // Input.h:66-85 on a file's first bytes
+  if (!n) return -1;
+  if (p[0] == '>') return LRA_IN_FASTA;
+  if (p[0] != '@') return -1;
+  const uint8_t* a = (const uint8_t*)memchr(p, '\n', n);
+  if (!a) return -1;
+  const uint8_t* b = (const uint8_t*)memchr(a + 1, '\n', n - (size_t)(a + 1 - p));
+  if (!b || b + 1 >= p + n) return -1;
+  return b[1] == '+' ? LRA_IN_FASTQ : -1;
+}
+
+}  // namespace
+
+int lra_ztext_sniff(const std::string& path, int* zmode) {
+  const int fd = open(path.c_str(), O_RDONLY);
+  if (fd < 0) return -1;
+  std::vector<uint8_t> head(1u << 20);
+  size_t n = 0;
+  while (n < head.size()) { const ssize_t k = read(fd, head.data() + n, head.size() - n); if (k <= 0) break; n += (size_t)k; }
+  close(fd);
+  if (n < 2 || head[0] != 0x1f || head[1] != 0x8b) return -1;
+  const size_t want = 65536 + 1024;
+  uint32_t total = 0, cdata = 0;
+  if (lra_bgzf_member(head.data(), n, &total, &cdata) == 1) {
+    *zmode = LRA_Z_BGZF;
+    std::string err;
+    std::unique_ptr<lra_hts_in, lra_hts_deleter> h(lra_hts_open(path, -2, &err));
+    if (!h) return -1;
+    while (h->buf.size() < want && h->next_block()) {}
+    return sniff_text_head(h->buf.data(), h->buf.size());
+  }
+  *zmode = LRA_Z_GZIP;
+  std::unique_ptr<lra_gz_stream> gz(new lra_gz_stream());
+  lra_gz_init(*gz, head.data(), n);
+  std::vector<uint8_t> out(want);
+  uint64_t got = 0;
+  (void)lra_gz_step(*gz, out.data(), out.size(), &got);   // (the head may end inside the member: what it gave is sniffed)
+  return sniff_text_head(out.data(), got);
+}
+
 namespace {
 
 bool parse_sam_aux(const std::string& f, std::string& aux) {   // "TG:T:value" -> its BAM binary form (sam_parse1)
@@ -428,13 +541,45 @@ bool is_fastq(std::istream& s) {                    // Input.h:66-85: '@', and '
   s.clear(); s.seekg(at);
   return res;
 }
+std::istream& txt(lra_reads* r) { return r->zmode != LRA_Z_PLAIN ? r->zstrm : r->strm; }   // the current FASTA / FASTQ file's bytes
+void close_txt(lra_reads* r) {
+  r->strm.close();
+  r->zstrm.rdbuf(nullptr); r->zbuf.reset(); r->zmode = LRA_Z_PLAIN;
+}
+bool zfault(lra_reads* r) {                         // a compression fault met while the last record was read (decision 4)
+  if (r->zmode == LRA_Z_PLAIN || !r->zbuf || r->zbuf->fault.empty()) return false;
+  r->open_ok = false;
+  r->error = r->zbuf->fault;
+  return true;
+}
 bool open_file(lra_reads* r) {                      // Input.h:87-168; SAM / BAM: the port's sniffing (decision 3)
-  r->strm.close(); r->strm.clear();
+  close_txt(r); r->strm.clear();
   r->hts.reset();
   r->strm.open(r->files[r->cur].c_str());
   if (is_fasta(r->strm)) { r->type = LRA_IN_FASTA; return true; }
   if (is_fastq(r->strm)) { r->type = LRA_IN_FASTQ; return true; }
   r->strm.close(); r->strm.clear();
+  if (r->open_flags & LRA_READS_COMPRESSED_TEXT) {
+    int zm = LRA_Z_PLAIN;
+    const int t = lra_ztext_sniff(r->files[r->cur], &zm);
+    if (t >= 0) {
+      if (zm == LRA_Z_BGZF) {
+        ztext_bgzf* z = new ztext_bgzf();
+        r->zbuf.reset(z);
+        z->path = r->files[r->cur];
+        std::string err;
+        z->h.reset(lra_hts_open(z->path, -2, &err));
+        if (!z->h) { close_txt(r); r->type = -1; return false; }
+      } else {
+        ztext_gzip* z = new ztext_gzip();
+        r->zbuf.reset(z);
+        z->path = r->files[r->cur];
+      }
+      r->type = t; r->zmode = zm;
+      r->zstrm.rdbuf(r->zbuf.get()); r->zstrm.clear();
+      return true;
+    }
+  }
   r->type = lra_hts_sniff(r->files[r->cur], nullptr);
   if (r->type < 0) return false;
   std::string err;
@@ -480,8 +625,8 @@ bool get_next(lra_reads* r, std::string& name, std::string& seq, std::string& qu
   name.clear(); seq.clear(); qual.clear();
   *hasq = false; *has_tag = false;
   if (!r->open_ok) return false;
-  if (r->type == 0 && r->strm.eof()) {                                     // any more FASTA files?
-    r->strm.close();
+  if (r->type == 0 && txt(r).eof()) {                                     // any more FASTA files?
+    close_txt(r);
     ++r->cur;
     if (r->cur >= r->files.size() || !open_file(r)) { r->open_ok = false; return false; }
   }
@@ -493,30 +638,32 @@ bool get_next(lra_reads* r, std::string& name, std::string& seq, std::string& qu
     if (r->passthrough) *has_tag = lra_format_aux((const uint8_t*)rec.aux.data(), rec.aux.size(), tag);
     return true;
   }
-  if (r->strm.eof()) return false;
+  if (txt(r).eof()) return false;
   if (r->type == 0) {
     std::string header;
-    std::getline(r->strm, header);
+    std::getline(txt(r), header);
     name = first_token_behind_first_char(header);
-    int c = r->strm.peek();
+    int c = txt(r).peek();
     while (c != EOF && c != '>') {
       std::string line;
-      std::getline(r->strm, line);
+      std::getline(txt(r), line);
       squeeze_upper(line);
       seq += line;
-      c = r->strm.peek();
+      c = txt(r).peek();
     }
-    if (c == EOF) r->strm.get();
+    if (c == EOF) txt(r).get();
+    if (zfault(r)) return false;
     return true;
   }
   std::string header, sep;
-  std::getline(r->strm, header); std::getline(r->strm, seq); std::getline(r->strm, sep); std::getline(r->strm, qual);
+  std::getline(txt(r), header); std::getline(txt(r), seq); std::getline(txt(r), sep); std::getline(txt(r), qual);
+  if (zfault(r)) return false;
   if (header.empty() || seq.empty() || sep.empty() || qual.empty()) {      // this file is over: the next one
-    r->strm.close();
+    close_txt(r);
     ++r->cur;
     if (r->cur >= r->files.size() || !open_file(r)) { r->open_ok = false; return false; }
     if (r->type >= LRA_IN_BAM) { r->hts_unread = true; return false; }   // Input.h:242-266: re-initialized, returns 0
-    if (r->type == 1) { std::getline(r->strm, header); std::getline(r->strm, seq); std::getline(r->strm, sep); std::getline(r->strm, qual); }
+    if (r->type == 1) { std::getline(txt(r), header); std::getline(txt(r), seq); std::getline(txt(r), sep); std::getline(txt(r), qual); if (zfault(r)) return false; }
   }
   if (header.empty() || seq.empty() || sep.empty() || qual.empty()) return false;
   name = first_token_behind_first_char(header);
@@ -536,9 +683,12 @@ bool get_next(lra_reads* r, std::string& name, std::string& seq, std::string& qu
 
 }  // namespace
 
-extern "C" int lra_reads_open(const char* const* files, int n_files, lra_reads** out) {
-  if (!files || n_files < 1 || !out) return LRA_ERR_INVALID;
+extern "C" int lra_reads_open(const char* const* files, int n_files, lra_reads** out) { return lra_reads_open_flags(files, n_files, 0, out); }
+
+extern "C" int lra_reads_open_flags(const char* const* files, int n_files, uint32_t flags, lra_reads** out) {
+  if (!files || n_files < 1 || !out || (flags & ~(uint32_t)LRA_READS_COMPRESSED_TEXT)) return LRA_ERR_INVALID;
   lra_reads* r = new lra_reads();
+  r->open_flags = flags;
   for (int i = 0; i < n_files; i++) r->files.push_back(files[i] ? files[i] : "");
   r->open_ok = open_file(r);
   if (!r->open_ok) { delete r; *out = nullptr; return LRA_ERR_INVALID; }   // the reference prints "Cannot determine format of input reads." and exits

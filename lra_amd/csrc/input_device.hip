@@ -14,6 +14,14 @@
 //             rd_name_len      per record: the name token (`ss >> c >> name` on the header line)                        -> exclusive scan
 //             rd_name_emit     the names, NUL-terminated, back to back
 //           FASTQ records are framed by line index mod 4 from the step's start (a step starts at a record); FASTA records by their header lines.
+//   compressed FASTA / FASTQ (lra_reads_open_flags with LRA_READS_COMPRESSED_TEXT; input.hip's decisions 3 and 4):
+//     BGZF    the host walks the members' headers in each step of compressed bytes (a member the step cut stays for the next step), the members are inflated
+//             on the device, a wave per member, behind the carried tail of the last step's text (the record the step cut, carried device to device), and
+//             the passes above run where the data lies: no text crosses the bus.  The chunk counts compressed bytes.
+//     gzip    that is not BGZF is one serial bit stream: the host inflates a step with bgzf.h's lra_gz_stream (window, bit buffer and an unfinished match
+//             kept across steps, members concatenated) into the page-locked step buffer; upload and passes as for a plain file.  The chunk counts output
+//             bytes.  This path is bound by ONE CPU thread (about 0.16 GB/s of text, half of that in bases): BGZF is the format to use at speed.
+//     A fault ends the file's steps: the step in front of it is parsed as one that the file goes on behind (whole records only), then the error stands.
 //   batch   the records a batch takes are contiguous runs of a step's records: their bases are copied device to device into the reader's d_seq (64 zero
 //           bytes behind the last), their names / qualities / bases once to page-locked host arrays.
 #include "common.h"
@@ -226,6 +234,11 @@ struct lra_reads_dev {
   DevBuf<unsigned long long> first_bad; DevBuf<uint8_t> c_aux;
   std::vector<uint8_t> h_aux;                      // the step's aux bytes (passthrough on)
   std::string pending_error;                       // the step stops at a problem: the error once its records are taken
+  // compressed FASTA / FASTQ: BGZF uses h_raw / d_comp / d_dec / d_boff / d_bstat as the BAM steps do (the step's text is d_dec[dec_cur][0, dec_len))
+  int zmode = LRA_Z_PLAIN;
+  std::vector<uint8_t> gz_comp; std::unique_ptr<lra_gz_stream> gz;   // gzip that is not BGZF: the compressed file, the decoder between steps
+  const unsigned char* d_text = nullptr;           // the step's text on the device, and what the host needs of it without its bytes:
+  uint64_t lines_in = 0;                           // its lines (the last one may lack its '\n')
   // records parsed on the host (SAM text) in the device form's batch: their bases go up at the batch's end
   std::string h_pend; std::vector<uint64_t> pend_at;
   ~lra_reads_dev() {
@@ -271,6 +284,26 @@ bool open_dev_file(lra_reads* r) {
   d->fd = open(r->files[r->cur].c_str(), O_RDONLY);
   d->type = d->fd >= 0 ? sniff(d->fd) : -1;
   d->len = d->consumed = 0; d->file_at_eof = false; d->fq_eof = false;
+  d->zmode = LRA_Z_PLAIN; d->pending_error.clear(); d->gz.reset(); d->gz_comp.clear();
+  if (d->fd >= 0 && d->type < 0 && (r->open_flags & LRA_READS_COMPRESSED_TEXT)) {   // gzip / BGZF FASTA or FASTQ (input.hip's sniffing)
+    int zm = LRA_Z_PLAIN;
+    const int t = lra_ztext_sniff(r->files[r->cur], &zm);
+    if (t >= 0) {
+      d->type = t; d->zmode = zm;
+      d->comp_file_off = 0; d->dec_len = d->dec_used = 0;
+      if (zm == LRA_Z_GZIP) {                                      // lra_gz_stream walks the whole compressed file as one array
+        for (;;) {
+          const size_t at = d->gz_comp.size();
+          d->gz_comp.resize(at + (4u << 20));
+          const ssize_t k = read(d->fd, d->gz_comp.data() + at, 4u << 20);
+          d->gz_comp.resize(at + (k > 0 ? (size_t)k : 0));
+          if (k <= 0) break;
+        }
+        d->gz.reset(new lra_gz_stream());
+        lra_gz_init(*d->gz, d->gz_comp.data(), d->gz_comp.size());
+      }
+    }
+  }
   d->rec.clear(); d->n_avail = d->next = 0; d->step_ends_file = false;
   d->seg_a = d->seg_b = 0;
   r->hts.reset();
@@ -326,20 +359,19 @@ int flush_segment(lra_ctx* ctx, lra_reads_dev* d) {
   return LRA_OK;
 }
 
-// the device passes over h_raw[0, len): the record table of the step
-int parse(lra_ctx* ctx, lra_reads_dev* d) {
+uint64_t padded_tiles(uint64_t len) { return std::max<uint64_t>(1, (len + RD_TILE - 1) / RD_TILE) * RD_TILE; }
+
+// the device passes over a step's text that lies on the device, raw[0, len) with zeros up to padded_tiles(len): the record table of the step.
+// last = the text's last byte (the host needs no other byte of it)
+int parse_text(lra_ctx* ctx, lra_reads_dev* d, const unsigned char* raw, uint64_t len, unsigned char last) {
   const int fasta = d->type == 0;
-  const uint64_t len = d->len, nt = std::max<uint64_t>(1, (len + RD_TILE - 1) / RD_TILE), padded = nt * RD_TILE;
+  const uint64_t nt = padded_tiles(len) / RD_TILE;
   hipStream_t st = ctx->stream;
-  if (!d->d_raw.ensure(padded)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc(%zu) failed", (size_t)padded);
   for (int i = 0; i < 4; i++)
     if (!d->cnt[i].ensure(nt) || !d->base[i].ensure(nt + 1)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
-  lra_time_begin(ctx, "input_h2d");
-  if (len) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_raw.p, d->h_raw.p, len, hipMemcpyHostToDevice, st));
-  LRA_HIP_CHECK(ctx, hipMemsetAsync(d->d_raw.p + len, 0, padded - len, st));
-  lra_time_end(ctx);
+  d->d_text = raw;
   lra_time_begin(ctx, "input_parse");
-  hipLaunchKernelGGL(rd_count_lines, dim3((unsigned)nt), dim3(RD_NT), 0, st, d->d_raw.p, fasta, d->cnt[0].p, d->cnt[1].p);
+  hipLaunchKernelGGL(rd_count_lines, dim3((unsigned)nt), dim3(RD_NT), 0, st, raw, fasta, d->cnt[0].p, d->cnt[1].p);
   if (int rc = lra_exclusive_scan(ctx, (long)nt, d->cnt[0].p, d->base[0].p)) return rc;
   if (int rc = lra_exclusive_scan(ctx, (long)nt, d->cnt[1].p, d->base[1].p)) return rc;
   lra_time_end(ctx);
@@ -348,7 +380,7 @@ int parse(lra_ctx* ctx, lra_reads_dev* d) {
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(&tot[1], d->base[1].p + nt, 8, hipMemcpyDeviceToHost, st));
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
   d->n_nl = tot[0];
-  const uint64_t lines_in = d->n_nl + (len && d->h_raw.p[len - 1] != '\n');
+  const uint64_t lines_in = d->lines_in = d->n_nl + (len && last != '\n');
   d->n_started = fasta ? tot[1] : (lines_in + 3) / 4;
   const uint64_t n = d->n_started;
   if (!d->nl_pos.ensure(d->n_nl + 1) || !d->d_rec.ensure(n + 1) || !d->name_len.ensure(n + 1) || !d->name_off.ensure(n + 2) || !d->c_seq.ensure(len + 1) ||
@@ -356,21 +388,21 @@ int parse(lra_ctx* ctx, lra_reads_dev* d) {
     return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
   lra_time_begin(ctx, "input_parse");
   LRA_HIP_CHECK(ctx, hipMemsetAsync(d->d_rec.p, 0, (n + 1) * sizeof(RecInfo), st));
-  hipLaunchKernelGGL(rd_emit_lines, dim3((unsigned)nt), dim3(RD_NT), 0, st, d->d_raw.p, d->base[0].p, d->nl_pos.p);
-  hipLaunchKernelGGL(rd_count_kept, dim3((unsigned)nt), dim3(RD_NT), 0, st, d->d_raw.p, len, fasta, d->base[0].p, d->nl_pos.p, d->cnt[2].p, d->cnt[3].p);
+  hipLaunchKernelGGL(rd_emit_lines, dim3((unsigned)nt), dim3(RD_NT), 0, st, raw, d->base[0].p, d->nl_pos.p);
+  hipLaunchKernelGGL(rd_count_kept, dim3((unsigned)nt), dim3(RD_NT), 0, st, raw, len, fasta, d->base[0].p, d->nl_pos.p, d->cnt[2].p, d->cnt[3].p);
   if (int rc = lra_exclusive_scan(ctx, (long)nt, d->cnt[2].p, d->base[2].p)) return rc;
   if (int rc = lra_exclusive_scan(ctx, (long)nt, d->cnt[3].p, d->base[3].p)) return rc;
-  hipLaunchKernelGGL(rd_emit, dim3((unsigned)nt), dim3(RD_NT), 0, st, d->d_raw.p, len, fasta, d->base[0].p, d->base[1].p, d->nl_pos.p, d->base[2].p, d->base[3].p,
+  hipLaunchKernelGGL(rd_emit, dim3((unsigned)nt), dim3(RD_NT), 0, st, raw, len, fasta, d->base[0].p, d->base[1].p, d->nl_pos.p, d->base[2].p, d->base[3].p,
                      d->c_seq.p, d->c_qual.p, d->d_rec.p);
   if (n) {
     const unsigned g = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(rd_name_len, dim3(g), dim3(256), 0, st, d->d_raw.p, len, fasta, n, d->base[3].p + nt, d->d_rec.p, d->name_len.p, d->c_qual.p);
+    hipLaunchKernelGGL(rd_name_len, dim3(g), dim3(256), 0, st, raw, len, fasta, n, d->base[3].p + nt, d->d_rec.p, d->name_len.p, d->c_qual.p);
     if (int rc = lra_exclusive_scan(ctx, (long)n, d->name_len.p, d->name_off.p)) return rc;
     uint64_t name_bytes = 0;
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(&name_bytes, d->name_off.p + n, 8, hipMemcpyDeviceToHost, st));
     LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     if (!d->c_names.ensure(name_bytes + 1)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
-    hipLaunchKernelGGL(rd_name_emit, dim3(g), dim3(256), 0, st, d->d_raw.p, n, d->name_off.p, d->d_rec.p, d->c_names.p);
+    hipLaunchKernelGGL(rd_name_emit, dim3(g), dim3(256), 0, st, raw, n, d->name_off.p, d->d_rec.p, d->c_names.p);
   }
   LRA_HIP_CHECK(ctx, hipGetLastError());
   lra_time_end(ctx);
@@ -387,6 +419,17 @@ int parse(lra_ctx* ctx, lra_reads_dev* d) {
   return LRA_OK;
 }
 
+// the device passes over h_raw[0, len): upload, then parse_text
+int parse(lra_ctx* ctx, lra_reads_dev* d) {
+  const uint64_t len = d->len, padded = padded_tiles(len);
+  if (!d->d_raw.ensure(padded)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc(%zu) failed", (size_t)padded);
+  lra_time_begin(ctx, "input_h2d");
+  if (len) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_raw.p, d->h_raw.p, len, hipMemcpyHostToDevice, ctx->stream));
+  LRA_HIP_CHECK(ctx, hipMemsetAsync(d->d_raw.p + len, 0, padded - len, ctx->stream));
+  lra_time_end(ctx);
+  return parse_text(ctx, d, d->d_raw.p, len, len ? (unsigned char)d->h_raw.p[len - 1] : 0);
+}
+
 // the next step of the current file: the carry of the last step, then up to `chunk` more bytes; a step that holds no whole record (and is not the file's
 // end) reads on, twice as much each time
 int next_step(lra_ctx* ctx, lra_reads* r) {
@@ -399,6 +442,11 @@ int next_step(lra_ctx* ctx, lra_reads* r) {
     if (!d->file_at_eof) {
       if (!d->h_raw.ensure(d->len + want + 1, d->len, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc(%zu) failed", (size_t)(d->len + want));
       uint64_t got = 0;
+      if (d->zmode == LRA_Z_GZIP) {                                // the next `want` bytes of the inflated text (one host thread)
+        const int zs = lra_gz_step(*d->gz, (uint8_t*)d->h_raw.p + d->len, want, &got);
+        if (zs) d->pending_error = r->files[r->cur] + ": a bad gzip member at compressed offset " + std::to_string(d->gz->member_at) + " (" + lra_gz_reason(zs) + ")";
+        if (zs || got < want) d->file_at_eof = true;
+      } else
       while (got < want) {
         const ssize_t k = read(d->fd, d->h_raw.p + d->len + got, (size_t)std::min<uint64_t>(want - got, 1ull << 30));
         if (k < 0) return lra_set_err(ctx, LRA_ERR_INVALID, "device reader: read of %s failed", r->files[r->cur].c_str());
@@ -409,19 +457,110 @@ int next_step(lra_ctx* ctx, lra_reads* r) {
     }
     if (int rc = parse(ctx, d)) return rc;
     const uint64_t n = d->n_started;
+    const bool final = d->file_at_eof && d->pending_error.empty();   // the text ends here (behind a fault it would have gone on: whole records only)
     uint64_t complete;
-    if (d->type == 0) complete = d->file_at_eof ? n : (n ? n - 1 : 0);
-    else if (d->file_at_eof) complete = d->n_nl / 4 + 1;           // through the first unit whose 4th getline meets the end of the file (4u + 3 >= n_nl)
+    if (d->type == 0) complete = final ? n : (n ? n - 1 : 0);
+    else if (final) complete = d->n_nl / 4 + 1;                    // through the first unit whose 4th getline meets the end of the file (4u + 3 >= n_nl)
     else complete = d->n_nl / 4;
     if (complete == 0 && !d->file_at_eof) { want = std::max(want, d->len) * 2; continue; }
     d->n_avail = complete;
     d->step_ends_file = d->file_at_eof;
-    d->consumed = d->file_at_eof ? d->len : (complete < n ? d->rec[complete].start : d->len);
+    d->consumed = final ? d->len : (complete < n ? d->rec[complete].start : d->len);
     d->next = d->seg_a = d->seg_b = 0;
     if (d->type == 1 && d->rec.size() < complete + 1) {            // units behind the end of the file: no bytes, their lines are empty
       const RecInfo s = d->rec.back();
       d->rec.resize(complete + 1, s);
     }
+    return LRA_OK;
+  }
+}
+
+// the next step of a BGZF FASTA / FASTQ file: whole members of up to `chunk` compressed bytes (a member the step cut stays on the host for the next one)
+// inflated behind the carried tail of the last step's text, then parse_text where the text lies.  A step that holds no whole record reads on.
+int next_step_bgzf_text(lra_ctx* ctx, lra_reads* r) {
+  lra_reads_dev* d = r->dev;
+  if (int rc = flush_segment(ctx, d)) return rc;
+  hipStream_t st = ctx->stream;
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  if (d->consumed) {
+    memmove(d->h_raw.p, d->h_raw.p + d->consumed, d->len - d->consumed);
+    d->len -= d->consumed; d->comp_file_off += d->consumed; d->consumed = 0;
+  }
+  const int src = d->dec_cur, dst = d->dec_cur ^ 1;
+  const uint64_t carry = d->dec_len - d->dec_used;
+  uint64_t want = d->chunk;
+  for (;;) {
+    if (!d->file_at_eof) {
+      if (!d->h_raw.ensure(d->len + want + 1, d->len, st)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc(%zu) failed", (size_t)(d->len + want));
+      uint64_t got = 0;
+      while (got < want) {
+        const ssize_t k = read(d->fd, d->h_raw.p + d->len + got, (size_t)std::min<uint64_t>(want - got, 1ull << 30));
+        if (k < 0) return lra_set_err(ctx, LRA_ERR_INVALID, "device reader: read of %s failed", r->files[r->cur].c_str());
+        if (k == 0) { d->file_at_eof = true; break; }
+        got += (uint64_t)k;
+      }
+      d->len += got;
+    }
+    std::vector<uint64_t> in_off(1, 0), out_off(1, carry);
+    std::string block_err;
+    const uint8_t* h = (const uint8_t*)d->h_raw.p;
+    uint64_t p = 0;
+    while (p < d->len) {
+      uint32_t total = 0, cdata = 0;
+      const int m = lra_bgzf_member(h + p, d->len - p, &total, &cdata);
+      if (m < 0) { block_err = "not a BGZF block"; break; }
+      if (m == 0 || p + total > d->len) { if (d->file_at_eof) block_err = "the file ends inside it"; break; }
+      const uint32_t isize = lra_le32(h + p + total - 4);
+      if (isize > 65536) { block_err = "a bad ISIZE"; break; }
+      p += total;
+      in_off.push_back(p); out_off.push_back(out_off.back() + isize);
+    }
+    const int nb = (int)in_off.size() - 1;
+    if (nb == 0 && block_err.empty() && !d->file_at_eof) { want = std::max(want, d->len) * 2; continue; }
+    if (!d->d_comp.ensure(p + 1) || !d->d_boff.ensure(2 * (size_t)(nb + 1)) || !d->d_bstat.ensure(nb + 1) || !d->d_dec[dst].ensure(padded_tiles(out_off.back()) + 64))
+      return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
+    lra_time_begin(ctx, "input_h2d");
+    if (p) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_comp.p, h, p, hipMemcpyHostToDevice, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_boff.p, in_off.data(), (nb + 1) * 8, hipMemcpyHostToDevice, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_boff.p + nb + 1, out_off.data(), (nb + 1) * 8, hipMemcpyHostToDevice, st));
+    lra_time_end(ctx);
+    if (carry) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_dec[dst].p, d->d_dec[src].p + d->dec_used, carry, hipMemcpyDeviceToDevice, st));
+    lra_time_begin(ctx, "input_inflate");
+    lra_bgzf_launch_inflate_lut(st, nb, d->d_comp.p, d->d_boff.p, d->d_boff.p + nb + 1, d->d_dec[dst].p, d->d_bstat.p);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    lra_time_end(ctx);
+    std::vector<int32_t> bst((size_t)nb);
+    if (nb) LRA_HIP_CHECK(ctx, hipMemcpyAsync(bst.data(), d->d_bstat.p, nb * 4, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    int good = nb;
+    for (int b = 0; b < nb; b++) if (bst[b]) { good = b; break; }
+    std::string err;                                               // (the messages of input.hip's lra_hts_in: both forms say the same)
+    if (good < nb) err = r->files[r->cur] + ": a bad BGZF block at compressed offset " + std::to_string(d->comp_file_off + in_off[good]) + " (" + lra_bgzf_reason(bst[good]) + ")";
+    else if (!block_err.empty()) err = r->files[r->cur] + ": a bad BGZF block at compressed offset " + std::to_string(d->comp_file_off + p) + " (" + block_err + ")";
+    const uint64_t dlen = out_off[good];
+    const bool at_end = !err.empty() || (d->file_at_eof && p == d->len);
+    const bool final = at_end && err.empty();
+    unsigned char last = 0;
+    LRA_HIP_CHECK(ctx, hipMemsetAsync(d->d_dec[dst].p + dlen, 0, padded_tiles(dlen) - dlen, st));
+    if (dlen) LRA_HIP_CHECK(ctx, hipMemcpyAsync(&last, d->d_dec[dst].p + dlen - 1, 1, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (int rc = parse_text(ctx, d, d->d_dec[dst].p, dlen, last)) return rc;
+    const uint64_t n = d->n_started;
+    uint64_t complete;
+    if (d->type == 0) complete = final ? n : (n ? n - 1 : 0);
+    else if (final) complete = d->n_nl / 4 + 1;
+    else complete = d->n_nl / 4;
+    if (complete == 0 && !at_end) { want = std::max(want, d->len) * 2; continue; }   // no whole record yet: read on
+    d->n_avail = complete;
+    d->step_ends_file = at_end;
+    d->pending_error = err;
+    d->next = d->seg_a = d->seg_b = 0;
+    if (d->type == 1 && d->rec.size() < complete + 1) {            // units behind the end of the file: no bytes, their lines are empty
+      const RecInfo s = d->rec.back();
+      d->rec.resize(complete + 1, s);
+    }
+    d->consumed = p;
+    d->dec_cur = dst; d->dec_len = dlen; d->dec_used = final ? dlen : (complete < n ? d->rec[complete].start : dlen);
     return LRA_OK;
   }
 }
@@ -586,16 +725,17 @@ int next_unit(lra_ctx* ctx, lra_reads* r, Unit* u, bool* have) {
   *have = false;
   while (d->next >= d->n_avail) {
     if (d->step_ends_file && d->started) {
+      if (!d->pending_error.empty()) { r->open_ok = false; r->error = d->pending_error; return LRA_OK; }   // a compression fault ended the file
       if (d->type == 1) { *u = Unit{d->next, false, true}; *have = true; d->fq_eof = true; }   // (not reached: the unit at the end carries the eof bit)
       return LRA_OK;
     }
     d->started = true;
-    if (int rc = next_step(ctx, r)) return rc;
+    if (int rc = d->zmode == LRA_Z_BGZF ? next_step_bgzf_text(ctx, r) : next_step(ctx, r)) return rc;
   }
   const uint64_t i = d->next++;
   u->idx = i;
   if (d->type == 0) { u->ok = true; u->eof_after = false; *have = true; return LRA_OK; }
-  const uint64_t lines_in = d->n_nl + (d->len && d->h_raw.p[d->len - 1] != '\n');
+  const uint64_t lines_in = d->lines_in;
   const uint64_t last = 4 * i + 3;
   bool ok = last < lines_in && (i >= d->n_started ? false : (d->rec[i].flags & 15) == 0);
   u->ok = ok;
@@ -621,6 +761,12 @@ int get_next_dev(lra_ctx* ctx, lra_reads* r, bool* got, uint64_t* idx, lra_hts_r
   lra_reads_dev* d = r->dev;
   *got = false; *host = false;
   if (!r->open_ok) return LRA_OK;
+  if (d->type <= LRA_IN_FASTQ && d->started && d->step_ends_file && d->next >= d->n_avail && !d->pending_error.empty()) {   // a compression fault ended the file
+    if (int rc = flush_segment(ctx, d)) return rc;
+    r->open_ok = false;
+    r->error = d->pending_error;
+    return LRA_OK;
+  }
   if (d->type == 0 && fasta_dry(d)) {
     if (int rc = flush_segment(ctx, d)) return rc;
     bool ok;
@@ -659,7 +805,8 @@ int get_next_dev(lra_ctx* ctx, lra_reads* r, bool* got, uint64_t* idx, lra_hts_r
   const uint64_t sl = b.seq - a.seq, ql = b.qual - a.qual;
   if (sl != ql) {
     std::string name(a.tok_len, '\0');
-    if (a.tok_len) memcpy(&name[0], d->h_raw.p + a.tok, a.tok_len);
+    if (a.tok_len && d->zmode == LRA_Z_BGZF) LRA_HIP_CHECK(ctx, hipMemcpy(&name[0], d->d_text + a.tok, a.tok_len, hipMemcpyDeviceToHost));   // (the text never was on the host)
+    else if (a.tok_len) memcpy(&name[0], d->h_raw.p + a.tok, a.tok_len);
     r->open_ok = false;
     r->error = "FASTQ record '" + name + "' of " + r->files[r->cur] + ": quality string of " + std::to_string(ql) + " characters for a read of " +
                std::to_string(sl) + " bases";
@@ -693,6 +840,7 @@ extern "C" int lra_reads_next_batch_device(lra_reads* r, lra_ctx* ctx, uint64_t 
     d->device = ctx->device;
     r->cur = 0;
     r->strm.close();
+    r->zstrm.rdbuf(nullptr); r->zbuf.reset(); r->zmode = LRA_Z_PLAIN;   // (the host form's handle on a compressed file)
     r->open_ok = open_dev_file(r);
   }
   d->b_seq = d->b_names = d->b_quals = 0;

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <fstream>
+#include <istream>
+#include <streambuf>
 #include <memory>
 #include <string>
 #include <vector>
@@ -13,6 +15,7 @@ void lra_reads_dev_free(lra_reads_dev* d);
 
 enum { LRA_READS_NO_FORM = 0, LRA_READS_HOST_FORM = 1, LRA_READS_DEVICE_FORM = 2 };
 enum { LRA_IN_FASTA = 0, LRA_IN_FASTQ = 1, LRA_IN_BAM = 2, LRA_IN_SAM = 3 };
+enum { LRA_Z_PLAIN = 0, LRA_Z_BGZF = 1, LRA_Z_GZIP = 2 };   // how a FASTA / FASTQ file is stored (lra_reads_open_flags with LRA_READS_COMPRESSED_TEXT)
 
 // one record of the device form's step table (input_device.hip, input_bam.hip: written on the device, copied back whole)
 struct RecInfo {
@@ -44,12 +47,21 @@ const char* lra_bgzf_reason(int status);          // a bgzf.h status in words
 bool lra_format_aux(const uint8_t* p, uint64_t n, std::string* out);
 // BAM's 4-bit base codes
 __host__ __device__ inline char lra_nt16_char(int c) { return "=ACMGRSVTWYHKDBN"[c & 15]; }
+// the host form's byte source of a compressed FASTA / FASTQ file (input.hip): the inflated bytes as a stream.  A compression fault ends the stream like the
+// end of a file and is named in `fault`; the bytes in front of it were delivered
+struct lra_ztext : std::streambuf { std::string fault; };
+// the format of a file that starts 1f 8b by its inflated head: LRA_IN_FASTA, LRA_IN_FASTQ or -1; *zmode = LRA_Z_BGZF / LRA_Z_GZIP
+int lra_ztext_sniff(const std::string& path, int* zmode);
+const char* lra_gz_reason(int status);            // a status of lra_gz_step in words
 struct lra_hts_deleter { void operator()(lra_hts_in* h) const { lra_hts_free(h); } };
 
 struct lra_reads {
   std::vector<std::string> files;
   size_t cur = 0;
   std::ifstream strm;
+  uint32_t open_flags = 0;                         // lra_reads_open_flags
+  int zmode = LRA_Z_PLAIN;                         // the current FASTA / FASTQ file's storage
+  std::unique_ptr<lra_ztext> zbuf; std::istream zstrm{nullptr};   // host form: the current compressed file's text (zmode != LRA_Z_PLAIN)
   int type = -1;                                   // LRA_IN_*
   bool open_ok = false;
   std::unique_ptr<lra_hts_in, lra_hts_deleter> hts;   // the current SAM / BAM file (host form; SAM in the device form)

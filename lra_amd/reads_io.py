@@ -6,6 +6,9 @@ import numpy as np
 from ._lib import load_library
 
 
+READS_COMPRESSED_TEXT = 1   # LRA_READS_COMPRESSED_TEXT
+
+
 class ReadBatchC(C.Structure):
     _fields_ = [("n_reads", C.c_int32), ("total_bases", C.c_uint64), ("seq", C.c_void_p), ("off", C.POINTER(C.c_uint64)), ("read_len", C.POINTER(C.c_int32)),
                 ("names", C.POINTER(C.c_char_p)), ("reads", C.POINTER(C.c_void_p)), ("quals", C.POINTER(C.c_char_p))]
@@ -14,14 +17,18 @@ class ReadBatchC(C.Structure):
 class ReadsFile:
     """ctx=None: lra_reads_next_batch (host parsing).  With a Context: lra_reads_next_batch_device (the parsing on that context's GPU; chunk = the bytes
     of a file it reads and parses per step, lra_reads_set_device_chunk; None keeps the library's default).  flag_remove: SAM / BAM records whose flag
-    meets it are skipped (-Flag); passthrough: each SAM / BAM read's aux fields in the batch's "tags" (--passthrough)."""
+    meets it are skipped (-Flag); passthrough: each SAM / BAM read's aux fields in the batch's "tags" (--passthrough).  compressed_text: gzip / BGZF
+    FASTA and FASTQ files are read (lra_reads_open_flags with LRA_READS_COMPRESSED_TEXT); without it they are refused, as the reference refuses them."""
 
-    def __init__(self, files, ctx=None, chunk=None, flag_remove=0, passthrough=False):
+    def __init__(self, files, ctx=None, chunk=None, flag_remove=0, passthrough=False, compressed_text=False):
         self.lib = load_library()
         self.ctx = ctx
         arr = (C.c_char_p * len(files))(*[f.encode() if isinstance(f, str) else f for f in files])
         self.h = C.c_void_p()
-        rc = self.lib.lra_reads_open(arr, len(files), C.byref(self.h))
+        if compressed_text:
+            rc = self.lib.lra_reads_open_flags(arr, len(files), READS_COMPRESSED_TEXT, C.byref(self.h))
+        else:
+            rc = self.lib.lra_reads_open(arr, len(files), C.byref(self.h))
         if rc != 0:
             raise IOError("cannot determine the format of the input reads (%d)" % rc)
         if chunk is not None:

@@ -1,7 +1,12 @@
 """Time the two forms of the read-file input on a FASTQ or BAM of bench size (needs the GPU): lra_reads_next_batch (host parsing) against
 lra_reads_next_batch_device (parsing on the device), in Mbases/s of whole batches, from the page cache.
 
-    python tools/time_input.py [--format fastq|bam] [--level 6] [--n-reads 28672] [--read-len 30000] [--out profiles/device_input.json]
+    python tools/time_input.py [--format fastq|bam|fastq-bgzf|fastq-gz] [--level 6] [--n-reads 28672] [--read-len 30000] [--out profiles/device_input.json]
+    python tools/time_input.py --format fastq-bgzf --inflate-kernel serial|lut      # the inflate stage alone over the file's member table
+
+--format fastq-bgzf / fastq-gz: the FASTQ of --format fastq (random per-read qualities) as BGZF members of htslib's size, or as one gzip member, at zlib
+level --level, opened with compressed_text.  --inflate-kernel times one of the two inflate kernels alone (bgzf_inflate: lra_bgzf_inflate_batch; bgzf_inflate_lut:
+lra_bgzf_inflate_lut_batch) over the SAME member table, twice, and prints a CRC-32 of the output so that two runs can be compared byte for byte.
 
 The BAM (--format bam) holds the same reads with random per-read qualities (a constant quality string compresses unrealistically well), in BGZF members of
 htslib's size at zlib level --level; its device form is broken down into the file read, host-to-device copies, inflate, framing, record decoding and
@@ -69,8 +74,56 @@ def write_bam(path, n_reads, read_len, level, seed=1):
     return len(raw)
 
 
+def write_fastq_compressed(path, n_reads, read_len, level, bgzf_members, seed=1):
+    """write_fastq's reads with random qualities, BGZF (members of 65280 bytes, compressed on 16 threads) or one gzip member"""
+    from concurrent.futures import ThreadPoolExecutor
+    from lra_amd import bgzf
+    rng = np.random.default_rng(seed)
+    g = synth.make_genome(4_000_000, seed=seed, repeat_frac=0.2, n_families=3).tobytes()
+    parts = []
+    for i in range(n_reads):
+        a = int(rng.integers(0, len(g) - read_len))
+        s = g[a:a + read_len]
+        parts.append(b"@read%d pos=%d\n%s\n+\n%s\n" % (i, a, s.lower() if i % 8 == 0 else s, (33 + rng.integers(2, 41, read_len)).astype(np.uint8).tobytes()))
+    raw = b"".join(parts)
+    del parts
+    if bgzf_members:
+        with ThreadPoolExecutor(16) as ex:
+            members = list(ex.map(lambda a: bgzf.member(raw[a:a + 65280], level), range(0, len(raw), 65280)))
+        data = b"".join(members) + bgzf.EOF_BLOCK
+    else:
+        data = bgzf.gzip_compress(raw, level)
+    with open(path, "wb") as f:
+        f.write(data)
+    return len(raw)
+
+
+def time_inflate(ctx, path, kernel, repeats=2):
+    """one inflate kernel alone over the BGZF file's member table: seconds per run (device events), GB/s of output, the output's CRC-32"""
+    import ctypes as C
+    import zlib
+    import torch
+    from lra_amd import bgzf
+    data = open(path, "rb").read()
+    in_off, out_off = bgzf.blocks(data)
+    n = len(in_off) - 1
+    dev = lambda a: torch.from_numpy(a.view(np.uint8)).cuda()
+    t_in, t_io, t_oo = dev(np.frombuffer(data, np.uint8).copy()), dev(np.array(in_off, np.uint64)), dev(np.array(out_off, np.uint64))
+    t_out, t_st = torch.zeros(out_off[-1] + 64, dtype=torch.uint8, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda")
+    fn = ctx.lib.lra_bgzf_inflate_batch if kernel == "serial" else ctx.lib.lra_bgzf_inflate_lut_batch
+    secs = []
+    for _ in range(repeats + 1):                                # the first run warms the code object up
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        rc = fn(ctx.h, n, t_in.data_ptr(), t_io.data_ptr(), t_oo.data_ptr(), t_out.data_ptr(), t_st.data_ptr())
+        secs.append(time.perf_counter() - t)
+        assert rc == 0 and int(t_st.abs().sum()) == 0, "a member failed"
+    crc = zlib.crc32(t_out[:out_off[-1]].cpu().numpy().tobytes()) & 0xffffffff
+    return dict(kernel=kernel, members=n, out_bytes=out_off[-1], seconds=secs[1:], gb_per_s=[out_off[-1] / s / 1e9 for s in secs[1:]], crc32="%08x" % crc)
+
+
 def run(files, max_bases, ctx=None, chunk=None):
-    rf = reads_io.ReadsFile(files, ctx=ctx, chunk=chunk)
+    rf = reads_io.ReadsFile(files, ctx=ctx, chunk=chunk, compressed_text=True)
     lib = rf.lib
     b = reads_io.ReadBatchC()
     import ctypes as C
@@ -93,8 +146,9 @@ def run(files, max_bases, ctx=None, chunk=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--format", choices=["fastq", "bam"], default="fastq")
-    ap.add_argument("--level", type=int, default=6, help="zlib level of the BAM's members")
+    ap.add_argument("--format", choices=["fastq", "bam", "fastq-bgzf", "fastq-gz"], default="fastq")
+    ap.add_argument("--level", type=int, default=6, help="zlib level of the compressed formats")
+    ap.add_argument("--inflate-kernel", choices=["serial", "lut"], default=None, help="time this inflate kernel alone over the BGZF file's members")
     ap.add_argument("--n-reads", type=int, default=28672)
     ap.add_argument("--read-len", type=int, default=30000)
     ap.add_argument("--max-bases", type=int, default=0, help="bases per batch (0: the whole bench batch, n-reads x read-len)")
@@ -106,13 +160,15 @@ def main():
     max_bases = args.max_bases or args.n_reads * args.read_len
     ctx = Context(0)
     with tempfile.TemporaryDirectory() as tmp:
-        fq = os.path.join(tmp, "reads.fq" if args.format == "fastq" else "reads.bam")
+        fq = os.path.join(tmp, {"fastq": "reads.fq", "bam": "reads.bam", "fastq-bgzf": "reads.fq.bgz", "fastq-gz": "reads.fq.gz"}[args.format])
         t = time.perf_counter()
         raw = None
         if args.format == "fastq":
             write_fastq(fq, args.n_reads, args.read_len)
-        else:
+        elif args.format == "bam":
             raw = write_bam(fq, args.n_reads, args.read_len, args.level)
+        else:
+            raw = write_fastq_compressed(fq, args.n_reads, args.read_len, args.level, args.format == "fastq-bgzf")
         size = os.path.getsize(fq)
         sys.stderr.write("wrote %s: %.2f GB in %.1f s\n" % (fq, size / 1e9, time.perf_counter() - t))
         buf = bytearray(size)
@@ -124,6 +180,14 @@ def main():
             reads.append(time.perf_counter() - t)
             assert got == size
         del buf
+        if args.inflate_kernel:
+            res = dict(format=args.format, level=args.level, file_bytes=size, inflate=time_inflate(ctx, fq, args.inflate_kernel, args.repeats))
+            print(json.dumps(res))
+            if args.out:
+                with open(args.out, "w") as f:
+                    json.dump(res, f, indent=1)
+            ctx.close()
+            return
         res = dict(format=args.format, level=args.level if raw else None, decompressed_bytes=raw, file_bytes=size, n_reads=args.n_reads, read_len=args.read_len, max_bases=max_bases, chunk=args.chunk,
                    file_read_s=min(reads[1:]), file_read_gb_per_s=size / min(reads[1:]) / 1e9)
         if not args.device_only:
@@ -132,7 +196,8 @@ def main():
         for _ in range(args.repeats):
             ctx.timing(True); ctx.timing_reset()
             r = run([fq], max_bases, ctx=ctx, chunk=args.chunk)
-            keys = ("input_h2d", "input_parse", "input_d2h") if raw is None else ("input_h2d", "input_inflate", "input_frame", "input_decode", "input_d2h")
+            keys = {"fastq": ("input_h2d", "input_parse", "input_d2h"), "bam": ("input_h2d", "input_inflate", "input_frame", "input_decode", "input_d2h"),
+                    "fastq-bgzf": ("input_h2d", "input_inflate", "input_parse", "input_d2h"), "fastq-gz": ("input_h2d", "input_parse", "input_d2h")}[args.format]
             r["breakdown_ms"] = {k: ctx.timing_get(k)[0] for k in keys}
             ctx.timing(False)
             if best is None or r["seconds"] < best["seconds"]:
