@@ -811,6 +811,24 @@ typedef struct lra_svsig_result {
 int lra_sv_signatures_batch(lra_ctx* ctx, int n_aln, const int32_t* d_blocks, const uint64_t* d_block_off, const char* d_qseq, const uint64_t* d_q_off,
                             const int32_t* d_q_len, const char* d_tseq, const uint64_t* d_t_off, int32_t min_len, lra_svsig_result* out);
 
+/* ---- a17: the CIGAR strings of every alignment, on the device ----------------------------------------------------------
+ * Replaces  the CIGAR field as Alignment::PrintSAM / PrintPAF write it (Alignment.h:640-650, :700-714): the clip in front (preClip, when > 0, and the
+ * clip op), the runs CalculateStatistics left ((length << 4) | op, op 0..3 = "=XID"; lra_calculate_statistics_batch's d_runs / d_run_off), each as its
+ * decimal length and its op, the clip behind (sufClip, when > 0).  d_pre_clip / d_suf_clip: per alignment, either may be NULL (no such clip; a clip
+ * <= 0 prints nothing); d_clip_op: per alignment 'S' or 'H' (NULL: 'S').  An alignment without runs and without clips has the empty string.
+ * Output (context-owned, valid until the next call on the context): alignment a's text at d_text + d_off[a], d_off[a + 1] - d_off[a] bytes, no
+ * terminators; n_bytes = d_off[n_aln]; nothing is written behind d_text + n_bytes.  Synchronous.  The device record stage (lra_map_records_device)
+ * builds every alignment's runs once with it, without clips: the same text goes into the alignment's own record and into the SA:Z of its group's
+ * other segments, under different clip ops.                                                                                                     */
+typedef struct lra_cigar_text_result {
+  int32_t n_aln;
+  uint64_t n_bytes;
+  const uint64_t* d_off;      /* [n_aln+1] */
+  const char* d_text;         /* [n_bytes] */
+} lra_cigar_text_result;
+int lra_cigar_text_batch(lra_ctx* ctx, int n_aln, const uint32_t* d_runs, const uint64_t* d_run_off, const int32_t* d_pre_clip, const int32_t* d_suf_clip,
+                         const uint8_t* d_clip_op, lra_cigar_text_result* out);
+
 /* ---- a15: junctions of split alignments ---------------------------------------------------------------------
  * Replaces   RefineBreakpoint(read, genome, leftAln, rightAln, opts)   (RefineBreakpoint.h:210-466; Map_lowacc.h:592, Map_highacc.h:725)
  * for n junctions: if the read bases between the two segments (in forward read coordinates) number 1..499, both segments are extended into
@@ -1265,6 +1283,8 @@ typedef struct lra_map_host lra_map_host;
 #define LRA_PACK_MD 2       /* the MD:Z strings (opts.printMD): launches lra_md_strings_batch; the pack's header word 10 = their bytes, word 11 = 1 */
 #define LRA_PACK_SVSIG 4    /* the SV signatures (opts.Printsvsig): launches lra_sv_signatures_batch with the context's svsig length
                              * (lra_ctx_set_svsig_len); the pack's header word 12 = the section's bytes, word 13 = 1.  The record text is unchanged */
+#define LRA_PACK_NORUNS 8   /* leave the CIGAR runs out (the pack's header word 6 = 0, the runs section is empty; run_off stays): what lra_map_records_device
+                             * copies -- its CIGAR text is built on the device.  lra_map_records_host on such a snapshot is LRA_ERR_INVALID when an alignment has runs */
 int lra_map_snapshot(lra_ctx* ctx, const lra_map_result* res, int with_blocks, lra_map_host** out);
 int lra_map_records_host(lra_map_host* snap, const lra_map_opts* opts, const char* const* names, const char* const* reads, const char* const* quals,
                          const int32_t* read_len, const char* const* chrom_names, const char* passthrough, int n_threads, const char** text, uint64_t* len,
@@ -1278,6 +1298,46 @@ int lra_map_records_tags(lra_ctx* ctx, const lra_map_result* res, const lra_map_
 int lra_map_records_host_tags(lra_map_host* snap, const lra_map_opts* opts, const char* const* names, const char* const* reads, const char* const* quals,
                               const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough, int n_threads, const char** text,
                               uint64_t* len, const uint64_t** rec_off);
+/* The record text built on the device.  For print formats 's' (SAM) and 'P' (PAF with CG:z:) *text, *len and (*rec_off)[n_reads + 1] are exactly what
+ * lra_map_records_host_tags gives for a snapshot of the same result under the same options (flags & LRA_PACK_MD: with MD:Z, opts.printMD; other flag
+ * bits are LRA_ERR_INVALID).  The split of work:
+ *   host    SetFromSegAlignment, AlignmentsOrder::Update, SimpleMapQV, the grouping and PrintNumAln, and every SHORT field of a record (name, flag,
+ *           chrom, pos, MAPQ, the clips, the tag block with NV:f: through libstdc++, the short parts of SA:Z, passthrough text, the unaligned
+ *           prefix), on n_threads threads (0: as lra_map_records_host) from a snapshot packed with LRA_PACK_NORUNS: the per-alignment arrays only --
+ *           neither the CIGAR runs nor a base nor a quality is copied or touched.  The result is a PIECE TABLE: per record, in order, literals (ranges
+ *           of one small blob) and references to long fields;
+ *   device  the long fields: every alignment's CIGAR text (lra_cigar_text_batch, built once, copied into its own record and every SA:Z that names
+ *           it), SEQ from the result's d_strands (forward, or at rc_base for a reverse-strand record; under -H a supplementary record's
+ *           [q_start, q_end)), QUAL from d_qual (read r's qualities at d_qual + d_qual_off[r], d_qual_off[n_reads + 1], an empty range for a read
+ *           without -- every non-NULL string of quals, as long as it is; a reverse-strand record's qualities stay as they came, Alignment.h:717-733; under -H a supplementary record's
+ *           [first_block_qpos, last_block_qend), PrintSAM's own quirk), MD:Z from lra_md_strings_batch.  A count pass over the pieces, a scan, one
+ *           copy pass cut by OUTPUT bytes, one device-to-host copy of the text into a page-locked buffer the context keeps.
+ * quals (host, nullable, entries NULL or starting with '*': the field is "*") says which reads HAVE qualities; the host reads a string's first byte
+ * only.  d_qual == NULL: the qualities of the reads that need them are uploaded from quals (the readers hand qualities over on the host today); with
+ * d_qual the host strings are not read behind their first byte.  reads (host) is read by the fall-through formats only and may be NULL for 's' / 'P':
+ * SEQ is the bases the batch was mapped from (d_strands), which the readers hand over upper-cased as they uploaded them.  passthrough: NULL, or one
+ * text per read (NULL entries: none), as lra_map_records_tags takes them.  Flagged, handed-back and unaligned reads follow lra_map_records_host's rules
+ * (an unaligned read's quality string is written as it is, a leading '*' too, as SimplePrintSAM does; one that is shorter than its read -- "*" -- is
+ * written as far as it goes, where the host form reads read_len bytes whatever the string holds).
+ * Formats 'p', 'b' and 'a' have no long per-base field worth moving ('a' is a debugging format): the call falls through to lra_map_snapshot +
+ * lra_map_records_host_tags and returns that text (in pageable memory).
+ * *text / *rec_off are owned by the context and valid until the next lra_map_records_device on it; the result's arrays must still be alive (call it
+ * where lra_map_snapshot would be called).  lra_map_records_device_last: where the last call's time and bytes went (zeros after a fall-through). */
+typedef struct lra_records_device_stats {
+  double ms_snapshot;      /* pack without the runs + its device-to-host copy + unpack */
+  double ms_cigar_md;      /* lra_cigar_text_batch (+ lra_md_strings_batch) */
+  double ms_pieces;        /* the host's piece table (wall) */
+  double ms_upload;        /* pieces, blob (+ qualities when they come from the host) */
+  double ms_kernels;       /* resolve, scan, copy */
+  double ms_copy_kernel;   /* of these: the copy pass alone (HIP events) */
+  double ms_text_copy;     /* the text, device to host (HIP events) */
+  uint64_t bytes_h2d, bytes_d2h, text_bytes, n_pieces;
+} lra_records_device_stats;
+int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* opts, const char* const* names, const char* const* reads,
+                           const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough,
+                           const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const char** text, uint64_t* len,
+                           const uint64_t** rec_off);
+int lra_map_records_device_last(lra_ctx* ctx, lra_records_device_stats* out);
 /* the reads of a snapshot whose status word is non-zero: their number; *status (optional) = the snapshot's status array [n_reads], owned by the snapshot */
 uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status);
 /* The record buffer of a batch as ONE device buffer -- what a rank sends to rank 0 in the single exchange step of the multi-GPU path (the

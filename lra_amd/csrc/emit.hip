@@ -3,6 +3,7 @@
 // reference's exact SAM / PAF / BED lines without linking the reference's Alignment class.
 //   Alignment::PrintBed :591-598, PrintPAF :600-656, PrintSAM :658-808, SimplePrintSAM :811-905   (Alignment.h)
 #include "common.h"
+#include "emit_fmt.h"
 #include <algorithm>
 #include <sstream>
 #include <string>
@@ -17,20 +18,10 @@ int deliver(const std::string& s, char* out, uint64_t cap, uint64_t* len) {
   return LRA_OK;
 }
 
-const char* tp_of(int typeofaln) { return typeofaln == 0 ? "P" : typeofaln == 1 ? "S" : "I"; }
-
 void clipped_cigar(std::ostream& o, const lra_aln_record& r, char clipOp) {
   if (r.pre_clip > 0) o << r.pre_clip << clipOp;
   o << (r.cigar ? r.cigar : "");
   if (r.suf_clip > 0) o << r.suf_clip << clipOp;
-}
-
-void unaligned_record(std::ostream& o, const lra_aln_record& r) {      // :663-681, :815-833
-  o << "4\t*\t0\t0\t*\t*\t0\t0\t";
-  o.write(r.read, r.read_len);
-  o << "\t";
-  if (r.qual == nullptr) o << "*";
-  else o << std::string(r.qual, (size_t)r.read_len);
 }
 
 }  // namespace
@@ -53,24 +44,8 @@ extern "C" int lra_format_bed(const lra_aln_record* r, char* out, uint64_t cap, 
 
 // (the text appended to s_: the record writers build a read's records in one string, once)
 int lra_format_paf_str(const lra_aln_record* r, int print_cigar, std::string& s_) {
-  if (!r) return LRA_ERR_INVALID;
-  std::ostringstream o;
-  const char strandChar = r->strand == 1 ? '-' : '+';
-  o << r->read_name << "\t" << r->read_len << "\t";
-  if (r->strand == 0) o << r->q_start << "\t" << r->q_end << "\t";
-  else o << (uint32_t)((uint32_t)r->read_len - r->q_end) << "\t" << (uint32_t)((uint32_t)r->read_len - r->q_start) << "\t";
-  o << strandChar << "\t" << r->chrom << "\t" << r->genome_len << "\t" << r->t_start << "\t" << r->t_end << "\t" << r->nm << "\t"
-    << r->nm + r->nmm + r->ndel + r->nins << "\t" << (int)(unsigned char)r->mapqv;
-  o << "\tOR:i:" << r->order << "\tNM:i:" << r->nmm + r->ndel + r->nins << "\tNX:i:" << r->nmm << "\tND:i:" << r->ndel << "\tTD:i:" << r->tdel
-    << "\tNI:i:" << r->nins << "\tTI:i:" << r->tins << "\tSD:i:" << r->nSmallDel << "\tME:i:" << r->nMedDel << "\tLD:i:" << r->nLargeDel
-    << "\tSI:i:" << r->nSmallIns << "\tMI:i:" << r->nMedIns << "\tLI:i:" << r->nLargeIns << "\tN0:i:" << r->NumOfAnchors0 << "\tNV:f:" << r->value
-    << "\tAS:i:" << (int)r->value << "\tTP:A:" << tp_of(r->typeofaln);
-  if (r->NumOfAnchors1 > 0) o << "\tNA:i:" << r->NumOfAnchors1;
-  if (r->runtime > 0) o << "\tRT:i:" << r->runtime;
-  if (print_cigar) { o << "\tCG:z:"; clipped_cigar(o, *r, 'S'); }
-  o << std::endl;
-  s_ += o.str();
-  return LRA_OK;
+  lra_str_sink k{s_};
+  return lra_fmt_paf(r, print_cigar, k);
 }
 extern "C" int lra_format_paf(const lra_aln_record* r, int print_cigar, char* out, uint64_t cap, uint64_t* len) {
   std::string s_;
@@ -80,51 +55,8 @@ extern "C" int lra_format_paf(const lra_aln_record* r, int print_cigar, char* ou
 
 // (the text appended to s_: the record writers build a read's records in one string, once)
 int lra_format_sam_str(const lra_aln_record* g, int n_group, int as, int hard_clip, const char* passthrough, std::string& s_) {
-  if (!g || n_group < 1 || as < 0 || as >= n_group) return LRA_ERR_INVALID;
-  const lra_aln_record& r = g[as];
-  // The long fields -- CIGAR, read, qualities: 40 KB of a 30 kb read's 43 KB record -- are appended to s_ as they are; the short ones go through an ostream as the
-  // reference's do (the float fields print through the same libstdc++), in pieces flushed between the long fields.
-  std::ostringstream o;
-  auto flush = [&]() { s_ += o.str(); o.str(std::string()); };
-  auto cigar = [&](const lra_aln_record& x, char clipOp) {               // clipped_cigar, appended
-    if (x.pre_clip > 0) { s_ += std::to_string(x.pre_clip); s_ += clipOp; }
-    if (x.cigar) s_ += x.cigar;
-    if (x.suf_clip > 0) { s_ += std::to_string(x.suf_clip); s_ += clipOp; }
-  };
-  o << r.read_name << "\t";
-  if (r.n_blocks == 0) unaligned_record(o, r);
-  else {
-    o << (unsigned int)r.flag << "\t" << r.chrom << "\t" << (uint32_t)(r.t_start + 1) << "\t" << (unsigned int)(unsigned char)r.mapqv << "\t";
-    flush();
-    cigar(r, (r.supplementary && hard_clip) ? 'H' : 'S');
-    o << "\t*\t0\t" << (uint32_t)(r.t_end - r.t_start) << "\t";
-    flush();
-    if (!r.supplementary) s_.append(r.read, (size_t)r.read_len);
-    else if (hard_clip) s_.append(r.read + r.q_start, (size_t)(r.q_end - r.q_start));
-    else s_.append(r.read, (size_t)r.read_len);
-    s_ += "\t";
-    if (r.qual == nullptr || r.qual[0] == '*') s_ += "*";
-    else if (r.supplementary && hard_clip) s_ += std::string(std::string(r.qual), r.first_block_qpos, r.last_block_qend - r.first_block_qpos);
-    else s_.append(r.qual, (size_t)r.read_len);
-    o << "\tNM:i:" << r.nmm + r.ndel + r.nins << "\tMM:i:" << r.nmm + r.ndel + r.nins << "\tNX:i:" << r.nmm << "\tND:i:" << r.ndel << "\tTD:i:" << r.tdel
-      << "\tNI:i:" << r.nins << "\tTI:i:" << r.tins << "\tNV:f:" << r.value << "\tAS:i:" << (int)r.value << "\tAO:i:" << r.order
-      << "\tN0:i:" << r.NumOfAnchors0 << "\tRT:i:" << r.runtime << "\tTP:A:" << tp_of(r.typeofaln)
-      << "\tSD:i:" << r.nSmallDel << "\tME:i:" << r.nMedDel << "\tLD:i:" << r.nLargeDel << "\tSI:i:" << r.nSmallIns << "\tMI:i:" << r.nMedIns
-      << "\tLI:i:" << r.nLargeIns;
-    if (r.md) o << "\tMD:Z:" << r.md;                                    // opts.printMD (:763-767); the string comes from lra_md_string
-    if (n_group > 1) o << "\tSA:Z:";
-    for (int ag = n_group - 1; ag >= 0; ag--) {
-      if (ag == as) continue;
-      o << g[ag].chrom << "," << (uint32_t)(g[ag].t_start + 1) << "," << (g[ag].strand == 0 ? "+" : "-") << ",";
-      flush();
-      cigar(g[ag], 'S');
-      o << "," << (unsigned int)(unsigned char)g[ag].mapqv << "," << (int)g[ag].nm << ";";
-    }
-  }
-  if (passthrough) o << "\t" << passthrough;
-  o << std::endl;
-  flush();
-  return LRA_OK;
+  lra_str_sink k{s_};
+  return lra_fmt_sam(g, n_group, as, hard_clip, passthrough, k);
 }
 extern "C" int lra_format_sam(const lra_aln_record* g, int n_group, int as, int hard_clip, const char* passthrough, char* out, uint64_t cap,
                               uint64_t* len) {
@@ -138,9 +70,9 @@ int lra_format_sam_simple_str(const lra_aln_record* rp, int hard_clip, const cha
   if (!rp) return LRA_ERR_INVALID;
   const lra_aln_record& r = *rp;
   std::ostringstream o;
+  if (r.n_blocks == 0) { lra_str_sink k{s_}; return lra_fmt_sam_simple_unaligned(r, passthrough, k); }
   o << r.read_name << "\t";
-  if (r.n_blocks == 0) unaligned_record(o, r);
-  else {
+  {
     o << (unsigned int)r.flag << "\t" << r.chrom << "\t" << (uint32_t)(r.t_start + 1) << "\t" << (unsigned int)(unsigned char)r.mapqv << "\t";
     clipped_cigar(o, r, hard_clip ? 'H' : 'S');
     o << "\t*\t0\t" << (uint32_t)(r.t_end - r.t_start) << "\t";

@@ -54,6 +54,7 @@ struct lra_map_state {
   std::vector<float> lut;                          // LogLookUpTable.h:9-15
   lra_text_buf last_text; std::vector<uint64_t> last_off; lra_map_sig last_sig;   // lra_map_records: sizing call -> filling call
   lra_text_buf sv_text; std::vector<uint64_t> sv_off;                             // lra_map_svsig: the text and read ranges of its last call
+  lra_text_buf dev_text; std::vector<uint64_t> dev_off; lra_records_device_stats dev_stats{};   // lra_map_records_device: rec_off (and a fall-through's text) of its last call
 };
 
 int lra_map_count_flagged(lra_ctx* ctx, lra_map_result* out);   // mapread.hip: counters.n_flagged_reads of a finished batch

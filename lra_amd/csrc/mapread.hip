@@ -13,6 +13,8 @@
 #include "scan.h"
 #include "map_state.h"
 #include "map_merge.h"
+#include "records.h"
+#include "emit_fmt.h"
 #include <chrono>
 #include <math.h>
 #include <stdlib.h>
@@ -1291,9 +1293,10 @@ extern "C" int lra_map_pack(lra_ctx* ctx, const lra_map_result* res, int with_bl
   if (!m) return LRA_ERR_INVALID;
   LRA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  if (with_blocks & ~(LRA_PACK_BLOCKS | LRA_PACK_MD | LRA_PACK_SVSIG)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_pack: unknown flags 0x%x", with_blocks);
+  if (with_blocks & ~(LRA_PACK_BLOCKS | LRA_PACK_MD | LRA_PACK_SVSIG | LRA_PACK_NORUNS)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_pack: unknown flags 0x%x", with_blocks);
   const bool withMd = (with_blocks & LRA_PACK_MD) != 0, withSv = (with_blocks & LRA_PACK_SVSIG) != 0;
-  const uint64_t nR = (uint64_t)res->n_reads, nJ = res->n_jobs, nA = res->n_alignments, nB = (with_blocks & LRA_PACK_BLOCKS) ? res->n_blocks : 0, nRuns = res->n_runs;
+  const uint64_t nR = (uint64_t)res->n_reads, nJ = res->n_jobs, nA = res->n_alignments, nB = (with_blocks & LRA_PACK_BLOCKS) ? res->n_blocks : 0,
+                 nRuns = (with_blocks & LRA_PACK_NORUNS) ? 0 : res->n_runs;           // LRA_PACK_NORUNS: the device record stage reads the runs where they are
   const uint64_t nCh = m->chrom_pos.size() - 1;
   // opts.printMD, opts.Printsvsig: the MD strings / SV signatures of the result's final blocks, from the reads on their strands (res->d_strands, addressed by the
   // read offsets behind them) and the genome
@@ -1462,11 +1465,59 @@ extern "C" int lra_map_snapshot(lra_ctx* ctx, const lra_map_result* res, int wit
   return LRA_OK;
 }
 
+// ---- lra_map_records_device, the host half: the records as a piece table (records.h) ------------------------------------------------------------
+namespace {
+struct lra_piece_part { std::vector<lra_rec_piece> pieces; std::string blob; std::vector<uint64_t> first; };   // a thread's range of reads; first: every read's first piece
+struct lra_piece_table { std::vector<lra_rec_piece> pieces; std::string blob; std::vector<uint64_t> read_piece; };
+// emit_fmt.h's sink: the short fields into the blob (literals that follow each other inside a read are one piece), the long ones as references
+struct lra_piece_sink {
+  lra_piece_part& P; size_t barrier;                                     // the read's first piece: no literal is joined across it
+  const lra_aln_record* base; const uint64_t* aln;                       // the read's records and their alignments
+  uint32_t read; int32_t read_len;
+  void push(uint32_t kind, uint64_t n, uint64_t src) { P.pieces.push_back(lra_rec_piece{kind, (uint32_t)n, src}); }
+  void lit(const std::string& t) {
+    if (t.empty()) return;
+    if (P.pieces.size() > barrier && P.pieces.back().kind == LRA_PIECE_LIT && P.pieces.back().src + P.pieces.back().len == P.blob.size() &&
+        (uint64_t)P.pieces.back().len + t.size() < 0xffffffffull) P.pieces.back().len += (uint32_t)t.size();
+    else push(LRA_PIECE_LIT, t.size(), P.blob.size());
+    P.blob += t;
+  }
+  void cigar(const lra_aln_record& x) { push(LRA_PIECE_CIGAR, 0, aln[&x - base]); }
+  void md(const lra_aln_record& x) { push(LRA_PIECE_MD, 0, aln[&x - base]); }
+  void range(uint32_t kind, size_t from, size_t n) {                     // a range of the read, cut to it
+    const size_t L = (size_t)std::max(read_len, 0);
+    from = std::min(from, L); n = std::min(n, L - from);
+    if (n) push(kind, n, ((uint64_t)read << 32) | (uint64_t)from);
+  }
+  void seq(const lra_aln_record& r, size_t from, size_t n) { range(r.strand ? LRA_PIECE_SEQ_RC : LRA_PIECE_SEQ_FW, from, n); }
+  void qual(const lra_aln_record& r) { range(LRA_PIECE_QUAL, 0, (size_t)r.read_len); }   // (an unaligned read's string goes out as it is, a leading '*' too)
+  void qual_sub(const lra_aln_record&, size_t pos, size_t n) { range(LRA_PIECE_QUAL, pos, n); }
+};
+// lra_output_read_str (rank.hip; OUTPUT, Mapping_ultility.h:453-493) for the two formats the device stage writes
+int piece_output_read(const lra_aln_group* groups, const int32_t* index, int n_groups, lra_aln_record* recs, int print_num_aln, char format, int hard_clip,
+                      const char* passthrough, const lra_aln_record* unaligned_rec, lra_piece_sink& k) {
+  if (n_groups > 0 && groups[index[0]].count > 0) {
+    const int na = std::min(n_groups, print_num_aln);
+    for (int a = 0; a < na; a++) {
+      const lra_aln_group& G = groups[index[a]];
+      lra_aln_record* S = recs + G.first;
+      for (int s = G.count - 1; s >= 0; s--) {
+        S[s].order = G.count - 1 - s;
+        const int rc = format == 's' ? lra_fmt_sam(S, G.count, s, hard_clip, passthrough, k) : lra_fmt_paf(&S[s], 1, k);
+        if (rc) return rc;
+      }
+    }
+  } else if (format == 's' && unaligned_rec) return lra_fmt_sam_simple_unaligned(*unaligned_rec, passthrough, k);
+  return LRA_OK;
+}
+}  // namespace
+
 // passthrough: the text behind every read's records; tags (when not NULL) instead: one per read, NULL = none (--passthrough of SAM / BAM input)
 static int records_host(lra_map_host* h, const lra_map_opts* o, const char* const* names, const char* const* reads, const char* const* quals,
                         const int32_t* read_len, const char* const* chrom_names, const char* passthrough, const char* const* tags, int n_threads,
-                        const char** text, uint64_t* len, const uint64_t** rec_off) {
-  if (!h || !o || !names || !reads || !read_len || !chrom_names || !len) return LRA_ERR_INVALID;
+                        const char** text, uint64_t* len, const uint64_t** rec_off, lra_piece_table* PT = nullptr, bool pieceMd = false) {
+  if (!h || !o || !names || (!reads && !PT) || !read_len || !chrom_names || !len) return LRA_ERR_INVALID;
+  if (PT && o->printFormat != 's' && o->printFormat != 'P') return LRA_ERR_INVALID;
   const size_t nA = h->nA, nJ = h->nJ;
   (void)nA;
   const int na = h->num_aln;
@@ -1474,8 +1525,9 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
   const std::vector<int32_t>&strand = h->strand, &supp = h->supp, &sec = h->sec, &n0 = h->n0, &n1 = h->n1, &chrom = h->chrom, &counts = h->counts, &blocks = h->blocks;
   const std::vector<float>& fval = h->fval; const lra_pod_buf<uint32_t>& runs = h->runs; const std::vector<uint32_t>&rstat = h->rstat, &ends = h->ends; const std::vector<uint8_t>& reached = h->reached;
   const bool pairwise = o->printFormat == 'a';
-  const bool withMd = h->has_md && o->printFormat == 's';                 // (only PrintSAM prints MD; SimplePrintSAM, PrintPAF, PrintBed do not)
-  if (withMd && h->md_off.size() != nA + 1) return LRA_ERR_INVALID;
+  const bool withMd = (PT ? pieceMd : h->has_md) && o->printFormat == 's';   // (only PrintSAM prints MD; SimplePrintSAM, PrintPAF, PrintBed do not)
+  if (withMd && !PT && h->md_off.size() != nA + 1) return LRA_ERR_INVALID;
+  if (!PT && nA && roff.size() == nA + 1 && runs.size() < roff[nA]) return LRA_ERR_INVALID;   // a snapshot packed with LRA_PACK_NORUNS has no CIGAR to print
   const bool hi = !o->bypassClustering;                                   // MapRead_highacc's tail (Map_highacc.h:733-789)
   if (pairwise && h->segText.size() != h->nA) return LRA_ERR_INVALID;
   // every read is independent: host threads take contiguous ranges of reads, each builds its own text; ranges are joined in read order
@@ -1484,18 +1536,20 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
   T = std::max(1, std::min(T, n_reads / 32 + 1));
   if (const char* e = getenv("LRA_RECORD_THREADS")) T = std::max(1, atoi(e));
   std::vector<std::string> part(T);
+  std::vector<lra_piece_part> ppart(PT ? T : 0);                         // lra_map_records_device: the threads write pieces, not text
   std::vector<std::vector<uint64_t>> plen(T);
   std::vector<int> prc(T, LRA_OK);
   auto work = [&](int tix) {
     const int lo = (int)((long)n_reads * tix / T), hi = (int)((long)n_reads * (tix + 1) / T);
     std::string& text = part[tix];
-    {                                                                     // room for the range's text: the reads, their CIGAR runs (~3.3 characters each), the tags
+    if (!PT) {                                                            // room for the range's text: the reads, their CIGAR runs (~3.3 characters each), the tags
       size_t want = 4096;
       for (int r = lo; r < hi; r++) want += (size_t)read_len[r] + 700;
       if (nJ && jo.size() > (size_t)hi * na) { const uint64_t a0 = jo[(size_t)lo * na], a1 = jo[(size_t)hi * na]; if (a1 < roff.size() && a0 <= a1) want += (size_t)((roff[a1] - roff[a0]) * 7 / 2) + (size_t)(a1 - a0) * 600; }
       text = part_take(want + want / 16);
     }
     std::vector<std::string> cigars, mds;
+    std::vector<uint64_t> alnOf;                                          // piece mode: the alignment of every record
     std::vector<lra_aln_record> recs;
     std::vector<int32_t> seg_off, index;
     std::vector<lra_aln_group> groups;
@@ -1503,7 +1557,8 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
     std::string rcRead;
     int rc = LRA_OK;
     for (int r = lo; r < hi; r++) {
-      recs.clear(); cigars.clear(); mds.clear(); seg_off.assign(1, 0); rcRead.clear();
+      recs.clear(); cigars.clear(); mds.clear(); seg_off.assign(1, 0); rcRead.clear(); alnOf.clear();
+      if (PT) ppart[tix].first.push_back(ppart[tix].pieces.size());
       const bool flagged = !rstat.empty() && rstat[r];
       if (flagged && (!o->flagged_unaligned || (rstat[r] & LRA_ST_DEFERRED))) { plen[tix].push_back(0); continue; }   // flagged read: no record (the caller routes it elsewhere; d_read_status, lra_map_host_flagged)
       // low-accuracy path: p == 0 left no SegAlignment (Map_lowacc.h:578-581); high-accuracy path: read.unaligned or alignments.size() == 0
@@ -1528,10 +1583,10 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
             // (a 30 kb read at 10 % error has ~6000 runs, nearly all of one or two digits: written through a pointer into room for the longest form, not appended one
             // by one -- the CIGAR strings were two thirds of the record threads' time)
             std::string cg;
-            const size_t nRuns = (size_t)(roff[a + 1] - roff[a]);
+            const size_t nRuns = PT ? 0 : (size_t)(roff[a + 1] - roff[a]);     // (piece mode: the CIGAR text is the device's)
             cg.resize(nRuns * 11 + 1);
             char* w = &cg[0];
-            for (uint64_t x = roff[a]; x < roff[a + 1]; x++) {
+            for (uint64_t x = roff[a]; x < roff[a] + nRuns; x++) {
               uint32_t v = runs[x] >> 4;
               if (v < 10) *w++ = (char)('0' + v);
               else if (v < 100) { *w++ = (char)('0' + v / 10); *w++ = (char)('0' + v % 10); }
@@ -1542,7 +1597,7 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
             cigars.push_back(std::move(cg));
             const int32_t* c = &counts[18 * a];
             lra_aln_record rec; memset(&rec, 0, sizeof rec);
-            rec.read_name = names[r]; rec.read = reads[r]; rec.qual = quals ? quals[r] : nullptr; rec.read_len = read_len[r];
+            rec.read_name = names[r]; rec.read = reads ? reads[r] : nullptr; rec.qual = quals ? quals[r] : nullptr; rec.read_len = read_len[r];
             rec.chrom = chrom_names[chrom[a]]; rec.genome_len = (uint32_t)(h->chrom_pos[chrom[a] + 1] - h->chrom_pos[chrom[a]]);
             rec.cigar = cigars.back().c_str();
             rec.strand = strand[a]; rec.supplementary = supp[a]; rec.is_secondary = sec[a];
@@ -1557,7 +1612,7 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
             // Alignment::read is the strand the segment lies on: strands[str] (the constructor call Map_lowacc.h:560 / Map_highacc.h:704, UpdateParameters Alignment.h:506-507),
             // so a reverse-strand record's SEQ is the read's reverse complement (its quality string stays as it came, Alignment.h:717-733).  Rounds 1-5 wrote the read as
             // it came for both strands: the emitters were pinned with the read they were GIVEN, and nothing pinned which read the composition gives them.
-            if (strand[a] && rcRead.empty()) {                            // CreateRC (SeqUtils.h:151)
+            if (strand[a] && rcRead.empty() && !PT) {                     // CreateRC (SeqUtils.h:151); piece mode: the strands are the device's
               const int L = read_len[r];
               rcRead.resize((size_t)L);
               for (int x = 0; x < L; x++) {
@@ -1566,7 +1621,8 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
               }
             }
             if (strand[a]) rec.read = rcRead.c_str();
-            if (withMd) {                                                 // opts.printMD: PrintSAM's MD:Z (Alignment.h:763-767)
+            if (withMd && PT) rec.md = "";                               // (the value is a piece)
+            else if (withMd) {                                            // opts.printMD: PrintSAM's MD:Z (Alignment.h:763-767)
               mds.emplace_back(h->md.data() + h->md_off[a], (size_t)(h->md_off[a + 1] - h->md_off[a]));
               rec.md = mds.back().c_str();
             }
@@ -1576,6 +1632,7 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
               rec.chrom_text = h->segText[a].data() - h->segStart[a];     // chrom_text[tPos] for the covered tPos only
             }
             recs.push_back(rec);
+            if (PT) alnOf.push_back(a);
           }
           seg_off.push_back((int32_t)recs.size());
         }
@@ -1584,8 +1641,12 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
       if (hi && !unaligned && recs.empty()) need = 0;                     // OUTPUT prints nothing: groups exist, the first has no segment, read.unaligned == 0 (Mapping_ultility.h:467-492)
       else if (unaligned || recs.empty()) {
         lra_aln_record un; memset(&un, 0, sizeof un);
-        un.read_name = names[r]; un.read = reads[r]; un.qual = quals ? quals[r] : nullptr; un.read_len = read_len[r];
+        un.read_name = names[r]; un.read = reads ? reads[r] : nullptr; un.qual = quals ? quals[r] : nullptr; un.read_len = read_len[r];
         const size_t before = text.size();
+        if (PT) {
+          lra_piece_sink k{ppart[tix], ppart[tix].pieces.size(), nullptr, nullptr, (uint32_t)r, read_len[r]};
+          if ((rc = piece_output_read(nullptr, nullptr, 0, nullptr, o->PrintNumAln, (char)o->printFormat, o->hardClip, tags ? tags[r] : passthrough, &un, k))) break;
+        } else
         if ((rc = lra_output_read_str(nullptr, nullptr, 0, nullptr, o->PrintNumAln, (char)o->printFormat, o->hardClip, tags ? tags[r] : passthrough, 1, &un, text))) break;
         need = text.size() - before;
       } else {
@@ -1597,6 +1658,10 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
           break;
         // (the records' text goes straight into the thread's part, written once: the sizing-then-filling calls of the C entry points formatted every record four times)
         const size_t before = text.size();
+        if (PT) {
+          lra_piece_sink k{ppart[tix], ppart[tix].pieces.size(), recs.data(), alnOf.data(), (uint32_t)r, read_len[r]};
+          if ((rc = piece_output_read(groups.data(), index.data(), n, recs.data(), o->PrintNumAln, (char)o->printFormat, o->hardClip, tags ? tags[r] : passthrough, nullptr, k))) break;
+        } else
         if ((rc = lra_output_read_str(groups.data(), index.data(), n, recs.data(), o->PrintNumAln, (char)o->printFormat, o->hardClip, tags ? tags[r] : passthrough, 0, nullptr, text))) break;
         need = text.size() - before;
       }
@@ -1615,6 +1680,20 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
   }
   if (rdbg) fprintf(stderr, "[records] %d threads: per-read work %.0f ms\n", T, wallr() - tr0);
   for (int t = 0; t < T; t++) if (prc[t]) return prc[t];
+  if (PT) {                                                              // the ranges' pieces joined in read order; a literal's place moves with its range's blob
+    size_t np = 0, nb = 0;
+    for (int t = 0; t < T; t++) { np += ppart[t].pieces.size(); nb += ppart[t].blob.size(); }
+    PT->pieces.clear(); PT->pieces.reserve(np); PT->blob.clear(); PT->blob.reserve(nb); PT->read_piece.clear(); PT->read_piece.reserve((size_t)n_reads + 1);
+    for (int t = 0; t < T; t++) {
+      const uint64_t p0 = PT->pieces.size(), b0 = PT->blob.size();
+      for (uint64_t f : ppart[t].first) PT->read_piece.push_back(p0 + f);
+      for (lra_rec_piece q : ppart[t].pieces) { if (q.kind == LRA_PIECE_LIT) q.src += b0; PT->pieces.push_back(q); }
+      PT->blob += ppart[t].blob;
+    }
+    PT->read_piece.push_back(PT->pieces.size());
+    *len = 0;
+    return LRA_OK;
+  }
   // the ranges' texts joined in read order: every thread copies its own part to its place (the pages of the joined text are first touched by 256 threads, not one)
   lra_text_buf& out = h->text;
   std::vector<size_t> pstart((size_t)T + 1, 0);
@@ -1769,4 +1848,107 @@ extern "C" int lra_map_records_tags(lra_ctx* ctx, const lra_map_result* res, con
                                     char* out, uint64_t cap, uint64_t* len, uint64_t* rec_off) {
   if (!passthrough) return LRA_ERR_INVALID;
   return map_records(ctx, res, o, names, reads, quals, read_len, chrom_names, nullptr, passthrough, out, cap, len, rec_off);
+}
+
+// ---- the record text built on the device (records.hip) ---------------------------------------------------------------------------------------------
+// The host half: a snapshot without the runs, the piece table on host threads; the device half: the CIGAR text, MD, the assembly.  See lra_hip.h.
+extern "C" int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
+                                      const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough,
+                                      const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const char** text, uint64_t* len,
+                                      const uint64_t** rec_off) {
+  if (!ctx || !res || !o || !names || !read_len || !chrom_names || !len || (flags & ~LRA_PACK_MD) || (d_qual && !d_qual_off)) return LRA_ERR_INVALID;
+  lra_map_state* m = ctx->map;
+  if (!m) return LRA_ERR_INVALID;
+  m->dev_stats = lra_records_device_stats{};
+  lra_records_device_stats& S = m->dev_stats;
+  auto wall = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  const int nR = res->n_reads;
+  const bool device = o->printFormat == 's' || o->printFormat == 'P';
+  lra_map_host* h = nullptr;
+  int rc;
+  if (!device) {                                                         // 'p', 'b', 'a': no long field worth moving -- the host path, its text kept by the context
+    if (!reads) return LRA_ERR_INVALID;
+    if ((rc = lra_map_snapshot(ctx, res, (o->printFormat == 'a' ? LRA_PACK_BLOCKS : 0) | (flags & LRA_PACK_MD), &h))) return rc;
+    const char* t = nullptr; const uint64_t* ro = nullptr;
+    rc = records_host(h, o, names, reads, quals, read_len, chrom_names, nullptr, passthrough, n_threads, &t, len, &ro);
+    if (!rc) {
+      m->dev_text.swap(h->text); m->dev_off.swap(h->rec_off);
+      if (text) *text = m->dev_text.data();
+      if (rec_off) *rec_off = m->dev_off.data();
+    }
+    lra_map_host_free(h);
+    return rc;
+  }
+  double t0 = wall();
+  if ((rc = lra_map_snapshot(ctx, res, LRA_PACK_NORUNS, &h))) return rc;
+  std::unique_ptr<lra_map_host> hold(h);
+  const uint64_t nA = h->nA;
+  S.bytes_d2h += PackLayout(nR, h->nJ, nA, 0, 0, h->chrom_pos.size() - 1).total;
+  double t1 = wall();
+  S.ms_snapshot = t1 - t0;
+  // the long fields the alignments own: the CIGAR text, and with LRA_PACK_MD the MD:Z values (as lra_map_pack makes them)
+  const bool withMd = (flags & LRA_PACK_MD) && o->printFormat == 's';
+  lra_cigar_text_result cg; memset(&cg, 0, sizeof cg);
+  lra_md_result md; memset(&md, 0, sizeof md);
+  hipStream_t st = ctx->stream;
+  if (nA) {
+    if (!res->d_run_off || !res->d_strands) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device: the result has no runs / reads to work on");
+    if ((rc = lra_cigar_text_batch(ctx, (int)nA, res->d_runs, res->d_run_off, nullptr, nullptr, nullptr, &cg))) return rc;
+    if (withMd) {
+      if (!ctx->seed || !ctx->seed->genome || !m->d_chrom_pos) return lra_set_err(ctx, LRA_ERR_INVALID, "LRA_PACK_MD: genome not loaded");
+      uint64_t* adr = (uint64_t*)lra_ensure(ctx, 187, 2 * (nA + 1) * 8);
+      if (!adr) return LRA_ERR_NOMEM;
+      const uint64_t* ro = (const uint64_t*)(res->d_strands + lra_strands_ro_at(res->rc_base));
+      hipLaunchKernelGGL(k_md_address, dim3((unsigned)((nA + 255) / 256)), dim3(256), 0, st, nA, res->d_aln_read, res->d_strand, res->d_chrom, ro, res->rc_base,
+                         (const uint64_t*)m->d_chrom_pos, adr, adr + nA + 1);
+      if ((rc = lra_md_strings_batch(ctx, (int)nA, res->d_blocks, res->d_block_off, res->d_strands, adr, nullptr, (const char*)ctx->seed->genome, adr + nA + 1, &md))) return rc;
+    }
+  }
+  double t2 = wall();
+  S.ms_cigar_md = t2 - t1;
+  lra_piece_table PT;
+  uint64_t dummy = 0;
+  if ((rc = records_host(h, o, names, reads, quals, read_len, chrom_names, nullptr, passthrough, n_threads, nullptr, &dummy, nullptr, &PT, withMd))) return rc;
+  double t3 = wall();
+  S.ms_pieces = t3 - t2;
+  // the qualities: the caller's device copy, or the strings of the reads that print them, uploaded through the context's page-locked staging
+  const char* dq = d_qual; const uint64_t* dqo = d_qual_off;
+  if (!dq) {
+    std::vector<uint64_t> qo((size_t)nR + 1, 0);
+    bool any = false;
+    for (const lra_rec_piece& p : PT.pieces)                             // (a string shorter than its read -- "*" -- is uploaded as far as it goes; the device cuts the piece to it)
+      if (p.kind == LRA_PIECE_QUAL) { const size_t r = (size_t)(p.src >> 32); qo[r + 1] = strnlen(quals[r], (size_t)std::max(read_len[r], 0)); any = true; }
+    if (any) {
+      for (int r = 0; r < nR; r++) qo[(size_t)r + 1] += qo[r];
+      const size_t offBytes = ((size_t)nR + 1) * 8, total = (size_t)qo[nR];
+      char* stage = (char*)lra_pinned(ctx, offBytes + total);
+      char* dev = (char*)lra_ensure(ctx, 169, offBytes + total + 64);
+      if (!stage || !dev) return LRA_ERR_NOMEM;
+      memcpy(stage, qo.data(), offBytes);
+      for (int r = 0; r < nR; r++) if (qo[(size_t)r + 1] > qo[r]) memcpy(stage + offBytes + qo[r], quals[r], (size_t)(qo[(size_t)r + 1] - qo[r]));
+      LRA_HIP_CHECK(ctx, hipMemcpyAsync(dev, stage, offBytes + total, hipMemcpyHostToDevice, st));
+      LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+      dqo = (const uint64_t*)dev; dq = dev + offBytes;
+      S.bytes_h2d += offBytes + total;
+    }
+  }
+  S.ms_upload = wall() - t3;
+  lra_rec_job J;
+  J.n_reads = nR; J.n_aln = nA; J.pieces = PT.pieces.data(); J.n_pieces = PT.pieces.size(); J.read_piece = PT.read_piece.data();
+  J.blob = PT.blob.data(); J.blob_bytes = PT.blob.size();
+  J.d_strands = res->d_strands; J.rc_base = res->rc_base;
+  J.d_read_off = res->d_strands ? (const uint64_t*)(res->d_strands + lra_strands_ro_at(res->rc_base)) : nullptr;
+  J.d_qual = dq; J.d_qual_off = dqo; J.d_cg = cg.d_text; J.d_cg_off = cg.d_off; J.d_md = withMd ? md.d_md : nullptr; J.d_md_off = withMd ? md.d_md_off : nullptr;
+  if (!J.d_strands && nR) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device: the result has no reads to work on");
+  m->dev_off.assign((size_t)nR + 1, 0);
+  m->dev_text.clear();
+  if ((rc = lra_records_assemble(ctx, J, text, len, m->dev_off.data(), &S))) return rc;
+  if (rec_off) *rec_off = m->dev_off.data();
+  return LRA_OK;
+}
+
+extern "C" int lra_map_records_device_last(lra_ctx* ctx, lra_records_device_stats* out) {
+  if (!ctx || !out || !ctx->map) return LRA_ERR_INVALID;
+  *out = ctx->map->dev_stats;
+  return LRA_OK;
 }

@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import chain, cluster, emit, local, refine, seed
-from .context import Context
+from .context import Context, ptr
 
 
 @dataclass
@@ -143,6 +143,13 @@ class MapResult(C.Structure):
                 [("rc_base", C.c_uint64), ("counters", MapCounters)])
 
 
+class RecordsDeviceStats(C.Structure):
+    """lra_records_device_stats (include/lra_hip.h)"""
+    _fields_ = [(k, C.c_double) for k in ("ms_snapshot", "ms_cigar_md", "ms_pieces", "ms_upload", "ms_kernels", "ms_copy_kernel", "ms_text_copy")] + \
+               [(k, C.c_uint64) for k in ("bytes_h2d", "bytes_d2h", "text_bytes", "n_pieces")]
+
+
+PACK_NORUNS = 8                                  # LRA_PACK_NORUNS: a pack / snapshot without the CIGAR runs (what lra_map_records_device copies)
 PACK_BLOCKS, PACK_MD, PACK_SVSIG = 1, 2, 4       # the flag word of lra_map_snapshot / lra_map_pack (LRA_PACK_BLOCKS, LRA_PACK_MD, LRA_PACK_SVSIG)
 
 READ_TYPES = {"ont": 0, "clr": 1, "ccs": 2, "contig": 3}
@@ -437,6 +444,34 @@ class LowAccMapper:
             lib.lra_map_host_free(snap)
         return out
 
+    def records_device(self, res: MapResult, args, passthrough=None, d_qual=None, d_qual_off=None, md=None, n_threads=0, as_list=True):
+        """lra_map_records_device: the batch's record text built on the device (formats 's' and 'P'; the others fall through to the host path) -- the bytes
+        records_host gives for a snapshot of the same result.  args: record_args(names, reads, quals); passthrough: None or one text per read (None entries:
+        none); d_qual / d_qual_off: the batch's qualities as device tensors (None: uploaded from args' quals); md (None: opts.printMD): MD:Z in SAM records.
+        Call it where snapshot() would be called: the result's arrays must be alive.  -> list of per-read bytes, or the total bytes when as_list is False."""
+        ctx = self.ctx
+        n = args["n"]
+        tags = None
+        if isinstance(passthrough, (list, tuple)):
+            tags = (C.c_char_p * n)(*[None if t is None else bytes(t) for t in passthrough])
+        elif passthrough is not None:
+            tags = (C.c_char_p * n)(*[bytes(passthrough)] * n)
+        flags = PACK_MD if (self.print_md if md is None else md) else 0
+        text = C.c_void_p(); ln = C.c_uint64(0); roff = C.POINTER(C.c_uint64)()
+        ctx.check(ctx.lib.lra_map_records_device(ctx.h, C.byref(res), C.byref(self.copts), args["names"], args["reads"], args["quals"], args["lens"], args["chroms"], tags,
+                                                 ptr(d_qual) if d_qual is not None else None, ptr(d_qual_off) if d_qual_off is not None else None, flags,
+                                                 int(n_threads), C.byref(text), C.byref(ln), C.byref(roff)))
+        if not as_list:
+            return ln.value
+        raw = C.string_at(text, ln.value) if ln.value else b""
+        return [raw[roff[i]:roff[i + 1]] for i in range(n)]
+
+    def records_device_stats(self):
+        """lra_map_records_device_last: where the last records_device call's time (ms) and bytes went."""
+        st = RecordsDeviceStats()
+        self.ctx.check(self.ctx.lib.lra_map_records_device_last(self.ctx.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
     # ------------------------------------------------------------------------------------------------------------------ the same, stage by stage
     def align_staged(self, rbatch) -> MapBatchResult:
         ctx, o, st = self.ctx, self.opts, self.stats
@@ -650,6 +685,8 @@ class HighAccMapper:
     fetch = LowAccMapper.fetch
     print_md = LowAccMapper.print_md
     svsig_len = LowAccMapper.svsig_len
+    records_device = LowAccMapper.records_device
+    records_device_stats = LowAccMapper.records_device_stats
     svsig_host = LowAccMapper.svsig_host
     sv_signatures = LowAccMapper.sv_signatures
     fetch_local_index = LowAccMapper.fetch_local_index

@@ -88,6 +88,26 @@ def fetch_md(ctx: Context, res: MdResult):
     return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
 
 
+class CigarTextResult(C.Structure):
+    """lra_cigar_text_result (include/lra_hip.h)"""
+    _fields_ = [("n_aln", C.c_int32), ("n_bytes", C.c_uint64), ("d_off", C.c_void_p), ("d_text", C.c_void_p)]
+
+
+def cigar_text_batch(ctx: Context, runs, run_off, pre_clip=None, suf_clip=None, clip_op=None, raw=False):
+    """lra_cigar_text_batch: the CIGAR string of every alignment from its runs ((length << 4) | op; device tensors: runs int32 / uint32 bits, run_off int64
+    [n + 1]) and optional per-alignment clips (int32) and clip ops (uint8 'S' / 'H') -> one bytes object per alignment; raw=True: the CigarTextResult."""
+    n = int(run_off.numel()) - 1
+    res = CigarTextResult()
+    p = lambda t: ptr(t) if t is not None else None
+    ctx.check(ctx.lib.lra_cigar_text_batch(ctx.h, n, p(runs) if runs is not None and runs.numel() else None, ptr(run_off), p(pre_clip), p(suf_clip), p(clip_op),
+                                           C.byref(res)))
+    if raw:
+        return res
+    off = ctx.to_host(res.d_off, n + 1, np.uint64) if n else np.zeros(1, np.uint64)
+    text = ctx.to_host(res.d_text, int(res.n_bytes), np.uint8).tobytes() if int(res.n_bytes) else b""
+    return [text[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+
 def md_of_refined(ctx: Context, b: RefineBatch, rres: RefineResult):
     """lra_md_strings_batch straight on the (context-owned) output of indel_refine_batch (the blocks CalculateStatistics saw)."""
     v = RefineBatch.__new__(RefineBatch)

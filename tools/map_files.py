@@ -1,6 +1,6 @@
 """Map read files against a genome FASTA and print the records as `lra align` would (needs the GPU):
 
-    python tools/map_files.py -ONT genome.fa reads.fq [more.fa ...] [-p s|p|pc|b|a] [-H] [--printMD] [-a] [--PrintNumAln N] [--refineBreakpoints] [-o out.sam]
+    python tools/map_files.py -ONT genome.fa reads.fq [more.fa ...] [-p s|p|pc|b|a] [-H] [--printMD] [-a] [--PrintNumAln N] [--refineBreakpoints] [-o out.sam] [--device-records]
 
 The reads are parsed on the device (lra_reads_next_batch_device) and mapped from the reader's device arrays; --host-input parses them on the host
 (lra_reads_next_batch) and maps through lra_map_reads_host, the same records.  The index: genome.fa.mms / genome.fa.gli when both exist (lra_read_mms /
@@ -65,6 +65,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=None, help="bytes the device reader reads and parses per step (default: the library's)")
     ap.add_argument("-Flag", dest="flag", type=int, default=0, help="SAM / BAM input: skip records whose flag meets this mask")
     ap.add_argument("--passthrough", action="store_true", help="SAM / BAM input: append each read's aux fields to its SAM records")
+    ap.add_argument("--device-records", action="store_true",
+                    help="build the record text on the device (lra_map_records_device; formats s and pc, the others fall through to the host path)")
     args = ap.parse_args()
     P = args.preset
     t0 = time.perf_counter()
@@ -111,7 +113,7 @@ def main():
     if fmt == "s":
         cl = ["lra", "align", "-" + P, args.genome, *args.reads, "-p", args.fmt] + (["-H"] if args.hard_clip else []) + (["--printMD"] if args.printMD else []) + \
              (["-a"] if args.store_all else []) + ["--PrintNumAln", str(args.PrintNumAln)] + (["--refineBreakpoints"] if args.refineBreakpoints else []) + \
-             (["-Flag", str(args.flag)] if args.flag else []) + (["--passthrough"] if args.passthrough else []) + (["-SV", *args.sv] if args.sv else [])
+             (["-Flag", str(args.flag)] if args.flag else []) + (["--passthrough"] if args.passthrough else []) + (["-SV", *args.sv] if args.sv else [])       # (--device-records is no lra option: the same records)
         out.write(mapread.LowAccMapper.sam_header(mapper, b"lra_amd", " ".join(cl).encode()))   # the lra command line: the same for either reader
     rf = reads_io.ReadsFile(args.reads, ctx=None if args.host_input else ctx, chunk=None if args.host_input else args.chunk, flag_remove=args.flag, compressed_text=True,
                             passthrough=args.passthrough)
@@ -138,6 +140,8 @@ def main():
             texts = mapper.records_host(snap, mapper.record_args(b["names"], b["seqs"], b["quals"]), passthrough=tags, free=False)
             for sig in mapper.svsig_host(snap, b["names"]):
                 sv_out.write(sig)
+        elif args.device_records:
+            texts = mapper.records_device(res, mapper.record_args(b["names"], b["seqs"], b["quals"]), passthrough=tags)
         else:
             texts = mapper.records(res, b["names"], b["seqs"], quals=b["quals"], passthrough=tags)
         for txt in texts:
