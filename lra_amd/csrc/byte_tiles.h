@@ -1,5 +1,5 @@
-// lra_amd/csrc/byte_tiles.h -- what the tiled byte-stream passes of the device readers share (input_device.hip: the read files; genome_device.hip: the
-// genome): the tile shape, the 128-bit load, the workgroup scan, and the growable device / page-locked buffers the readers own.
+// lra_amd/csrc/byte_tiles.h -- what the tiled byte-stream passes of the device readers share (input_device.hip: the read files; genome.hip: the
+// genome; zsource.hip: their BGZF steps): the tile shape, the 128-bit load, the workgroup scan, and the growable device / page-locked buffers the readers own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,6 +9,7 @@
 namespace {
 
 constexpr int RD_NT = 256, RD_BPT = 16, RD_TILE = RD_NT * RD_BPT;   // a workgroup per 4 KiB tile, 16 bytes per lane (one 128-bit load)
+inline uint64_t padded_tiles(uint64_t len) { return std::max<uint64_t>(1, (len + RD_TILE - 1) / RD_TILE) * RD_TILE; }   // the bytes of the tiles over len bytes
 
 __device__ inline void load16(const unsigned char* __restrict__ raw, uint64_t p, unsigned char b[RD_BPT]) {
   const uint4 v = *reinterpret_cast<const uint4*>(raw + p);
@@ -35,6 +36,8 @@ __device__ inline uint32_t block_excl(uint32_t v, uint32_t* sh, uint32_t* tot) {
 
 // C-locale isspace: what `std::stringstream >>` skips
 __device__ inline bool is_ws(unsigned char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
+
+}  // namespace
 
 template <typename T> struct DevBuf {
   T* p = nullptr; size_t n = 0;
@@ -64,5 +67,3 @@ template <typename T> struct PinBuf {
   }
   void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
 };
-
-}  // namespace

@@ -21,9 +21,10 @@
 //   d. A genome of 2^32 bases or more is LRA_ERR_INVALID: the global index's positions are 32-bit.
 //   e. Of several faults in a file the first in file order is reported, by both forms: the data in front of a bad compressed member is parsed first.
 //
-// Compressed input.  BGZF: the host walks the member headers, a step's members are inflated by input_bam.hip's wave-per-member kernel (device form) or
-// by the same decoder on the host (host form); CRC-32 and ISIZE are checked, a bad member is named by its compressed offset.  Other gzip is one serial
-// bit stream: bgzf.h's lra_gz_stream inflates it on the host a step at a time in both forms; the device form uploads each inflated step.
+// Compressed input (zsource.h).  BGZF: the host walks the member headers, a step's members are inflated by input_bam.hip's wave-per-member kernel (device
+// form: lra_bgzf_step) or by the same decoder on the host (host form: lra_bgzf_source); CRC-32 and ISIZE are checked, a bad member is named by its
+// compressed offset.  Other gzip is one serial bit stream: lra_gzip_source inflates it on the host a step at a time in both forms; the device form
+// uploads each inflated step.
 //
 // The device form reads the file in steps (lra_genome_set_device_chunk) into page-locked memory and runs byte-stream passes over each step, 4 KiB
 // per workgroup, 16 bytes per lane:
@@ -40,17 +41,13 @@
 // is the difference of two table entries, closed on the host.
 #include "common.h"
 #include "scan.h"
-#include "bam_kernels.h"
-#include "bgzf.h"
-#include "byte_tiles.h"
+#include "zsource.h"
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
 #include <algorithm>
 #include <string>
 #include <vector>
-
-int lra_bgzf_inflate_one(const uint8_t* in, uint64_t in_len, uint8_t* out, uint64_t isize);   // input.hip
 
 namespace {
 
@@ -218,15 +215,6 @@ __global__ void gn_name_emit(const unsigned char* __restrict__ raw, uint64_t n_r
 enum { GN_PLAIN = 0, GN_GZIP = 1, GN_BGZF = 2 };
 enum { GN_NO_FORM = 0, GN_HOST_FORM = 1, GN_DEVICE_FORM = 2 };
 
-const char* gz_reason(int st) {
-  switch (st) {
-    case LRA_GZ_ERR_HEADER: return "not a gzip member";
-    case LRA_GZ_ERR_TRUNCATED: return "the file ends inside it";
-    case LRA_BGZF_ERR_ISIZE: return "its ISIZE is not the size of its data";
-    default: return lra_bgzf_reason(st);
-  }
-}
-
 }  // namespace
 
 struct lra_genome {
@@ -243,22 +231,22 @@ struct lra_genome {
   // where the bytes come from (plain text and gzip; BGZF in the host form): a step of the file's data at a time
   bool src_eof = false;
   std::string src_error;                            // a bad compressed member: reported once the data in front of it is parsed
-  std::vector<uint8_t> comp; uint64_t comp_pos = 0, comp_file_off = 0;   // gzip: the whole file; BGZF: the compressed bytes read ahead
-  lra_gz_stream* gz = nullptr;
+  std::unique_ptr<lra_gzip_source> gz;              // gzip: the whole file
+  lra_bgzf_source bz;                               // BGZF in the host form: the compressed bytes read ahead
   // the device form
   int device = -1;
   char* d_seq = nullptr; uint64_t d_cap = 0;
   bool skip = true, first_at_ls = true;             // rule 1 is still looking; the next step's first byte stands at a line start
-  PinBuf<char> h_raw, h_comp;
+  PinBuf<char> h_raw;
   DevBuf<unsigned char> d_raw; DevBuf<uint32_t> cnt[3]; DevBuf<uint64_t> base[3]; DevBuf<uint64_t> nl_pos; DevBuf<GnRec> d_rec, d_cr; DevBuf<GnCells> cells;
   DevBuf<uint32_t> name_len; DevBuf<uint64_t> name_off; DevBuf<char> c_names;
-  DevBuf<uint8_t> d_comp, d_dec[2]; DevBuf<uint64_t> d_boff; DevBuf<int32_t> d_bstat;
+  lra_bgzf_step z;                                  // BGZF in the device form
   void release_work() {
-    h_raw.release(); h_comp.release(); d_raw.release(); nl_pos.release(); d_rec.release(); d_cr.release(); cells.release(); name_len.release(); name_off.release();
-    c_names.release(); d_comp.release(); d_dec[0].release(); d_dec[1].release(); d_boff.release(); d_bstat.release();
+    h_raw.release(); d_raw.release(); nl_pos.release(); d_rec.release(); d_cr.release(); cells.release(); name_len.release(); name_off.release();
+    c_names.release(); z.release();
     for (int i = 0; i < 3; i++) { cnt[i].release(); base[i].release(); }
-    std::vector<uint8_t>().swap(comp);
-    delete gz; gz = nullptr;
+    bz.clear();
+    gz.reset();
     if (fd >= 0) close(fd);
     fd = -1;
   }
@@ -284,72 +272,32 @@ std::string cr_error(const lra_genome* g, uint64_t idx) {
 }
 std::string too_long(const lra_genome* g) { return g->path + ": a genome of 2^32 bases or more (the global index's positions are 32-bit)"; }
 
-bool read_all(int fd, uint8_t* dst, uint64_t want, uint64_t* got) {   // up to `want` bytes; less: the end of the file
-  *got = 0;
-  while (*got < want) {
-    const ssize_t k = read(fd, dst + *got, (size_t)std::min<uint64_t>(want - *got, 1ull << 30));
-    if (k < 0) return false;
-    if (k == 0) break;
-    *got += (uint64_t)k;
-  }
-  return true;
-}
-
 // The next step of the file's data (plain text, gzip; BGZF for the host form) into dst[0, cap): *got bytes; src_eof: no byte of the file's data is
 // behind them (the end of the file, or a bad member: src_error).  BGZF needs cap >= 65536.
 int next_bytes(lra_genome* g, uint8_t* dst, uint64_t cap, uint64_t* got) {
   *got = 0;
   if (g->src_eof) return LRA_OK;
   if (g->kind == GN_PLAIN) {
-    if (!read_all(g->fd, dst, cap, got)) return fail(g, g->path + ": read failed");
+    if (!lra_read_all(g->fd, dst, cap, got)) return fail(g, g->path + ": read failed");
     g->src_eof = *got < cap;
     return LRA_OK;
   }
   if (g->kind == GN_GZIP) {
-    if (!g->gz) {                                   // one serial bit stream: the compressed file as one array
-      g->comp.resize(g->file_size);
-      uint64_t k = 0;
-      if (!read_all(g->fd, g->comp.data(), g->file_size, &k)) return fail(g, g->path + ": read failed");
-      g->comp.resize(k);
-      g->gz = new lra_gz_stream();
-      lra_gz_init(*g->gz, g->comp.data(), k);
+    if (!g->gz) {
+      g->gz.reset(new lra_gzip_source());
+      if (!g->gz->load(g->fd)) return fail(g, g->path + ": read failed");
     }
-    const int st = lra_gz_step(*g->gz, dst, cap, got);
-    if (st) g->src_error = g->path + ": a bad gzip member at compressed offset " + std::to_string(g->gz->member_at) + " (" + gz_reason(st) + ")";
-    g->src_eof = st != 0 || g->gz->phase == 5;
+    g->gz->step(dst, cap, got);
+    if (!g->gz->err.empty()) g->src_error = g->path + ": " + g->gz->err;
+    g->src_eof = g->gz->done;
     return LRA_OK;
   }
-  bool file_eof = false;
-  for (;;) {                                        // BGZF on the host: whole members while they fit
-    const uint64_t have = g->comp.size() - g->comp_pos;
-    uint32_t total = 0, cdata = 0;
-    const uint8_t* in = g->comp.data() + g->comp_pos;
-    const int m = have ? lra_bgzf_member(in, have, &total, &cdata) : 0;
-    const std::string at = g->path + ": a bad BGZF block at compressed offset " + std::to_string(g->comp_file_off + g->comp_pos);
-    if (m < 0) { g->src_error = at + " (not a BGZF block)"; g->src_eof = true; return LRA_OK; }
-    if (m == 1 && have >= total) {
-      const uint32_t isize = lra_le32(in + total - 4);
-      if (isize > 65536) { g->src_error = at + " (a bad ISIZE)"; g->src_eof = true; return LRA_OK; }
-      if (isize > cap - *got) return LRA_OK;
-      const int st = lra_bgzf_inflate_one(in, total, dst + *got, isize);
-      if (st) { g->src_error = at + " (" + lra_bgzf_reason(st) + ")"; g->src_eof = true; return LRA_OK; }
-      *got += isize; g->comp_pos += total;
-      continue;
-    }
-    if (file_eof) {
-      if (have) g->src_error = at + " (the file ends inside it)";
-      g->src_eof = true;
-      return LRA_OK;
-    }
-    g->comp.erase(g->comp.begin(), g->comp.begin() + g->comp_pos);
-    g->comp_file_off += g->comp_pos; g->comp_pos = 0;
-    const size_t old = g->comp.size(), want = 1 << 20;
-    g->comp.resize(old + want);
-    uint64_t k = 0;
-    if (!read_all(g->fd, g->comp.data() + old, want, &k)) return fail(g, g->path + ": read failed");
-    g->comp.resize(old + k);
-    file_eof = k < want;
-  }
+  uint32_t isize = 0;
+  while (g->bz.peek(&isize) && isize <= cap - *got && g->bz.take(dst + *got)) *got += isize;   // BGZF on the host: whole members while they fit
+  if (g->bz.read_failed) return fail(g, g->path + ": read failed");
+  if (!g->bz.err.empty()) g->src_error = g->path + ": " + g->bz.err;
+  g->src_eof = !g->bz.err.empty() || g->bz.at_end();
+  return LRA_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -463,7 +411,7 @@ int parse_step(lra_genome* g, lra_ctx* ctx, const unsigned char* raw, uint64_t l
   hipStream_t st = ctx->stream;
   *cut = len;
   if (!len) return LRA_OK;
-  const uint64_t nt = (len + RD_TILE - 1) / RD_TILE;
+  const uint64_t nt = padded_tiles(len) / RD_TILE;
   const dim3 grid((unsigned)nt), block(RD_NT);
   for (int i = 0; i < 3; i++)
     if (!g->cnt[i].ensure(nt) || !g->base[i].ensure(nt + 1)) return GN_NOMEM(ctx);
@@ -581,7 +529,7 @@ int read_device_bytes(lra_genome* g, lra_ctx* ctx) {
     uint64_t got = 0;
     const int rc = next_bytes(g, (uint8_t*)g->h_raw.p + carry, g->chunk, &got);   // (gzip: inflated here, on the host)
     if (rc) return rc;
-    const uint64_t len = carry + got, padded = std::max<uint64_t>(1, (len + RD_TILE - 1) / RD_TILE) * RD_TILE;
+    const uint64_t len = carry + got, padded = padded_tiles(len);
     if (!g->d_raw.ensure(padded)) return GN_NOMEM(ctx);
     lra_time_begin(ctx, "genome_h2d");
     if (len) LRA_HIP_CHECK(ctx, hipMemcpyAsync(g->d_raw.p, g->h_raw.p, len, hipMemcpyHostToDevice, st));
@@ -612,71 +560,18 @@ uint64_t bgzf_data_size(int fd) {
   return sum;
 }
 
-// BGZF: whole members of up to a step of compressed bytes (a member the step cut stays on the host), inflated on the device behind the bytes the
-// last step left (carried device to device), parsed where they lie
+// BGZF: whole members of up to a step of compressed bytes, inflated on the device behind the bytes the last step left (lra_bgzf_step), parsed where
+// they lie
 int read_device_bgzf(lra_genome* g, lra_ctx* ctx) {
-  hipStream_t st = ctx->stream;
-  uint64_t comp_len = 0, comp_off = 0, carry = 0, carry_at = 0;
-  int cur = 0;
-  bool file_eof = false;
-  uint64_t want = g->chunk;
   for (;;) {
-    if (!file_eof) {
-      if (!g->h_comp.ensure(comp_len + want, comp_len, st)) return GN_NOMEM(ctx);
-      uint64_t got = 0;
-      if (!read_all(g->fd, (uint8_t*)g->h_comp.p + comp_len, want, &got)) return fail(g, g->path + ": read failed");
-      file_eof = got < want;
-      comp_len += got;
-    }
-    std::vector<uint64_t> in_off(1, 0), out_off(1, carry);
-    std::string block_err;
-    const uint8_t* h = (const uint8_t*)g->h_comp.p;
-    uint64_t p = 0;
-    while (p < comp_len) {                          // the members: one hop per header
-      uint32_t total = 0, cdata = 0;
-      const int m = lra_bgzf_member(h + p, comp_len - p, &total, &cdata);
-      if (m < 0) { block_err = "not a BGZF block"; break; }
-      if (m == 0 || p + total > comp_len) { if (file_eof) block_err = "the file ends inside it"; break; }
-      const uint32_t isize = lra_le32(h + p + total - 4);
-      if (isize > 65536) { block_err = "a bad ISIZE"; break; }
-      p += total;
-      in_off.push_back(p); out_off.push_back(out_off.back() + isize);
-    }
-    const int nb = (int)in_off.size() - 1;
-    if (nb == 0 && block_err.empty() && !file_eof) { want = std::max(want, comp_len) * 2; continue; }
-    want = g->chunk;
-    const int dst = cur ^ 1;
-    const uint64_t dlen_all = out_off.back(), padded_all = std::max<uint64_t>(1, (dlen_all + RD_TILE - 1) / RD_TILE) * RD_TILE;
-    if (!g->d_comp.ensure(p + 1) || !g->d_boff.ensure(2 * (size_t)(nb + 1)) || !g->d_bstat.ensure(nb + 1) || !g->d_dec[dst].ensure(padded_all)) return GN_NOMEM(ctx);
-    lra_time_begin(ctx, "genome_h2d");
-    if (p) LRA_HIP_CHECK(ctx, hipMemcpyAsync(g->d_comp.p, h, p, hipMemcpyHostToDevice, st));
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(g->d_boff.p, in_off.data(), (nb + 1) * 8, hipMemcpyHostToDevice, st));
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(g->d_boff.p + nb + 1, out_off.data(), (nb + 1) * 8, hipMemcpyHostToDevice, st));
-    lra_time_end(ctx);
-    if (carry) LRA_HIP_CHECK(ctx, hipMemcpyAsync(g->d_dec[dst].p, g->d_dec[cur].p + carry_at, carry, hipMemcpyDeviceToDevice, st));
-    lra_time_begin(ctx, "genome_inflate");
-    lra_bgzf_launch_inflate(st, nb, g->d_comp.p, g->d_boff.p, g->d_boff.p + nb + 1, g->d_dec[dst].p, g->d_bstat.p);
-    LRA_HIP_CHECK(ctx, hipGetLastError());
-    lra_time_end(ctx);
-    std::vector<int32_t> bst((size_t)nb);
-    if (nb) LRA_HIP_CHECK(ctx, hipMemcpyAsync(bst.data(), g->d_bstat.p, nb * 4, hipMemcpyDeviceToHost, st));
-    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    int good = nb;
-    for (int b = 0; b < nb; b++) if (bst[b]) { good = b; break; }
-    const std::string at = g->path + ": a bad BGZF block at compressed offset ";
-    if (good < nb) g->src_error = at + std::to_string(comp_off + in_off[good]) + " (" + lra_bgzf_reason(bst[good]) + ")";
-    else if (!block_err.empty()) g->src_error = at + std::to_string(comp_off + p) + " (" + block_err + ")";
-    const uint64_t dlen = out_off[good];
-    const bool final = !g->src_error.empty() || (file_eof && p == comp_len);
-    const uint64_t padded = std::max<uint64_t>(1, (dlen + RD_TILE - 1) / RD_TILE) * RD_TILE;
-    LRA_HIP_CHECK(ctx, hipMemsetAsync(g->d_dec[dst].p + dlen, 0, padded - dlen, st));
-    uint64_t cut = dlen;
-    if (int rc = parse_step(g, ctx, g->d_dec[dst].p, dlen, final, &cut)) return rc;
-    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    cur = dst; carry = dlen - cut; carry_at = cut;
-    if (final) return LRA_OK;
-    memmove(g->h_comp.p, g->h_comp.p + p, comp_len - p);
-    comp_len -= p; comp_off += p;
+    uint64_t want = g->chunk;
+    const int rc = g->z.fill(ctx, g->fd, &want, lra_bgzf_launch_inflate, "genome_h2d", "genome_inflate");
+    if (rc) return rc == LRA_ERR_NOMEM ? GN_NOMEM(ctx) : rc == LRA_ERR_INVALID ? fail(g, g->path + ": read failed") : rc;
+    if (!g->z.err.empty()) g->src_error = g->path + ": " + g->z.err;
+    uint64_t cut = g->z.dlen;
+    if (int rc2 = parse_step(g, ctx, g->z.data, g->z.dlen, g->z.at_end, &cut)) return rc2;
+    g->z.commit(cut);
+    if (g->z.at_end) return LRA_OK;
   }
 }
 
@@ -689,10 +584,10 @@ extern "C" int lra_genome_open(const char* path, lra_genome** out) {
   struct stat sb;
   if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { if (fd >= 0) close(fd); return LRA_ERR_INVALID; }
   lra_genome* g = new lra_genome();
-  g->path = path; g->fd = fd; g->file_size = (uint64_t)sb.st_size;
+  g->path = path; g->fd = g->bz.fd = fd; g->file_size = (uint64_t)sb.st_size;
   std::vector<uint8_t> head(65536);
   uint64_t k = 0;
-  if (!read_all(fd, head.data(), head.size(), &k) || lseek(fd, 0, SEEK_SET) != 0) { delete g; return LRA_ERR_INVALID; }
+  if (!lra_read_all(fd, head.data(), head.size(), &k) || lseek(fd, 0, SEEK_SET) != 0) { delete g; return LRA_ERR_INVALID; }
   uint32_t total = 0, cdata = 0;
   if (k && lra_bgzf_member(head.data(), k, &total, &cdata) == 1) g->kind = GN_BGZF;
   else if (k >= 3 && head[0] == 0x1f && head[1] == 0x8b && head[2] == 8) g->kind = GN_GZIP;

@@ -31,7 +31,7 @@
 #include "common.h"
 #include "map_state.h"
 #include "reads_state.h"
-#include "bgzf.h"
+#include "zsource.h"
 #include <fcntl.h>
 #include <unistd.h>
 #include <cmath>
@@ -47,32 +47,6 @@
 
 namespace {
 
-const uint32_t* crc_table() {
-  static uint32_t t[256];
-  static bool init = [] { for (uint32_t i = 0; i < 256; i++) t[i] = lra_crc32_table_entry(i); return true; }();
-  (void)init;
-  return t;
-}
-
-}  // namespace
-
-const char* lra_bgzf_reason(int st) {
-  switch (st) {
-    case LRA_BGZF_ERR_HEADER: return "not a BGZF block";
-    case LRA_BGZF_ERR_INPUT: return "its data ends early";
-    case LRA_BGZF_ERR_OUTPUT: return "more data than its ISIZE";
-    case LRA_BGZF_ERR_CODE: return "an invalid DEFLATE code";
-    case LRA_BGZF_ERR_DIST: return "a distance before the block's start";
-    case LRA_BGZF_ERR_STORED: return "a stored block's LEN / NLEN disagree";
-    case LRA_BGZF_ERR_SIZE: return "less data than its ISIZE";
-    case LRA_BGZF_ERR_CRC: return "a CRC-32 mismatch";
-    case LRA_BGZF_ERR_ISIZE: return "a bad ISIZE";
-    default: return "a bad block";
-  }
-}
-
-namespace {
-
 // first line of text: a SAM header line ('@', two letters, a tab) or at least 11 tab-separated fields
 bool looks_like_sam(const uint8_t* p, size_t n) {
   size_t e = 0;
@@ -85,76 +59,32 @@ bool looks_like_sam(const uint8_t* p, size_t n) {
 
 }  // namespace
 
-int lra_bgzf_inflate_one(const uint8_t* in, uint64_t in_len, uint8_t* out, uint64_t isize) {   // a member, host side: inflate, ISIZE, CRC
-  uint32_t total = 0, cdata = 0;
-  if (lra_bgzf_member(in, in_len, &total, &cdata) != 1 || total != in_len) return LRA_BGZF_ERR_HEADER;
-  if (lra_le32(in + total - 4) != isize || isize > 65536) return LRA_BGZF_ERR_ISIZE;
-  lra_inflate_tables t;
-  uint32_t produced = 0;
-  int rc = lra_inflate_raw(in + cdata, total - cdata - 8, out, (uint32_t)isize, t, &produced);
-  if (rc) return rc;
-  if (produced != isize) return LRA_BGZF_ERR_SIZE;
-  if (lra_crc32_update(0, out, isize, crc_table()) != lra_le32(in + total - 8)) return LRA_BGZF_ERR_CRC;
-  return LRA_BGZF_OK;
-}
-
 struct lra_hts_in {
-  int fd = -1;
   int type = -1;
   bool bgzf = false;
   std::string path;
-  std::vector<uint8_t> comp; size_t comp_pos = 0; uint64_t comp_file_off = 0; bool file_eof = false;   // compressed bytes read ahead (comp[comp_pos..])
+  lra_bgzf_source src;                            // the file's bytes read ahead; src.err: a bad block / truncated file, the stream stops there
   std::vector<uint8_t> buf; size_t pos = 0;       // decompressed bytes; buf[pos..] not consumed
-  std::string err;                                // a bad block / truncated file: the stream stops there
   uint64_t n_rec = 0;
-  ~lra_hts_in() { if (fd >= 0) close(fd); }
-  bool read_more(size_t want) {
-    if (file_eof) return false;
-    if (comp_pos > (1u << 20)) { comp.erase(comp.begin(), comp.begin() + comp_pos); comp_file_off += comp_pos; comp_pos = 0; }
-    const size_t at = comp.size();
-    comp.resize(at + want);
-    size_t got = 0;
-    while (got < want) {
-      const ssize_t k = read(fd, comp.data() + at + got, want - got);
-      if (k <= 0) { file_eof = true; break; }
-      got += (size_t)k;
-    }
-    comp.resize(at + got);
-    return got > 0;
-  }
-  // the next block (BGZF) or the next bytes (plain text) behind buf; false: none (err set if the stream is bad)
+  ~lra_hts_in() { if (src.fd >= 0) close(src.fd); }
+  // the next block (BGZF) or the next bytes (plain text) behind buf; false: none (src.err set if the stream is bad)
   bool next_block() {
     if (pos > (1u << 20)) { buf.erase(buf.begin(), buf.begin() + pos); pos = 0; }
-    if (!err.empty()) return false;
+    if (!src.err.empty()) return false;
     if (!bgzf) {
-      const size_t have = comp.size() - comp_pos;
-      if (!have && !read_more(1 << 20)) return false;
-      buf.insert(buf.end(), comp.begin() + comp_pos, comp.end());
-      comp_pos = comp.size();
+      if (src.pos == src.comp.size() && !src.refill(1 << 20)) return false;
+      buf.insert(buf.end(), src.comp.begin() + src.pos, src.comp.end());
+      src.pos = src.comp.size();
       return true;
     }
-    for (;;) {
-      uint32_t total = 0, cdata = 0;
-      const size_t have = comp.size() - comp_pos;
-      const int m = have ? lra_bgzf_member(comp.data() + comp_pos, have, &total, &cdata) : 0;
-      if (m < 0) { err = "a bad BGZF block at compressed offset " + std::to_string(comp_file_off + comp_pos) + " (not a BGZF block)"; return false; }
-      if (m == 1 && have >= total) {
-        const uint8_t* in = comp.data() + comp_pos;
-        const uint32_t isize = lra_le32(in + total - 4);
-        const size_t at = buf.size();
-        if (isize > 65536) { err = "a bad BGZF block at compressed offset " + std::to_string(comp_file_off + comp_pos) + " (a bad ISIZE)"; return false; }
-        buf.resize(at + isize);
-        const int st = lra_bgzf_inflate_one(in, total, buf.data() + at, isize);
-        if (st) { buf.resize(at); err = "a bad BGZF block at compressed offset " + std::to_string(comp_file_off + comp_pos) + " (" + lra_bgzf_reason(st) + ")"; return false; }
-        comp_pos += total;
-        if (isize) return true;
-        continue;                                  // an empty block (the EOF marker may stand anywhere)
-      }
-      if (!read_more(1 << 20)) {
-        if (have) { err = "a bad BGZF block at compressed offset " + std::to_string(comp_file_off + comp_pos) + " (the file ends inside it)"; }
-        return false;
-      }
+    uint32_t isize = 0;
+    while (src.peek(&isize)) {
+      const size_t at = buf.size();
+      buf.resize(at + isize);
+      if (!src.take(buf.data() + at)) { buf.resize(at); return false; }
+      if (isize) return true;                      // (an empty block: the EOF marker may stand anywhere)
     }
+    return false;
   }
   bool more(size_t need) { while (buf.size() - pos < need) if (!next_block()) return false; return true; }
   bool getline(std::string& line) {                // SAM text: the next line without its '\n'; false at the end
@@ -170,7 +100,7 @@ struct lra_hts_in {
       }
       const size_t rel = buf.size() - pos;         // (next_block may move the bytes in front of pos away)
       if (!next_block()) {
-        if (!err.empty() || pos >= buf.size()) return false;
+        if (!src.err.empty() || pos >= buf.size()) return false;
         line.assign((const char*)buf.data() + pos, buf.size() - pos);
         pos = buf.size();
         return true;
@@ -186,8 +116,8 @@ int lra_hts_sniff(const std::string& path, uint64_t* header) {
   const int fd = open(path.c_str(), O_RDONLY);
   if (fd < 0) return -1;
   std::vector<uint8_t> head(65536 + 1024);
-  size_t n = 0;
-  while (n < head.size()) { const ssize_t k = read(fd, head.data() + n, head.size() - n); if (k <= 0) break; n += (size_t)k; }
+  uint64_t n = 0;
+  (void)lra_read_all(fd, head.data(), head.size(), &n);
   close(fd);
   if (n >= 2 && head[0] == 0x1f && head[1] == 0x8b) {
     uint32_t total = 0, cdata = 0;
@@ -215,10 +145,10 @@ int lra_hts_sniff(const std::string& path, uint64_t* header) {
 lra_hts_in* lra_hts_open(const std::string& path, int type, std::string* err) {
   lra_hts_in* h = new lra_hts_in();
   h->path = path; h->type = type;
-  h->fd = open(path.c_str(), O_RDONLY);
-  if (h->fd < 0) { *err = "cannot open " + path; delete h; return nullptr; }
-  h->read_more(1 << 16);
-  h->bgzf = h->comp.size() >= 2 && h->comp[0] == 0x1f && h->comp[1] == 0x8b;
+  h->src.fd = open(path.c_str(), O_RDONLY);
+  if (h->src.fd < 0) { *err = "cannot open " + path; delete h; return nullptr; }
+  h->src.refill(1 << 16);
+  h->bgzf = h->src.comp.size() >= 2 && h->src.comp[0] == 0x1f && h->src.comp[1] == 0x8b;
   if (type == LRA_IN_BAM) {                        // magic, l_text, text, n_ref, refs
     auto i32 = [&](size_t at) { return (int32_t)lra_le32(h->buf.data() + at); };
     bool ok = h->more(12) && memcmp(h->buf.data(), "BAM\1", 4) == 0;
@@ -233,7 +163,7 @@ lra_hts_in* lra_hts_open(const std::string& path, int type, std::string* err) {
       ok = ok && ln >= 0 && h->more((size_t)at + 8 + ln);
       at += 8 + ln;
     }
-    if (!ok) { *err = path + ": not a valid BAM header" + (h->err.empty() ? "" : " (" + h->err + ")"); delete h; return nullptr; }
+    if (!ok) { *err = path + ": not a valid BAM header" + (h->src.err.empty() ? "" : " (" + h->src.err + ")"); delete h; return nullptr; }
     h->pos = (size_t)at;
   } else if (type == LRA_IN_SAM) {                  // the header lines
     for (;;) {
@@ -242,18 +172,9 @@ lra_hts_in* lra_hts_open(const std::string& path, int type, std::string* err) {
       std::string line;
       h->getline(line);
     }
-    if (!h->err.empty()) { *err = path + ": " + h->err; delete h; return nullptr; }
+    if (!h->src.err.empty()) { *err = path + ": " + h->src.err; delete h; return nullptr; }
   }
   return h;
-}
-
-const char* lra_gz_reason(int st) {
-  switch (st) {
-    case LRA_GZ_ERR_HEADER: return "not a gzip member";
-    case LRA_GZ_ERR_TRUNCATED: return "the file ends inside it";
-    case LRA_BGZF_ERR_ISIZE: return "its ISIZE is not the size of its data";
-    default: return lra_bgzf_reason(st);
-  }
 }
 
 namespace {
@@ -267,7 +188,7 @@ struct ztext_bgzf : lra_ztext {
     if (!fault.empty() || !h) return traits_type::eof();
     h->pos = h->buf.size();
     if (!h->next_block()) {
-      if (!h->err.empty()) fault = path + ": " + h->err;
+      if (!h->src.err.empty()) fault = path + ": " + h->src.err;
       return traits_type::eof();
     }
     char* b = (char*)h->buf.data();
@@ -278,34 +199,25 @@ struct ztext_bgzf : lra_ztext {
 
 struct ztext_gzip : lra_ztext {
   std::string path, next_fault;
-  std::vector<uint8_t> comp;
+  lra_gzip_source src;
   std::vector<char> out;
-  lra_gz_stream gz;
-  bool loaded = false, done = false;
+  bool loaded = false;
   int_type underflow() override {
     if (gptr() < egptr()) return traits_type::to_int_type(*gptr());
-    if (!loaded) {                                 // the whole compressed file: lra_gz_stream walks one array
+    if (!loaded) {
       loaded = true;
       const int fd = open(path.c_str(), O_RDONLY);
-      if (fd < 0) { done = true; next_fault = "cannot open " + path; }
+      if (fd < 0) { src.done = true; next_fault = "cannot open " + path; }
       else {
-        for (;;) {
-          const size_t at = comp.size();
-          comp.resize(at + (4u << 20));
-          const ssize_t k = read(fd, comp.data() + at, 4u << 20);
-          comp.resize(at + (k > 0 ? (size_t)k : 0));
-          if (k <= 0) break;
-        }
+        (void)src.load(fd);                        // (a failed read ends the file)
         close(fd);
-        lra_gz_init(gz, comp.data(), comp.size());
         out.resize(1u << 20);
       }
     }
-    if (done) { fault = next_fault; return traits_type::eof(); }
+    if (src.done) { fault = next_fault; return traits_type::eof(); }
     uint64_t got = 0;
-    const int st = lra_gz_step(gz, (uint8_t*)out.data(), out.size(), &got);
-    if (st) next_fault = path + ": a bad gzip member at compressed offset " + std::to_string(gz.member_at) + " (" + lra_gz_reason(st) + ")";
-    if (st || got < out.size()) done = true;
+    src.step((uint8_t*)out.data(), out.size(), &got);
+    if (!src.err.empty()) next_fault = path + ": " + src.err;
     if (!got) { fault = next_fault; return traits_type::eof(); }
     setg(out.data(), out.data(), out.data() + got);
     return traits_type::to_int_type(*gptr());
@@ -329,8 +241,8 @@ int lra_ztext_sniff(const std::string& path, int* zmode) {
   const int fd = open(path.c_str(), O_RDONLY);
   if (fd < 0) return -1;
   std::vector<uint8_t> head(1u << 20);
-  size_t n = 0;
-  while (n < head.size()) { const ssize_t k = read(fd, head.data() + n, head.size() - n); if (k <= 0) break; n += (size_t)k; }
+  uint64_t n = 0;
+  (void)lra_read_all(fd, head.data(), head.size(), &n);
   close(fd);
   if (n < 2 || head[0] != 0x1f || head[1] != 0x8b) return -1;
   const size_t want = 65536 + 1024;
@@ -426,13 +338,13 @@ int lra_hts_next(lra_hts_in* h, lra_hts_rec* rec, std::string* err) {
   rec->aux.clear();
   if (h->type == LRA_IN_BAM) {
     if (!h->more(4)) {
-      if (!h->err.empty()) { *err = h->path + ": " + h->err; return -1; }
+      if (!h->src.err.empty()) { *err = h->path + ": " + h->src.err; return -1; }
       if (h->pos == h->buf.size()) return 0;
       *err = where + ": cut by the end of the file"; return -1;
     }
     const uint32_t bs = lra_le32(h->buf.data() + h->pos);
     if (bs < 32) { *err = where + ": a bad record (block_size " + std::to_string(bs) + ")"; return -1; }
-    if (!h->more(4 + (size_t)bs)) { *err = h->err.empty() ? where + ": cut by the end of the file" : h->path + ": " + h->err; return -1; }
+    if (!h->more(4 + (size_t)bs)) { *err = h->src.err.empty() ? where + ": cut by the end of the file" : h->path + ": " + h->src.err; return -1; }
     const uint8_t* p = h->buf.data() + h->pos + 4;
     const uint32_t l_name = p[8], n_cig = lra_le16(p + 12), flag = lra_le16(p + 14);
     const int32_t l_seq = (int32_t)lra_le32(p + 16);
@@ -454,7 +366,7 @@ int lra_hts_next(lra_hts_in* h, lra_hts_rec* rec, std::string* err) {
   }
   std::string line;
   if (!h->getline(line)) {
-    if (!h->err.empty()) { *err = h->path + ": " + h->err; return -1; }
+    if (!h->src.err.empty()) { *err = h->path + ": " + h->src.err; return -1; }
     return 0;
   }
   std::vector<std::string> f;

@@ -10,6 +10,7 @@
 //                  and its entry of the step's record table -- the layout the FASTQ steps produce, so that one batch stage serves both
 #include "common.h"
 #include "reads_state.h"
+#include "zsource.h"
 #include "bam_kernels.h"
 #include "bgzf.h"
 
@@ -161,8 +162,6 @@ extern "C" int lra_bgzf_inflate_batch(lra_ctx* ctx, int n_blocks, const uint8_t*
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return LRA_OK;
 }
-
-int lra_bgzf_inflate_one(const uint8_t* in, uint64_t in_len, uint8_t* out, uint64_t isize);   // input.hip
 
 extern "C" int lra_bgzf_inflate_host(int n_blocks, const uint8_t* in, const uint64_t* in_off, const uint64_t* out_off, uint8_t* out, int32_t* status) {
   if (n_blocks < 0 || (n_blocks && (!in || !in_off || !out_off || !out || !status))) return LRA_ERR_INVALID;

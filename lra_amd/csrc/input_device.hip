@@ -15,9 +15,10 @@
 //             rd_name_emit     the names, NUL-terminated, back to back
 //           FASTQ records are framed by line index mod 4 from the step's start (a step starts at a record); FASTA records by their header lines.
 //   compressed FASTA / FASTQ (lra_reads_open_flags with LRA_READS_COMPRESSED_TEXT; input.hip's decisions 3 and 4):
-//     BGZF    the host walks the members' headers in each step of compressed bytes (a member the step cut stays for the next step), the members are inflated
-//             on the device, a wave per member, behind the carried tail of the last step's text (the record the step cut, carried device to device), and
-//             the passes above run where the data lies: no text crosses the bus.  The chunk counts compressed bytes.
+//     BGZF    zsource.h's lra_bgzf_step, the step BAM and the genome use too: the host walks the members' headers in each step of compressed bytes (a member
+//             the step cut stays for the next step), the members are inflated on the device, a wave per member, behind the carried tail of the last step's
+//             text (the record the step cut, carried device to device), and the passes above run where the data lies: no text crosses the bus.  The chunk
+//             counts compressed bytes.
 //     gzip    that is not BGZF is one serial bit stream: the host inflates a step with bgzf.h's lra_gz_stream (window, bit buffer and an unfinished match
 //             kept across steps, members concatenated) into the page-locked step buffer; upload and passes as for a plain file.  The chunk counts output
 //             bytes.  This path is bound by ONE CPU thread (about 0.16 GB/s of text, half of that in bases): BGZF is the format to use at speed.
@@ -27,9 +28,7 @@
 #include "common.h"
 #include "reads_state.h"
 #include "scan.h"
-#include "bam_kernels.h"
-#include "bgzf.h"
-#include "byte_tiles.h"
+#include "zsource.h"
 #include <fcntl.h>
 #include <unistd.h>
 #include <algorithm>
@@ -225,18 +224,16 @@ struct lra_reads_dev {
   std::vector<const char*> name_ptr, seq_ptr, qual_ptr;
   uint64_t seg_a = 0, seg_b = 0;                   // the pending run of this step's records [seg_a, seg_b) not yet copied to the batch
   uint64_t b_seq = 0, b_names = 0, b_quals = 0;    // the batch's bytes so far
-  // BAM (input_bam.hip's kernels): h_raw holds compressed bytes; a step inflates its whole members behind the carried tail of the last step's data
+  // BAM (input_bam.hip's kernels) and BGZF FASTA / FASTQ: a step inflates the file's next whole members behind the carried tail of the last step's data
+  lra_bgzf_step z;
   uint64_t bam_skip = 0;                           // header bytes still to skip in the decompressed stream
-  uint64_t comp_file_off = 0;                      // file offset of h_raw[0]
   uint64_t bam_rec_base = 0;                       // records framed by the file's earlier steps
-  DevBuf<uint8_t> d_comp, d_dec[2]; int dec_cur = 0; uint64_t dec_len = 0, dec_used = 0;
-  DevBuf<uint64_t> d_boff, rec_pos, bam_out; DevBuf<int32_t> d_bstat; DevBuf<uint32_t> bcnt[5]; DevBuf<uint64_t> boffs[5];
+  DevBuf<uint64_t> rec_pos, bam_out; DevBuf<uint32_t> bcnt[5]; DevBuf<uint64_t> boffs[5];
   DevBuf<unsigned long long> first_bad; DevBuf<uint8_t> c_aux;
   std::vector<uint8_t> h_aux;                      // the step's aux bytes (passthrough on)
   std::string pending_error;                       // the step stops at a problem: the error once its records are taken
-  // compressed FASTA / FASTQ: BGZF uses h_raw / d_comp / d_dec / d_boff / d_bstat as the BAM steps do (the step's text is d_dec[dec_cur][0, dec_len))
-  int zmode = LRA_Z_PLAIN;
-  std::vector<uint8_t> gz_comp; std::unique_ptr<lra_gz_stream> gz;   // gzip that is not BGZF: the compressed file, the decoder between steps
+  int zmode = LRA_Z_PLAIN;                         // compressed FASTA / FASTQ: BGZF through z (the step's text is z.data[0, z.dlen))
+  std::unique_ptr<lra_gzip_source> gz;             // gzip that is not BGZF: inflated on the host into h_raw
   const unsigned char* d_text = nullptr;           // the step's text on the device, and what the host needs of it without its bytes:
   uint64_t lines_in = 0;                           // its lines (the last one may lack its '\n')
   // records parsed on the host (SAM text) in the device form's batch: their bases go up at the batch's end
@@ -246,7 +243,7 @@ struct lra_reads_dev {
     h_raw.release(); d_raw.release(); nl_pos.release(); d_rec.release(); name_len.release(); name_off.release();
     for (int i = 0; i < 4; i++) { cnt[i].release(); base[i].release(); }
     c_seq.release(); c_qual.release(); c_names.release(); d_seq.release(); d_off.release(); h_seq.release(); h_names.release(); h_quals.release();
-    d_comp.release(); d_dec[0].release(); d_dec[1].release(); d_boff.release(); rec_pos.release(); bam_out.release(); d_bstat.release();
+    z.release(); rec_pos.release(); bam_out.release();
     for (int i = 0; i < 5; i++) { bcnt[i].release(); boffs[i].release(); }
     first_bad.release(); c_aux.release();
   }
@@ -261,8 +258,8 @@ int sniff(int fd) {
   std::string head;
   char buf[65536];
   for (;;) {
-    const ssize_t k = read(fd, buf, sizeof buf);
-    if (k <= 0) break;
+    uint64_t k = 0;
+    if (!lra_read_all(fd, buf, sizeof buf, &k) || !k) break;
     head.append(buf, (size_t)k);
     const size_t a = head.find('\n');
     if (a != std::string::npos && head.find('\n', a + 1) != std::string::npos && head.size() > head.find('\n', a + 1) + 1) break;
@@ -284,24 +281,13 @@ bool open_dev_file(lra_reads* r) {
   d->fd = open(r->files[r->cur].c_str(), O_RDONLY);
   d->type = d->fd >= 0 ? sniff(d->fd) : -1;
   d->len = d->consumed = 0; d->file_at_eof = false; d->fq_eof = false;
-  d->zmode = LRA_Z_PLAIN; d->pending_error.clear(); d->gz.reset(); d->gz_comp.clear();
+  d->zmode = LRA_Z_PLAIN; d->pending_error.clear(); d->gz.reset(); d->z.reset();
   if (d->fd >= 0 && d->type < 0 && (r->open_flags & LRA_READS_COMPRESSED_TEXT)) {   // gzip / BGZF FASTA or FASTQ (input.hip's sniffing)
     int zm = LRA_Z_PLAIN;
     const int t = lra_ztext_sniff(r->files[r->cur], &zm);
     if (t >= 0) {
       d->type = t; d->zmode = zm;
-      d->comp_file_off = 0; d->dec_len = d->dec_used = 0;
-      if (zm == LRA_Z_GZIP) {                                      // lra_gz_stream walks the whole compressed file as one array
-        for (;;) {
-          const size_t at = d->gz_comp.size();
-          d->gz_comp.resize(at + (4u << 20));
-          const ssize_t k = read(d->fd, d->gz_comp.data() + at, 4u << 20);
-          d->gz_comp.resize(at + (k > 0 ? (size_t)k : 0));
-          if (k <= 0) break;
-        }
-        d->gz.reset(new lra_gz_stream());
-        lra_gz_init(*d->gz, d->gz_comp.data(), d->gz_comp.size());
-      }
+      if (zm == LRA_Z_GZIP) { d->gz.reset(new lra_gzip_source()); (void)d->gz->load(d->fd); }   // (a failed read ends the file)
     }
   }
   d->rec.clear(); d->n_avail = d->next = 0; d->step_ends_file = false;
@@ -311,7 +297,7 @@ bool open_dev_file(lra_reads* r) {
     uint64_t header = 0;
     d->type = lra_hts_sniff(r->files[r->cur], &header);
     if (d->type == LRA_IN_BAM) {
-      d->bam_skip = header; d->comp_file_off = 0; d->bam_rec_base = 0; d->dec_len = d->dec_used = 0; d->pending_error.clear();
+      d->bam_skip = header; d->bam_rec_base = 0;
     } else if (d->type == LRA_IN_SAM) {                            // parsed on the host: the compatibility path
       std::string err;
       r->hts.reset(lra_hts_open(r->files[r->cur], LRA_IN_SAM, &err));
@@ -358,8 +344,6 @@ int flush_segment(lra_ctx* ctx, lra_reads_dev* d) {
   }
   return LRA_OK;
 }
-
-uint64_t padded_tiles(uint64_t len) { return std::max<uint64_t>(1, (len + RD_TILE - 1) / RD_TILE) * RD_TILE; }
 
 // the device passes over a step's text that lies on the device, raw[0, len) with zeros up to padded_tiles(len): the record table of the step.
 // last = the text's last byte (the host needs no other byte of it)
@@ -430,6 +414,15 @@ int parse(lra_ctx* ctx, lra_reads_dev* d) {
   return parse_text(ctx, d, d->d_raw.p, len, len ? (unsigned char)d->h_raw.p[len - 1] : 0);
 }
 
+// a failure of a step's plumbing in the reader's words (lra_bgzf_step::fill returns the last two bare)
+int step_failed(lra_ctx* ctx, lra_reads* r, int rc) {
+  const size_t pinned = r->dev->z.nomem_pinned;
+  if (rc == LRA_ERR_NOMEM && pinned) return lra_set_err(ctx, rc, "device reader: hipHostMalloc(%zu) failed", pinned);
+  if (rc == LRA_ERR_NOMEM) return lra_set_err(ctx, rc, "device reader: hipMalloc failed");
+  if (rc == LRA_ERR_INVALID) return lra_set_err(ctx, rc, "device reader: read of %s failed", r->files[r->cur].c_str());
+  return rc;
+}
+
 // the next step of the current file: the carry of the last step, then up to `chunk` more bytes; a step that holds no whole record (and is not the file's
 // end) reads on, twice as much each time
 int next_step(lra_ctx* ctx, lra_reads* r) {
@@ -443,15 +436,12 @@ int next_step(lra_ctx* ctx, lra_reads* r) {
       if (!d->h_raw.ensure(d->len + want + 1, d->len, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc(%zu) failed", (size_t)(d->len + want));
       uint64_t got = 0;
       if (d->zmode == LRA_Z_GZIP) {                                // the next `want` bytes of the inflated text (one host thread)
-        const int zs = lra_gz_step(*d->gz, (uint8_t*)d->h_raw.p + d->len, want, &got);
-        if (zs) d->pending_error = r->files[r->cur] + ": a bad gzip member at compressed offset " + std::to_string(d->gz->member_at) + " (" + lra_gz_reason(zs) + ")";
-        if (zs || got < want) d->file_at_eof = true;
-      } else
-      while (got < want) {
-        const ssize_t k = read(d->fd, d->h_raw.p + d->len + got, (size_t)std::min<uint64_t>(want - got, 1ull << 30));
-        if (k < 0) return lra_set_err(ctx, LRA_ERR_INVALID, "device reader: read of %s failed", r->files[r->cur].c_str());
-        if (k == 0) { d->file_at_eof = true; break; }
-        got += (uint64_t)k;
+        d->gz->step((uint8_t*)d->h_raw.p + d->len, want, &got);
+        if (!d->gz->err.empty()) d->pending_error = r->files[r->cur] + ": " + d->gz->err;
+        d->file_at_eof = d->gz->done;
+      } else {
+        if (!lra_read_all(d->fd, d->h_raw.p + d->len, want, &got)) return step_failed(ctx, r, LRA_ERR_INVALID);
+        d->file_at_eof = got < want;
       }
       d->len += got;
     }
@@ -475,163 +465,53 @@ int next_step(lra_ctx* ctx, lra_reads* r) {
   }
 }
 
-// the next step of a BGZF FASTA / FASTQ file: whole members of up to `chunk` compressed bytes (a member the step cut stays on the host for the next one)
-// inflated behind the carried tail of the last step's text, then parse_text where the text lies.  A step that holds no whole record reads on.
+// the next step of a BGZF FASTA / FASTQ file: whole members of up to `chunk` compressed bytes inflated behind the carried tail of the last step's text
+// (lra_bgzf_step), then parse_text where the text lies.  A step that holds no whole record reads on.
 int next_step_bgzf_text(lra_ctx* ctx, lra_reads* r) {
   lra_reads_dev* d = r->dev;
   if (int rc = flush_segment(ctx, d)) return rc;
   hipStream_t st = ctx->stream;
-  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  if (d->consumed) {
-    memmove(d->h_raw.p, d->h_raw.p + d->consumed, d->len - d->consumed);
-    d->len -= d->consumed; d->comp_file_off += d->consumed; d->consumed = 0;
-  }
-  const int src = d->dec_cur, dst = d->dec_cur ^ 1;
-  const uint64_t carry = d->dec_len - d->dec_used;
+  lra_bgzf_step& z = d->z;
   uint64_t want = d->chunk;
   for (;;) {
-    if (!d->file_at_eof) {
-      if (!d->h_raw.ensure(d->len + want + 1, d->len, st)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc(%zu) failed", (size_t)(d->len + want));
-      uint64_t got = 0;
-      while (got < want) {
-        const ssize_t k = read(d->fd, d->h_raw.p + d->len + got, (size_t)std::min<uint64_t>(want - got, 1ull << 30));
-        if (k < 0) return lra_set_err(ctx, LRA_ERR_INVALID, "device reader: read of %s failed", r->files[r->cur].c_str());
-        if (k == 0) { d->file_at_eof = true; break; }
-        got += (uint64_t)k;
-      }
-      d->len += got;
-    }
-    std::vector<uint64_t> in_off(1, 0), out_off(1, carry);
-    std::string block_err;
-    const uint8_t* h = (const uint8_t*)d->h_raw.p;
-    uint64_t p = 0;
-    while (p < d->len) {
-      uint32_t total = 0, cdata = 0;
-      const int m = lra_bgzf_member(h + p, d->len - p, &total, &cdata);
-      if (m < 0) { block_err = "not a BGZF block"; break; }
-      if (m == 0 || p + total > d->len) { if (d->file_at_eof) block_err = "the file ends inside it"; break; }
-      const uint32_t isize = lra_le32(h + p + total - 4);
-      if (isize > 65536) { block_err = "a bad ISIZE"; break; }
-      p += total;
-      in_off.push_back(p); out_off.push_back(out_off.back() + isize);
-    }
-    const int nb = (int)in_off.size() - 1;
-    if (nb == 0 && block_err.empty() && !d->file_at_eof) { want = std::max(want, d->len) * 2; continue; }
-    if (!d->d_comp.ensure(p + 1) || !d->d_boff.ensure(2 * (size_t)(nb + 1)) || !d->d_bstat.ensure(nb + 1) || !d->d_dec[dst].ensure(padded_tiles(out_off.back()) + 64))
-      return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
-    lra_time_begin(ctx, "input_h2d");
-    if (p) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_comp.p, h, p, hipMemcpyHostToDevice, st));
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_boff.p, in_off.data(), (nb + 1) * 8, hipMemcpyHostToDevice, st));
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_boff.p + nb + 1, out_off.data(), (nb + 1) * 8, hipMemcpyHostToDevice, st));
-    lra_time_end(ctx);
-    if (carry) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_dec[dst].p, d->d_dec[src].p + d->dec_used, carry, hipMemcpyDeviceToDevice, st));
-    lra_time_begin(ctx, "input_inflate");
-    lra_bgzf_launch_inflate_lut(st, nb, d->d_comp.p, d->d_boff.p, d->d_boff.p + nb + 1, d->d_dec[dst].p, d->d_bstat.p);
-    LRA_HIP_CHECK(ctx, hipGetLastError());
-    lra_time_end(ctx);
-    std::vector<int32_t> bst((size_t)nb);
-    if (nb) LRA_HIP_CHECK(ctx, hipMemcpyAsync(bst.data(), d->d_bstat.p, nb * 4, hipMemcpyDeviceToHost, st));
-    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    int good = nb;
-    for (int b = 0; b < nb; b++) if (bst[b]) { good = b; break; }
-    std::string err;                                               // (the messages of input.hip's lra_hts_in: both forms say the same)
-    if (good < nb) err = r->files[r->cur] + ": a bad BGZF block at compressed offset " + std::to_string(d->comp_file_off + in_off[good]) + " (" + lra_bgzf_reason(bst[good]) + ")";
-    else if (!block_err.empty()) err = r->files[r->cur] + ": a bad BGZF block at compressed offset " + std::to_string(d->comp_file_off + p) + " (" + block_err + ")";
-    const uint64_t dlen = out_off[good];
-    const bool at_end = !err.empty() || (d->file_at_eof && p == d->len);
-    const bool final = at_end && err.empty();
+    if (int rc = z.fill(ctx, d->fd, &want, lra_bgzf_launch_inflate_lut, "input_h2d", "input_inflate")) return step_failed(ctx, r, rc);
+    const bool final = z.at_end && z.err.empty();
     unsigned char last = 0;
-    LRA_HIP_CHECK(ctx, hipMemsetAsync(d->d_dec[dst].p + dlen, 0, padded_tiles(dlen) - dlen, st));
-    if (dlen) LRA_HIP_CHECK(ctx, hipMemcpyAsync(&last, d->d_dec[dst].p + dlen - 1, 1, hipMemcpyDeviceToHost, st));
+    if (z.dlen) LRA_HIP_CHECK(ctx, hipMemcpyAsync(&last, z.data + z.dlen - 1, 1, hipMemcpyDeviceToHost, st));
     LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    if (int rc = parse_text(ctx, d, d->d_dec[dst].p, dlen, last)) return rc;
+    if (int rc = parse_text(ctx, d, z.data, z.dlen, last)) return rc;
     const uint64_t n = d->n_started;
     uint64_t complete;
     if (d->type == 0) complete = final ? n : (n ? n - 1 : 0);
     else if (final) complete = d->n_nl / 4 + 1;
     else complete = d->n_nl / 4;
-    if (complete == 0 && !at_end) { want = std::max(want, d->len) * 2; continue; }   // no whole record yet: read on
+    if (complete == 0 && !z.at_end) { want = std::max(want, z.comp_len) * 2; continue; }   // no whole record yet: read on
     d->n_avail = complete;
-    d->step_ends_file = at_end;
-    d->pending_error = err;
+    d->step_ends_file = z.at_end;
+    d->pending_error = z.err.empty() ? z.err : r->files[r->cur] + ": " + z.err;
     d->next = d->seg_a = d->seg_b = 0;
     if (d->type == 1 && d->rec.size() < complete + 1) {            // units behind the end of the file: no bytes, their lines are empty
       const RecInfo s = d->rec.back();
       d->rec.resize(complete + 1, s);
     }
-    d->consumed = p;
-    d->dec_cur = dst; d->dec_len = dlen; d->dec_used = final ? dlen : (complete < n ? d->rec[complete].start : dlen);
+    z.commit(final ? z.dlen : (complete < n ? d->rec[complete].start : z.dlen));
     return LRA_OK;
   }
 }
 
-// the next step of a BAM file: whole BGZF members of up to `chunk` compressed bytes (a member the step cut stays on the host for the next one) inflated
-// behind the undecoded tail of the last step's data (a record the step cut, carried device to device), framed and decoded into the step's record
-// table.  A step that holds no whole record (and is not the file's end) reads on, twice as much each time.
+// the next step of a BAM file: whole BGZF members of up to `chunk` compressed bytes inflated behind the undecoded tail of the last step's data, a record
+// the step cut (lra_bgzf_step), framed and decoded into the step's record table.  A step that holds no whole record (and is not the file's end) reads
+// on, twice as much each time.
 int next_step_bam(lra_ctx* ctx, lra_reads* r) {
   lra_reads_dev* d = r->dev;
   if (int rc = flush_segment(ctx, d)) return rc;
   hipStream_t st = ctx->stream;
-  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  if (d->consumed) {
-    memmove(d->h_raw.p, d->h_raw.p + d->consumed, d->len - d->consumed);
-    d->len -= d->consumed; d->comp_file_off += d->consumed; d->consumed = 0;
-  }
-  const int src = d->dec_cur, dst = d->dec_cur ^ 1;
-  const uint64_t carry = d->dec_len - d->dec_used;
+  lra_bgzf_step& z = d->z;
   uint64_t want = d->chunk;
   for (;;) {
-    if (!d->file_at_eof) {
-      if (!d->h_raw.ensure(d->len + want + 1, d->len, st)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc(%zu) failed", (size_t)(d->len + want));
-      uint64_t got = 0;
-      while (got < want) {
-        const ssize_t k = read(d->fd, d->h_raw.p + d->len + got, (size_t)std::min<uint64_t>(want - got, 1ull << 30));
-        if (k < 0) return lra_set_err(ctx, LRA_ERR_INVALID, "device reader: read of %s failed", r->files[r->cur].c_str());
-        if (k == 0) { d->file_at_eof = true; break; }
-        got += (uint64_t)k;
-      }
-      d->len += got;
-    }
-    // the members: host walk of the BGZF headers, one hop per member
-    std::vector<uint64_t> in_off(1, 0), out_off(1, carry);
-    std::string block_err;
-    const uint8_t* h = (const uint8_t*)d->h_raw.p;
-    uint64_t p = 0;
-    while (p < d->len) {
-      uint32_t total = 0, cdata = 0;
-      const int m = lra_bgzf_member(h + p, d->len - p, &total, &cdata);
-      if (m < 0) { block_err = "not a BGZF block"; break; }
-      if (m == 0 || p + total > d->len) { if (d->file_at_eof) block_err = "the file ends inside it"; break; }
-      const uint32_t isize = lra_le32(h + p + total - 4);
-      if (isize > 65536) { block_err = "a bad ISIZE"; break; }
-      p += total;
-      in_off.push_back(p); out_off.push_back(out_off.back() + isize);
-    }
-    const int nb = (int)in_off.size() - 1;
-    if (nb == 0 && block_err.empty() && !d->file_at_eof) { want = std::max(want, d->len) * 2; continue; }
-    const uint64_t dlen_all = out_off.back();
-    if (!d->d_comp.ensure(p + 1) || !d->d_boff.ensure(2 * (size_t)(nb + 1)) || !d->d_bstat.ensure(nb + 1) || !d->d_dec[dst].ensure(dlen_all + 64))
-      return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
-    lra_time_begin(ctx, "input_h2d");
-    if (p) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_comp.p, h, p, hipMemcpyHostToDevice, st));
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_boff.p, in_off.data(), (nb + 1) * 8, hipMemcpyHostToDevice, st));
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_boff.p + nb + 1, out_off.data(), (nb + 1) * 8, hipMemcpyHostToDevice, st));
-    lra_time_end(ctx);
-    if (carry) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_dec[dst].p, d->d_dec[src].p + d->dec_used, carry, hipMemcpyDeviceToDevice, st));
-    lra_time_begin(ctx, "input_inflate");
-    lra_bgzf_launch_inflate(st, nb, d->d_comp.p, d->d_boff.p, d->d_boff.p + nb + 1, d->d_dec[dst].p, d->d_bstat.p);
-    LRA_HIP_CHECK(ctx, hipGetLastError());
-    lra_time_end(ctx);
-    std::vector<int32_t> bst((size_t)nb);
-    if (nb) LRA_HIP_CHECK(ctx, hipMemcpyAsync(bst.data(), d->d_bstat.p, nb * 4, hipMemcpyDeviceToHost, st));
-    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    int good = nb;
-    for (int b = 0; b < nb; b++) if (bst[b]) { good = b; break; }
-    std::string err;
-    if (good < nb) err = r->files[r->cur] + ": a bad BGZF block at compressed offset " + std::to_string(d->comp_file_off + in_off[good]) + " (" + lra_bgzf_reason(bst[good]) + ")";
-    else if (!block_err.empty()) err = r->files[r->cur] + ": a bad BGZF block at compressed offset " + std::to_string(d->comp_file_off + p) + " (" + block_err + ")";
-    const uint64_t dlen = out_off[good];
-    const bool at_end = !err.empty() || (d->file_at_eof && p == d->len);   // no byte of the file behind this step's data
+    if (int rc = z.fill(ctx, d->fd, &want, lra_bgzf_launch_inflate, "input_h2d", "input_inflate")) return step_failed(ctx, r, rc);
+    const uint64_t dlen = z.dlen;
+    const bool at_end = z.at_end;                                  // no byte of the file behind this step's data
     // the header, then the chain of block_size fields
     const uint64_t start = std::min(d->bam_skip, dlen);
     const uint64_t cap = (dlen - start) / 36 + 1;
@@ -639,13 +519,13 @@ int next_step_bam(lra_ctx* ctx, lra_reads* r) {
     uint64_t fr[4] = {0, start, 0, 0};
     lra_time_begin(ctx, "input_frame");
     if (dlen > start) {
-      lra_bam_launch_frame(st, d->d_dec[dst].p, start, dlen, d->rec_pos.p, cap, d->bam_out.p);
+      lra_bam_launch_frame(st, z.data, start, dlen, d->rec_pos.p, cap, d->bam_out.p);
       LRA_HIP_CHECK(ctx, hipMemcpyAsync(fr, d->bam_out.p, 32, hipMemcpyDeviceToHost, st));
       LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     }
     lra_time_end(ctx);
     const uint64_t n = fr[0];
-    if (n == 0 && !at_end && fr[2] == 0 && dlen > start) { want = std::max(want, d->len) * 2; continue; }   // one record longer than the step
+    if (n == 0 && !at_end && fr[2] == 0 && dlen > start) { want = std::max(want, z.comp_len) * 2; continue; }   // one record longer than the step
     // the records: validate, flagRemove, counts -> scans -> emit
     for (int i = 0; i < 5; i++)
       if (!d->bcnt[i].ensure(n + 1) || !d->boffs[i].ensure(n + 2)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
@@ -655,7 +535,7 @@ int next_step_bam(lra_ctx* ctx, lra_reads* r) {
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->first_bad.p, &none, 8, hipMemcpyHostToDevice, st));
     uint32_t* cnt[5]; uint64_t* offs[5];
     for (int i = 0; i < 5; i++) { cnt[i] = d->bcnt[i].p; offs[i] = d->boffs[i].p; }
-    lra_bam_launch_count(st, d->d_dec[dst].p, d->rec_pos.p, n, r->flag_remove, cnt, d->first_bad.p);
+    lra_bam_launch_count(st, z.data, d->rec_pos.p, n, r->flag_remove, cnt, d->first_bad.p);
     for (int i = 0; i < 5; i++) if (int rc = lra_exclusive_scan(ctx, (long)n, cnt[i], offs[i])) return rc;
     uint64_t tot[5];
     for (int i = 0; i < 5; i++) LRA_HIP_CHECK(ctx, hipMemcpyAsync(&tot[i], offs[i] + n, 8, hipMemcpyDeviceToHost, st));
@@ -665,7 +545,7 @@ int next_step_bam(lra_ctx* ctx, lra_reads* r) {
     const uint64_t n_kept = tot[0];
     if (!d->c_seq.ensure(tot[1] + 1) || !d->c_qual.ensure(tot[2] + n_kept + 1) || !d->c_names.ensure(tot[3] + 1) || !d->c_aux.ensure(tot[4] + 1))
       return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc failed");
-    lra_bam_launch_emit(st, d->d_dec[dst].p, d->rec_pos.p, n, d->bcnt[0].p, offs, d->c_seq.p, d->c_qual.p, d->c_names.p, d->c_aux.p, d->d_rec.p);
+    lra_bam_launch_emit(st, z.data, d->rec_pos.p, n, d->bcnt[0].p, offs, d->c_seq.p, d->c_qual.p, d->c_names.p, d->c_aux.p, d->d_rec.p);
     LRA_HIP_CHECK(ctx, hipGetLastError());
     lra_time_end(ctx);
     d->rec.resize(n_kept + 1);
@@ -685,15 +565,14 @@ int next_step_bam(lra_ctx* ctx, lra_reads* r) {
     d->pending_error.clear();
     if (fb < n) d->pending_error = where + ": a bad record";         // (the messages of input.hip's lra_hts_next: both forms say the same)
     else if (fr[2]) d->pending_error = where + ": a bad record (block_size " + std::to_string(fr[3]) + ")";
-    else if (!err.empty()) d->pending_error = err;
+    else if (!z.err.empty()) d->pending_error = r->files[r->cur] + ": " + z.err;
     else if (at_end && fr[1] < dlen) d->pending_error = where + ": cut by the end of the file";
     d->n_avail = fb < n ? kept_before_bad : n_kept;
     d->next = d->seg_a = d->seg_b = 0;
     d->step_ends_file = at_end || !d->pending_error.empty();
     d->bam_skip -= start;
     d->bam_rec_base += n;
-    d->consumed = p;
-    d->dec_cur = dst; d->dec_len = dlen; d->dec_used = fr[1];
+    z.commit(fr[1]);
     return LRA_OK;
   }
 }

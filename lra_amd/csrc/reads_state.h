@@ -43,7 +43,6 @@ lra_hts_in* lra_hts_open(const std::string& path, int type, std::string* err);
 // 1: a record; 0: the file is over; -1: it stops here (*err names the reason)
 int lra_hts_next(lra_hts_in* h, lra_hts_rec* rec, std::string* err);
 // sam_format1's text behind the 11th tab for BAM aux bytes; false: none (no aux fields)
-const char* lra_bgzf_reason(int status);          // a bgzf.h status in words
 bool lra_format_aux(const uint8_t* p, uint64_t n, std::string* out);
 // BAM's 4-bit base codes
 __host__ __device__ inline char lra_nt16_char(int c) { return "=ACMGRSVTWYHKDBN"[c & 15]; }
@@ -52,7 +51,6 @@ __host__ __device__ inline char lra_nt16_char(int c) { return "=ACMGRSVTWYHKDBN"
 struct lra_ztext : std::streambuf { std::string fault; };
 // the format of a file that starts 1f 8b by its inflated head: LRA_IN_FASTA, LRA_IN_FASTQ or -1; *zmode = LRA_Z_BGZF / LRA_Z_GZIP
 int lra_ztext_sniff(const std::string& path, int* zmode);
-const char* lra_gz_reason(int status);            // a status of lra_gz_step in words
 struct lra_hts_deleter { void operator()(lra_hts_in* h) const { lra_hts_free(h); } };
 
 struct lra_reads {
