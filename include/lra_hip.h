@@ -829,6 +829,39 @@ typedef struct lra_cigar_text_result {
 int lra_cigar_text_batch(lra_ctx* ctx, int n_aln, const uint32_t* d_runs, const uint64_t* d_run_off, const int32_t* d_pre_clip, const int32_t* d_suf_clip,
                          const uint8_t* d_clip_op, lra_cigar_text_result* out);
 
+/* ---- a17 (print format 'a'): the alignment strings and the pairwise text of every alignment, on the device (pairwise.hip) ----------------
+ * Replaces  CreateAlignmentStrings (Alignment.h:247-331) and the rows of PrintPairwise (:564-589)  on the final blocks.  Arguments as
+ * lra_md_strings_batch (d_q_len is not read).
+ * lra_alignment_strings_batch: alignment a's three strings are d_q / d_a / d_t + d_col_off[a], d_col_off[a + 1] - d_col_off[a] bytes each, byte for byte
+ * what lra_alignment_strings gives (pair columns carry '|' or '*' by seqMap equality, the net query gap comes first with ' ' over '-', then the net text
+ * gap, then the gaps' common stretch as pair columns; characters as stored); d_ref_len[a] = Alignment::refLen as lra_alignment_strings leaves it: the
+ * last block's tPos + length, 0 without blocks.  n_cols = d_col_off[n_aln].
+ * lra_pairwise_text_batch: alignment a's text at d_text + d_off[a], d_off[a + 1] - d_off[a] bytes: what lra_format_pairwise writes behind the name line
+ * and the "Interval:" line (first_q / first_t = the first block's qPos / tPos), 46 * ceil(c / 50) + 3 c bytes for c columns, built straight from the
+ * blocks without the strings.  n_bytes = d_off[n_aln]; nothing is written behind d_text + n_bytes.
+ * Outside the contract (the contents are unspecified, nothing is read or written out of range): blocks that overlap -- a negative length or gap, which
+ * the reference asserts on and the pipeline does not make; a literal '-' in a read or a chromosome (the host form counts a row's coordinates from the
+ * characters).  Output context-owned, valid until the next call on the context (n_aln == 0: LRA_OK, no arrays).  Synchronous.                        */
+typedef struct lra_aln_strings_result {
+  int32_t n_aln;
+  uint64_t n_cols;
+  const uint64_t* d_col_off;  /* [n_aln+1] */
+  const uint32_t* d_ref_len;  /* [n_aln] */
+  const char* d_q;            /* [n_cols] each */
+  const char* d_a;
+  const char* d_t;
+} lra_aln_strings_result;
+int lra_alignment_strings_batch(lra_ctx* ctx, int n_aln, const int32_t* d_blocks, const uint64_t* d_block_off, const char* d_qseq, const uint64_t* d_q_off,
+                                const int32_t* d_q_len, const char* d_tseq, const uint64_t* d_t_off, lra_aln_strings_result* out);
+typedef struct lra_pairwise_text_result {
+  int32_t n_aln;
+  uint64_t n_bytes;
+  const uint64_t* d_off;      /* [n_aln+1] */
+  const char* d_text;         /* [n_bytes] */
+} lra_pairwise_text_result;
+int lra_pairwise_text_batch(lra_ctx* ctx, int n_aln, const int32_t* d_blocks, const uint64_t* d_block_off, const char* d_qseq, const uint64_t* d_q_off,
+                            const int32_t* d_q_len, const char* d_tseq, const uint64_t* d_t_off, lra_pairwise_text_result* out);
+
 /* ---- a15: junctions of split alignments ---------------------------------------------------------------------
  * Replaces   RefineBreakpoint(read, genome, leftAln, rightAln, opts)   (RefineBreakpoint.h:210-466; Map_lowacc.h:592, Map_highacc.h:725)
  * for n junctions: if the read bases between the two segments (in forward read coordinates) number 1..499, both segments are extended into
@@ -1298,7 +1331,7 @@ int lra_map_records_tags(lra_ctx* ctx, const lra_map_result* res, const lra_map_
 int lra_map_records_host_tags(lra_map_host* snap, const lra_map_opts* opts, const char* const* names, const char* const* reads, const char* const* quals,
                               const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough, int n_threads, const char** text,
                               uint64_t* len, const uint64_t** rec_off);
-/* The record text built on the device.  For print formats 's' (SAM) and 'P' (PAF with CG:z:) *text, *len and (*rec_off)[n_reads + 1] are exactly what
+/* The record text built on the device.  For print formats 's' (SAM), 'P' (PAF with CG:z:) and 'a' (pairwise) *text, *len and (*rec_off)[n_reads + 1] are exactly what
  * lra_map_records_host_tags gives for a snapshot of the same result under the same options (flags & LRA_PACK_MD: with MD:Z, opts.printMD; other flag
  * bits are LRA_ERR_INVALID).  The split of work:
  *   host    SetFromSegAlignment, AlignmentsOrder::Update, SimpleMapQV, the grouping and PrintNumAln, and every SHORT field of a record (name, flag,
@@ -1314,18 +1347,21 @@ int lra_map_records_host_tags(lra_map_host* snap, const lra_map_opts* opts, cons
  *           copy pass cut by OUTPUT bytes, one device-to-host copy of the text into a page-locked buffer the context keeps.
  * quals (host, nullable, entries NULL or starting with '*': the field is "*") says which reads HAVE qualities; the host reads a string's first byte
  * only.  d_qual == NULL: the qualities of the reads that need them are uploaded from quals (the readers hand qualities over on the host today); with
- * d_qual the host strings are not read behind their first byte.  reads (host) is read by the fall-through formats only and may be NULL for 's' / 'P':
+ * d_qual the host strings are not read behind their first byte.  reads (host) is read by the fall-through formats only and may be NULL for 's' / 'P' / 'a':
  * SEQ is the bases the batch was mapped from (d_strands), which the readers hand over upper-cased as they uploaded them.  passthrough: NULL, or one
  * text per read (NULL entries: none), as lra_map_records_tags takes them.  Flagged, handed-back and unaligned reads follow lra_map_records_host's rules
  * (an unaligned read's quality string is written as it is, a leading '*' too, as SimplePrintSAM does; one that is shorter than its read -- "*" -- is
  * written as far as it goes, where the host form reads read_len bytes whatever the string holds).
- * Formats 'p', 'b' and 'a' have no long per-base field worth moving ('a' is a debugging format): the call falls through to lra_map_snapshot +
- * lra_map_records_host_tags and returns that text (in pageable memory).
+ * Print format 'a' (pairwise) is a device format too: per printed segment the name line and the "Interval:" line are host literals (from the counters
+ * t_start / t_end the snapshot carries) and the rows are one piece, lra_pairwise_text_batch on the result's own blocks, strands and the genome (which must
+ * be loaded) -- no block and no base crosses to the host; flags and quals are not used by this format; its limits are lra_pairwise_text_batch's.
+ * Formats 'p' and 'b' have no long per-base field worth moving: the call falls through to lra_map_snapshot + lra_map_records_host_tags and returns that
+ * text (in pageable memory).
  * *text / *rec_off are owned by the context and valid until the next lra_map_records_device on it; the result's arrays must still be alive (call it
  * where lra_map_snapshot would be called).  lra_map_records_device_last: where the last call's time and bytes went (zeros after a fall-through). */
 typedef struct lra_records_device_stats {
   double ms_snapshot;      /* pack without the runs + its device-to-host copy + unpack */
-  double ms_cigar_md;      /* lra_cigar_text_batch (+ lra_md_strings_batch) */
+  double ms_cigar_md;      /* lra_cigar_text_batch (+ lra_md_strings_batch); format 'a': lra_pairwise_text_batch */
   double ms_pieces;        /* the host's piece table (wall) */
   double ms_upload;        /* pieces, blob (+ qualities when they come from the host) */
   double ms_kernels;       /* resolve, scan, copy */

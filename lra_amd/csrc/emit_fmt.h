@@ -2,9 +2,10 @@
 //   lra_str_sink    (emit.hip)     the text itself: the long fields -- CIGAR, read, qualities, MD -- are appended to a string as they are;
 //   lra_piece_sink  (mapread.hip)  the piece table of lra_map_records_device: the short fields go to a literal blob, a long field becomes a reference
 //                                  that records.hip resolves and copies on the device.
-// A sink has  lit(text)  cigar(rec) (the runs' text, without clips)  seq(rec, from, n)  qual(rec) (read_len characters)  qual_sub(rec, pos, n)  md(rec).
+// A sink has  lit(text)  cigar(rec) (the runs' text, without clips)  seq(rec, from, n)  qual(rec) (read_len characters)  qual_sub(rec, pos, n)  md(rec);
+// the piece sink also  pairwise(rec)  (the rows of print format 'a': the string form is emit.hip's lra_format_pairwise on the alignment strings).
 // The short fields go through an ostream as the reference's do (the float fields print through the same libstdc++), flushed in front of every long field.
-//   Alignment::PrintPAF :600-656, PrintSAM :658-808, SimplePrintSAM :811-905   (Alignment.h)
+//   Alignment::PrintPAF :600-656, PrintSAM :658-808, SimplePrintSAM :811-905, PrintPairwise :564-589   (Alignment.h)
 #pragma once
 #include "common.h"
 #include <sstream>
@@ -109,6 +110,19 @@ inline int lra_fmt_sam(const lra_aln_record* g, int n_group, int as, int hard_cl
   if (passthrough) o << "\t" << passthrough;
   o << std::endl;
   flush();
+  return LRA_OK;
+}
+
+// PrintPairwise (:564-589) of one segment: the name line, "Interval:\tchrom:first_t-(first_t + refLen)" -- refLen as CreateAlignmentStrings leaves it is the
+// END of the last block (refStart = 0, :330), so the sum is what is printed -- and the rows.  t_start / t_end are the first block's tPos and the last
+// block's tPos + length (CalculateStatistics' counters).
+template <typename Sink>
+inline int lra_fmt_pairwise(const lra_aln_record& r, Sink& k) {
+  std::ostringstream o;
+  o << r.read_name << std::endl;
+  if (r.n_blocks > 0) o << "Interval:\t" << r.chrom << ":" << (int)r.t_start << "-" << (uint32_t)(r.t_start + r.t_end) << std::endl;
+  k.lit(o.str());
+  k.pairwise(r);
   return LRA_OK;
 }
 

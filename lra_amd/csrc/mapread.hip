@@ -1484,6 +1484,7 @@ struct lra_piece_sink {
   }
   void cigar(const lra_aln_record& x) { push(LRA_PIECE_CIGAR, 0, aln[&x - base]); }
   void md(const lra_aln_record& x) { push(LRA_PIECE_MD, 0, aln[&x - base]); }
+  void pairwise(const lra_aln_record& x) { push(LRA_PIECE_PAIRWISE, 0, aln[&x - base]); }
   void range(uint32_t kind, size_t from, size_t n) {                     // a range of the read, cut to it
     const size_t L = (size_t)std::max(read_len, 0);
     from = std::min(from, L); n = std::min(n, L - from);
@@ -1493,7 +1494,7 @@ struct lra_piece_sink {
   void qual(const lra_aln_record& r) { range(LRA_PIECE_QUAL, 0, (size_t)r.read_len); }   // (an unaligned read's string goes out as it is, a leading '*' too)
   void qual_sub(const lra_aln_record&, size_t pos, size_t n) { range(LRA_PIECE_QUAL, pos, n); }
 };
-// lra_output_read_str (rank.hip; OUTPUT, Mapping_ultility.h:453-493) for the two formats the device stage writes
+// lra_output_read_str (rank.hip; OUTPUT, Mapping_ultility.h:453-493) for the three formats the device stage writes
 int piece_output_read(const lra_aln_group* groups, const int32_t* index, int n_groups, lra_aln_record* recs, int print_num_aln, char format, int hard_clip,
                       const char* passthrough, const lra_aln_record* unaligned_rec, lra_piece_sink& k) {
   if (n_groups > 0 && groups[index[0]].count > 0) {
@@ -1503,7 +1504,7 @@ int piece_output_read(const lra_aln_group* groups, const int32_t* index, int n_g
       lra_aln_record* S = recs + G.first;
       for (int s = G.count - 1; s >= 0; s--) {
         S[s].order = G.count - 1 - s;
-        const int rc = format == 's' ? lra_fmt_sam(S, G.count, s, hard_clip, passthrough, k) : lra_fmt_paf(&S[s], 1, k);
+        const int rc = format == 's' ? lra_fmt_sam(S, G.count, s, hard_clip, passthrough, k) : format == 'a' ? lra_fmt_pairwise(S[s], k) : lra_fmt_paf(&S[s], 1, k);
         if (rc) return rc;
       }
     }
@@ -1517,14 +1518,14 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
                         const int32_t* read_len, const char* const* chrom_names, const char* passthrough, const char* const* tags, int n_threads,
                         const char** text, uint64_t* len, const uint64_t** rec_off, lra_piece_table* PT = nullptr, bool pieceMd = false) {
   if (!h || !o || !names || (!reads && !PT) || !read_len || !chrom_names || !len) return LRA_ERR_INVALID;
-  if (PT && o->printFormat != 's' && o->printFormat != 'P') return LRA_ERR_INVALID;
+  if (PT && o->printFormat != 's' && o->printFormat != 'P' && o->printFormat != 'a') return LRA_ERR_INVALID;
   const size_t nA = h->nA, nJ = h->nJ;
   (void)nA;
   const int na = h->num_aln;
   const std::vector<uint64_t>& jo = h->jo; const std::vector<uint64_t>& roff = h->roff; const std::vector<uint64_t>& boff = h->boff;
   const std::vector<int32_t>&strand = h->strand, &supp = h->supp, &sec = h->sec, &n0 = h->n0, &n1 = h->n1, &chrom = h->chrom, &counts = h->counts, &blocks = h->blocks;
   const std::vector<float>& fval = h->fval; const lra_pod_buf<uint32_t>& runs = h->runs; const std::vector<uint32_t>&rstat = h->rstat, &ends = h->ends; const std::vector<uint8_t>& reached = h->reached;
-  const bool pairwise = o->printFormat == 'a';
+  const bool pairwise = o->printFormat == 'a' && !PT;                     // (piece mode: the rows are the device's, from the blocks where they are)
   const bool withMd = (PT ? pieceMd : h->has_md) && o->printFormat == 's';   // (only PrintSAM prints MD; SimplePrintSAM, PrintPAF, PrintBed do not)
   if (withMd && !PT && h->md_off.size() != nA + 1) return LRA_ERR_INVALID;
   if (!PT && nA && roff.size() == nA + 1 && runs.size() < roff[nA]) return LRA_ERR_INVALID;   // a snapshot packed with LRA_PACK_NORUNS has no CIGAR to print
@@ -1851,7 +1852,7 @@ extern "C" int lra_map_records_tags(lra_ctx* ctx, const lra_map_result* res, con
 }
 
 // ---- the record text built on the device (records.hip) ---------------------------------------------------------------------------------------------
-// The host half: a snapshot without the runs, the piece table on host threads; the device half: the CIGAR text, MD, the assembly.  See lra_hip.h.
+// The host half: a snapshot without the runs, the piece table on host threads; the device half: the CIGAR text, MD, the pairwise rows, the assembly.  See lra_hip.h.
 extern "C" int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
                                       const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough,
                                       const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const char** text, uint64_t* len,
@@ -1863,12 +1864,13 @@ extern "C" int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, c
   lra_records_device_stats& S = m->dev_stats;
   auto wall = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const int nR = res->n_reads;
-  const bool device = o->printFormat == 's' || o->printFormat == 'P';
+  const bool pairwise = o->printFormat == 'a';
+  const bool device = o->printFormat == 's' || o->printFormat == 'P' || pairwise;
   lra_map_host* h = nullptr;
   int rc;
-  if (!device) {                                                         // 'p', 'b', 'a': no long field worth moving -- the host path, its text kept by the context
+  if (!device) {                                                         // 'p', 'b': no long field worth moving -- the host path, its text kept by the context
     if (!reads) return LRA_ERR_INVALID;
-    if ((rc = lra_map_snapshot(ctx, res, (o->printFormat == 'a' ? LRA_PACK_BLOCKS : 0) | (flags & LRA_PACK_MD), &h))) return rc;
+    if ((rc = lra_map_snapshot(ctx, res, flags & LRA_PACK_MD, &h))) return rc;
     const char* t = nullptr; const uint64_t* ro = nullptr;
     rc = records_host(h, o, names, reads, quals, read_len, chrom_names, nullptr, passthrough, n_threads, &t, len, &ro);
     if (!rc) {
@@ -1886,22 +1888,26 @@ extern "C" int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, c
   S.bytes_d2h += PackLayout(nR, h->nJ, nA, 0, 0, h->chrom_pos.size() - 1).total;
   double t1 = wall();
   S.ms_snapshot = t1 - t0;
-  // the long fields the alignments own: the CIGAR text, and with LRA_PACK_MD the MD:Z values (as lra_map_pack makes them)
+  // the long fields the alignments own: the CIGAR text, and with LRA_PACK_MD the MD:Z values (as lra_map_pack makes them); format 'a': the pairwise rows
   const bool withMd = (flags & LRA_PACK_MD) && o->printFormat == 's';
   lra_cigar_text_result cg; memset(&cg, 0, sizeof cg);
   lra_md_result md; memset(&md, 0, sizeof md);
+  lra_pairwise_text_result pw; memset(&pw, 0, sizeof pw);
   hipStream_t st = ctx->stream;
   if (nA) {
     if (!res->d_run_off || !res->d_strands) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device: the result has no runs / reads to work on");
-    if ((rc = lra_cigar_text_batch(ctx, (int)nA, res->d_runs, res->d_run_off, nullptr, nullptr, nullptr, &cg))) return rc;
-    if (withMd) {
-      if (!ctx->seed || !ctx->seed->genome || !m->d_chrom_pos) return lra_set_err(ctx, LRA_ERR_INVALID, "LRA_PACK_MD: genome not loaded");
+    if (!pairwise && (rc = lra_cigar_text_batch(ctx, (int)nA, res->d_runs, res->d_run_off, nullptr, nullptr, nullptr, &cg))) return rc;
+    if (withMd || pairwise) {
+      if (!res->d_aln_read || !res->d_strand || !res->d_chrom || !res->d_blocks || !res->d_block_off)
+        return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device: the result has no blocks to work on");
+      if (!ctx->seed || !ctx->seed->genome || !m->d_chrom_pos) return lra_set_err(ctx, LRA_ERR_INVALID, "LRA_PACK_MD / print format 'a': genome not loaded");
       uint64_t* adr = (uint64_t*)lra_ensure(ctx, 187, 2 * (nA + 1) * 8);
       if (!adr) return LRA_ERR_NOMEM;
       const uint64_t* ro = (const uint64_t*)(res->d_strands + lra_strands_ro_at(res->rc_base));
       hipLaunchKernelGGL(k_md_address, dim3((unsigned)((nA + 255) / 256)), dim3(256), 0, st, nA, res->d_aln_read, res->d_strand, res->d_chrom, ro, res->rc_base,
                          (const uint64_t*)m->d_chrom_pos, adr, adr + nA + 1);
-      if ((rc = lra_md_strings_batch(ctx, (int)nA, res->d_blocks, res->d_block_off, res->d_strands, adr, nullptr, (const char*)ctx->seed->genome, adr + nA + 1, &md))) return rc;
+      if (withMd && (rc = lra_md_strings_batch(ctx, (int)nA, res->d_blocks, res->d_block_off, res->d_strands, adr, nullptr, (const char*)ctx->seed->genome, adr + nA + 1, &md))) return rc;
+      if (pairwise && (rc = lra_pairwise_text_batch(ctx, (int)nA, res->d_blocks, res->d_block_off, res->d_strands, adr, nullptr, (const char*)ctx->seed->genome, adr + nA + 1, &pw))) return rc;
     }
   }
   double t2 = wall();
@@ -1939,6 +1945,7 @@ extern "C" int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, c
   J.d_strands = res->d_strands; J.rc_base = res->rc_base;
   J.d_read_off = res->d_strands ? (const uint64_t*)(res->d_strands + lra_strands_ro_at(res->rc_base)) : nullptr;
   J.d_qual = dq; J.d_qual_off = dqo; J.d_cg = cg.d_text; J.d_cg_off = cg.d_off; J.d_md = withMd ? md.d_md : nullptr; J.d_md_off = withMd ? md.d_md_off : nullptr;
+  J.d_pw = pw.d_text; J.d_pw_off = pw.d_off;
   if (!J.d_strands && nR) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device: the result has no reads to work on");
   m->dev_off.assign((size_t)nR + 1, 0);
   m->dev_text.clear();

@@ -3,8 +3,8 @@
 #include "common.h"
 
 // A record is a run of pieces.  src: LIT the offset in the literal blob; SEQ_FW / SEQ_RC and QUAL (read << 32) | the first byte inside the read;
-// CIGAR and MD the alignment.  len: the bytes (CIGAR and MD: filled in on the device).
-enum { LRA_PIECE_LIT = 0, LRA_PIECE_SEQ_FW = 1, LRA_PIECE_SEQ_RC = 2, LRA_PIECE_QUAL = 3, LRA_PIECE_CIGAR = 4, LRA_PIECE_MD = 5 };
+// CIGAR, MD and PAIRWISE (the rows of print format 'a', pairwise.hip) the alignment.  len: the bytes (CIGAR, MD and PAIRWISE: filled in on the device).
+enum { LRA_PIECE_LIT = 0, LRA_PIECE_SEQ_FW = 1, LRA_PIECE_SEQ_RC = 2, LRA_PIECE_QUAL = 3, LRA_PIECE_CIGAR = 4, LRA_PIECE_MD = 5, LRA_PIECE_PAIRWISE = 6 };
 struct lra_rec_piece { uint32_t kind, len; uint64_t src; };
 static_assert(sizeof(lra_rec_piece) == 16, "the piece table is uploaded as it is");
 
@@ -17,5 +17,6 @@ struct lra_rec_job {
   const char* d_qual = nullptr; const uint64_t* d_qual_off = nullptr;   // [n_reads + 1]; a read without qualities has an empty range
   const char* d_cg = nullptr; const uint64_t* d_cg_off = nullptr;
   const char* d_md = nullptr; const uint64_t* d_md_off = nullptr;
+  const char* d_pw = nullptr; const uint64_t* d_pw_off = nullptr;
 };
 int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& job, const char** text, uint64_t* len, uint64_t* h_rec_off, lra_records_device_stats* stats);

@@ -1,4 +1,4 @@
-// lra_amd/csrc/records.hip -- the record text of a batch (print formats 's' and 'P') built on the device (gfx950): the CIGAR strings from the runs, and
+// lra_amd/csrc/records.hip -- the record text of a batch (print formats 's', 'P' and 'a') built on the device (gfx950): the CIGAR strings from the runs, and
 // the records from a PIECE TABLE the host writes (mapread.hip: lra_map_records_device).
 //
 // CIGAR text (lra_cigar_text_batch).  Flat over the batch's runs, so an alignment of 10^5 runs is 10^5 lanes like everything else: cg_count writes the
@@ -8,7 +8,7 @@
 // C is 0 and no lane looks for its alignment.
 //
 // Records (lra_records_assemble).  A piece is 16 bytes: a literal (a range of the host's literal blob), a range of a read on one strand, a range of a
-// read's qualities, the CIGAR text or the MD:Z value of an alignment.  rc_resolve gives every piece its length and source address, a scan its place, and
+// read's qualities, the CIGAR text, the MD:Z value or the pairwise rows (pairwise.hip) of an alignment.  rc_resolve gives every piece its length and source address, a scan its place, and
 // rc_copy cuts the OUTPUT into chunks of RC_CHUNK bytes, one wave each, as sv_copy does: the wave finds the first piece under its chunk and copies the
 // pieces' parts that lie in it, so a 1 Mb contig's SEQ is 256 waves and a chunk of 200-byte records is one wave.  The destination is written in aligned
 // dwords (a lane's dword is put together from the two aligned source dwords around it), bytes at a part's ragged ends.  rc_rec_off reads every read's
@@ -85,6 +85,7 @@ struct RcArgs {
   const unsigned char* qual; const uint64_t* qual_off;         // NULL: no read has qualities
   const unsigned char* cg; const uint64_t* cg_off;
   const unsigned char* md; const uint64_t* md_off;             // NULL: no MD pieces
+  const unsigned char* pw; const uint64_t* pw_off;             // NULL: no PAIRWISE pieces
   uint32_t* len; const unsigned char** src;                    // per piece
   const uint64_t* at;                                          // the lengths' exclusive prefix [n_pieces + 1]
   unsigned char* out; uint64_t n_out; uint64_t* rec_off;
@@ -118,6 +119,9 @@ __global__ void __launch_bounds__(256) rc_resolve(RcArgs A) {
       break;
     case LRA_PIECE_MD:
       if (A.md && p.src < A.n_aln) { n = A.md_off[p.src + 1] - A.md_off[p.src]; s = A.md + A.md_off[p.src]; }
+      break;
+    case LRA_PIECE_PAIRWISE:
+      if (A.pw && p.src < A.n_aln) { n = A.pw_off[p.src + 1] - A.pw_off[p.src]; s = A.pw + A.pw_off[p.src]; }
       break;
     default: break;
   }
@@ -250,6 +254,7 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
   A.strands = (const unsigned char*)J.d_strands; A.read_off = J.d_read_off; A.rc_base = J.rc_base;
   A.qual = (const unsigned char*)J.d_qual; A.qual_off = J.d_qual_off;
   A.cg = (const unsigned char*)J.d_cg; A.cg_off = J.d_cg_off; A.md = (const unsigned char*)J.d_md; A.md_off = J.d_md_off;
+  A.pw = (const unsigned char*)J.d_pw; A.pw_off = J.d_pw_off;
   A.len = (uint32_t*)w; w += sz(nP, 4);
   A.src = (const unsigned char**)w; w += sz(nP, 8);
   uint64_t* at = (uint64_t*)w; w += sz(nP + 1, 8);

@@ -445,7 +445,7 @@ class LowAccMapper:
         return out
 
     def records_device(self, res: MapResult, args, passthrough=None, d_qual=None, d_qual_off=None, md=None, n_threads=0, as_list=True):
-        """lra_map_records_device: the batch's record text built on the device (formats 's' and 'P'; the others fall through to the host path) -- the bytes
+        """lra_map_records_device: the batch's record text built on the device (formats 's', 'P' and 'a'; the others fall through to the host path) -- the bytes
         records_host gives for a snapshot of the same result.  args: record_args(names, reads, quals); passthrough: None or one text per read (None entries:
         none); d_qual / d_qual_off: the batch's qualities as device tensors (None: uploaded from args' quals); md (None: opts.printMD): MD:Z in SAM records.
         Call it where snapshot() would be called: the result's arrays must be alive.  -> list of per-read bytes, or the total bytes when as_list is False."""

@@ -108,6 +108,49 @@ def cigar_text_batch(ctx: Context, runs, run_off, pre_clip=None, suf_clip=None, 
     return [text[int(off[i]):int(off[i + 1])] for i in range(n)]
 
 
+class AlnStringsResult(C.Structure):
+    """lra_aln_strings_result (include/lra_hip.h)"""
+    _fields_ = [("n_aln", C.c_int32), ("n_cols", C.c_uint64), ("d_col_off", C.c_void_p), ("d_ref_len", C.c_void_p), ("d_q", C.c_void_p), ("d_a", C.c_void_p),
+                ("d_t", C.c_void_p)]
+
+
+class PairwiseTextResult(C.Structure):
+    """lra_pairwise_text_result (include/lra_hip.h)"""
+    _fields_ = [("n_aln", C.c_int32), ("n_bytes", C.c_uint64), ("d_off", C.c_void_p), ("d_text", C.c_void_p)]
+
+
+PAIRWISE_WIDTH = 50                 # columns per printed row (PrintPairwise)
+PAIRWISE_GROUP_ROWS = 16            # pairwise.hip's PW_GROUP_ROWS: the rows one wave of the emit kernel stages in its LDS tile (the tests place alignments around it)
+
+
+def alignment_strings_batch(ctx: Context, b: RefineBatch):
+    """lra_alignment_strings_batch: CreateAlignmentStrings of every alignment of a RefineBatch-shaped input, on the device ->
+    ([(query string, alignment string, text string) per alignment], ref_len uint32[n])."""
+    res = AlnStringsResult()
+    ctx.check(ctx.lib.lra_alignment_strings_batch(ctx.h, b.n, ptr(b.blocks), ptr(b.block_off), ptr(b.q_seq), ptr(b.q_off), ptr(b.q_len), ptr(b.t_seq), ptr(b.t_off),
+                                                  C.byref(res)))
+    n, nc = int(res.n_aln), int(res.n_cols)
+    if not n:
+        return [], np.zeros(0, np.uint32)
+    off = ctx.to_host(res.d_col_off, n + 1, np.uint64)
+    q, a, t = (ctx.to_host(p, nc, np.uint8).tobytes() if nc else b"" for p in (res.d_q, res.d_a, res.d_t))
+    return [(q[int(off[i]):int(off[i + 1])], a[int(off[i]):int(off[i + 1])], t[int(off[i]):int(off[i + 1])]) for i in range(n)], ctx.to_host(res.d_ref_len, n, np.uint32)
+
+
+def pairwise_text_batch(ctx: Context, b: RefineBatch, raw=False):
+    """lra_pairwise_text_batch: the rows Alignment::PrintPairwise prints for every alignment of a RefineBatch-shaped input (everything behind the name and
+    Interval lines), built on the device from the blocks -> one bytes object per alignment; raw=True: the PairwiseTextResult."""
+    res = PairwiseTextResult()
+    ctx.check(ctx.lib.lra_pairwise_text_batch(ctx.h, b.n, ptr(b.blocks), ptr(b.block_off), ptr(b.q_seq), ptr(b.q_off), ptr(b.q_len), ptr(b.t_seq), ptr(b.t_off),
+                                              C.byref(res)))
+    if raw:
+        return res
+    n = int(res.n_aln)
+    off = ctx.to_host(res.d_off, n + 1, np.uint64) if n else np.zeros(1, np.uint64)
+    text = ctx.to_host(res.d_text, int(res.n_bytes), np.uint8).tobytes() if int(res.n_bytes) else b""
+    return [text[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+
 def md_of_refined(ctx: Context, b: RefineBatch, rres: RefineResult):
     """lra_md_strings_batch straight on the (context-owned) output of indel_refine_batch (the blocks CalculateStatistics saw)."""
     v = RefineBatch.__new__(RefineBatch)

@@ -66,7 +66,7 @@ def main():
     ap.add_argument("-Flag", dest="flag", type=int, default=0, help="SAM / BAM input: skip records whose flag meets this mask")
     ap.add_argument("--passthrough", action="store_true", help="SAM / BAM input: append each read's aux fields to its SAM records")
     ap.add_argument("--device-records", action="store_true",
-                    help="build the record text on the device (lra_map_records_device; formats s and pc, the others fall through to the host path)")
+                    help="build the record text on the device (lra_map_records_device; formats s, pc and a, the others fall through to the host path)")
     args = ap.parse_args()
     P = args.preset
     t0 = time.perf_counter()
