@@ -89,7 +89,7 @@ int lra_ctx_set_svsig_len(lra_ctx* ctx, int len);
 int lra_ctx_svsig_len(lra_ctx* ctx);
 /* ABI version of the loaded library (tests check it against this header). */
 int lra_abi_version(void);
-#define LRA_ABI_VERSION 9   /* 9: lra_ctx_release_buffers; later, additively (no struct or signature changed): lra_ctx_set_store_all, lra_ctx_store_all; SV signatures: lra_sv_signatures_batch, lra_ctx_set_svsig_len, lra_ctx_svsig_len, lra_map_svsig_host, lra_map_svsig; SAM / BAM input: lra_reads_set_flag_remove, lra_reads_set_passthrough, lra_reads_batch_tags, lra_map_records_tags, lra_map_records_host_tags, lra_bgzf_inflate_batch, lra_bgzf_inflate_host; the genome reader: lra_genome_open, _read_host, _read_device, _info, _names, _host_seq, _device_seq, _install, _last_error, _set_device_chunk, _close; 8: lra_map_opts_apply_local_index, lra_ctx_local_index_params, lra_ctx_load_local_index (the .gli file's k / w / window override the options', as glIndex.Read does); 7: lra_sort_pairs_batch;  2: lra_map_opts.defer_matches, lra_map_counters.n_deferred_reads; 3: lra_map_opts.flagged_unaligned, lra_map_counters.n_flagged_reads, lra_map_host_flagged; 4: lra_reads_last_error, a corrupt FASTQ record is LRA_ERR_INVALID; lra_map_opts.defer_seed_matches; 5: lra_seed_prefetch, lra_ctx_adopt_seed, lra_map_reads_lowacc_front / _back, lra_map_back_release; 6: a failed front half hands over an error batch (one back call per front call), separate n_handed_back_reads counter, lra_map_host_trim */
+#define LRA_ABI_VERSION 9   /* 9: lra_ctx_release_buffers; later, additively (no struct or signature changed): lra_aog_class_of_batch; lra_ctx_set_store_all, lra_ctx_store_all; SV signatures: lra_sv_signatures_batch, lra_ctx_set_svsig_len, lra_ctx_svsig_len, lra_map_svsig_host, lra_map_svsig; SAM / BAM input: lra_reads_set_flag_remove, lra_reads_set_passthrough, lra_reads_batch_tags, lra_map_records_tags, lra_map_records_host_tags, lra_bgzf_inflate_batch, lra_bgzf_inflate_host; the genome reader: lra_genome_open, _read_host, _read_device, _info, _names, _host_seq, _device_seq, _install, _last_error, _set_device_chunk, _close; 8: lra_map_opts_apply_local_index, lra_ctx_local_index_params, lra_ctx_load_local_index (the .gli file's k / w / window override the options', as glIndex.Read does); 7: lra_sort_pairs_batch;  2: lra_map_opts.defer_matches, lra_map_counters.n_deferred_reads; 3: lra_map_opts.flagged_unaligned, lra_map_counters.n_flagged_reads, lra_map_host_flagged; 4: lra_reads_last_error, a corrupt FASTQ record is LRA_ERR_INVALID; lra_map_opts.defer_seed_matches; 5: lra_seed_prefetch, lra_ctx_adopt_seed, lra_map_reads_lowacc_front / _back, lra_map_back_release; 6: a failed front half hands over an error batch (one back call per front call), separate n_handed_back_reads counter, lra_map_host_trim */
 
 /* Convenience for hosts without their own HIP binding: synchronous device->host copy on the
  * context's stream (a C++ host would call hipMemcpy itself).                                */
@@ -641,6 +641,20 @@ int lra_affine_one_gap_align_batch(lra_ctx* ctx, int n, const char* d_qseq, cons
                                    const int32_t* d_k, int m, int mm, int indel,
                                    int32_t* d_score, int32_t* d_nblocks, int32_t* d_blocks,
                                    const uint64_t* d_block_off, int32_t* d_status);
+/* Which of its kernels lra_affine_one_gap_align_batch gives a problem -- the classification arithmetic the device code itself calls, run on the
+ * host: no context, no GPU, host arrays in and out.  For n problems of lengths q_len[p] x t_len[p] and band k[p] under the scoring (m, mm, indel):
+ * cls_out[p] = the size class (0-9: the anti-diagonal sweep over score matrices in LDS, 2 and 6 the same in an HBM work slot of 4 / 8 MiB; 10-12: scores
+ * in registers; 14-18: one lane per problem), or -1 where the batch call answers LRA_ST_RANGE; path_out[p] = the form of that class's kernel, bits
+ * below (0 where cls_out[p] is -1).  Diagnostic: what the tests use to aim inputs at every form and at both sides of every size limit.          */
+#define LRA_AOG_PATH_SUFFIX 1          /* the length difference exceeds the band: second (suffix) band and the long gap ("alignTop")    */
+#define LRA_AOG_PATH_SCORES_MASK 6     /* where the prefix band's scores live during the sweep:                                         */
+#define LRA_AOG_PATH_SCORES_LDS 0      /*   the flat matrices (classes 0-9 but 2, 6) or the lane kernel's previous row, in LDS          */
+#define LRA_AOG_PATH_SCORES_REGS 2     /*   registers, two diagonals per lane (classes 10-12; 2 / 6 with k + 2 <= 64)                   */
+#define LRA_AOG_PATH_SCORES_ROLLING 4  /*   three rotating anti-diagonal windows in LDS (classes 2 / 6)                                 */
+#define LRA_AOG_PATH_SCORES_HBM 6      /*   the flat matrices in the HBM work slot (classes 2 / 6)                                      */
+#define LRA_AOG_PATH_CODES_LDS 8       /* the sequence codes the sweep reads are in LDS (else: in the HBM work slot)                    */
+int lra_aog_class_of_batch(int n, const int32_t* q_len, const int32_t* t_len, const int32_t* k, int m, int mm, int indel,
+                           int32_t* cls_out, int32_t* path_out);
 
 /* ---- a13 (DP leaf): the alignment between two consecutive chain anchors -------------------------------------
  * Replaces   RefineByLinearAlignment(btc_curReadEnd, btc_curGenomeEnd, btc_nextReadStart, btc_nextGenomeStart, str, chromIndex,

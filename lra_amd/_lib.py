@@ -168,6 +168,7 @@ SYMBOLS = {
                                           C.c_int, C.c_int, C.c_int, _vp]),
     "lra_affine_one_gap_align_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int,
                                                   C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "lra_aog_class_of_batch": (C.c_int, [C.c_int, _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p]),
 }
 
 

@@ -93,3 +93,27 @@ def affine_one_gap_align_batch(ctx, q_list, t_list, k_list, m, mm, indel):
     b = AogBatch(ctx, q_list, t_list, k_list, m, mm, indel)
     b.run()
     return b.results()
+
+
+# lra_aog_class_of_batch's path code (include/lra_hip.h, LRA_AOG_PATH_*)
+PATH_SUFFIX, PATH_SCORES_MASK, PATH_CODES_LDS = 1, 6, 8
+PATH_SCORES_LDS, PATH_SCORES_REGS, PATH_SCORES_ROLLING, PATH_SCORES_HBM = 0, 2, 4, 6
+
+
+def aog_class_of_batch(q_len, t_len, k, m=4, mm=-3, indel=-4):
+    """Which kernel form affine_one_gap_align_batch gives each (q_len, t_len, k) problem: (class int32[n], path int32[n]);
+    class -1 = LRA_ST_RANGE.  The library's own classification arithmetic, run on the host (no context, no GPU)."""
+    import ctypes as C
+    from ._lib import load_library
+    q = np.ascontiguousarray(q_len, dtype=np.int32)
+    t = np.ascontiguousarray(t_len, dtype=np.int32)
+    kk = np.ascontiguousarray(k, dtype=np.int32)
+    assert q.shape == t.shape == kk.shape and q.ndim == 1
+    cls = np.empty(q.size, dtype=np.int32)
+    path = np.empty(q.size, dtype=np.int32)
+    i32p = C.POINTER(C.c_int32)
+    rc = load_library().lra_aog_class_of_batch(int(q.size), q.ctypes.data_as(i32p), t.ctypes.data_as(i32p), kk.ctypes.data_as(i32p), int(m), int(mm), int(indel),
+                                                cls.ctypes.data_as(i32p), path.ctypes.data_as(i32p))
+    if rc != 0:
+        raise ValueError("lra_aog_class_of_batch: %d" % rc)
+    return cls, path

@@ -44,6 +44,12 @@ constexpr int LN_ARROW_WORDS = LN_MAX * LN_ROWW, LN_PREV_WORDS = LN_MAX + 2, LN_
 constexpr int LN_BYTES = 64 * (4 * LN_ARROW_WORDS + 4 * LN_PREV_WORDS + 2 * LN_CODE_BYTES);
 constexpr int NCLS = 19;
 constexpr int CLASS_S_BYTES = 2560;       // per 16-lane group: 4 problems per wave, 16 per workgroup (anti-diagonals <= 16 cells)
+constexpr long HBM_SLOT_BYTES = 4L << 20;   // class 2: one HBM work slot
+constexpr long HBM_SLOT_B_BYTES = 8L << 20; // class 6: the few larger ones; a problem that needs more is LRA_ST_RANGE
+constexpr int ROLL_WINDOW = 256;          // classes 2 / 6: cells of one rotating anti-diagonal window in LDS (three of them)
+constexpr int ROLL_CODE_BYTES = 4096;     // classes 2 / 6: LDS behind the windows for the two sequences' codes
+constexpr int REG_S_BYTES = 2048, REG_M_BYTES = 8192, REG_L_BYTES = 32768;   // classes 10 (16 lanes), 11 (32 lanes), 12 (64 lanes)
+constexpr int REG_L_USED = 16384;   // largest arrows + codes footprint of class 12 (above: the HBM class, whose sweep is in registers too)
 
 __device__ __forceinline__ int code_n(unsigned char c) {  // SeqUtils.h:42-75 (seqMapN)
   if (c < 8) return c & 3;
@@ -63,7 +69,8 @@ struct Geo {
   int nUsed;  // prefix-matrix slots that can ever be read back: rows j < tB when only the prefix band is used
 };
 
-__device__ __forceinline__ bool make_geo(int qLen, int tLen, int k0, Geo& g) {
+// ---- the classification arithmetic: one copy, called by the kernels and by the host (lra_aog_class_of_batch) ----
+__host__ __device__ __forceinline__ bool make_geo(int qLen, int tLen, int k0, Geo& g) {
   g.qLen = qLen; g.tLen = tLen;
   g.diag = max(1, min(qLen, tLen));                 // :162
   int k = min(g.diag, k0);                          // :194
@@ -83,9 +90,60 @@ __device__ __forceinline__ bool make_geo(int qLen, int tLen, int k0, Geo& g) {
 __host__ __device__ __forceinline__ long align4(long x) { return (x + 3) & ~3L; }
 
 // bytes of working memory one problem needs (same carve order as carve())
-__device__ __forceinline__ long need_bytes(const Geo& g) {
+__host__ __device__ __forceinline__ long need_bytes(const Geo& g) {
   long suf = g.top ? (4L * g.n + align4(g.n)) : 0;
   return 4L * g.nUsed + align4(g.nUsed) + suf + 16L * (g.diag + 1) + align4(g.qLen + 1) + align4(g.tLen + 1);
+}
+
+// ... and of solve_reg (arrows + codes only)
+__host__ __device__ __forceinline__ long need_bytes_reg(const Geo& g) { return align4(g.nUsed) + align4(g.qLen + 1) + align4(g.tLen + 1); }
+
+// a problem the kernels take at all: lengths and band sane, the matrices below 2^28 slots, every score's offset from MISS below 2^28.  P: where the problem's
+// qLen / tLen / k0 live, S: where the scoring lives (m, mm, indel) -- the kernels' Problem and BatchArgs, the host's Shape and Scoring
+struct Shape { int qLen, tLen, k0; };
+struct Scoring { int m, mm, indel; };
+template <typename P, typename S>
+__host__ __device__ __forceinline__ bool problem_ok(const P& pr, const S& a, Geo& g) {
+  bool ok = pr.qLen >= 0 && pr.tLen >= 0 && pr.k0 >= 1 && make_geo(pr.qLen, pr.tLen, pr.k0, g);
+  long mx = max(abs(a.m), max(abs(a.mm), abs(a.indel)));
+  return ok && ((long)(pr.qLen + pr.tLen + 16) * (mx + 1) < (1L << 28));
+}
+
+// The class of a problem solve() / solve_reg() / the lane kernel take (see the launches below); -1: LRA_ST_RANGE, larger than the class 6 slot.
+__host__ __device__ __forceinline__ int class_of(const Geo& g) {
+  const long need = need_bytes(g);
+  int cls = need <= CLASS_A_BYTES ? 0 : need <= CLASS_M1_BYTES ? 4 : need <= CLASS_M2_BYTES ? 5 : need <= CLASS_B_BYTES ? 1 : 2;
+  if (g.k + 1 <= 32) cls = cls == 0 ? 7 : cls == 4 ? 8 : cls == 5 ? 9 : cls;                              // anti-diagonals of at most 32 cells: two problems per wave
+  if (need <= CLASS_S_BYTES && g.k + 1 <= 16) cls = 3;
+  if (cls == 2 && need > HBM_SLOT_BYTES) cls = 6;
+  if (cls == 6 && need > HBM_SLOT_B_BYTES) return -1;
+  if (!g.top) {                                                     // prefix band only: scores in registers (solve_reg), arrows + codes in LDS
+    const long nr = need_bytes_reg(g);
+    if (g.qLen <= LN_MAX && g.tLen <= LN_MAX) { const int mx = max(g.qLen, g.tLen); cls = mx <= 3 ? 14 : mx <= 6 ? 15 : mx <= 10 ? 16 : mx <= 16 ? 17 : 18; }
+    else if (g.k + 2 <= 16 && nr <= REG_S_BYTES) cls = 10;
+    else if (g.k + 2 <= 32 && nr <= REG_M_BYTES) cls = 11;
+    else if (g.k + 2 <= 64 && nr <= REG_L_USED) cls = 12;
+  }
+  return cls;
+}
+
+// How solve() runs a problem that lives in an HBM work slot (classes 2 / 6; G lanes per problem)
+__host__ __device__ __forceinline__ bool hbm_codes_in_lds(const Geo& g) { return g.qLen + g.tLen + 2 <= ROLL_CODE_BYTES; }
+__host__ __device__ __forceinline__ bool hbm_in_regs(const Geo& g, int G) { return g.k + 2 <= G; }   // the band's diagonals fit the lanes two apiece: scores in registers (reg_fill)
+__host__ __device__ __forceinline__ bool hbm_rolling(const Geo& g, int G) { return !g.top && (hbm_in_regs(g, G) || (2 * g.k + 3 <= ROLL_WINDOW && hbm_codes_in_lds(g))); }
+
+// The path code of lra_aog_class_of_batch (LRA_AOG_PATH_*): which form of the class's kernel the problem takes
+__host__ __device__ __forceinline__ int path_of(const Geo& g, int cls) {
+  int path = g.top ? LRA_AOG_PATH_SUFFIX : 0;
+  if (cls == 2 || cls == 6) {
+    const bool rolling = hbm_rolling(g, 64);
+    path |= !rolling ? LRA_AOG_PATH_SCORES_HBM : hbm_in_regs(g, 64) ? LRA_AOG_PATH_SCORES_REGS : LRA_AOG_PATH_SCORES_ROLLING;
+    if (rolling && hbm_codes_in_lds(g)) path |= LRA_AOG_PATH_CODES_LDS;     // (not rolling: the codes stay in the work slot)
+  } else {
+    path |= (cls >= 10 && cls <= 12) ? LRA_AOG_PATH_SCORES_REGS : LRA_AOG_PATH_SCORES_LDS;
+    path |= LRA_AOG_PATH_CODES_LDS;
+  }
+  return path;
 }
 
 struct Work {
@@ -225,10 +283,10 @@ __device__ __forceinline__ void solve(int wlane, const Problem& pr, const Geo& g
   // two predecessors' anti-diagonals only, and without the suffix band nothing reads a score again but the corner's); HBM keeps the arrows.  The matrices of
   // such a problem are ~1 MB and every cell was written twice (fill + sweep): 5 B per cell -> 1 B.
   // (with the band's diagonals two to a lane the sweep keeps the scores in registers -- reg_fill -- and the codes may stay in the HBM work area when they outgrow LDS)
-  const bool codesInLds = qLen + tLen + 2 <= 4096;
-  const bool rolling = roll != nullptr && !g.top && (k + 2 <= G || (2 * k + 3 <= 256 && codesInLds));
-  // ... and the sequence codes sit behind the windows (roll[768 ..], one byte each), so that a sweep step touches HBM only to store its arrows
-  unsigned char* lq = (unsigned char*)(roll + 768); unsigned char* lt = lq + (qLen + 1);
+  const bool codesInLds = hbm_codes_in_lds(g);
+  const bool rolling = roll != nullptr && hbm_rolling(g, G);
+  // ... and the sequence codes sit behind the windows (roll[3 * ROLL_WINDOW ..], one byte each), so that a sweep step touches HBM only to store its arrows
+  unsigned char* lq = (unsigned char*)(roll + 3 * ROLL_WINDOW); unsigned char* lt = lq + (qLen + 1);
   if (rolling && codesInLds) {
     for (int x = lane; x <= qLen; x += G) lq[x] = x ? code_n((unsigned char)pr.q[x - 1]) : 0;
     for (int x = lane; x <= tLen; x += G) lt[x] = x ? code_n((unsigned char)pr.t[x - 1]) : 0;
@@ -276,10 +334,10 @@ __device__ __forceinline__ void solve(int wlane, const Problem& pr, const Geo& g
     };
     const int Wd = 2 * k + 3;
     const int sLast = (qB - 1) + (tB - 1);
-    const bool inRegs = k + 2 <= G;                                      // the band's diagonals fit the lanes two apiece: scores in registers (reg_fill)
+    const bool inRegs = hbm_in_regs(g, G);
     if (inRegs) rollResult = codesInLds ? reg_fill<G>(lane, gbase, g, m, mm, indel, w.pPre, lq, lt) : reg_fill<G>(lane, gbase, g, m, mm, indel, w.pPre, w.qc, w.tc);
     for (int s = 0; !inRegs && s <= max(sLast, 0); s++) {
-      int* cur = roll + (s % 3) * 256; const int* p1 = roll + ((s + 2) % 3) * 256; const int* p2 = roll + ((s + 1) % 3) * 256;
+      int* cur = roll + (s % 3) * ROLL_WINDOW; const int* p1 = roll + ((s + 2) % 3) * ROLL_WINDOW; const int* p2 = roll + ((s + 1) % 3) * ROLL_WINDOW;
       int jlo = max(1, max(s - qB + 1, (s - k + 1) >> 1));
       if (s - k < 0) jlo = max(1, s - qB + 1);
       const int jhi = min(tB - 1, min(s - 1, (s + k) >> 1));
@@ -450,7 +508,7 @@ __device__ __forceinline__ void solve(int wlane, const Problem& pr, const Geo& g
   // ---- prefix trace back (:589-629), lane 0 -- or, with the arrows in HBM only (rolling), all lanes in step on the same state over a window of rows staged in
   // LDS: the walk is a chain of dependent one-byte loads a row apart (a cache line each); a window serves at least as many steps as it has rows
   if (rolling) {
-    unsigned char* chunk = (unsigned char*)(roll + 768 + 1024);          // chunkBytes (8 KB; what a wave asks for sets how many fit a CU)
+    unsigned char* chunk = (unsigned char*)(roll + 3 * ROLL_WINDOW + ROLL_CODE_BYTES / 4);          // chunkBytes (8 KB; what a wave asks for sets how many fit a CU)
     const int chRows = max(1, chunkBytes / R);
     int cLo = 1, cHi = 0;
     auto arrowAt = [&](int i, int j) -> int {
@@ -626,9 +684,6 @@ __device__ __forceinline__ void solve_reg(int wlane, const Problem& pr, const Ge
     *out_status = status;
   }
 }
-__device__ __forceinline__ long need_bytes_reg(const Geo& g) { return align4(g.nUsed) + align4(g.qLen + 1) + align4(g.tLen + 1); }
-constexpr int REG_S_BYTES = 2048, REG_M_BYTES = 8192, REG_L_BYTES = 32768;   // classes 10 (16 lanes), 11 (32 lanes), 12 (64 lanes)
-constexpr int REG_L_USED = 16384;   // largest arrows + codes footprint of class 12 (above: the HBM class, whose sweep is in registers too)
 
 struct BatchArgs {
   int n;
@@ -649,9 +704,7 @@ __device__ __forceinline__ bool load_problem(const BatchArgs& a, int p, Problem&
   pr.q = a.qseq + a.q_off[p]; pr.t = a.tseq + a.t_off[p];
   pr.qLen = a.q_len[p]; pr.tLen = a.t_len[p]; pr.k0 = a.k[p];
   pr.m = a.m; pr.mm = a.mm; pr.indel = a.indel;
-  bool ok = pr.qLen >= 0 && pr.tLen >= 0 && pr.k0 >= 1 && make_geo(pr.qLen, pr.tLen, pr.k0, g);
-  long mx = max(abs(a.m), max(abs(a.mm), abs(a.indel)));
-  range_ok = ok && ((long)(pr.qLen + pr.tLen + 16) * (mx + 1) < (1L << 28));
+  range_ok = problem_ok(pr, a, g);
   return range_ok;
 }
 
@@ -661,19 +714,8 @@ constexpr int CLS_ITEMS = 16;
 __device__ __forceinline__ int classify_one(const BatchArgs& a, int p) {
   Problem pr; Geo g; int ok;
   if (!load_problem(a, p, pr, g, ok)) { a.score[p] = 0; a.nblocks[p] = 0; a.status[p] = LRA_ST_RANGE; return -1; }
-  long need = need_bytes(g);
-  int cls = need <= CLASS_A_BYTES ? 0 : need <= CLASS_M1_BYTES ? 4 : need <= CLASS_M2_BYTES ? 5 : need <= CLASS_B_BYTES ? 1 : 2;
-  if (g.k + 1 <= 32) cls = cls == 0 ? 7 : cls == 4 ? 8 : cls == 5 ? 9 : cls;                              // anti-diagonals of at most 32 cells: two problems per wave
-  if (need <= CLASS_S_BYTES && g.k + 1 <= 16) cls = 3;
-  if (cls == 2 && need > a.gslot_bytes) cls = 6;
-  if (cls == 6 && need > a.gslotB_bytes) { a.score[p] = 0; a.nblocks[p] = 0; a.status[p] = LRA_ST_RANGE; return -1; }
-  if (!g.top) {                                                     // prefix band only: scores in registers (solve_reg), arrows + codes in LDS
-    const long nr = need_bytes_reg(g);
-    if (g.qLen <= LN_MAX && g.tLen <= LN_MAX) { const int mx = max(g.qLen, g.tLen); cls = mx <= 3 ? 14 : mx <= 6 ? 15 : mx <= 10 ? 16 : mx <= 16 ? 17 : 18; }
-    else if (g.k + 2 <= 16 && nr <= REG_S_BYTES) cls = 10;
-    else if (g.k + 2 <= 32 && nr <= REG_M_BYTES) cls = 11;
-    else if (g.k + 2 <= 64 && nr <= REG_L_USED) cls = 12;
-  }
+  const int cls = class_of(g);
+  if (cls < 0) { a.score[p] = 0; a.nblocks[p] = 0; a.status[p] = LRA_ST_RANGE; }
   return cls;
 }
 __global__ void __launch_bounds__(1024) aog_classify(BatchArgs a) {
@@ -926,9 +968,9 @@ int lra_aog_launch_device(lra_ctx* ctx, int n, const char* d_qseq, const char* d
   // class 2: 4 MiB slots, 8 per CU (two-stage batches: 6 -- step 955 -> 939 ms) -- with the scores of most of these problems in LDS (rolling, see solve) a wave's HBM traffic is its
   // arrows, and a CU can keep more of them in flight; class 6: 8 MiB slots, one per CU, for the rare larger problem (1.5 kb x 1.5 kb at k = 60, 5 kb x 5 kb at k = 15)
   const int perCu = ctx->pipelined ? 6 : 8;
-  a.gslots = ctx->num_cu * perCu; a.gslot_bytes = 4L << 20;
+  a.gslots = ctx->num_cu * perCu; a.gslot_bytes = HBM_SLOT_BYTES;
   a.chunk_bytes = 8192;
-  a.gslotsB = ctx->num_cu; a.gslotB_bytes = 8L << 20;
+  a.gslotsB = ctx->num_cu; a.gslotB_bytes = HBM_SLOT_B_BYTES;
   a.gscratch = (char*)lra_scratch(ctx, 1, (size_t)a.gslots * a.gslot_bytes + (size_t)a.gslotsB * a.gslotB_bytes);
   if (!a.gscratch) return LRA_ERR_NOMEM;
   a.gscratchB = a.gscratch + (size_t)a.gslots * a.gslot_bytes;
@@ -957,6 +999,8 @@ int lra_aog_launch_device(lra_ctx* ctx, int n, const char* d_qseq, const char* d
   hipLaunchKernelGGL(aog_classify, dim3(cblocks), dim3(1024), 0, ctx->stream, a);
   hipLaunchKernelGGL(aog_offsets, dim3(1), dim3(64), 0, ctx->stream, a);
   hipLaunchKernelGGL(aog_scatter, dim3(cblocks), dim3(1024), 0, ctx->stream, a);
+  // (the grids below decide how many problems of a class are in flight; tests/test_aog_classes.py::resident_groups mirrors them to give every LDS slice / HBM
+  // slot a second problem -- a grid changed here is changed there)
   int wgA = min((n + 3) / 4, ctx->num_cu * 5);
   int wgB = min(n, ctx->num_cu * 2);
   int wgC = min(n, a.gslots);
@@ -1002,8 +1046,8 @@ int lra_aog_launch_device(lra_ctx* ctx, int n, const char* d_qseq, const char* d
   hipLaunchKernelGGL(aog_reg_kernel<12>, dim3(min(n, ctx->num_cu * 10)), dim3(64), REG_L_USED, s3, a);
   lra_time_end(ctx, s3);
   lra_time_begin(ctx, "aog_hbm");
-  hipLaunchKernelGGL(aog_kernel<2>, dim3(wgC), dim3(64), (3 * 256 + 1024) * 4 + a.chunk_bytes, sm, a);
-  hipLaunchKernelGGL(aog_kernel<6>, dim3(min(n, a.gslotsB)), dim3(64), (3 * 256 + 1024) * 4 + a.chunk_bytes, sm, a);
+  hipLaunchKernelGGL(aog_kernel<2>, dim3(wgC), dim3(64), 3 * ROLL_WINDOW * 4 + ROLL_CODE_BYTES + a.chunk_bytes, sm, a);
+  hipLaunchKernelGGL(aog_kernel<6>, dim3(min(n, a.gslotsB)), dim3(64), 3 * ROLL_WINDOW * 4 + ROLL_CODE_BYTES + a.chunk_bytes, sm, a);
   lra_time_end(ctx);
   lra_side_join(ctx, 1); lra_side_join(ctx, 2); lra_side_join(ctx, 3);
   LRA_HIP_CHECK(ctx, hipGetLastError());
@@ -1018,4 +1062,18 @@ extern "C" int lra_affine_one_gap_align_batch(lra_ctx* ctx, int n, const char* d
                                               const uint64_t* d_block_off, int32_t* d_status) {
   return lra_aog_launch_device(ctx, n, d_qseq, d_tseq, d_q_off, d_q_len, d_t_off, d_t_len, d_k, m, mm, indel, d_score, d_nblocks,
                                d_blocks, d_block_off, d_status);
+}
+
+extern "C" int lra_aog_class_of_batch(int n, const int32_t* q_len, const int32_t* t_len, const int32_t* k, int m, int mm, int indel,
+                                      int32_t* cls_out, int32_t* path_out) {
+  if (n < 0 || (n > 0 && (!q_len || !t_len || !k || !cls_out || !path_out))) return LRA_ERR_INVALID;
+  const Scoring sc = {m, mm, indel};
+  for (int p = 0; p < n; p++) {
+    Geo g;
+    const Shape sh = {q_len[p], t_len[p], k[p]};
+    const int cls = problem_ok(sh, sc, g) ? class_of(g) : -1;
+    cls_out[p] = cls;
+    path_out[p] = cls < 0 ? 0 : path_of(g, cls);
+  }
+  return LRA_OK;
 }
