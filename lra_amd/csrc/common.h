@@ -30,7 +30,7 @@ struct lra_ctx {
   int num_cu = 256;
   lra_seed_state* seed = nullptr;
   lra_cluster_state* clus = nullptr;
-  lra_map_state* map = nullptr;                       // mapread.hip: chromosome table, the genome's local index
+  lra_map_state* map = nullptr;                       // map_reference.hip: chromosome table, the genome's local index
   void* aux = nullptr; size_t aux_bytes = 0;          // AffineOneGapAlign blocks of refine fallbacks
   void* out_buf = nullptr; size_t out_bytes = 0;
   void* pin_buf = nullptr; size_t pin_bytes = 0;      // page-locked host staging of the large device-to-host copies (lra_pinned)

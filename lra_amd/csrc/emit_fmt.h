@@ -1,6 +1,6 @@
 // lra_amd/csrc/emit_fmt.h -- the SAM / PAF record writers over a SINK, so that one body serves both forms of the record stage:
 //   lra_str_sink    (emit.hip)     the text itself: the long fields -- CIGAR, read, qualities, MD -- are appended to a string as they are;
-//   lra_piece_sink  (mapread.hip)  the piece table of lra_map_records_device: the short fields go to a literal blob, a long field becomes a reference
+//   lra_piece_sink  (map_output.hip)  the piece table of lra_map_records_device: the short fields go to a literal blob, a long field becomes a reference
 //                                  that records.hip resolves and copies on the device.
 // A sink has  lit(text)  cigar(rec) (the runs' text, without clips)  seq(rec, from, n)  qual(rec) (read_len characters)  qual_sub(rec, pos, n)  md(rec);
 // the piece sink also  pairwise(rec)  (the rows of print format 'a': the string form is emit.hip's lra_format_pairwise on the alignment strings).

@@ -6,6 +6,7 @@
 #pragma once
 #include "common.h"
 #include "scan.h"
+#include "map_state.h"
 
 namespace lra_merge {
 
@@ -76,7 +77,6 @@ static __global__ void __launch_bounds__(64) k_gather_reads(int n, const uint32_
 static inline int merge_passes(lra_ctx* ctx, int slot, uint64_t S, int na, const uint64_t* d_src, PassView A, PassView B, uint64_t nA, uint64_t nBk, uint64_t nRn,
                                size_t extra, char** extra_at, lra_map_result* out) {
   hipStream_t st = ctx->stream;
-  auto grid = [](uint64_t n) { return dim3((unsigned)((n + 255) / 256)); };
   char* mg = (char*)lra_ensure(ctx, slot, 2 * al256((S + 2) * 4) + al256((S + 2) * 8) + 12 * al256((nA + 2) * 4) + 3 * al256((nA + 2) * 8) + al256((nA + 1) * 72) + al256((nBk + 1) * 12) +
                                           al256((nRn + 1) * 4) + al256(extra + 8) + 8192);
   if (!mg) return LRA_ERR_NOMEM;

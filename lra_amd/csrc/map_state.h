@@ -1,4 +1,5 @@
-// lra_amd/csrc/map_state.h -- what the drivers of the path (mapread.hip: MapRead_lowacc, mapread_highacc.hip: MapRead_highacc) keep per context.
+// lra_amd/csrc/map_state.h -- what the drivers of the path (mapread.hip: MapRead_lowacc, mapread_highacc.hip: MapRead_highacc) keep per context (map_reference.hip),
+// and the stages both of them run the same way (map_common.hip).
 #pragma once
 #include <stdlib.h>
 #include "common.h"
@@ -58,13 +59,53 @@ struct lra_map_state {
 };
 
 int lra_map_count_flagged(lra_ctx* ctx, lra_map_result* out);   // mapread.hip: counters.n_flagged_reads of a finished batch
-int lra_map_check_shared(lra_ctx* ctx);   // mapread.hip: borrowed reference data still current?
-// RefineBreakpoint over the consecutive SegAlignments of every job (Map_lowacc.h:586-596, Map_highacc.h:723-727); mapread.hip
-int lra_refine_breakpoints(lra_ctx* ctx, uint64_t nJ, uint64_t nA, const uint64_t* d_job_aln_off, const int32_t* d_strand, const uint64_t* q_off, const int32_t* q_len,
-                           const uint64_t* t_off, const int64_t* t_len, const char* strands, const char* genome, lra_refine_result* fres);
+int lra_map_check_shared(lra_ctx* ctx);   // map_reference.hip: borrowed reference data still current?
+int lra_seed_share(lra_ctx* dst, lra_ctx* src);   // seed.hip: dst borrows src's genome and global index
+int lra_seed_check_shared(lra_ctx* ctx);          // seed.hip: the same question for the genome and the global index
 
 // The strands buffer of a batch (lra_map_result::d_strands: the reads forward, then at rc_base reverse complemented, 64 bytes of zeros) carries
 // the batch's read offsets [n_reads + 1] behind it at this byte: what the record stage (LRA_PACK_MD, LRA_PACK_SVSIG) addresses the reads with once the caller's
 // d_read_off may have been reused -- they travel with the strands through the two-stage handover and the passes' merges.  One copy per batch.
 inline size_t lra_strands_ro_at(uint64_t rc_base) { return (size_t)((2 * rc_base + 64 + 7) & ~(uint64_t)7); }
 inline size_t lra_strands_bytes(uint64_t rc_base, int n_reads) { return lra_strands_ro_at(rc_base) + ((size_t)n_reads + 1) * 8; }
+
+// RefineBreakpoint over the consecutive SegAlignments of every job (Map_lowacc.h:586-596, Map_highacc.h:723-727); map_common.hip
+int lra_refine_breakpoints(lra_ctx* ctx, uint64_t nJ, uint64_t nA, const uint64_t* d_job_aln_off, const int32_t* d_strand, const uint64_t* q_off, const int32_t* q_len,
+                           const uint64_t* t_off, const int64_t* t_len, const char* strands, const char* genome, lra_refine_result* fres);
+// ---- what both drivers do the same way (map_common.hip); the library's own, not part of its ABI
+#pragma GCC visibility push(hidden)
+inline dim3 grid(uint64_t n) { return dim3((unsigned)((n + 255) / 256)); }   // 256 threads per block over n items
+
+// A batch may be mapped: the reference is loaded (gli_required: the genome's local index with it), a local index that is there was built with the options' k / w /
+// window, and borrowed reference data is still its owner's current one.
+int lra_map_ready(lra_ctx* ctx, const lra_map_opts* o, bool gli_required);
+// a1-a4: the batch's seed result -- the one adopted ahead of the call (lra_seed_prefetch, lra_ctx_adopt_seed) when it was made from these reads with these parameters,
+// lra_seed_batch otherwise.  defer_T > 0 (opts.defer_seed_matches): the reads with more tier-1 matches than that are handed back.
+int lra_map_seed(lra_ctx* ctx, int n_reads, const char* d_seq, const uint64_t* d_read_off, int K, int W, int max_freq, uint32_t defer_T, lra_seed_result* sres);
+// the strands buffer described above, in slot 57: *both
+int lra_map_strands(lra_ctx* ctx, int n_reads, const char* d_seq, const uint64_t* d_read_off, uint64_t tot, char** both);
+// the offsets of the 2 n_reads sequences in it, as the reads' local index wants them (slot 58), or nullptr
+uint64_t* lra_map_strand_offsets(lra_ctx* ctx, int n_reads, const uint64_t* d_read_off, uint64_t tot);
+// tinyOpts of LocalRefineAlignment (Map_lowacc.h:233-240, Map_highacc.h:404-409)
+lra_lra_opts lra_map_lra_opts(const lra_map_opts* o);
+// Every SegAlignment of a batch addressed (which read, its strand's bases, its chromosome: slots 59-63) and through IndelRefineAlignment (or, opts.skipBandedRefine,
+// passed on as it is); fres.d_status kept in slot 64.  What follows -- folding that status into the reads', RefineBreakpoint, CalculateStatistics -- differs between
+// the drivers and stays with them.
+struct lra_map_finish {
+  uint32_t* aln_read = nullptr; uint64_t* q_off = nullptr; int32_t* q_len = nullptr; uint64_t* t_off = nullptr; int64_t* t_len = nullptr;
+  lra_refine_result fres{};
+};
+int lra_map_finish_alignments(lra_ctx* ctx, const lra_map_opts* o, int num_aln, uint64_t n_jobs, const lra_alignments_result* ares, const uint64_t* d_read_off,
+                              const char* both, uint64_t tot, int endAlign, lra_map_finish* f);
+// the stage results as the caller sees them
+void lra_map_fill_result(lra_map_result* out, int num_aln, uint64_t n_jobs, const lra_alignments_result& ares, const lra_map_finish& f, const lra_stats_result& tres,
+                         const char* both, uint64_t tot, uint8_t* job_reached, uint32_t* read_status);
+
+double lra_wall_ms();   // a steady clock, in milliseconds
+// LRA_STAGE_DBG=1: the wall time of every stage call (device work + the host-side sizing round trips around it) on stderr; does nothing otherwise
+struct lra_stage_timer {
+  lra_ctx* ctx; bool on; double t_prev = 0;
+  explicit lra_stage_timer(lra_ctx* c);
+  void operator()(const char* name);
+};
+#pragma GCC visibility pop

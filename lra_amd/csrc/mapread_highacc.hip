@@ -51,13 +51,6 @@ T* up(lra_ctx* ctx, int slot, const std::vector<T>& v) {
 template <typename T>
 T* room(lra_ctx* ctx, int slot, size_t n) { return (T*)lra_ensure(ctx, slot, (n + 4) * sizeof(T)); }
 
-inline dim3 grid(uint64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
-__global__ void k_add_off2(int n, const uint64_t* __restrict__ off, uint64_t add, uint64_t* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i <= n) out[i] = off[i];
-  if (i >= 1 && i <= n) out[n + i] = off[i] + add;
-}
 __global__ void k_iota(uint64_t n, uint64_t* o64, int32_t* o32) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i <= n) { if (o64) o64[i] = i; if (o32) o32[i] = (int32_t)i; }
@@ -154,22 +147,6 @@ __global__ void k_piece_fields(uint64_t nPieces, const uint64_t* __restrict__ uO
   cStrand[p] = it >= 0 ? (strand[it] != 0) : 0; cChrom[p] = it >= 0 ? chrom[it] : 0;
   cValue[p] = jobValue[pieceJob[p]]; cN0[p] = jobN0[pieceJob[p]]; cN1[p] = (int32_t)n;
 }
-__global__ void k_aln_address2(uint64_t n_jobs, int num_aln, const uint64_t* __restrict__ job_aln_off, const int32_t* __restrict__ strand,
-                               const int32_t* __restrict__ chrom, const uint64_t* __restrict__ read_off, uint64_t rc_base, const uint64_t* __restrict__ chrom_pos,
-                               uint32_t* __restrict__ aln_read, uint64_t* __restrict__ q_off, int32_t* __restrict__ q_len, uint64_t* __restrict__ t_off,
-                               int64_t* __restrict__ t_len) {
-  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n_jobs) return;
-  const uint32_t r = (uint32_t)(j / (uint64_t)num_aln);
-  for (uint64_t a = job_aln_off[j]; a < job_aln_off[j + 1]; a++) {
-    aln_read[a] = r;
-    q_off[a] = read_off[r] + (strand[a] ? rc_base : 0);
-    q_len[a] = (int32_t)(read_off[r + 1] - read_off[r]);
-    const int c = chrom[a];
-    t_off[a] = chrom_pos[c];
-    t_len[a] = (int64_t)(chrom_pos[c + 1] - chrom_pos[c]);
-  }
-}
 // the reference calls CalculateStatistics twice (Map_highacc.h:721, :731); tdel, tins and the six size-class counters are never reset between
 // the calls (Alignment.h:440-512; only the constructor zeroes them, :85-86), so the second call's values sit on top of the first call's
 __global__ void k_add_counts(uint64_t nA, int32_t* counts, const int32_t* __restrict__ first) {
@@ -178,39 +155,7 @@ __global__ void k_add_counts(uint64_t nA, int32_t* counts, const int32_t* __rest
   for (int k = 4; k < 12; k++) counts[18 * a + k] += first[18 * a + k];
 }
 
-
 }  // namespace
-
-extern "C" void lra_map_opts_preset_ccs(lra_map_opts* o) {
-  if (!o) return;
-  memset(o, 0, sizeof *o);
-  // -CCS (lra.cpp:306-340) over the defaults of Options.h:127-230.  globalK: the preset says 25, but `lra align` then reads the index file, and ReadIndex
-  // overwrites opts.globalK with the K the index was built with (MMIndex.h:409, lra.cpp:623) -- 17 for `lra index -CCS` (lra.cpp:890-896); globalW stays 20.
-  o->globalK = 17; o->globalW = 20; o->globalMaxFreq = 150;
-  o->localK = 7; o->localW = 5; o->localMaxFreq = 15; o->localIndexWindow = 256;
-  o->refineBand = 7; o->localMatch = 4; o->localMismatch = -3; o->localIndel = -4; o->localBand = 15;
-  o->refineSpaceDist = 30000; o->anchorstoosparse = 0.005f; o->splitdist = 50000; o->window = 100;
-  o->second_anchorbonus = 2.0f; o->bypassClustering = 0; o->skipBandedRefine = 0; o->refineBreakpoint = 0;
-  o->clean.globalK = 17; o->clean.cleanMaxDiag = 150; o->clean.minDiagCluster = 10; o->clean.bypassClustering = 0; o->clean.cleanClustersize = 100;
-  o->clean.SecondCleanMinDiagCluster = 30; o->clean.SecondCleanMaxDiag = 100; o->clean.punish_anchorfreq = 10; o->clean.anchorPerlength = 10;
-  o->sdp.rate = 10.0f; o->sdp.NumAln = 2; o->sdp.alnthres = 0.7f; o->sdp.gapopen = 4.0f; o->sdp.gapextend = 15.0f; o->sdp.gaproot = 1.5f;
-  o->sdp.gapCeiling1 = 2000; o->sdp.gapCeiling2 = 3000; o->sdp.mode = 0; o->sdp.globalK = 17;
-  o->readType = LRA_READ_CCS; o->hardClip = 1; o->PrintNumAln = 1; o->printFormat = 's';
-  o->fine.globalK = 17; o->fine.RoughClustermaxGap = 500; o->fine.maxDiag = 500; o->fine.maxGap = 400; o->fine.minClusterSize = 10; o->fine.minUniqueStretchNum = 1;
-  o->fine.minUniqueStretchDist = 50;
-  o->merge_dist = 100;
-}
-
-extern "C" void lra_map_opts_preset_contig(lra_map_opts* o) {
-  if (!o) return;
-  lra_map_opts_preset_ccs(o);
-  // -CONTIG (lra.cpp:268-305): what differs from -CCS on this path
-  o->globalK = 19; o->globalW = 10; o->globalMaxFreq = 30; o->refineBand = 50; o->refineSpaceDist = 50000;
-  o->clean.globalK = 19; o->clean.minDiagCluster = 30;
-  o->sdp.rate = 1.0f; o->sdp.gapextend = 20.0f; o->sdp.gapCeiling1 = 3000; o->sdp.gapCeiling2 = 5000; o->sdp.globalK = 19;
-  o->fine.globalK = 19; o->fine.maxDiag = 100; o->fine.maxGap = 500;
-  o->readType = LRA_READ_CONTIG;
-}
 
 // One pass over a batch.  sparse_pass = false: every read whose chains' clusters are dense enough (Map_highacc.h:413-416, sparse == 0) is taken through the path with
 // K = opts.globalK; the others are listed in *sparse_reads and left without chains.  sparse_pass = true (the batch holds such reads only): the clusters go through
@@ -233,15 +178,7 @@ static int highacc_core(lra_ctx* ctx, int n_reads, const char* d_seq, const uint
   if ((rc = dl(ctx, h_read_off, d_read_off, (size_t)R + 1))) return rc;
   // ---- a1-a4 (MapRead.h:169-203), a5 (Map_highacc.h:41-42)
   lra_seed_result sres;
-  {
-    // (lra align -a, lra_ctx_set_store_all: the sketch alone takes w = 1, MapRead.h:172-176; W -- and Wt below -- stay opts.globalW)
-    const int seedW = ctx->store_all ? 1 : W;
-    const bool ahead = ctx->ahead.valid && ctx->ahead.n_reads == R && ctx->ahead.d_seq == d_seq && ctx->ahead.d_read_off == d_read_off &&
-                       ctx->ahead.k == K && ctx->ahead.w == seedW && ctx->ahead.max_freq == o->globalMaxFreq;   // (lra_seed_prefetch + lra_ctx_adopt_seed)
-    ctx->ahead.valid = false;
-    if (ahead) sres = ctx->ahead.res;
-    else if ((rc = lra_seed_batch(ctx, R, d_seq, d_read_off, K, seedW, o->globalMaxFreq, &sres))) return rc;
-  }
+  if ((rc = lra_map_seed(ctx, R, d_seq, d_read_off, K, W, o->globalMaxFreq, 0, &sres))) return rc;   // (W -- and Wt below -- stay opts.globalW under lra align -a)
   lra_cluster_result cres;
   if ((rc = lra_clean_matches_batch(ctx, &o->clean, CH, nChr, &cres))) return rc;
   lra_fine_result fc;
@@ -254,12 +191,8 @@ static int highacc_core(lra_ctx* ctx, int n_reads, const char* d_seq, const uint
   if (nC == 0) { cl_moff.assign(1, 0); }
   for (int r = 0; r < R; r++) hstat[r] |= st32[r];
   // the reads forward, then reverse complemented (strands[2], MapRead.h:166-168)
-  char* both = (char*)lra_ensure(ctx, 57, lra_strands_bytes(tot, R));
-  if (!both) return LRA_ERR_NOMEM;
-  LRA_HIP_CHECK(ctx, hipMemcpyAsync(both, d_seq, tot, hipMemcpyDeviceToDevice, st));
-  LRA_HIP_CHECK(ctx, hipMemsetAsync(both + 2 * tot, 0, 64, st));
-  LRA_HIP_CHECK(ctx, hipMemcpyAsync(both + lra_strands_ro_at(tot), d_read_off, ((size_t)R + 1) * 8, hipMemcpyDeviceToDevice, st));
-  if ((rc = lra_create_rc_batch(ctx, R, d_seq, d_read_off, both + tot))) return rc;
+  char* both = nullptr;
+  if ((rc = lra_map_strands(ctx, R, d_seq, d_read_off, tot, &both))) return rc;
   const int na = std::max(1, o->sdp.NumAln);
   const uint64_t S = (uint64_t)R * na;
   // the chains of all reads, in (read, h) order
@@ -369,9 +302,9 @@ static int highacc_core(lra_ctx* ctx, int n_reads, const char* d_seq, const uint
   if (!job_reached || !read_status) return LRA_ERR_NOMEM;
   h_reached.assign(S, 0);
   lra_alignments_result ares; memset(&ares, 0, sizeof ares);
-  lra_refine_result fres; memset(&fres, 0, sizeof fres);
+  lra_map_finish f;
+  lra_refine_result& fres = f.fres;
   lra_stats_result tres; memset(&tres, 0, sizeof tres);
-  uint32_t* aln_read = nullptr;
   lra_map_counters& cnt = out->counters;
   cnt.n_minimizers = sres.n_minimizers; cnt.n_matches = sres.n_matches; cnt.n_clusters = nC;
   uint64_t nA = 0;
@@ -388,13 +321,10 @@ static int highacc_core(lra_ctx* ctx, int n_reads, const char* d_seq, const uint
     else {
       // ---- REFINEclusters (:429-447): the read's two local indexes (:398-402), every cluster re-seeded window by window; anchorfreq inherited (:444)
       if (!m->gli_buf) return lra_set_err(ctx, LRA_ERR_INVALID, "a read takes the REFINEclusters branch: the genome's local index is needed (lra_ctx_build_local_index)");
-      if (m->gli_window != o->localIndexWindow || m->gli_k != o->localK || m->gli_w != o->localW)
-        return lra_set_err(ctx, LRA_ERR_INVALID, "the genome's local index has k = %d, w = %d, windows of %d bases; the options say %d, %d, %d (lra_map_opts_apply_local_index: glIndex.Read overrides them)",
-                           m->gli_k, m->gli_w, m->gli_window, o->localK, o->localW, o->localIndexWindow);
-      uint64_t* off2 = (uint64_t*)lra_ensure(ctx, 58, (2 * (size_t)R + 2) * 8);
+      if ((rc = lra_map_ready(ctx, o, true))) return rc;
+      const uint64_t* off2 = lra_map_strand_offsets(ctx, R, d_read_off, tot);
       uint8_t* active = (uint8_t*)lra_ensure(ctx, 65, 2 * (size_t)R + 64);
       if (!off2 || !active) return LRA_ERR_NOMEM;
-      hipLaunchKernelGGL(k_add_off2, dim3((R + 256) / 256), dim3(256), 0, st, R, d_read_off, tot, off2);
       LRA_HIP_CHECK(ctx, hipMemsetAsync(active, 1, 2 * (size_t)R, st));
       lra_local_index_result rli;
       if ((rc = lra_local_index_masked_batch(ctx, 2 * R, both, off2, active, o->localK, o->localW, o->localIndexWindow, o->localMaxFreq, &rli))) return rc;
@@ -566,9 +496,7 @@ static int highacc_core(lra_ctx* ctx, int n_reads, const char* d_seq, const uint
     uint64_t* d_jco = up(ctx, 161, job_co); uint32_t* d_jrd = up(ctx, 162, job_rd); int32_t* d_jh = up(ctx, 163, job_h); uint32_t* d_jlsc = up(ctx, 164, job_lsc);
     if (!d_jco || !d_jrd || !d_jh || !d_jlsc) return LRA_ERR_NOMEM;
     // ---- a13, the walk (LocalRefineAlignment.h:577-766) with tinyOpts (:404-409, :466-467)
-    lra_lra_opts lo; lo.localW = o->localW; lo.globalW = o->localW; lo.localMaxFreq = o->localMaxFreq; lo.match = o->localMatch; lo.mismatch = o->localMismatch;
-    lo.indel = o->localIndel; lo.localBand = o->localBand; lo.refineBySDP = 1; lo.isOnt = (o->readType == LRA_READ_ONT || o->readType == LRA_READ_CLR) ? 1 : 0;
-    lo.gapopen = o->sdp.gapopen; lo.gapextend = o->sdp.gapextend; lo.gaproot = o->sdp.gaproot; lo.gapCeiling1 = o->sdp.gapCeiling1; lo.gapCeiling2 = o->sdp.gapCeiling2;
+    const lra_lra_opts lo = lra_map_lra_opts(o);
     if ((rc = lra_local_refine_highacc_batch(ctx, S, d_jco, d_jrd, d_jh, d_jlsc, P, uOff, pStrand, pChrom, pValue, pN0, pN1, nU, uq, ut, ul, d_read_off, both, tot, genome, CH,
                                              nChr, &lo, &ares))) return rc;
     nA = ares.n_alignments;
@@ -576,36 +504,21 @@ static int highacc_core(lra_ctx* ctx, int n_reads, const char* d_seq, const uint
     if ((rc = dl(ctx, st32, ares.d_status, (size_t)S))) return rc;
     for (uint64_t s = 0; s < S; s++) hstat[s / na] |= st32[s];
     // ---- a14 (endAlign = true), a16, a15, a16 again on every SegAlignment (Map_highacc.h:717-732)
-    aln_read = (uint32_t*)lra_ensure(ctx, 59, (nA + 1) * 4);
-    uint64_t* q_off = (uint64_t*)lra_ensure(ctx, 60, (nA + 1) * 8);
-    int32_t* q_len = (int32_t*)lra_ensure(ctx, 61, (nA + 1) * 4);
-    uint64_t* t_off = (uint64_t*)lra_ensure(ctx, 62, (nA + 1) * 8);
-    int64_t* t_len = (int64_t*)lra_ensure(ctx, 63, (nA + 1) * 8);
-    if (!aln_read || !q_off || !q_len || !t_off || !t_len) return LRA_ERR_NOMEM;
-    hipLaunchKernelGGL(k_aln_address2, grid(S), dim3(256), 0, st, S, na, ares.d_job_aln_off, ares.d_strand, ares.d_chrom, d_read_off, tot, (const uint64_t*)m->d_chrom_pos,
-                       aln_read, q_off, q_len, t_off, t_len);
+    if ((rc = lra_map_finish_alignments(ctx, o, na, S, &ares, d_read_off, both, tot, 1, &f))) return rc;
     if (nA) {
-      if (o->skipBandedRefine) {
-        fres.n_aln = (int)nA; fres.n_blocks = ares.n_blocks; fres.d_block_off = ares.d_block_off; fres.d_blocks = ares.d_blocks; fres.d_status = nullptr;
-      } else if ((rc = lra_indel_refine_batch(ctx, (int)nA, ares.d_blocks, ares.d_block_off, ares.n_blocks, both, q_off, q_len, genome, t_off, t_len, o->refineBand,
-                                              o->localMatch, o->localMismatch, o->localIndel, 1, &fres))) return rc;
       if (fres.d_status) {
-        int32_t* keep = (int32_t*)lra_ensure(ctx, 64, (nA + 1) * 4);
-        if (!keep) return LRA_ERR_NOMEM;
-        LRA_HIP_CHECK(ctx, hipMemcpyAsync(keep, fres.d_status, nA * 4, hipMemcpyDeviceToDevice, st));
-        fres.d_status = keep;
         std::vector<int32_t> fst; std::vector<uint32_t> ar;
-        if ((rc = dl(ctx, fst, (const int32_t*)keep, nA)) || (rc = dl(ctx, ar, (const uint32_t*)aln_read, nA))) return rc;
+        if ((rc = dl(ctx, fst, fres.d_status, nA)) || (rc = dl(ctx, ar, (const uint32_t*)f.aln_read, nA))) return rc;
         for (uint64_t a = 0; a < nA; a++) hstat[ar[a]] |= (uint32_t)fst[a];
       }
-      if ((rc = lra_calculate_statistics_batch(ctx, (int)nA, fres.d_blocks, fres.d_block_off, both, q_off, q_len, genome, t_off, m->lut.data(), (int)m->lut.size(), &tres)))
+      if ((rc = lra_calculate_statistics_batch(ctx, (int)nA, fres.d_blocks, fres.d_block_off, both, f.q_off, f.q_len, genome, f.t_off, m->lut.data(), (int)m->lut.size(), &tres)))
         return rc;
       int32_t* first_counts = (int32_t*)lra_ensure(ctx, 165, (nA + 1) * 18 * 4);
       if (!first_counts) return LRA_ERR_NOMEM;
       LRA_HIP_CHECK(ctx, hipMemcpyAsync(first_counts, tres.d_counts, nA * 18 * 4, hipMemcpyDeviceToDevice, st));
       if (!o->refineBreakpoint &&                                         // sic: `if (opts.refineBreakpoint == false)` (:723)
-          (rc = lra_refine_breakpoints(ctx, S, nA, ares.d_job_aln_off, ares.d_strand, q_off, q_len, t_off, t_len, both, genome, &fres))) return rc;
-      if ((rc = lra_calculate_statistics_batch(ctx, (int)nA, fres.d_blocks, fres.d_block_off, both, q_off, q_len, genome, t_off, m->lut.data(), (int)m->lut.size(), &tres)))
+          (rc = lra_refine_breakpoints(ctx, S, nA, ares.d_job_aln_off, ares.d_strand, f.q_off, f.q_len, f.t_off, f.t_len, both, genome, &fres))) return rc;
+      if ((rc = lra_calculate_statistics_batch(ctx, (int)nA, fres.d_blocks, fres.d_block_off, both, f.q_off, f.q_len, genome, f.t_off, m->lut.data(), (int)m->lut.size(), &tres)))
         return rc;
       hipLaunchKernelGGL(k_add_counts, grid(nA), dim3(256), 0, st, nA, (int32_t*)tres.d_counts, (const int32_t*)first_counts);
     }
@@ -621,13 +534,7 @@ static int highacc_core(lra_ctx* ctx, int n_reads, const char* d_seq, const uint
   }
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
   LRA_HIP_CHECK(ctx, hipGetLastError());
-  out->num_aln = na; out->n_jobs = S; out->n_alignments = nA; out->n_blocks = fres.n_blocks; out->n_runs = tres.n_runs;
-  out->d_job_aln_off = ares.d_job_aln_off; out->d_job_status = ares.d_status; out->d_job_reached = job_reached; out->d_read_status = read_status;
-  out->d_aln_read = aln_read; out->d_strand = ares.d_strand; out->d_supp = ares.d_supp; out->d_secondary = ares.d_secondary; out->d_n0 = ares.d_n0; out->d_n1 = ares.d_n1;
-  out->d_chrom = ares.d_chrom; out->d_first_sdp_value = ares.d_value;
-  out->d_block_off = fres.d_block_off; out->d_blocks = fres.d_blocks; out->d_refine_status = fres.d_status;
-  out->d_counts = tres.d_counts; out->d_value = tres.d_value; out->d_run_off = tres.d_run_off; out->d_runs = tres.d_runs;
-  out->d_strands = both; out->rc_base = tot;
+  lra_map_fill_result(out, na, S, ares, f, tres, both, tot, job_reached, read_status);
   cnt.n_segments = fres.n_segments; cnt.n_rows = fres.n_rows; cnt.n_cells = fres.n_cells; cnt.n_aog = fres.n_aog;
   return LRA_OK;
 }
@@ -642,14 +549,9 @@ extern "C" int lra_map_reads_highacc_batch(lra_ctx* ctx, int n_reads, const char
 static int highacc_batch_impl(lra_ctx* ctx, int n_reads, const char* d_seq, const uint64_t* d_read_off, uint64_t total_bases, const lra_map_opts* o, lra_map_result* out) {
   if (!ctx || !o || !out || n_reads < 0) return LRA_ERR_INVALID;
   memset(out, 0, sizeof *out);
-  lra_map_state* m = ctx->map;
-  if (!m || m->chrom_pos.size() < 2 || !ctx->seed || !ctx->seed->genome || !ctx->seed->idx_key)
-    return lra_set_err(ctx, LRA_ERR_INVALID, "reference not loaded (genome, global index, chromosome table)");
+  { int rcs = lra_map_ready(ctx, o, false); if (rcs) return rcs; }
   if (o->bypassClustering) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_reads_highacc_batch is the path of opts.bypassClustering == 0 (-CCS, -CONTIG)");
-  if (m->gli_buf && (m->gli_window != o->localIndexWindow || m->gli_k != o->localK || m->gli_w != o->localW))    // (whether or not a read of this batch takes the branch that reads glIndex)
-    return lra_set_err(ctx, LRA_ERR_INVALID, "the genome's local index has k = %d, w = %d, windows of %d bases; the options say %d, %d, %d (lra_map_opts_apply_local_index: glIndex.Read overrides them)",
-                       m->gli_k, m->gli_w, m->gli_window, o->localK, o->localW, o->localIndexWindow);
-  { int rcs = lra_map_check_shared(ctx); if (rcs) return rcs; }
+  lra_map_state* m = ctx->map;
   out->n_reads = n_reads;
   m->last_text.clear(); m->last_sig = lra_map_sig{};
   if (n_reads == 0) return LRA_OK;
@@ -706,11 +608,8 @@ static int highacc_batch_impl(lra_ctx* ctx, int n_reads, const char* d_seq, cons
       else srcSlot[s] = s;
     }
   for (int i = 0; i < R2; i++) hsA[sparse[i]] = hsB[i];
-  PassView B;
-  B.jo = o2.d_job_aln_off; B.strand = o2.d_strand; B.supp = o2.d_supp; B.sec = o2.d_secondary; B.n0 = o2.d_n0; B.n1 = o2.d_n1; B.chrom = o2.d_chrom; B.fval = o2.d_first_sdp_value;
-  B.boff = o2.d_block_off; B.blocks = o2.d_blocks; B.rstat = o2.d_refine_status; B.counts = o2.d_counts; B.value = o2.d_value; B.roff = o2.d_run_off; B.runs = o2.d_runs;
+  PassView B = lra_merge::view_of(o2);
   if (nA1 == 0) A.jo = nullptr;
-  if (o2.n_alignments == 0) B.jo = nullptr;
   const uint64_t nA = nA1 + o2.n_alignments, nBk = nB1 + o2.n_blocks, nRn = nR1 + o2.n_runs;
   A.jstat = nullptr; B.jstat = nullptr;                                    // every stage's status bits are in the read's status word already
   uint64_t* d_src = up(ctx, 175, srcSlot);
@@ -718,14 +617,11 @@ static int highacc_batch_impl(lra_ctx* ctx, int n_reads, const char* d_seq, cons
   lra_map_result mo; memset(&mo, 0, sizeof mo);
   if ((rc = lra_merge::merge_passes(ctx, 171, S, na, d_src, A, B, nA, nBk, nRn, 0, nullptr, &mo))) return rc;
   // the batch's strands buffer again (the second pass overwrote it with its own reads)
-  char* both = (char*)lra_ensure(ctx, 57, lra_strands_bytes(total_bases, R));
   uint8_t* job_reached = (uint8_t*)lra_ensure(ctx, 82, S + 64);
   uint32_t* read_status = (uint32_t*)lra_ensure(ctx, 81, ((size_t)R + 1) * 4);
-  if (!both || !job_reached || !read_status) return LRA_ERR_NOMEM;
-  LRA_HIP_CHECK(ctx, hipMemcpyAsync(both, d_seq, total_bases, hipMemcpyDeviceToDevice, st));
-  LRA_HIP_CHECK(ctx, hipMemsetAsync(both + 2 * total_bases, 0, 64, st));
-  LRA_HIP_CHECK(ctx, hipMemcpyAsync(both + lra_strands_ro_at(total_bases), d_read_off, ((size_t)R + 1) * 8, hipMemcpyDeviceToDevice, st));
-  if ((rc = lra_create_rc_batch(ctx, R, d_seq, d_read_off, both + total_bases))) return rc;
+  if (!job_reached || !read_status) return LRA_ERR_NOMEM;
+  char* both = nullptr;
+  if ((rc = lra_map_strands(ctx, R, d_seq, d_read_off, total_bases, &both))) return rc;
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(job_reached, hrA.data(), S, hipMemcpyHostToDevice, st));
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(read_status, hsA.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));

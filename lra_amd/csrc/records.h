@@ -1,4 +1,4 @@
-// lra_amd/csrc/records.h -- the piece table between the host half (mapread.hip) and the device half (records.hip) of lra_map_records_device.
+// lra_amd/csrc/records.h -- the piece table between the host half (map_output.hip) and the device half (records.hip) of lra_map_records_device.
 #pragma once
 #include "common.h"
 

@@ -1,7 +1,7 @@
 """MapRead_lowacc for a batch of reads (reference: Map_lowacc.h:33-640, called from MapRead, MapRead.h:169-263).
 
 The drop-in boundary is the C ABI: lra_map_reads_lowacc_batch (every stage between the read bases and the alignments' statistics, on the
-device) and lra_map_records (SetFromSegAlignment, AlignmentsOrder, SimpleMapQV, OUTPUT on the host) in lra_amd/csrc/mapread.hip;
+device; lra_amd/csrc/mapread.hip) and lra_map_records (SetFromSegAlignment, AlignmentsOrder, SimpleMapQV, OUTPUT on the host; lra_amd/csrc/map_output.hip);
 LowAccMapper.align / .records are thin ctypes wrappers over them.  align_staged / records_staged drive the same stages one library call at
 a time from Python -- the form the stage-by-stage parity tests hook into; both forms must give identical results (tests/test_mapread.py).
 
@@ -57,6 +57,7 @@ class LowAccOptions:
     SecondCleanMaxDiag: int = 100
     bypassClustering: bool = True
     refineBreakpoint: bool = False     # --refineBreakpoints (lra.cpp:262)
+    skipBandedRefine: bool = False     # --skipBandedRefine (lra.cpp:259): no IndelRefineAlignment
     read_type: str = "ont"
     hardClip: bool = True
     PrintNumAln: int = 1
@@ -257,7 +258,7 @@ class LowAccMapper:
         for n in ("globalK", "globalW", "globalMaxFreq", "localK", "localW", "localMaxFreq", "localIndexWindow", "refineBand", "localMatch", "localMismatch",
                   "localIndel", "refineSpaceDist", "anchorstoosparse", "splitdist", "window", "second_anchorbonus"):
             setattr(m, n, getattr(o, n))
-        m.bypassClustering = int(o.bypassClustering); m.refineBreakpoint = int(o.refineBreakpoint)
+        m.bypassClustering = int(o.bypassClustering); m.refineBreakpoint = int(o.refineBreakpoint); m.skipBandedRefine = int(o.skipBandedRefine)
         m.clean.globalK = o.globalK; m.clean.bypassClustering = int(o.bypassClustering); m.clean.SecondCleanMaxDiag = o.SecondCleanMaxDiag
         m.sdp.globalK = o.globalK; m.sdp.rate = o.initial_anchorbonus; m.sdp.alnthres = o.alnthres
         m.readType = READ_TYPES[o.read_type]; m.hardClip = int(o.hardClip); m.PrintNumAln = o.PrintNumAln; m.printFormat = ord(o.printFormat)

@@ -81,7 +81,7 @@ struct oracle_map_opts {
   int globalK, globalW, globalMaxFreq, localK, localW, localMaxFreq, localIndexWindow, refineBand, match, mismatch, indel, localBand, refineSpaceDist;
   float anchorstoosparse; int splitdist, window; float initial_anchorbonus, second_anchorbonus, alnthres; int NumAln;
   float gapopen, gapextend, gaproot; int gapCeiling1, gapCeiling2;
-  int refineBreakpoint, stats, limitrefine, isOnt;
+  int refineBreakpoint, stats, limitrefine, isOnt, skipBandedRefine;
   lra_clean_opts clean;
 };
 
@@ -310,6 +310,7 @@ void map_read(const char* read, uint32_t L, const Ref& R, const oracle_map_opts&
       break;
     }
     for (Seg& s : segs) {                                                // a14 (:582)
+      if (o.skipBandedRefine) { s.blocks = s.a13; s.refine_status = 0; continue; }   // `if (opts.skipBandedRefine == false)`
       const char* sb = s.strand == 0 ? fwd : rc;
       const long nb = (long)s.a13.size() / 3;
       const int* b = s.a13.data();

@@ -11,7 +11,7 @@ import oracle_lib as O
 
 ONT = dict(globalK=17, globalW=10, globalMaxFreq=150, localK=10, localW=5, localMaxFreq=15, localIndexWindow=256, refineBand=7, match=4, mismatch=-1,
            indel=-2, refineSpaceDist=30000, anchorstoosparse=0.005, splitdist=50000, window=100, initial_anchorbonus=20.0, second_anchorbonus=2.0,
-           alnthres=0.65, SecondCleanMaxDiag=100, refineBreakpoint=False)
+           alnthres=0.65, SecondCleanMaxDiag=100, refineBreakpoint=False, skipBandedRefine=False)
 CLR = dict(ONT, globalK=15, globalMaxFreq=250, refineBand=20, initial_anchorbonus=15.0, second_anchorbonus=6.0, alnthres=0.50, SecondCleanMaxDiag=120)
 
 _CHROM_CACHE = {}
@@ -149,7 +149,10 @@ def map_read_lowacc_py(read: bytes, genome: bytes, idx_key, idx_pos, g_index, op
         for s in segs:
             sb = fwd if s["strand"] == 0 else rc
             # a14 (Map_lowacc.h:582-585)
-            refined, rst = O.indel_refine(s["blocks"], sb, chrom_bytes(s["chrom"]), o["refineBand"], o["match"], o["mismatch"], o["indel"])
+            if o["skipBandedRefine"]:
+                refined, rst = s["blocks"], 0
+            else:
+                refined, rst = O.indel_refine(s["blocks"], sb, chrom_bytes(s["chrom"]), o["refineBand"], o["match"], o["mismatch"], o["indel"])
             out.append(dict(s, a13_blocks=s["blocks"], blocks=refined, refine_status=rst))
         if o["refineBreakpoint"]:                                          # a15 (Map_lowacc.h:586-596): segments come right to left on the read
             for si in range(1, len(out)):
@@ -175,7 +178,8 @@ class MapOpts(C.Structure):
                                         "indel", "localBand", "refineSpaceDist")] +
                 [("anchorstoosparse", C.c_float), ("splitdist", C.c_int), ("window", C.c_int), ("initial_anchorbonus", C.c_float), ("second_anchorbonus", C.c_float),
                  ("alnthres", C.c_float), ("NumAln", C.c_int), ("gapopen", C.c_float), ("gapextend", C.c_float), ("gaproot", C.c_float), ("gapCeiling1", C.c_int),
-                 ("gapCeiling2", C.c_int), ("refineBreakpoint", C.c_int), ("stats", C.c_int), ("limitrefine", C.c_int), ("isOnt", C.c_int), ("clean", O.CleanOpts)])
+                 ("gapCeiling2", C.c_int), ("refineBreakpoint", C.c_int), ("stats", C.c_int), ("limitrefine", C.c_int), ("isOnt", C.c_int), ("skipBandedRefine", C.c_int),
+                 ("clean", O.CleanOpts)])
 
 
 def _c_opts(opts, clean_opts, stats):
@@ -190,6 +194,7 @@ def _c_opts(opts, clean_opts, stats):
     for n in ("gapopen", "gapextend", "gaproot", "gapCeiling1", "gapCeiling2"):
         setattr(m, n, O.SDP_ONT[n])
     m.refineBreakpoint = int(bool(o["refineBreakpoint"])); m.stats = int(bool(stats)); m.limitrefine = 1; m.isOnt = 1
+    m.skipBandedRefine = int(bool(o["skipBandedRefine"]))
     m.clean = clean_opts or O.CleanOpts(**dict(O.CLEAN_PRESETS["ONT"], globalK=o["globalK"], SecondCleanMaxDiag=o["SecondCleanMaxDiag"]))
     return m
 

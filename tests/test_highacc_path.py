@@ -363,7 +363,7 @@ def _sv_reads(genome, rng, err, n_plain=10):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("preset", ["ccs", "ccs-bp", "ccs-k17", "contig", "ccs-sparse", "ccs-gli", "contig-gli", "ccs-sparse-gli"])
+@pytest.mark.parametrize("preset", ["ccs", "ccs-bp", "ccs-skip", "ccs-k17", "contig", "ccs-sparse", "ccs-gli", "contig-gli", "ccs-sparse-gli"])
 def test_map_reads_highacc_match_oracle_pipeline(ctx, oracle, preset):
     """lra_map_reads_highacc_batch against MapRead_highacc composed from the oracle's stage functions (tests/oracle_pipeline.map_read_highacc): every
     SegAlignment of every chain -- strand, Supplymentary, ISsecondary, NumOfAnchors0/1, the chain's value, the refined blocks, the counters the two
@@ -387,6 +387,8 @@ def test_map_reads_highacc_match_oracle_pipeline(ctx, oracle, preset):
                              np.concatenate([sim(30_000, 15_000), sim(350_000, 12_000, True), sim(45_000, 15_000)])] + reads[10:]
     if preset == "ccs-bp":
         over["refineBreakpoint"] = 1; oo["refineBreakpoint"] = True
+    if preset == "ccs-skip":                                              # --skipBandedRefine (Map_highacc.h:717): no IndelRefineAlignment, on both sides
+        over["skipBandedRefine"] = 1; oo["skipBandedRefine"] = True
     if preset == "ccs-k17":                                               # denser seeds: more clusters per read, more second chains
         over.update({"globalK": 17, "globalW": 10, "clean.globalK": 17, "sdp.globalK": 17, "fine.globalK": 17}); oo.update(globalK=17, globalW=10); ip = (17, 10, 150, 15, 1)
     if preset == "ccs-sparse":                                            # a slightly thinner global index (one minimizer per 18 bases instead of 15; the reads are sketched with W = 20): clusters at ~0.01 anchors per base, so some

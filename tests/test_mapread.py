@@ -155,11 +155,12 @@ def test_map_reads_to_sam(ctx):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("preset", ["ont", "clr", "ont-bp", "ont-2chr", "ont-rep", "ont-defer", "ont-defer-all", "ont-onepass", "ont-gli", "clr-gli", "ont-gli-2chr"])
+@pytest.mark.parametrize("preset", ["ont", "clr", "ont-bp", "ont-skip", "ont-2chr", "ont-rep", "ont-defer", "ont-defer-all", "ont-onepass", "ont-gli", "clr-gli", "ont-gli-2chr"])
 def test_map_reads_match_oracle_pipeline(ctx, oracle, preset):
     """The C boundary against the oracle's stage functions composed on the CPU (tests/oracle_pipeline.py): every SegAlignment of every
     primary chain -- strand, Supplymentary, NumOfAnchors0/1, FirstSDPValue, the refined blocks -- bit for bit, on plain reads, reads with a
-    deletion / an inversion / a translocated half, and a read that cannot align."""
+    deletion / an inversion / a translocated half, and a read that cannot align.  ont-skip: --skipBandedRefine on both sides (Map_lowacc.h:582): the blocks
+    LocalRefineAlignment made go to CalculateStatistics as they are."""
     import oracle_lib
     import oracle_pipeline as OP
     from lra_amd import seed, mapread
@@ -167,11 +168,11 @@ def test_map_reads_match_oracle_pipeline(ctx, oracle, preset):
     genome = synth.make_genome(500_000, seed=31, repeat_frac=0.25, n_families=3)
     gli = preset.endswith("-gli") or "-gli-" in preset                     # the local index as `lra index` writes it and glIndex.Read hands it to the path: windows of 2048 bases
     preset = preset.replace("-gli", "")                                    # (LocalIndex(0), MMIndex.h:110-127, lra.cpp:989); without a .gli file `lra align` builds it with opts.localIndexWindow = 256
-    o = mapread.clr_options() if preset == "clr" else mapread.LowAccOptions(refineBreakpoint=(preset == "ont-bp"))     # ont-bp: --refineBreakpoints
+    o = mapread.clr_options() if preset == "clr" else mapread.LowAccOptions(refineBreakpoint=(preset == "ont-bp"), skipBandedRefine=(preset == "ont-skip"))     # ont-bp: --refineBreakpoints
     o.localIndexWindow = 2048 if gli else 256
     # ont-defer / -all / onepass: lra_map_opts.defer_matches -- some / all / none of the reads go through the driver's second, concurrent pass; same results
     o.deferMatches = {"ont-defer": 800, "ont-defer-all": 1, "ont-onepass": 0}.get(preset)
-    oo = dict(OP.CLR if preset == "clr" else dict(OP.ONT, refineBreakpoint=(preset == "ont-bp")), localIndexWindow=o.localIndexWindow)
+    oo = dict(OP.CLR if preset == "clr" else dict(OP.ONT, refineBreakpoint=(preset == "ont-bp"), skipBandedRefine=(preset == "ont-skip")), localIndexWindow=o.localIndexWindow)
     err, mix = (0.15, (20, 30, 50)) if preset == "clr" else (0.10, (30, 35, 35))
     ik, ip = synth.build_global_index(genome, o.globalK, o.globalW, 100)
     reads, truth = synth.simulate_reads(genome, 10, 8000, 2500, err, mix, seed=11)
@@ -221,6 +222,7 @@ def test_map_reads_match_oracle_pipeline(ctx, oracle, preset):
                 assert out["refine_status"][a] == s["refine_status"] == 0, (r, p, a)
                 b = out["blocks"][int(out["block_off"][a]):int(out["block_off"][a + 1])]
                 assert np.array_equal(b, s["blocks"]), (r, p, a, len(b), len(s["blocks"]))
+                assert preset != "ont-skip" or np.array_equal(b, s["a13_blocks"]), (r, p, a)
                 ec, ev, eruns, _ = s["stats"]                                                  # CalculateStatistics: counters, NV bits, CIGAR runs
                 assert out["counts"][a].tolist() == [ec[k] for k in O_STAT_NAMES], (r, p, a)
                 assert np.float32(out["value"][a]).view(np.uint32) == np.float32(ev).view(np.uint32), (r, p, a)
