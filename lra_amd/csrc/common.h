@@ -38,13 +38,13 @@ struct lra_ctx {
   uint64_t* scan_tmp = nullptr;
   // lra_side_fork / lra_side_join: further streams for kernels that would only extend a stage's tail on the context's own stream
   static constexpr int N_SIDE = 4;
-  hipStream_t side[N_SIDE] = {}; hipEvent_t ev_fork = nullptr, ev_join[N_SIDE] = {}, ev_mid = nullptr;   // ev_mid: a point on a side stream the main stream waits for (sdp.hip: the large reads' build)
+  hipStream_t side[N_SIDE] = {}; hipEvent_t ev_fork = nullptr, ev_join[N_SIDE] = {}, ev_mid = nullptr;   // ev_mid: a point on a side stream the main stream waits for (sdp.hip, emit_builds: the large reads' build)
   void* gbuf[192] = {};   // growable result / work buffers (lra_ensure)
   size_t gbytes[192] = {};
   // kernel timing
   bool sdp_inner = false;                    // local_refine.hip: its small inner sparse DP is timed under "sdp_inner_*"
   bool sort_short = false;                   // the exact sort: a launch of its own for the short lists (set by the sparse DP around its sorts: hundreds of tuples per list)
-  const char* sort_tag = "sort"; const char* sort_fb_tag = "sort_fallback";   // timing names of the exact-sort kernels (sdp.hip retags them)
+  const char* sort_tag = "sort"; const char* sort_fb_tag = "sort_fallback";   // timing names of the exact-sort kernels (sdp.hip's Retag renames them for the length of a call)
   bool timing = false;
   std::vector<lra_time_rec> recs;
   std::vector<hipEvent_t> free_events;

@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_lds_dma_lane_layout(tmp_path):
-    """sdp_process fetches the next point's sub-problem descriptors with global_load_lds_dwordx4 (lra_amd/csrc/sdp.hip, NODE_FETCH): a lane's 16 bytes must land at
+    """sdp_process fetches the next point's sub-problem descriptors with global_load_lds_dwordx4 (lra_amd/csrc/sdp_process.hip, NODE_FETCH): a lane's 16 bytes must land at
     the LDS base + 16 * lane, and lanes that are switched off must write nothing (the buffers hold 36 slots, the lanes beyond never have a visit)."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     exe = str(tmp_path / "lds_dma")

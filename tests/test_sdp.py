@@ -121,15 +121,8 @@ def _compare(out, num_aln, reads_in, read_lens, opts_kw):
     return n_ok
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("sizes", ["estimated", "outgrown", "counted"])
-def test_hip_sdp_random_clusters(ctx, sizes, monkeypatch):
-    """`sizes`: how a read's blocks are laid out -- from the per-point estimate (the default: no count pass), from estimates so low that most reads outgrow them and
-    are counted and built again, and from the count pass for every read (LRA_SDP_ONEPASS=0)."""
-    if sizes == "outgrown":
-        monkeypatch.setenv("LRA_SDP_ESTIMATE", "2.0,0.5")
-    if sizes == "counted":
-        monkeypatch.setenv("LRA_SDP_ONEPASS", "0")
+def _random_read_mix():
+    """162 reads of 0 .. 599 anchors (0 .. 1298 points; 90 of them below 40 points): the oracle accepts every one under each of _MIX_OPTS"""
     rng = np.random.default_rng(77)
     reads_in = []
     for k in range(160):
@@ -140,7 +133,23 @@ def test_hip_sdp_random_clusters(ctx, sizes, monkeypatch):
     reads_in.insert(5, (np.array([0], np.int32), np.zeros(0, np.uint8), np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.int32)))   # read without clusters
     reads_in.insert(9, (np.array([0, 1], np.int32), np.array([1], np.uint8), np.array([5], np.uint32), np.array([100], np.uint32), np.array([17], np.int32)))
     read_lens = [max(300, int(q.max()) + 200) if len(q) else 300 for (_, _, q, _, _) in reads_in]
-    for kw in (dict(), dict(NumAln=3, alnthres=0.3, rate=3.0), dict(gapopen=4.0, gapextend=20.0, gapCeiling1=3000, gapCeiling2=5000, rate=1.0)):
+    return reads_in, read_lens
+
+
+_MIX_OPTS = (dict(), dict(NumAln=3, alnthres=0.3, rate=3.0), dict(gapopen=4.0, gapextend=20.0, gapCeiling1=3000, gapCeiling2=5000, rate=1.0))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sizes", ["estimated", "outgrown", "counted"])
+def test_hip_sdp_random_clusters(ctx, sizes, monkeypatch):
+    """`sizes`: how a read's blocks are laid out -- from the per-point estimate (the default: no count pass), from estimates so low that most reads outgrow them and
+    are counted and built again, and from the count pass for every read (LRA_SDP_ONEPASS=0)."""
+    if sizes == "outgrown":
+        monkeypatch.setenv("LRA_SDP_ESTIMATE", "2.0,0.5")
+    if sizes == "counted":
+        monkeypatch.setenv("LRA_SDP_ONEPASS", "0")
+    reads_in, read_lens = _random_read_mix()
+    for kw in _MIX_OPTS:
         res, out = _run_hip(ctx, reads_in, read_lens, kw)
         n = _compare(out, res.num_aln, reads_in, read_lens, kw)
         assert n > 40
@@ -312,8 +321,34 @@ def test_hip_sdp_workgroup_kernel(ctx, which, window, monkeypatch):
     assert _compare(out, int(res.num_aln), reads_in, read_lens, kw) >= len(reads_in) - 1
 
 
+@pytest.mark.gpu
+def test_hip_sdp_workgroup_reads_outgrow_their_estimate(ctx, monkeypatch):
+    """The second attempt with workgroup reads in it: the threshold lowered to 40 points (72 of the mix's reads) and estimates that most reads outgrow, so the reads that
+    come back are counted exactly with the large ones on the side stream, built again, and the workgroup launch takes its variant from the counted rows / columns."""
+    monkeypatch.setenv("LRA_SDP_BIG_POINTS", "40")
+    monkeypatch.setenv("LRA_SDP_ESTIMATE", "2.0,0.5")
+    reads_in, read_lens = _random_read_mix()
+    for kw, n_chains in zip(_MIX_OPTS, (81, 133, 71)):                     # (the oracle's chains over the mix, counted on the CPU)
+        res, out = _run_hip(ctx, reads_in, read_lens, kw)
+        assert _compare(out, res.num_aln, reads_in, read_lens, kw) == n_chains
+        assert int((out["status"][:len(reads_in)] == 0).sum()) >= 162      # every read has an oracle result, so _compare skipped none
+
+
+@pytest.mark.gpu
+def test_hip_sdp_workgroup_reads_only(ctx, monkeypatch):
+    """A batch without a single wave-per-read job: every read is above the (lowered) threshold, so nothing is forked -- the large reads' build and their workgroup
+    ProcessPoint launch run on the main stream."""
+    monkeypatch.setenv("LRA_SDP_BIG_POINTS", "40")
+    rng = np.random.default_rng(23)
+    reads_in = [_random_clusters(rng, nc, per, span, ties) for nc, per, span, ties in [(6, 80, 30000, False), (3, 150, 20000, True), (10, 30, 30000, True)]]   # 420, 346, 314 points
+    read_lens = [40000] * len(reads_in)
+    res, out = _run_hip(ctx, reads_in, read_lens, {})
+    assert _compare(out, int(res.num_aln), reads_in, read_lens, {}) == 2   # (the oracle's chains, counted on the CPU)
+    assert int((out["status"][:3] == 0).sum()) >= 3                        # the oracle has a result for all three reads: none skipped
+
+
 def _load_jobs(path):
-    """jobs written by LRA_SDP_DUMP (lra_amd/csrc/sdp.hip): header (mode, clusters, anchors, read length), rate, cluster offsets, strands, q, t, len"""
+    """jobs written by LRA_SDP_DUMP (lra_amd/csrc/sdp_diag.hip, diag_dump): header (mode, clusters, anchors, read length), rate, cluster offsets, strands, q, t, len"""
     b = open(path, "rb").read(); at = 0; jobs = []
     while at < len(b):
         mode, nc, total, rl = (int(x) for x in np.frombuffer(b, np.int32, 4, at)); at += 16
