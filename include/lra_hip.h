@@ -190,6 +190,14 @@ typedef struct lra_seed_result {
 } lra_seed_result;
 int lra_seed_batch(lra_ctx* ctx, int n_reads, const char* d_seq, const uint64_t* d_read_off, int k, int w,
                    int max_freq, lra_seed_result* out);
+/* A caller's match list as the context's current seed result, in the place of lra_seed_batch's: the input of lra_clean_matches_batch (which reads the matches and
+ * nothing else of the seed stage), for tests that craft the matches.  Device arrays, CSR by read, every read's forward-strand matches first (the layout
+ * SeparateMatchesByStrand leaves): d_match_off u64[n_reads + 1] (from 0, not decreasing), d_n_forward u32[n_reads] (<= the read's matches), d_qpos / d_tpos u32[m]
+ * and d_qkey u64[m] (the read minimizer's key, AVGfreq's input), m = d_match_off[n_reads] < 2^32.  Copied device to device on the context's stream into the seed
+ * stage's own arrays (grown as lra_seed_batch grows them); needs neither genome nor index.  `out` (may be NULL): the result as lra_seed_batch reports it, with no
+ * minimizers and zeroed d_match_qi / d_match_ti.  LRA_ERR_INVALID for a malformed CSR.                                                                          */
+int lra_seed_set_matches(lra_ctx* ctx, int n_reads, const uint64_t* d_match_off, const uint32_t* d_n_forward, const uint32_t* d_qpos, const uint32_t* d_tpos,
+                         const uint64_t* d_qkey, lra_seed_result* out);
 
 /* The seeding of the NEXT batch beside the current one.  The per-read path is a chain of launches that are as long as their largest reads: much of a batch's time the
  * device has room, and a1-a4 of the batch after it fit there.  `side` is a second context of the same device that shares the mapping context's reference data

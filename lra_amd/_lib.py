@@ -48,6 +48,7 @@ SYMBOLS = {
     "lra_sort_minimizers_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "lra_sort_pairs_batch": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]),
     "lra_seed_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "lra_seed_set_matches": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lra_map_reads_lowacc_front": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint64, _vp]),
     "lra_map_reads_lowacc_back": (C.c_int, [_vp, _vp, _vp, _vp]),
     "lra_map_back_release": (C.c_int, [_vp]),

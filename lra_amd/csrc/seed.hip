@@ -1507,6 +1507,64 @@ extern "C" int lra_seed_batch(lra_ctx* ctx, int n_reads, const char* d_seq, cons
   return LRA_OK;
 }
 
+// A match list from the caller in the place of a1-a4's: the clean stage (cluster.hip) reads nothing else of the seed state.  Copies only, no kernel.
+extern "C" int lra_seed_set_matches(lra_ctx* ctx, int n_reads, const uint64_t* d_match_off, const uint32_t* d_n_forward, const uint32_t* d_qpos, const uint32_t* d_tpos,
+                                    const uint64_t* d_qkey, lra_seed_result* out) {
+  if (!ctx || n_reads < 0) return LRA_ERR_INVALID;
+  if (n_reads > 0 && (!d_match_off || !d_n_forward)) return lra_set_err(ctx, LRA_ERR_INVALID, "match offsets and forward counts are required");
+  lra_seed_state* s = seed_state(ctx);
+  ctx->ahead.valid = false;                                               // (this call overwrites the buffers of a result adopted ahead of its batch, if there is one)
+  LRA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (out) { memset(out, 0, sizeof(*out)); out->n_reads = n_reads; }
+  s->last_n_reads = 0; s->last_n_matches = 0;
+  if (n_reads == 0) return LRA_OK;
+  // the CSR is checked on the host: the clean stage indexes the match arrays with it
+  std::vector<uint64_t> off((size_t)n_reads + 1);
+  std::vector<uint32_t> nf((size_t)n_reads);
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(off.data(), d_match_off, off.size() * 8, hipMemcpyDeviceToHost, st));
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(nf.data(), d_n_forward, nf.size() * 4, hipMemcpyDeviceToHost, st));
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  if (off[0] != 0) return lra_set_err(ctx, LRA_ERR_INVALID, "match_off[0] must be 0");
+  for (int r = 0; r < n_reads; r++)
+    if (off[r + 1] < off[r] || (uint64_t)nf[r] > off[r + 1] - off[r])
+      return lra_set_err(ctx, LRA_ERR_INVALID, "read %d: match_off must not decrease and n_forward must not exceed the read's matches", r);
+  const uint64_t total_m = off[n_reads];
+  if (total_m >= (1ULL << 32)) return lra_set_err(ctx, LRA_ERR_INVALID, "too many matches (%llu)", (unsigned long long)total_m);
+  if (total_m && (!d_qpos || !d_tpos || !d_qkey)) return lra_set_err(ctx, LRA_ERR_INVALID, "match arrays are required");
+  if ((size_t)n_reads > s->cap_reads) {
+    size_t c = (size_t)n_reads + n_reads / 4 + 64;
+    if (!regrow(s->counts32, c) || !regrow(s->counts64, c) || !regrow(s->mm_off, c + 1) || !regrow(s->match_off, c + 1) ||
+        !regrow(s->n_forward, c) || !regrow(s->cap_cnt, c) || !regrow(s->cap_off, c + 1))
+      { s->cap_reads = 0; return lra_set_err(ctx, LRA_ERR_NOMEM, "per-read arrays"); }
+    s->cap_reads = c;
+  }
+  if (total_m > s->cap_match || !s->sep_qpos) {
+    size_t c = total_m + total_m / 4 + 1024;
+    if (!regrow(s->match_qi, c) || !regrow(s->match_ti, c) || !regrow(s->sep_qpos, c) || !regrow(s->sep_tpos, c) || !regrow(s->sep_qkey, c))
+      { s->cap_match = 0; return lra_set_err(ctx, LRA_ERR_NOMEM, "match arrays (%llu matches)", (unsigned long long)total_m); }
+    s->cap_match = c;
+  }
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(s->match_off, d_match_off, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToDevice, st));
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(s->n_forward, d_n_forward, (size_t)n_reads * 4, hipMemcpyDeviceToDevice, st));
+  LRA_HIP_CHECK(ctx, hipMemsetAsync(s->mm_off, 0, ((size_t)n_reads + 1) * 8, st));   // no minimizers stand behind these matches
+  if (total_m) {
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(s->sep_qpos, d_qpos, total_m * 4, hipMemcpyDeviceToDevice, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(s->sep_tpos, d_tpos, total_m * 4, hipMemcpyDeviceToDevice, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(s->sep_qkey, d_qkey, total_m * 8, hipMemcpyDeviceToDevice, st));
+    LRA_HIP_CHECK(ctx, hipMemsetAsync(s->match_qi, 0, total_m * 4, st));
+    LRA_HIP_CHECK(ctx, hipMemsetAsync(s->match_ti, 0, total_m * 4, st));
+  }
+  s->last_n_reads = n_reads; s->last_n_matches = total_m;
+  if (out) {
+    out->n_matches = total_m;
+    out->d_mm_off = s->mm_off; out->d_mm_key = s->mm_key; out->d_mm_pos = s->mm_pos;
+    out->d_match_off = s->match_off; out->d_match_qi = s->match_qi; out->d_match_ti = s->match_ti;
+    out->d_n_forward = s->n_forward; out->d_sep_qpos = s->sep_qpos; out->d_sep_tpos = s->sep_tpos;
+  }
+  return LRA_OK;
+}
+
 extern "C" int lra_seed_prefetch(lra_ctx* side, int n_reads, const char* d_seq, const uint64_t* d_read_off, int k, int w, int max_freq) {
   if (!side) return LRA_ERR_INVALID;
   side->ahead.valid = false;

@@ -57,6 +57,21 @@ def seed_batch(ctx: Context, batch: ReadBatch, k, w, max_freq):
     return res
 
 
+def set_matches(ctx: Context, match_off, n_forward, qpos, tpos, qkey):
+    """lra_seed_set_matches: host arrays (CSR by read, each read's forward-strand matches first) become the context's current seed result -- the input of
+    cluster.clean_matches_batch.  Needs no genome and no index.  Returns the SeedResult (no minimizers)."""
+    off = np.ascontiguousarray(match_off, dtype=np.uint64)
+    nf = np.ascontiguousarray(n_forward, dtype=np.uint32)
+    q = np.ascontiguousarray(qpos, dtype=np.uint32); t = np.ascontiguousarray(tpos, dtype=np.uint32); k = np.ascontiguousarray(qkey, dtype=np.uint64)
+    assert len(off) == len(nf) + 1 and len(q) == len(t) == len(k)
+    dev = lambda a, view: torch.from_numpy(np.concatenate([a, np.zeros(1, a.dtype)]).view(view)).to(ctx.device)
+    d_off, d_nf, d_q, d_t, d_k = dev(off, np.int64), dev(nf, np.int32), dev(q, np.int32), dev(t, np.int32), dev(k, np.int64)
+    res = SeedResult()
+    ctx.check(ctx.lib.lra_seed_set_matches(ctx.h, len(nf), ptr(d_off), ptr(d_nf), ptr(d_q), ptr(d_t), ptr(d_k), C.byref(res)))
+    torch.cuda.synchronize(ctx.device)                                  # (the copies read the tensors above)
+    return res
+
+
 def seed_prefetch(side: Context, batch: ReadBatch, k, w, max_freq):
     """a1-a4 of a batch AHEAD of its mapping call, on a side context (own host thread, own stream; shares the mapping context's reference data); the mapping
     context takes the result with adopt_seed and its next lra_map_reads_*_batch on the same batch starts from it (include/lra_hip.h: lra_seed_prefetch)."""

@@ -14,6 +14,17 @@
 #include <unordered_map>
 #include <vector>
 
+// Hit counts of the branches below, for the tests that must know which of them their inputs reach (tests/oracle_lib.py: CLEAN_COUNTERS names the slots).
+enum {
+  CC_NO_NEIGHBOUR, CC_MINDIAG_ZERO, CC_RUN_TOO_SHORT,
+  CC_BYPASS_DROP, CC_BYPASS_GE2, CC_BYPASS_GE1_5, CC_BYPASS_KEEP,
+  CC_DROP, CC_GE4, CC_GE1_5, CC_GT1_LONG, CC_GT1_SHORT, CC_KEEP,
+  CC_SR_EXIT_GE_LEN, CC_SR_EXIT_LE_ZERO, CC_SR_EXIT_ONE_MATCH,
+  CC_SR_NONE_LONG, CC_SR_ONE_LONG, CC_SR_SEVERAL_LONG, CC_SR_INNER_SPAN,
+  CC_N
+};
+static long g_clean_hits[CC_N];
+
 namespace {
 struct M { uint32_t q, t; uint64_t key; };
 
@@ -32,11 +43,19 @@ int header_find(const uint64_t* pos, int npos, uint64_t query) {         // Geno
 
 void second_round(std::vector<int>& count, int out_counter, std::vector<M>& m, int MinDiagCluster, int CleanMaxDiag,
                   std::vector<char>& orig, int os, int oe, int strand) { // :802-868
-  if (MinDiagCluster >= oe - os) return;
-  if (MinDiagCluster <= 0) { for (int i = os; i < oe; i++) { orig[i] = 1; count[i] = out_counter; } return; }
-  if (oe - os <= 1) return;
+  if (MinDiagCluster >= oe - os) { g_clean_hits[CC_SR_EXIT_GE_LEN]++; return; }
+  if (MinDiagCluster <= 0) { g_clean_hits[CC_SR_EXIT_LE_ZERO]++; for (int i = os; i < oe; i++) { orig[i] = 1; count[i] = out_counter; } return; }
+  if (oe - os <= 1) { g_clean_hits[CC_SR_EXIT_ONE_MATCH]++; return; }
   std::vector<char> fw(oe - os, 0), rv(oe - os, 0);
   for (int i = os + 1; i < oe; i++) if (std::labs(diag_diff(m[i], m[i - 1], strand)) < CleanMaxDiag) fw[i - 1 - os] = 1;
+  {                                                                      // (counters only) the sub-runs that are long enough, before the passes rewrite the flags
+    int nlong = 0, open = -1;
+    for (int i = os; i < oe; i++) {
+      if (open < 0 && fw[i - os]) open = i;
+      else if (open >= 0 && !fw[i - os]) { if (i - open + 1 >= MinDiagCluster) nlong++; open = -1; }
+    }
+    g_clean_hits[nlong == 0 ? CC_SR_NONE_LONG : nlong == 1 ? CC_SR_ONE_LONG : CC_SR_SEVERAL_LONG]++;
+  }
   bool prev = false; int ds = 0;
   for (int i = os; i < oe; i++) {
     if (!prev && fw[i - os]) ds = i;
@@ -60,8 +79,18 @@ void second_round(std::vector<int>& count, int out_counter, std::vector<M>& m, i
     if (fw[i - os] && rv[i - os]) { orig[i] = 1; count[i] = out_counter; }
     else orig[i] = 0;
   }
+  int first = -1, last = -1;
+  for (int i = os; i < oe; i++) if (orig[i]) { if (first < 0) first = i; last = i; }
+  if (first > os && last >= 0 && last < oe - 1) g_clean_hits[CC_SR_INNER_SPAN]++;
 }
 }  // namespace
+
+// the hit counts since the last reset (CC_N slots)
+extern "C" int oracle_clean_counters(long* out, int reset) {
+  if (out) for (int i = 0; i < CC_N; i++) out[i] = g_clean_hits[i];
+  if (reset) for (int i = 0; i < CC_N; i++) g_clean_hits[i] = 0;
+  return CC_N;
+}
 
 // One strand of one read.  Inputs: the matches (read pos, genome pos, read minimizer key incl. strand
 // bit).  Outputs: cleaned sorted matches (out_q/out_t, capacity n) and clusters (capacity n each).
@@ -95,10 +124,11 @@ extern "C" long oracle_clean_matches(const uint32_t* qpos, const uint32_t* tpos,
     if (prev && !onDiag[i]) largest = std::max(largest, (int)i - diagStart + 1);
     prev = onDiag[i];
   }
-  if (!startSet) return 0;                                               // :600-603
+  if (!startSet) { g_clean_hits[CC_NO_NEIGHBOUR]++; return 0; }          // :600-603
   largest = std::max(largest, (int)n - diagStart);
   int minDiagCluster = (int)std::floor(largest / 10);                    // :608-609
   if (minDiagCluster >= o->minDiagCluster) minDiagCluster = o->minDiagCluster;
+  if (minDiagCluster == 0) g_clean_hits[CC_MINDIAG_ZERO]++;
   std::vector<int> count(n, -1);
   std::vector<char> second(n, 0);
   int counter = 0;
@@ -109,6 +139,7 @@ extern "C" long oracle_clean_matches(const uint32_t* qpos, const uint32_t* tpos,
       if (prev && !onDiag[i]) {
         const int len = (int)i - diagStart + 1;
         if (len < minDiagCluster) {
+          g_clean_hits[CC_RUN_TOO_SHORT]++;
           for (int j = diagStart; j <= i; j++) second[j] = 0;
         } else {
           std::unordered_map<uint64_t, int> mc;                          // AVGfreq :550-564
@@ -118,35 +149,41 @@ extern "C" long oracle_clean_matches(const uint32_t* qpos, const uint32_t* tpos,
           int MinDiagCluster = 0;
           const int cc = o->cleanClustersize;
           if (o->bypassClustering) {                                     // :635-657
-            if (avgfreq >= 3.0f && len < 10) { for (int j = diagStart; j <= i; j++) second[j] = 0; }
+            if (avgfreq >= 3.0f && len < 10) { g_clean_hits[CC_BYPASS_DROP]++; for (int j = diagStart; j <= i; j++) second[j] = 0; }
             else if (avgfreq >= 2.0f && len >= cc) {
+              g_clean_hits[CC_BYPASS_GE2]++;
               MinDiagCluster = o->SecondCleanMinDiagCluster + std::floor((avgfreq - 1.5f) / 1.0f) * o->punish_anchorfreq +
                                std::floor((len - cc) / cc) * o->anchorPerlength;
               second_round(count, counter, m, MinDiagCluster, o->SecondCleanMaxDiag, second, diagStart, (int)i + 1, strand);
             } else if (avgfreq >= 1.5f && len >= cc) {
+              g_clean_hits[CC_BYPASS_GE1_5]++;
               MinDiagCluster = o->SecondCleanMinDiagCluster + std::floor((avgfreq - 1.5f) / 1.5f) * o->punish_anchorfreq +
                                std::floor((len - cc) / cc) * o->anchorPerlength;
               second_round(count, counter, m, MinDiagCluster, o->SecondCleanMaxDiag, second, diagStart, (int)i + 1, strand);
-            } else { for (int j = diagStart; j <= i; j++) { second[j] = 1; count[j] = counter; } }
+            } else { g_clean_hits[CC_BYPASS_KEEP]++; for (int j = diagStart; j <= i; j++) { second[j] = 1; count[j] = counter; } }
           } else {                                                       // :659-693
-            if (avgfreq >= 3.0f && len < 10) { for (int j = diagStart; j <= i; j++) second[j] = 0; }
+            if (avgfreq >= 3.0f && len < 10) { g_clean_hits[CC_DROP]++; for (int j = diagStart; j <= i; j++) second[j] = 0; }
             else if (avgfreq >= 4.0f && len >= cc) {
+              g_clean_hits[CC_GE4]++;
               MinDiagCluster = o->SecondCleanMinDiagCluster + std::floor((avgfreq - 1.5f) / 1.0f) * o->punish_anchorfreq +
                                std::floor((len - cc) / cc) * o->anchorPerlength;
               second_round(count, counter, m, MinDiagCluster, o->SecondCleanMaxDiag, second, diagStart, (int)i + 1, strand);
             } else if (avgfreq >= 1.5f && len >= cc) {
+              g_clean_hits[CC_GE1_5]++;
               MinDiagCluster = o->SecondCleanMinDiagCluster + std::floor((avgfreq - 1.5f) / 1.5f) * o->punish_anchorfreq +
                                std::floor((len - cc) / cc) * o->anchorPerlength;
               second_round(count, counter, m, MinDiagCluster, o->SecondCleanMaxDiag, second, diagStart, (int)i + 1, strand);
             } else if (avgfreq > 1.0f && len >= cc) {
+              g_clean_hits[CC_GT1_LONG]++;
               MinDiagCluster = o->SecondCleanMinDiagCluster - (5 - std::floor((avgfreq - 1.0f) / 0.1f)) * (o->punish_anchorfreq / 2) +
                                std::floor((len - cc) / cc) * (o->anchorPerlength / 2);
               second_round(count, counter, m, MinDiagCluster, o->SecondCleanMaxDiag, second, diagStart, (int)i + 1, strand);
             } else if (avgfreq > 1.0f) {
+              g_clean_hits[CC_GT1_SHORT]++;
               MinDiagCluster = o->SecondCleanMinDiagCluster - (5 - std::floor((avgfreq - 1.0f) / 0.1f)) * (o->punish_anchorfreq / 2) -
                                std::floor((cc - (int)i + diagStart - 1) / 15) * (o->anchorPerlength / 2);
               second_round(count, counter, m, MinDiagCluster, o->SecondCleanMaxDiag, second, diagStart, (int)i + 1, strand);
-            } else { for (int j = diagStart; j <= i; j++) { second[j] = 1; count[j] = counter; } }
+            } else { g_clean_hits[CC_KEEP]++; for (int j = diagStart; j <= i; j++) { second[j] = 1; count[j] = counter; } }
           }
         }
         counter++;

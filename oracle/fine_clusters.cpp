@@ -24,6 +24,19 @@ extern "C" long oracle_clean_matches(const uint32_t* qpos, const uint32_t* tpos,
 
 struct oracle_fine_opts { int globalK, RoughClustermaxGap, maxDiag, maxGap, minClusterSize, minUniqueStretchNum, minUniqueStretchDist; };
 
+// Hit counts of the branches below, for the tests that must know which of them their inputs reach (tests/oracle_lib.py: FINE_COUNTERS names the slots).
+enum {
+  FC_FREQ_GE10, FC_MERGE, FC_PUSH, FC_FREQ_ONE, FC_FREQ_ONE_POP_CHROM, FC_ONE_GROUP, FC_WHOLE_SPLIT, FC_BACKWARD_PICK, FC_FORWARD_PICK, FC_LEFTOVER,
+  FC_POP_CHROM, FC_POP_SIZE, FC_POP_QSPAN_ZERO, FC_POP_RATIO, FC_LEFTOVER_POP_CHROM, FC_LEFTOVER_POP_RATIO, FC_UB_EMPTY, FC_UB_QSPAN_ZERO,
+  FC_N
+};
+static long g_fine_hits[FC_N];
+extern "C" int oracle_fine_counters(long* out, int reset) {
+  if (out) for (int i = 0; i < FC_N; i++) out[i] = g_fine_hits[i];
+  if (reset) for (int i = 0; i < FC_N; i++) g_fine_hits[i] = 0;
+  return FC_N;
+}
+
 namespace {
 
 struct Mt { uint32_t q, t; };
@@ -71,6 +84,7 @@ void split_rough(const std::vector<Mt>& m, int start, int end, int strand, float
                  const oracle_fine_opts& o) {
   if (end - start == 0) return;
   if (anchorfreq >= 10.0f) {
+    g_fine_hits[FC_FREQ_GE10]++;
     Split s{start, end, bq0, bq1, bt0, bt1, strand, anchorfreq, {}};
     for (int q = start; q < end; q++) s.idx.push_back(q);
     split.push_back(std::move(s));
@@ -83,11 +97,13 @@ void split_rough(const std::vector<Mt>& m, int start, int end, int strand, float
     // (the chromIndex tests of :1388 / :1392 compare values that are all -1 on this path; the final call :1420 has no such test)
     (void)lastCall;
     if (split.size() > cur_s && close_to_previous(split.back(), sq0, st0, st1, o)) {                       // MergeTwoClusters :1351-1355
+      g_fine_hits[FC_MERGE]++;
       Split& a = split.back();
       a.qStart = std::min(a.qStart, sq0); a.qEnd = std::max(a.qEnd, sq1); a.tStart = std::min(a.tStart, st0); a.tEnd = std::max(a.tEnd, st1);
       for (int q = split_cs; q < e; q++) a.idx.push_back(q);
       a.end = e;
     } else {
+      g_fine_hits[FC_PUSH]++;
       Split s{split_cs, e, sq0, sq1, st0, st1, strand, anchorfreq, {}};
       for (int q = split_cs; q < e; q++) s.idx.push_back(q);
       split.push_back(std::move(s));
@@ -114,11 +130,12 @@ void store_fine(const std::vector<Mt>& m, const Split& sp, std::vector<FCluster>
   if (smi.size() == 1) return;
   auto M = [&](int i) -> const Mt& { return m[smi[i]]; };
   if (std::fabs(anchorfreq - 1.0f) <= 0.005) {                             // :900-942
+    g_fine_hits[FC_FREQ_ONE]++;
     clusters.push_back(FCluster()); clusters.back().strand = strand;
     for (size_t i = 0; i < smi.size(); i++) clusters.back().matches.push_back(M((int)i));
     set_bounds(clusters.back(), K);
     clusters.back().chromIndex = ri; clusters.back().anchorfreq = 1.0f;
-    if (chrom_index(clusters.back(), pos, npos)) clusters.pop_back();
+    if (chrom_index(clusters.back(), pos, npos)) { g_fine_hits[FC_FREQ_ONE_POP_CHROM]++; clusters.pop_back(); }
     return;
   }
   std::vector<int> match_num, pos_start;                                   // :948-965
@@ -130,7 +147,7 @@ void store_fine(const std::vector<Mt>& m, const Split& sp, std::vector<FCluster>
   }
   int u_start = 0, u_end = 0, u_maxstart = 0, u_maxend = 0, max_pos = 0;
   std::vector<int> Start, End;
-  if (match_num.size() == 1) { u_maxstart = 0; u_maxend = 1; Start.push_back(0); End.push_back(1); }          // :972-978
+  if (match_num.size() == 1) { g_fine_hits[FC_ONE_GROUP]++; u_maxstart = 0; u_maxend = 1; Start.push_back(0); End.push_back(1); }          // :972-978
   else {
     int k = 0;
     const int nm = (int)match_num.size();
@@ -150,6 +167,7 @@ void store_fine(const std::vector<Mt>& m, const Split& sp, std::vector<FCluster>
   clusters.push_back(FCluster()); clusters.back().strand = strand;
   std::vector<char> AddOrNot(Start.size(), 0);
   if (c_e - c_s == (int)smi.size()) {                                      // :1051-1057
+    g_fine_hits[FC_WHOLE_SPLIT]++;
     for (int i = c_s; i < c_e; i++) clusters.back().matches.push_back(M(i));
     clusters.back().anchorfreq = anchorfreq;
     AddOrNot[0] = 1;
@@ -163,14 +181,14 @@ void store_fine(const std::vector<Mt>& m, const Split& sp, std::vector<FCluster>
       StretchOfOne.push_back(max_pos); AddOrNot[max_pos] = 1;
       for (int i = max_pos - 1; i >= 0; i--) {
         const int i_m = pos_start[End[i] - 1];
-        if (near_(i_m, prev_anchor)) { StretchOfOne.push_back(i); AddOrNot[i] = 1; prev_anchor = pos_start[Start[i]]; }
+        if (near_(i_m, prev_anchor)) { g_fine_hits[FC_BACKWARD_PICK]++; StretchOfOne.push_back(i); AddOrNot[i] = 1; prev_anchor = pos_start[Start[i]]; }
       }
     }
     prev_anchor = c_e - 1;                                                 // :1081-1099 towards the end
     if (max_pos < (int)Start.size()) {
       for (int i = max_pos + 1; i < (int)Start.size(); i++) {
         const int i_m = pos_start[Start[i]];
-        if (near_(i_m, prev_anchor)) { StretchOfOne.push_front(i); AddOrNot[i] = 1; prev_anchor = pos_start[End[i] - 1]; }
+        if (near_(i_m, prev_anchor)) { g_fine_hits[FC_FORWARD_PICK]++; StretchOfOne.push_front(i); AddOrNot[i] = 1; prev_anchor = pos_start[End[i] - 1]; }
       }
     }
     int prev_stretch = -1, p_s = 0, p_e = 0;
@@ -199,22 +217,23 @@ void store_fine(const std::vector<Mt>& m, const Split& sp, std::vector<FCluster>
   clusters.back().chromIndex = ri;
   if (!clusters.empty()) {                                                 // :1282-1295
     FCluster& b = clusters.back();
-    if (chrom_index(b, pos, npos)) clusters.pop_back();
-    else if ((long)b.matches.size() <= o.minClusterSize) clusters.pop_back();
-    else if (b.qEnd == b.qStart) clusters.pop_back();
-    else if ((long)b.tEnd - (long)b.tStart >= 5 * ((long)b.qEnd - (long)b.qStart)) clusters.pop_back();
+    if (chrom_index(b, pos, npos)) { g_fine_hits[FC_POP_CHROM]++; clusters.pop_back(); }
+    else if ((long)b.matches.size() <= o.minClusterSize) { g_fine_hits[FC_POP_SIZE]++; clusters.pop_back(); }
+    else if (b.qEnd == b.qStart) { g_fine_hits[FC_POP_QSPAN_ZERO]++; clusters.pop_back(); }
+    else if ((long)b.tEnd - (long)b.tStart >= 5 * ((long)b.qEnd - (long)b.qStart)) { g_fine_hits[FC_POP_RATIO]++; clusters.pop_back(); }
   }
   for (size_t ar = 0; ar < AddOrNot.size(); ar++) {                         // :1297-1323 the long stretches that were left out
     if (!AddOrNot[ar] && End[ar] - Start[ar] >= 15) {
+      g_fine_hits[FC_LEFTOVER]++;
       clusters.push_back(FCluster()); clusters.back().strand = strand;
       for (int i = pos_start[Start[ar]]; i < pos_start[End[ar] - 1] + 1; i++) clusters.back().matches.push_back(M(i));
       set_bounds(clusters.back(), K);
       clusters.back().chromIndex = ri; clusters.back().anchorfreq = anchorfreq;
-      if (chrom_index(clusters.back(), pos, npos)) clusters.pop_back();
-      if (clusters.empty()) { ub = 1; return; }                            // :1305 reads clusters.back() of an empty vector
+      if (chrom_index(clusters.back(), pos, npos)) { g_fine_hits[FC_LEFTOVER_POP_CHROM]++; clusters.pop_back(); }
+      if (clusters.empty()) { g_fine_hits[FC_UB_EMPTY]++; ub = 1; return; }                            // :1305 reads clusters.back() of an empty vector
       const FCluster& b = clusters.back();
-      if ((long)b.qEnd - (long)b.qStart == 0) { ub = 1; return; }
-      if (((long)b.tEnd - (long)b.tStart) / ((long)b.qEnd - (long)b.qStart) >= 5) clusters.pop_back();
+      if ((long)b.qEnd - (long)b.qStart == 0) { g_fine_hits[FC_UB_QSPAN_ZERO]++; ub = 1; return; }
+      if (((long)b.tEnd - (long)b.tStart) / ((long)b.qEnd - (long)b.qStart) >= 5) { g_fine_hits[FC_LEFTOVER_POP_RATIO]++; clusters.pop_back(); }
     }
   }
 }

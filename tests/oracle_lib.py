@@ -155,6 +155,34 @@ def clean_matches(qpos, tpos, qkey, strand, opts: "CleanOpts", chrom_pos):
                                               tStart=ts[:ncl].copy(), tEnd=te[:ncl].copy(), chrom=ch[:ncl].copy(), freq=fr[:ncl].copy())
 
 
+# the slots of oracle_clean_counters (oracle/clustering.cpp: enum CC_*), in order
+CLEAN_COUNTERS = ["no_neighbour", "min_diag_zero", "run_too_short",
+                  "bypass_drop", "bypass_ge2", "bypass_ge1_5", "bypass_keep",
+                  "drop", "ge4", "ge1_5", "gt1_long", "gt1_short", "keep",
+                  "sr_exit_ge_len", "sr_exit_le_zero", "sr_exit_one_match",
+                  "sr_none_long", "sr_one_long", "sr_several_long", "sr_inner_span"]
+# the slots of oracle_fine_counters (oracle/fine_clusters.cpp: enum FC_*), in order
+FINE_COUNTERS = ["freq_ge10", "merge", "push", "freq_one", "freq_one_pop_chrom", "one_group", "whole_split", "backward_pick", "forward_pick", "leftover",
+                 "pop_chrom", "pop_size", "pop_qspan_zero", "pop_ratio", "leftover_pop_chrom", "leftover_pop_ratio", "ub_empty", "ub_qspan_zero"]
+
+
+def _counters(fn, names, reset):
+    out = np.zeros(len(names), dtype=np.int64)
+    n = fn(_p(out, C.c_long), 1 if reset else 0)
+    assert n == len(names), (n, len(names))
+    return dict(zip(names, out.tolist()))
+
+
+def clean_counters(reset=False):
+    """Hit counts of the branches of oracle_clean_matches since the last reset (a process-wide table; the fine-cluster oracle runs the clean stage too)."""
+    return _counters(lib().oracle_clean_counters, CLEAN_COUNTERS, reset)
+
+
+def fine_counters(reset=False):
+    """Hit counts of the branches of oracle_matches_to_fine_clusters since the last reset."""
+    return _counters(lib().oracle_fine_counters, FINE_COUNTERS, reset)
+
+
 def linear_extend_cluster(q, t, strand, box, prev_box, next_box, anchorfreq, read: bytes, chrom: bytes, K=17, skiprepetitive=True, trim=False):
     """One chain element of the cluster version of LinearExtend (LinearExtend.h:136-352); t relative to the chromosome.
     -> dict(q, t, len, overlap, box, sorted_q, sorted_t)"""
