@@ -1273,6 +1273,33 @@ int lra_reads_set_device_chunk(lra_reads* r, uint64_t bytes);
 int lra_reads_set_flag_remove(lra_reads* r, uint32_t flags);
 int lra_reads_set_passthrough(lra_reads* r, int on);
 int lra_reads_batch_tags(const lra_reads* r, const char* const** tags);
+/* What a batch of lra_reads_next_batch_device keeps on the device besides its bases (additive to ABI 9; mode 0, the default, is the reader as it was).
+ * Only before the first batch (after it: LRA_ERR_INVALID, as lra_reads_set_flag_remove); bits outside the two below: LRA_ERR_INVALID.  It is a setter and
+ * no bit of lra_reads_open_flags, which refuses every flag but LRA_READS_COMPRESSED_TEXT as before.
+ *   LRA_READS_DEV_QUAL     every batch also leaves its qualities on the device: lra_reads_batch_device_quals gives d_qual and d_qual_off[n_reads + 1], owned
+ *                          by the reader and valid until the next call on r.  Read i's qualities are d_qual[d_qual_off[i], d_qual_off[i + 1]), as they are
+ *                          in batch->quals[i]; the range is empty for a read without (FASTA, a BAM record with 0xff qualities, SAM '*') -- exactly what
+ *                          lra_map_records_device takes as d_qual / d_qual_off (64 zero bytes lie behind the last string).  The bytes never touch the
+ *                          host: every run of a step's records goes from the step's buffer to d_qual through lra_pack_strings_batch's kernel; records
+ *                          the device form parses on the host (SAM text) have theirs uploaded into the same array.  A batch that ends in an error has
+ *                          the ranges of exactly the reads it holds.  The host arrays of the batch are unchanged.  Cost: one byte of device memory per
+ *                          base of the batch on top of d_seq (0.86 GB for a batch of 0.86 G bases).
+ *   LRA_READS_DEV_NO_HOST  for a caller that reads neither the bases nor the qualities on the host (lra_map_records_device with formats 's' / 'P' / 'a').
+ *                          Requires LRA_READS_DEV_QUAL (without it: LRA_ERR_INVALID).  The device-to-host copies of bases and qualities and the
+ *                          page-locked buffers behind them are skipped: batch->seq is NULL, every batch->reads[i] is NULL, and batch->quals[i] is NULL
+ *                          for a read without qualities, else a stub -- the string's first byte (none for an empty string) and a NUL, which is all
+ *                          lra_map_records_device reads of it.  Names, off, read_len, tags, the batch cut and every error rule and text stay as they are.
+ * lra_reads_batch_device_quals: LRA_ERR_INVALID on a reader without LRA_READS_DEV_QUAL, on one that uses lra_reads_next_batch, and before the first batch. */
+#define LRA_READS_DEV_QUAL 1
+#define LRA_READS_DEV_NO_HOST 2
+int lra_reads_set_device_resident(lra_reads* r, uint32_t mode);
+int lra_reads_batch_device_quals(const lra_reads* r, const char** d_qual, const uint64_t** d_qual_off);
+/* n strings that lie anywhere in one device buffer, packed back to back (additive to ABI 9): string i is the d_dst_off[i + 1] - d_dst_off[i] bytes at
+ * d_src + d_src_pos[i] and goes to d_dst + d_dst_off[i]; d_dst_off[n + 1] ascends from d_dst_off[0] = 0 (another value: LRA_ERR_INVALID).  Exactly
+ * d_dst[0, d_dst_off[n]) is written.  Of the source, the aligned 4-byte words that hold a byte of a string are read and nothing else (a source range and
+ * the destination must not overlap).  One wave per 4096 bytes of OUTPUT, whatever the strings' lengths: a string of 1 MB is 256 waves, 20 strings of 200
+ * bytes are one.  n = 0 and empty strings are legal.  Device arrays, on ctx's device and stream, complete at return. */
+int lra_pack_strings_batch(lra_ctx* ctx, uint64_t n, const char* d_src, const uint64_t* d_src_pos, const uint64_t* d_dst_off, char* d_dst);
 /* BGZF inflate (the SAM/BAM spec's section 4.1; RFC 1951 / 1952), the stage the BAM reader runs: member i is in[in_off[i], in_off[i + 1]) -- a gzip
  * member with a 'BC' field whose BSIZE + 1 is its length --, its data goes to out[out_off[i], out_off[i + 1]), which must be its ISIZE (<= 65536).
  * status[i]: 0, or the reason the member is bad (1 header, 2 data ends early, 3 more than ISIZE, 4 invalid code, 5 distance before the block, 6 stored
@@ -1368,8 +1395,8 @@ int lra_map_records_host_tags(lra_map_host* snap, const lra_map_opts* opts, cons
  *           [first_block_qpos, last_block_qend), PrintSAM's own quirk), MD:Z from lra_md_strings_batch.  A count pass over the pieces, a scan, one
  *           copy pass cut by OUTPUT bytes, one device-to-host copy of the text into a page-locked buffer the context keeps.
  * quals (host, nullable, entries NULL or starting with '*': the field is "*") says which reads HAVE qualities; the host reads a string's first byte
- * only.  d_qual == NULL: the qualities of the reads that need them are uploaded from quals (the readers hand qualities over on the host today); with
- * d_qual the host strings are not read behind their first byte.  reads (host) is read by the fall-through formats only and may be NULL for 's' / 'P' / 'a':
+ * only.  d_qual == NULL: the qualities of the reads that need them are uploaded from quals; a device reader with LRA_READS_DEV_QUAL hands over d_qual / d_qual_off
+ * themselves (lra_reads_batch_device_quals), and with d_qual the host strings are not read behind their first byte.  reads (host) is read by the fall-through formats only and may be NULL for 's' / 'P' / 'a':
  * SEQ is the bases the batch was mapped from (d_strands), which the readers hand over upper-cased as they uploaded them.  passthrough: NULL, or one
  * text per read (NULL entries: none), as lra_map_records_tags takes them.  Flagged, handed-back and unaligned reads follow lra_map_records_host's rules
  * (an unaligned read's quality string is written as it is, a leading '*' too, as SimplePrintSAM does; one that is shorter than its read -- "*" -- is

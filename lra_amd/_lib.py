@@ -73,6 +73,9 @@ SYMBOLS = {
     "lra_reads_set_flag_remove": (C.c_int, [_vp, C.c_uint32]),
     "lra_reads_set_passthrough": (C.c_int, [_vp, C.c_int]),
     "lra_reads_batch_tags": (C.c_int, [_vp, _vp]),
+    "lra_reads_set_device_resident": (C.c_int, [_vp, C.c_uint32]),
+    "lra_reads_batch_device_quals": (C.c_int, [_vp, _vp, _vp]),
+    "lra_pack_strings_batch": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, _vp]),
     "lra_bgzf_inflate_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lra_bgzf_inflate_lut_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lra_bgzf_inflate_host": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp]),

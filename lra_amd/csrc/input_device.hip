@@ -25,7 +25,12 @@
 //     A fault ends the file's steps: the step in front of it is parsed as one that the file goes on behind (whole records only), then the error stands.
 //   batch   the records a batch takes are contiguous runs of a step's records: their bases are copied device to device into the reader's d_seq (64 zero
 //           bytes behind the last), their names / qualities / bases once to page-locked host arrays.
+//   lra_reads_set_device_resident: with LRA_READS_DEV_QUAL a batch keeps its qualities on the device too -- every segment's strings go from the step's
+//           c_qual (one NUL slot behind every record) to the reader's d_qual back to back (lra_pack_strings_launch, pack_strings.hip), the ranges
+//           d_qual_off come from the host's record walk as d_off does; with LRA_READS_DEV_NO_HOST the copies of bases and qualities to the host are
+//           skipped: the batch's quals are stubs (rd_first_qual: every string's first byte).
 #include "common.h"
+#include "chunk_copy.h"
 #include "reads_state.h"
 #include "scan.h"
 #include "zsource.h"
@@ -182,6 +187,14 @@ __global__ void rd_name_emit(const unsigned char* __restrict__ raw, uint64_t n_r
   rec[r].name = o;
 }
 
+// LRA_READS_DEV_NO_HOST: per read the first byte of its quality string (0 for an empty one): what the host keeps of the qualities
+__global__ void rd_first_qual(uint64_t n, const char* __restrict__ d_qual, const uint64_t* __restrict__ d_qual_off, char* __restrict__ first) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const uint64_t a = d_qual_off[r];
+  first[r] = d_qual_off[r + 1] > a ? d_qual[a] : (char)0;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -218,6 +231,16 @@ struct lra_reads_dev {
   // the batch
   DevBuf<char> d_seq; DevBuf<uint64_t> d_off;
   PinBuf<char> h_seq, h_names, h_quals;
+  // lra_reads_set_device_resident: the batch's qualities back to back on the device (+ 64 bytes: the record stage reads aligned dwords), their ranges,
+  // a segment's table for the packing pass (its strings' ends from 0, then their places in c_qual), and with LRA_READS_DEV_NO_HOST the strings' first bytes
+  uint32_t resident = 0;
+  bool batch_made = false;                         // a batch has been read: lra_reads_batch_device_quals has something to give
+  DevBuf<char> d_qual; DevBuf<uint64_t> d_qual_off, d_seg; DevBuf<char> d_first;
+  PinBuf<char> h_first; PinBuf<uint64_t> h_seg;
+  std::vector<uint64_t> dq_off;                    // d_qual_off on the host
+  std::vector<char> stub;                          // LRA_READS_DEV_NO_HOST: two bytes per read, its quality string's first byte and a NUL
+  std::string h_pendq; std::vector<uint64_t> pendq_at;   // the qualities of records parsed on the host: uploaded at the batch's end, as h_pend is
+  uint64_t b_dq = 0;                               // the batch's bytes of d_qual so far
   std::vector<uint64_t> off, name_off_h, qual_off_h;
   std::vector<int32_t> len_h;
   std::vector<uint8_t> hasq;
@@ -246,6 +269,7 @@ struct lra_reads_dev {
     z.release(); rec_pos.release(); bam_out.release();
     for (int i = 0; i < 5; i++) { bcnt[i].release(); boffs[i].release(); }
     first_bad.release(); c_aux.release();
+    d_qual.release(); d_qual_off.release(); d_seg.release(); d_first.release(); h_first.release(); h_seg.release();
   }
 };
 
@@ -308,15 +332,37 @@ bool open_dev_file(lra_reads* r) {
   return d->type >= 0;
 }
 
-int grow_batch_seq(lra_ctx* ctx, lra_reads_dev* d, uint64_t want) {
-  if (want <= d->d_seq.n) return LRA_OK;
-  const size_t m = std::max((size_t)want, d->d_seq.n * 2);
+// a batch array on the device grown to `want` bytes, its first `used` bytes kept
+int grow_batch_bytes(lra_ctx* ctx, DevBuf<char>& buf, uint64_t used, uint64_t want) {
+  if (want <= buf.n) return LRA_OK;
+  const size_t m = std::max((size_t)want, buf.n * 2);
   char* q = nullptr;
   if (hipMalloc((void**)&q, m) != hipSuccess) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipMalloc(%zu) failed", m);
-  if (d->b_seq) LRA_HIP_CHECK(ctx, hipMemcpyAsync(q, d->d_seq.p, d->b_seq, hipMemcpyDeviceToDevice, ctx->stream));
+  if (used) LRA_HIP_CHECK(ctx, hipMemcpyAsync(q, buf.p, used, hipMemcpyDeviceToDevice, ctx->stream));
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (d->d_seq.p) (void)hipFree(d->d_seq.p);
-  d->d_seq.p = q; d->d_seq.n = m;
+  if (buf.p) (void)hipFree(buf.p);
+  buf.p = q; buf.n = m;
+  return LRA_OK;
+}
+int grow_batch_seq(lra_ctx* ctx, lra_reads_dev* d, uint64_t want) { return grow_batch_bytes(ctx, d->d_seq, d->b_seq, want); }
+
+// LRA_READS_DEV_QUAL: the quality strings of the step's records [a, b) behind the batch's in d_qual.  The segment's table goes up through a page-locked
+// buffer of its own; the stream is drained first, since the last segment's table may still be in flight through it (a batch takes a run per step or file).
+int pack_segment_quals(lra_ctx* ctx, lra_reads_dev* d, uint64_t a, uint64_t b) {
+  const uint64_t m = b - a, nq = d->rec[b].qual - d->rec[a].qual;
+  if (!nq) return LRA_OK;
+  if (int rc = grow_batch_bytes(ctx, d->d_qual, d->b_dq, d->b_dq + nq + 64)) return rc;
+  LRA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));           // the last segment's table has been read
+  if (!d->h_seg.ensure(2 * m + 1, 0, ctx->stream) || !d->d_seg.ensure(2 * m + 1)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: allocation failed");
+  uint64_t* end = d->h_seg.p; uint64_t* pos = end + m + 1;
+  for (uint64_t i = 0; i < m; i++) { end[i] = d->rec[a + i].qual - d->rec[a].qual; pos[i] = d->rec[a + i].qual + a + i; }
+  end[m] = nq;
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_seg.p, d->h_seg.p, (2 * m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  lra_time_begin(ctx, "input_pack_quals");
+  lra_pack_strings_launch(ctx->stream, ctx->num_cu, m, d->c_qual.p, d->d_seg.p + m + 1, d->d_seg.p, d->d_qual.p + d->b_dq, nq);
+  lra_time_end(ctx);
+  LRA_HIP_CHECK(ctx, hipGetLastError());
+  d->b_dq += nq;
   return LRA_OK;
 }
 
@@ -332,7 +378,11 @@ int flush_segment(lra_ctx* ctx, lra_reads_dev* d) {
   if (ns) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_seq.p + d->b_seq, d->c_seq.p + A.seq, ns, hipMemcpyDeviceToDevice, ctx->stream));
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->h_names.p + d->b_names, d->c_names.p + A.name, nn, hipMemcpyDeviceToHost, ctx->stream));
   d->b_seq += ns; d->b_names += nn;
-  if (d->type == LRA_IN_FASTQ || d->type == LRA_IN_BAM) {
+  const bool has_quals = d->type == LRA_IN_FASTQ || d->type == LRA_IN_BAM;
+  if (has_quals && (d->resident & LRA_READS_DEV_QUAL))
+    if (int rc = pack_segment_quals(ctx, d, a, b)) return rc;
+  if (d->resident & LRA_READS_DEV_NO_HOST) return LRA_OK;           // (the host keeps a stub per read: made at the batch's end)
+  if (has_quals) {
     const uint64_t nq = (B.qual + b) - (A.qual + a);
     if (!d->h_quals.ensure(d->b_quals + nq, d->b_quals, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc failed");
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->h_quals.p + d->b_quals, d->c_qual.p + A.qual + a, nq, hipMemcpyDeviceToHost, ctx->stream));
@@ -726,6 +776,9 @@ extern "C" int lra_reads_next_batch_device(lra_reads* r, lra_ctx* ctx, uint64_t 
   d->seg_a = d->seg_b = d->next;
   d->off.assign(1, 0); d->name_off_h.assign(1, 0); d->qual_off_h.assign(1, 0); d->len_h.clear(); d->hasq.clear();
   d->h_pend.clear(); d->pend_at.clear();
+  d->b_dq = 0; d->dq_off.assign(1, 0); d->h_pendq.clear(); d->pendq_at.clear();
+  d->batch_made = true;
+  const bool dev_qual = d->resident & LRA_READS_DEV_QUAL, no_host = d->resident & LRA_READS_DEV_NO_HOST;
   r->tags.clear(); r->tag_ptr.clear();
   std::vector<uint8_t> hast;
   uint64_t total = 0;
@@ -738,10 +791,17 @@ extern "C" int lra_reads_next_batch_device(lra_reads* r, lra_ctx* ctx, uint64_t 
     if (host) {                                                    // a SAM record: its bytes straight into the batch's arrays
       const uint64_t sl = hrec.seq.size(), nn = hrec.name.size() + 1, nq = hrec.qual.size() + 1;
       if (int rc = grow_batch_seq(ctx, d, d->b_seq + sl + 64)) return rc;
-      if (!d->h_names.ensure(d->b_names + nn, d->b_names, ctx->stream) || !d->h_quals.ensure(d->b_quals + nq, d->b_quals, ctx->stream))
+      if (!d->h_names.ensure(d->b_names + nn, d->b_names, ctx->stream) || (!no_host && !d->h_quals.ensure(d->b_quals + nq, d->b_quals, ctx->stream)))
         return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: hipHostMalloc failed");
       memcpy(d->h_names.p + d->b_names, hrec.name.c_str(), nn);
-      memcpy(d->h_quals.p + d->b_quals, hrec.qual.c_str(), nq);
+      if (!no_host) memcpy(d->h_quals.p + d->b_quals, hrec.qual.c_str(), nq);
+      if (dev_qual) {                                              // (a record without qualities has an empty string here)
+        if (int rc = grow_batch_bytes(ctx, d->d_qual, d->b_dq, d->b_dq + hrec.qual.size() + 64)) return rc;
+        d->pendq_at.push_back(d->b_dq); d->pendq_at.push_back(d->h_pendq.size()); d->pendq_at.push_back(hrec.qual.size());
+        d->h_pendq += hrec.qual;
+        d->b_dq += hrec.qual.size();
+        d->dq_off.push_back(d->b_dq);
+      }
       d->pend_at.push_back(d->b_seq); d->pend_at.push_back(d->h_pend.size()); d->pend_at.push_back(sl);
       d->h_pend += hrec.seq;
       d->b_seq += sl; d->b_names += nn; d->b_quals += nq;
@@ -767,6 +827,7 @@ extern "C" int lra_reads_next_batch_device(lra_reads* r, lra_ctx* ctx, uint64_t 
     d->qual_off_h.push_back(d->qual_off_h.back() + (d->type != LRA_IN_FASTA ? (c.qual - a.qual) + 1 : 1));
     d->len_h.push_back((int32_t)sl);
     d->hasq.push_back(d->type == LRA_IN_FASTQ || (d->type == LRA_IN_BAM && (a.flags & 1)));
+    if (dev_qual) d->dq_off.push_back(d->dq_off.back() + (d->type != LRA_IN_FASTA ? c.qual - a.qual : 0));
   }
   if (int rc = flush_segment(ctx, d)) return rc;
   const size_t n = d->len_h.size();
@@ -774,23 +835,66 @@ extern "C" int lra_reads_next_batch_device(lra_reads* r, lra_ctx* ctx, uint64_t 
   if (int rc = grow_batch_seq(ctx, d, total + 64)) return rc;
   for (size_t k = 0; k < d->pend_at.size(); k += 3)               // the SAM records' bases
     if (d->pend_at[k + 2]) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_seq.p + d->pend_at[k], d->h_pend.data() + d->pend_at[k + 1], d->pend_at[k + 2], hipMemcpyHostToDevice, ctx->stream));
-  if (!d->d_off.ensure(n + 1) || !d->h_seq.ensure(total + 64, 0, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: allocation failed");
-  if (!d->h_names.ensure(d->b_names + 1, d->b_names, ctx->stream) || !d->h_quals.ensure(d->b_quals + 1, d->b_quals, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: allocation failed");
+  if (!d->d_off.ensure(n + 1) || (!no_host && !d->h_seq.ensure(total + 64, 0, ctx->stream))) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: allocation failed");
+  if (!d->h_names.ensure(d->b_names + 1, d->b_names, ctx->stream) || (!no_host && !d->h_quals.ensure(d->b_quals + 1, d->b_quals, ctx->stream)))
+    return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: allocation failed");
   LRA_HIP_CHECK(ctx, hipMemsetAsync(d->d_seq.p + total, 0, 64, ctx->stream));
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_off.p, d->off.data(), (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  lra_time_begin(ctx, "input_d2h");
-  LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->h_seq.p, d->d_seq.p, total + 64, hipMemcpyDeviceToHost, ctx->stream));
-  lra_time_end(ctx);
+  if (dev_qual) {                                                  // the ranges, the host-parsed records' strings, 64 zero bytes behind the last
+    if (int rc = grow_batch_bytes(ctx, d->d_qual, d->b_dq, d->b_dq + 64)) return rc;
+    if (!d->d_qual_off.ensure(n + 1)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: allocation failed");
+    for (size_t k = 0; k < d->pendq_at.size(); k += 3)
+      if (d->pendq_at[k + 2]) LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_qual.p + d->pendq_at[k], d->h_pendq.data() + d->pendq_at[k + 1], d->pendq_at[k + 2], hipMemcpyHostToDevice, ctx->stream));
+    LRA_HIP_CHECK(ctx, hipMemsetAsync(d->d_qual.p + d->b_dq, 0, 64, ctx->stream));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->d_qual_off.p, d->dq_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (no_host && n) {                                              // what the host keeps of the qualities: every string's first byte
+    if (!d->d_first.ensure(n) || !d->h_first.ensure(n, 0, ctx->stream)) return lra_set_err(ctx, LRA_ERR_NOMEM, "device reader: allocation failed");
+    hipLaunchKernelGGL(rd_first_qual, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (uint64_t)n, d->d_qual.p, d->d_qual_off.p, d->d_first.p);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    lra_time_begin(ctx, "input_d2h");
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->h_first.p, d->d_first.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    lra_time_end(ctx);
+  } else if (!no_host) {
+    lra_time_begin(ctx, "input_d2h");
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(d->h_seq.p, d->d_seq.p, total + 64, hipMemcpyDeviceToHost, ctx->stream));
+    lra_time_end(ctx);
+  }
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   d->name_ptr.resize(n); d->seq_ptr.resize(n); d->qual_ptr.resize(n);
+  if (no_host) d->stub.assign(2 * n, 0);
   for (size_t k = 0; k < n; k++) {
-    d->name_ptr[k] = d->h_names.p + d->name_off_h[k]; d->seq_ptr[k] = d->h_seq.p + d->off[k];
-    d->qual_ptr[k] = d->hasq[k] ? d->h_quals.p + d->qual_off_h[k] : nullptr;
+    d->name_ptr[k] = d->h_names.p + d->name_off_h[k];
+    if (no_host) {
+      d->seq_ptr[k] = nullptr;
+      d->stub[2 * k] = d->h_first.p[k];
+      d->qual_ptr[k] = d->hasq[k] ? d->stub.data() + 2 * k : nullptr;
+    } else {
+      d->seq_ptr[k] = d->h_seq.p + d->off[k];
+      d->qual_ptr[k] = d->hasq[k] ? d->h_quals.p + d->qual_off_h[k] : nullptr;
+    }
   }
   r->tag_ptr.resize(n);
   for (size_t k = 0; k < n; k++) r->tag_ptr[k] = hast[k] ? r->tags[k].c_str() : nullptr;
-  b->n_reads = (int32_t)n; b->total_bases = total; b->seq = d->h_seq.p; b->off = d->off.data(); b->read_len = d->len_h.data();
+  b->n_reads = (int32_t)n; b->total_bases = total; b->seq = no_host ? nullptr : d->h_seq.p; b->off = d->off.data(); b->read_len = d->len_h.data();
   b->names = d->name_ptr.data(); b->reads = d->seq_ptr.data(); b->quals = d->qual_ptr.data();
   *d_seq = d->d_seq.p; *d_off = d->d_off.p;
   return r->error.empty() ? LRA_OK : LRA_ERR_INVALID;
+}
+
+extern "C" int lra_reads_set_device_resident(lra_reads* r, uint32_t mode) {
+  if (!r || r->form != LRA_READS_NO_FORM) return LRA_ERR_INVALID;
+  if (mode & ~(uint32_t)(LRA_READS_DEV_QUAL | LRA_READS_DEV_NO_HOST)) return LRA_ERR_INVALID;
+  if ((mode & LRA_READS_DEV_NO_HOST) && !(mode & LRA_READS_DEV_QUAL)) return LRA_ERR_INVALID;
+  if (!r->dev) r->dev = new lra_reads_dev();
+  r->dev->resident = mode;
+  return LRA_OK;
+}
+
+extern "C" int lra_reads_batch_device_quals(const lra_reads* r, const char** d_qual, const uint64_t** d_qual_off) {
+  if (!r || !d_qual || !d_qual_off) return LRA_ERR_INVALID;
+  *d_qual = nullptr; *d_qual_off = nullptr;
+  if (r->form != LRA_READS_DEVICE_FORM || !r->dev || !(r->dev->resident & LRA_READS_DEV_QUAL) || !r->dev->batch_made) return LRA_ERR_INVALID;
+  *d_qual = r->dev->d_qual.p; *d_qual_off = r->dev->d_qual_off.p;
+  return LRA_OK;
 }

@@ -11,9 +11,11 @@
 // read's qualities, the CIGAR text, the MD:Z value or the pairwise rows (pairwise.hip) of an alignment.  rc_resolve gives every piece its length and source address, a scan its place, and
 // rc_copy cuts the OUTPUT into chunks of RC_CHUNK bytes, one wave each, as sv_copy does: the wave finds the first piece under its chunk and copies the
 // pieces' parts that lie in it, so a 1 Mb contig's SEQ is 256 waves and a chunk of 200-byte records is one wave.  The destination is written in aligned
-// dwords (a lane's dword is put together from the two aligned source dwords around it), bytes at a part's ragged ends.  rc_rec_off reads every read's
+// dwords (a lane's dword is put together from the two aligned source dwords around it), bytes at a part's ragged ends.  The loop is chunk_copy.h's, which
+// lra_pack_strings_batch (pack_strings.hip) runs too.  rc_rec_off reads every read's
 // first byte off the scan.  The host reads one number (the text's bytes), then the text and rec_off in one copy each.
 #include "common.h"
+#include "chunk_copy.h"
 #include "records.h"
 #include "scan.h"
 #include <algorithm>
@@ -134,38 +136,10 @@ __global__ void __launch_bounds__(256) rc_rec_off(RcArgs A) {
   if (r <= A.n_reads) A.rec_off[r] = A.at[A.read_piece[r]];
 }
 
-// n bytes from src to dst by one wave: dst in aligned dwords, each from the two aligned source dwords around it (an aligned dword that holds one byte
-// of the source is read whole: it lies in that byte's page), bytes in front of the first aligned dword and behind the last
-__device__ __forceinline__ void wave_copy(unsigned char* dst, const unsigned char* src, uint64_t n, int lane) {
-  const uint64_t head = min(n, (uint64_t)((4 - ((uintptr_t)dst & 3)) & 3));
-  if ((uint64_t)lane < head) dst[lane] = src[lane];
-  dst += head; src += head; n -= head;
-  const uint64_t nd = n >> 2;
-  uint32_t* d32 = (uint32_t*)dst;
-  const uint32_t sh = (uint32_t)((uintptr_t)src & 3) * 8;
-  const uint32_t* s32 = (const uint32_t*)((uintptr_t)src & ~(uintptr_t)3);
-  if (sh == 0) for (uint64_t i = lane; i < nd; i += 64) d32[i] = s32[i];
-  else for (uint64_t i = lane; i < nd; i += 64) d32[i] = (s32[i] >> sh) | (s32[i + 1] << (32 - sh));
-  const uint64_t tail = n & 3;
-  if ((uint64_t)lane < tail) dst[4 * nd + lane] = src[4 * nd + lane];
-}
-
-// one wave per chunk of the output bytes
+// one wave per chunk of the output bytes (chunk_copy.h)
 __global__ void __launch_bounds__(256) rc_copy(RcArgs A) {
-  const int lane = threadIdx.x & 63;
   const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-  const uint64_t n_chunks = (A.n_out + RC_CHUNK - 1) / RC_CHUNK;
-  for (uint64_t c = wave; c < n_chunks; c += n_waves) {
-    const uint64_t lo = c * RC_CHUNK, hi = min(lo + (uint64_t)RC_CHUNK, A.n_out);
-    uint64_t p = 0, e = A.n_pieces - 1;                        // the first piece whose bytes end behind lo
-    while (p < e) { const uint64_t mid = (p + e) >> 1; if (A.at[mid + 1] <= lo) p = mid + 1; else e = mid; }
-    for (; p < A.n_pieces; p++) {
-      const uint64_t b = A.at[p];
-      if (b >= hi) break;
-      const uint64_t from = max(lo, b), to = min(hi, b + A.len[p]);
-      if (to > from) wave_copy(A.out + from, A.src[p] + (from - b), to - from, lane);
-    }
-  }
+  chunk_copy<RC_CHUNK>(A.out, A.n_out, A.n_pieces, A.at, [&](uint64_t p) { return A.src[p]; }, wave, n_waves, threadIdx.x & 63);
 }
 
 inline size_t sz(size_t n, size_t e) { return (n * e + 255) & ~(size_t)255; }

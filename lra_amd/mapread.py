@@ -414,14 +414,16 @@ class LowAccMapper:
         raw = C.string_at(text, ln.value)
         return [raw[roff[i]:roff[i + 1]] for i in range(n)]
 
-    def record_args(self, names, reads, quals=None):
-        """The per-read host arrays lra_map_records_host takes (built once per batch; keep the returned object alive during the call)."""
+    def record_args(self, names, reads, quals=None, lens=None):
+        """The per-read host arrays lra_map_records_host takes (built once per batch; keep the returned object alive during the call).  reads=None
+        with lens (the reads' lengths): no host copy of the bases, which records_device does not read for formats 's' / 'P' / 'a'."""
         n = len(names)
         enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
-        nm = [enc(x) for x in names]; rd = [bytes(x) for x in reads]
-        return dict(n=n, keep=(nm, rd), names=(C.c_char_p * n)(*nm), reads=(C.c_char_p * n)(*rd),
+        nm = [enc(x) for x in names]; rd = [bytes(x) for x in reads] if reads is not None else None
+        return dict(n=n, keep=(nm, rd), names=(C.c_char_p * n)(*nm), reads=(C.c_char_p * n)(*rd) if rd is not None else None,
                     quals=(C.c_char_p * n)(*[None if q is None else bytes(q) for q in quals]) if quals is not None else None,
-                    lens=(C.c_int32 * n)(*[len(x) for x in rd]), chroms=(C.c_char_p * len(self.chrom_names))(*self.chrom_names))
+                    lens=(C.c_int32 * n)(*([len(x) for x in rd] if rd is not None else [int(x) for x in lens])),
+                    chroms=(C.c_char_p * len(self.chrom_names))(*self.chrom_names))
 
     def records_host(self, snap, args, passthrough=None, n_threads=0, free=True, as_list=True):
         """lra_map_records_host on a snapshot (host threads only; callable from another Python thread while the device runs the next batch:
@@ -448,7 +450,8 @@ class LowAccMapper:
     def records_device(self, res: MapResult, args, passthrough=None, d_qual=None, d_qual_off=None, md=None, n_threads=0, as_list=True):
         """lra_map_records_device: the batch's record text built on the device (formats 's', 'P' and 'a'; the others fall through to the host path) -- the bytes
         records_host gives for a snapshot of the same result.  args: record_args(names, reads, quals); passthrough: None or one text per read (None entries:
-        none); d_qual / d_qual_off: the batch's qualities as device tensors (None: uploaded from args' quals); md (None: opts.printMD): MD:Z in SAM records.
+        none); d_qual / d_qual_off: the batch's qualities as device tensors or raw device addresses (a device reader's batch["d_qual"] / ["d_qual_off"];
+        None: uploaded from args' quals); md (None: opts.printMD): MD:Z in SAM records.
         Call it where snapshot() would be called: the result's arrays must be alive.  -> list of per-read bytes, or the total bytes when as_list is False."""
         ctx = self.ctx
         n = args["n"]

@@ -7,6 +7,9 @@ from ._lib import load_library
 
 
 READS_COMPRESSED_TEXT = 1   # LRA_READS_COMPRESSED_TEXT
+READS_DEV_QUAL = 1          # LRA_READS_DEV_QUAL
+READS_DEV_NO_HOST = 2       # LRA_READS_DEV_NO_HOST
+PACK_CHUNK = 4096           # pack_strings.hip's PK_CHUNK: output bytes per wave of lra_pack_strings_batch (the tests' shapes)
 
 
 class ReadBatchC(C.Structure):
@@ -18,9 +21,11 @@ class ReadsFile:
     """ctx=None: lra_reads_next_batch (host parsing).  With a Context: lra_reads_next_batch_device (the parsing on that context's GPU; chunk = the bytes
     of a file it reads and parses per step, lra_reads_set_device_chunk; None keeps the library's default).  flag_remove: SAM / BAM records whose flag
     meets it are skipped (-Flag); passthrough: each SAM / BAM read's aux fields in the batch's "tags" (--passthrough).  compressed_text: gzip / BGZF
-    FASTA and FASTQ files are read (lra_reads_open_flags with LRA_READS_COMPRESSED_TEXT); without it they are refused, as the reference refuses them."""
+    FASTA and FASTQ files are read (lra_reads_open_flags with LRA_READS_COMPRESSED_TEXT); without it they are refused, as the reference refuses them.
+    device_quals (device form): every batch keeps its qualities on the device too (LRA_READS_DEV_QUAL; the batch's d_qual / d_qual_off); no_host_copy
+    (needs device_quals): the bases and qualities are not copied to the host (LRA_READS_DEV_NO_HOST; the batch's seqs is None, its quals are stubs)."""
 
-    def __init__(self, files, ctx=None, chunk=None, flag_remove=0, passthrough=False, compressed_text=False):
+    def __init__(self, files, ctx=None, chunk=None, flag_remove=0, passthrough=False, compressed_text=False, device_quals=False, no_host_copy=False):
         self.lib = load_library()
         self.ctx = ctx
         arr = (C.c_char_p * len(files))(*[f.encode() if isinstance(f, str) else f for f in files])
@@ -40,10 +45,18 @@ class ReadsFile:
             if self.lib.lra_reads_set_flag_remove(self.h, int(flag_remove)) != 0 or self.lib.lra_reads_set_passthrough(self.h, int(bool(passthrough))) != 0:
                 self.close()
                 raise ValueError("lra_reads_set_flag_remove / lra_reads_set_passthrough failed")
+        self.device_quals, self.no_host_copy = bool(device_quals), bool(no_host_copy)
+        if device_quals or no_host_copy:
+            mode = (READS_DEV_QUAL if device_quals else 0) | (READS_DEV_NO_HOST if no_host_copy else 0)
+            rc = self.lib.lra_reads_set_device_resident(self.h, mode) if ctx is not None else -1
+            if rc != 0:
+                self.close()
+                raise ValueError("lra_reads_set_device_resident(%d) failed (%d): device_quals needs the device form, no_host_copy needs device_quals" % (mode, rc))
 
     def next_batch(self, max_bases):
         """-> None at the end, else dict(names, seqs, quals (None for FASTA reads), off, raw=(ReadBatchC kept alive until the next call)); the device form
-        adds d_seq / d_off (device pointers, valid until the next call) and n / total_bases"""
+        adds d_seq / d_off (device pointers, valid until the next call) and n / total_bases, with device_quals d_qual / d_qual_off (the same); with
+        no_host_copy seqs is None, read_len holds the reads' lengths and quals are stubs (None, or the string's first byte)"""
         b = ReadBatchC()
         if self.ctx is None:
             rc = self.lib.lra_reads_next_batch(self.h, C.c_uint64(int(max_bases)), C.byref(b))
@@ -56,13 +69,18 @@ class ReadsFile:
         out = None
         if n:
             off = np.ctypeslib.as_array(b.off, shape=(n + 1,)).copy()
-            seq = C.string_at(b.seq, int(b.total_bases))
+            seq = C.string_at(b.seq, int(b.total_bases)) if b.seq else None
             tags = C.POINTER(C.c_char_p)()
             self.lib.lra_reads_batch_tags(self.h, C.byref(tags))
-            out = dict(names=[b.names[i] for i in range(n)], seqs=[seq[int(off[i]):int(off[i + 1])] for i in range(n)], quals=[b.quals[i] for i in range(n)], off=off, raw=b,
+            out = dict(names=[b.names[i] for i in range(n)], seqs=[seq[int(off[i]):int(off[i + 1])] for i in range(n)] if seq is not None else None, quals=[b.quals[i] for i in range(n)], off=off, raw=b,
                        tags=[tags[i] for i in range(n)] if tags else [None] * n)
             if dev is not None:
-                out.update(d_seq=dev[0], d_off=dev[1], n=n, total_bases=int(b.total_bases))
+                out.update(d_seq=dev[0], d_off=dev[1], n=n, total_bases=int(b.total_bases), read_len=[int(b.read_len[i]) for i in range(n)])
+                if self.device_quals:
+                    d_qual, d_qual_off = C.c_void_p(), C.c_void_p()
+                    if self.lib.lra_reads_batch_device_quals(self.h, C.byref(d_qual), C.byref(d_qual_off)) != 0:
+                        raise RuntimeError("lra_reads_batch_device_quals failed")
+                    out.update(d_qual=d_qual.value, d_qual_off=d_qual_off.value)
         if rc != 0:
             err = self.lib.lra_reads_last_error(self.h) or b""
             if not err and self.ctx is not None:

@@ -115,8 +115,12 @@ def main():
              (["-a"] if args.store_all else []) + ["--PrintNumAln", str(args.PrintNumAln)] + (["--refineBreakpoints"] if args.refineBreakpoints else []) + \
              (["-Flag", str(args.flag)] if args.flag else []) + (["--passthrough"] if args.passthrough else []) + (["-SV", *args.sv] if args.sv else [])       # (--device-records is no lra option: the same records)
         out.write(mapread.LowAccMapper.sam_header(mapper, b"lra_amd", " ".join(cl).encode()))   # the lra command line: the same for either reader
+    # --device-records with device input: the qualities stay on the device from the reader to the record text; the host copies of bases and qualities
+    # are switched off where nothing reads them (the formats the device builds; -SV prints from a host snapshot)
+    dev_quals = args.device_records and not args.host_input
+    no_host = dev_quals and fmt in ("s", "c", "a") and not args.sv
     rf = reads_io.ReadsFile(args.reads, ctx=None if args.host_input else ctx, chunk=None if args.host_input else args.chunk, flag_remove=args.flag, compressed_text=True,
-                            passthrough=args.passthrough)
+                            passthrough=args.passthrough, device_quals=dev_quals, no_host_copy=no_host)
     sv_out = open(args.sv[1], "wb") if args.sv else None
     t_read = t_map = t_rec = 0.0
     n_reads = n_bases = n_batches = 0
@@ -141,7 +145,8 @@ def main():
             for sig in mapper.svsig_host(snap, b["names"]):
                 sv_out.write(sig)
         elif args.device_records:
-            texts = mapper.records_device(res, mapper.record_args(b["names"], b["seqs"], b["quals"]), passthrough=tags)
+            texts = mapper.records_device(res, mapper.record_args(b["names"], b["seqs"], b["quals"], lens=b.get("read_len")), passthrough=tags,
+                                          d_qual=b.get("d_qual"), d_qual_off=b.get("d_qual_off"))
         else:
             texts = mapper.records(res, b["names"], b["seqs"], quals=b["quals"], passthrough=tags)
         for txt in texts:

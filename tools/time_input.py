@@ -3,6 +3,13 @@ lra_reads_next_batch_device (parsing on the device), in Mbases/s of whole batche
 
     python tools/time_input.py [--format fastq|bam|fastq-bgzf|fastq-gz] [--level 6] [--n-reads 28672] [--read-len 30000] [--out profiles/device_input.json]
     python tools/time_input.py --format fastq-bgzf --inflate-kernel serial|lut      # the inflate stage alone over the file's member table
+    python tools/time_input.py --resident 0,1,3 --device-only --warm-reader         # lra_reads_set_device_resident's modes side by side
+
+--resident: the device form once per listed mode (0: as before; 1: LRA_READS_DEV_QUAL; 3: | LRA_READS_DEV_NO_HOST), each with the batch's device-to-host
+bytes (the tool's own count of what the reader copies: names always, bases and qualities unless mode 3, one byte per read in mode 3) and the page-locked
+bytes the reader holds for its batch arrays (what the batch's host arrays need, before the buffers' growth headroom).  --warm-reader times the SECOND
+pass of one reader over the file list given twice (FASTA / FASTQ only: nothing is read behind a BAM file), so the first pass has sized every buffer:
+the time per batch of a reader that maps many batches.
 
 --format fastq-bgzf / fastq-gz: the FASTQ of --format fastq (random per-read qualities) as BGZF members of htslib's size, or as one gzip member, at zlib
 level --level, opened with compressed_text.  --inflate-kernel times one of the two inflate kernels alone (bgzf_inflate: lra_bgzf_inflate_batch; bgzf_inflate_lut:
@@ -122,12 +129,21 @@ def time_inflate(ctx, path, kernel, repeats=2):
     return dict(kernel=kernel, members=n, out_bytes=out_off[-1], seconds=secs[1:], gb_per_s=[out_off[-1] / s / 1e9 for s in secs[1:]], crc32="%08x" % crc)
 
 
-def run(files, max_bases, ctx=None, chunk=None):
-    rf = reads_io.ReadsFile(files, ctx=ctx, chunk=chunk, compressed_text=True)
+def run(files, max_bases, ctx=None, chunk=None, resident=0, warm=False):
+    kw = dict(device_quals=bool(resident & 1), no_host_copy=bool(resident & 2)) if resident else {}      # (mode 0 runs on a library without the setter too)
+    rf = reads_io.ReadsFile(files * 2 if warm else files, ctx=ctx, chunk=chunk, compressed_text=True, **kw)
     lib = rf.lib
     b = reads_io.ReadBatchC()
     import ctypes as C
     n_reads = n_bases = n_batches = 0
+    d2h = pinned = 0
+    if warm:                                                    # the first pass over the file sizes the reader's buffers
+        tot = 0
+        while tot < sum_bases(files):
+            d_seq, d_off = C.c_void_p(), C.c_void_p()
+            rc = lib.lra_reads_next_batch_device(rf.h, ctx.h, C.c_uint64(max_bases), C.byref(b), C.byref(d_seq), C.byref(d_off))
+            assert rc == 0 and b.n_reads, rc
+            tot += int(b.total_bases)
     t = time.perf_counter()
     while True:
         if ctx is None:
@@ -139,9 +155,27 @@ def run(files, max_bases, ctx=None, chunk=None):
         if b.n_reads == 0:
             break
         n_reads += b.n_reads; n_bases += int(b.total_bases); n_batches += 1
+        if ctx is not None:                                     # what this batch brought to the host, and the page-locked bytes under its host arrays
+            t_acc = time.perf_counter()                         # (this bookkeeping is taken out of the time)
+            qp = C.cast(b.quals, C.POINTER(C.c_void_p))
+            names = sum(len(b.names[i]) + 1 for i in range(b.n_reads))
+            quals = sum(b.read_len[i] + 1 if qp[i] else 1 for i in range(b.n_reads))
+            nb = names + (b.n_reads if resident & 2 else int(b.total_bases) + 64 + quals)
+            d2h += nb; pinned = max(pinned, nb)
+            t += time.perf_counter() - t_acc
     dt = time.perf_counter() - t
     rf.close()
-    return dict(seconds=dt, reads=n_reads, bases=n_bases, batches=n_batches, mbases_per_s=n_bases / dt / 1e6)
+    out = dict(seconds=dt, reads=n_reads, bases=n_bases, batches=n_batches, mbases_per_s=n_bases / dt / 1e6, ms_per_batch=dt * 1e3 / max(n_batches, 1))
+    if ctx is not None:
+        out.update(resident=resident, warm_reader=warm, d2h_bytes_per_batch=d2h // max(n_batches, 1), pinned_batch_bytes=pinned)
+    return out
+
+
+_BASES = {}
+
+
+def sum_bases(files):
+    return sum(_BASES[f] for f in files)
 
 
 def main():
@@ -155,6 +189,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=None)
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--device-only", action="store_true", help="skip the host form (for a profiler run)")
+    ap.add_argument("--resident", default="0", help="comma-separated lra_reads_set_device_resident modes to time (0, 1, 3)")
+    ap.add_argument("--warm-reader", action="store_true", help="time the second pass of one reader over the file (its buffers sized by the first)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     max_bases = args.max_bases or args.n_reads * args.read_len
@@ -170,6 +206,7 @@ def main():
         else:
             raw = write_fastq_compressed(fq, args.n_reads, args.read_len, args.level, args.format == "fastq-bgzf")
         size = os.path.getsize(fq)
+        _BASES[fq] = args.n_reads * args.read_len
         sys.stderr.write("wrote %s: %.2f GB in %.1f s\n" % (fq, size / 1e9, time.perf_counter() - t))
         buf = bytearray(size)
         reads = []
@@ -192,10 +229,25 @@ def main():
                    file_read_s=min(reads[1:]), file_read_gb_per_s=size / min(reads[1:]) / 1e9)
         if not args.device_only:
             res["host"] = min((run([fq], max_bases) for _ in range(args.repeats)), key=lambda r: r["seconds"])
+        modes = [int(m) for m in args.resident.split(",")]
+        res["device_resident"] = {}
+        for mode in modes[1:] if modes[0] == 0 else modes:      # the new modes; mode 0 is the "device" entry below
+            runs = []
+            for _ in range(args.repeats):
+                ctx.timing(True); ctx.timing_reset()
+                r = run([fq], max_bases, ctx=ctx, chunk=args.chunk, resident=mode, warm=args.warm_reader)
+                r["breakdown_ms"] = {k: ctx.timing_get(k)[0] for k in ("input_h2d", "input_parse", "input_decode", "input_d2h", "input_pack_quals")}
+                ctx.timing(False)
+                runs.append(r)
+            best_m = min(runs, key=lambda r: r["seconds"])
+            best_m["all_seconds"] = [r["seconds"] for r in runs]
+            res["device_resident"][str(mode)] = best_m
         best = None
+        all_s = []
         for _ in range(args.repeats):
             ctx.timing(True); ctx.timing_reset()
-            r = run([fq], max_bases, ctx=ctx, chunk=args.chunk)
+            r = run([fq], max_bases, ctx=ctx, chunk=args.chunk, warm=args.warm_reader)
+            all_s.append(r["seconds"])
             keys = {"fastq": ("input_h2d", "input_parse", "input_d2h"), "bam": ("input_h2d", "input_inflate", "input_frame", "input_decode", "input_d2h"),
                     "fastq-bgzf": ("input_h2d", "input_inflate", "input_parse", "input_d2h"), "fastq-gz": ("input_h2d", "input_parse", "input_d2h")}[args.format]
             r["breakdown_ms"] = {k: ctx.timing_get(k)[0] for k in keys}
@@ -203,6 +255,7 @@ def main():
             if best is None or r["seconds"] < best["seconds"]:
                 best = r
         res["device"] = best
+        res["device"]["all_seconds"] = all_s
         bd = best["breakdown_ms"]
         res["device"]["breakdown_ms"]["file_read"] = res["file_read_s"] * 1e3
         res["device"]["breakdown_ms"]["other_host"] = best["seconds"] * 1e3 - res["file_read_s"] * 1e3 - sum(v for k, v in bd.items() if k != "file_read")

@@ -4,7 +4,9 @@
 
   host    lra_map_snapshot + lra_map_records_host at 4 and 12 threads (the CIGAR runs copied to the host, the text written by host threads);
   device  lra_map_records_device (a snapshot without the runs, the piece table on host threads, the long fields and the assembly on the device),
-          split as lra_map_records_device_last reports it, with the qualities uploaded from the host and with the qualities already on the device.
+          split as lra_map_records_device_last reports it, with the qualities uploaded from the host, with the qualities already on the device, and
+          (format s / P) with the batch read back through a device reader with LRA_READS_DEV_QUAL | LRA_READS_DEV_NO_HOST from a FASTQ of the same reads
+          and qualities: records_device on the READER's d_qual / d_qual_off, stub quals and no host reads ("device_quals_from_reader").
 Per form: wall ms and host CPU-seconds per batch (time.process_time: every thread of the process), median and range over the repeats after one
 warm-up call; device-to-host bytes; the copy pass's GB/s (bytes read + bytes written over its HIP-event time).  One JSON line at the end.
 format a (pairwise): the host form is the snapshot with every block and one copy per alignment of the bases under it; the device form builds the rows with
@@ -100,12 +102,29 @@ def main():
         out["host_%d" % T] = r
         print("host  %2d threads: wall %.1f ms (%.1f-%.1f)  cpu %.3f s (%.3f-%.3f)  text %.3f GB" % (T, *r["wall_ms"], *r["cpu_s"], nb[-1] / 1e9), flush=True)
     forms = (("device_quals_from_host", {}), ("device_quals_on_device", dict(d_qual=dq, d_qual_off=qoff))) if fmt != "a" else (("device", {}),)
+    rf = tmp = None
+    if fmt != "a":                                                          # the same reads and qualities through a device reader that keeps them on the device
+        import tempfile
+        from lra_amd import reads_io
+        tmp = tempfile.TemporaryDirectory()
+        fq = os.path.join(tmp.name, "reads.fq")
+        with open(fq, "wb", buffering=1 << 24) as f:
+            for i in range(n):
+                f.write(b"@%s\n%s\n+\n%s\n" % (names[i], rl[i], ql[i]))
+        rf = reads_io.ReadsFile([fq], ctx=ctx, device_quals=True, no_host_copy=True)
+        b = rf.next_batch(int(off[-1]))
+        assert b["n"] == n and b["seqs"] is None and b["names"] == names
+        stub = mapper.record_args(names, None, b["quals"], lens=b["read_len"])
+        forms += (("device_quals_from_reader", dict(d_qual=b["d_qual"], d_qual_off=b["d_qual_off"], _args=stub)),)
+    texts = {}
     for label, kw in forms:
+        kw = dict(kw)
+        a = kw.pop("_args", args)
         for T in (4, 12):
             parts = []
             got = []
             def devf():
-                got.append(mapper.records_device(res, args, n_threads=T, as_list=False, **kw))
+                got.append(mapper.records_device(res, a, n_threads=T, as_list=False, **kw))
                 parts.append(mapper.records_device_stats())
             r = timed(devf)
             last = parts[-1]
@@ -116,9 +135,13 @@ def main():
             ck = r["ms_copy_kernel"][0]
             r["copy_GBps"] = 2 * last["text_bytes"] / max(ck, 1e-6) / 1e6
             out["%s_%d" % (label, T)] = r
+            texts[label] = got[-1]
             print("%s %2d threads: wall %.1f ms (%.1f-%.1f)  cpu %.3f s (%.3f-%.3f)  snapshot %.1f  cigar+md %.1f  pieces %.1f  upload %.1f  kernels %.1f (copy %.2f = %.0f GB/s)  "
                   "text copy %.1f ms  d2h %.3f GB  h2d %.3f GB" % (label, T, *r["wall_ms"], *r["cpu_s"], r["ms_snapshot"][0], r["ms_cigar_md"][0], r["ms_pieces"][0], r["ms_upload"][0],
                                                                    r["ms_kernels"][0], ck, r["copy_GBps"], r["ms_text_copy"][0], last["bytes_d2h"] / 1e9, last["bytes_h2d"] / 1e9), flush=True)
+    if rf is not None:
+        assert texts["device_quals_from_reader"] == texts["device_quals_from_host"], texts   # the same number of bytes (the tests compare the bytes)
+        rf.close(); tmp.cleanup()
     if fmt == "a" and not out["device_4"]["fell_through"]:
         out["pairwise_kernels"] = pairwise_kernels(ctx, mapper, res, args, out["device_4"]["text_bytes"])
     print(json.dumps(out))
