@@ -16,6 +16,8 @@ CODE = np.zeros(256, dtype=np.int64)
 for i, c in enumerate(b"ACGT"):
     CODE[c] = i
     CODE[c + 32] = i
+for i in range(8):
+    CODE[i] = i & 3                       # SeqUtils.h:8 (seqMap): the bytes 0..7 are bases already
 BASES = np.frombuffer(b"ACGT", dtype=np.uint8)
 
 
@@ -118,7 +120,8 @@ def simulate_reads(genome, n_reads, mean_len, sd_len, err, mix=(30, 35, 35), see
 
 def canonical_keys(seq, k):
     """Per position p (0..n-k): (masked key, strand) of the canonical k-mer, as the reference defines it
-    (MinCount.h:60-61: forward if fwd < rc else reverse-complement with bit 63 set)."""
+    (MinCount.h:60-61: forward if fwd < rc else reverse-complement with bit 63 set; the comparison and the key are without bit 63, which only k = 32
+    reaches)."""
     c = CODE[seq]
     n = len(seq) - k + 1
     fwd = np.zeros(n, dtype=np.uint64)
@@ -126,8 +129,9 @@ def canonical_keys(seq, k):
     for i in range(k):
         fwd = (fwd << np.uint64(2)) | c[i:i + n].astype(np.uint64)
         rc |= (np.uint64(3) - c[i:i + n].astype(np.uint64)) << np.uint64(2 * i)
-    use_f = fwd < rc
-    key = np.where(use_f, fwd, rc)
+    m63 = np.uint64((1 << 63) - 1)
+    use_f = (fwd & m63) < (rc & m63)
+    key = np.where(use_f, fwd, rc) & m63
     return key, ~use_f
 
 

@@ -11,9 +11,12 @@
 //                 golden in tests/golden/comparelists_golden.json.
 //   a2 PINNED  -- it IS libstdc++'s std::sort with the reference's comparator (the
 //                 permutation of equal keys is an implementation property of libstdc++).
-//   a1, a4 PARITY UNPINNED -- MinCount.h and MapRead.h include htslib/kseq.h (htslib is
-//                 not in this image and is not vendored by the reference), so they
-//                 cannot be compiled here; restated from the source text only.
+//   a1 PINNED  -- positions bit-exact against the reference's StoreMinimizers compiled from MinCount.h in
+//                 place (oracle/ref_harness/minimizers_ref.cpp; MinCount.h's htslib/kseq.h include is
+//                 unused and met by an empty stand-in), golden in tests/golden/minimizers_golden.json;
+//                 the keys by oracle_kmer_stream's pin below.
+//   a4 PARITY UNPINNED -- MapRead.h needs htslib (not in this image, not vendored by the
+//                 reference), so it cannot be compiled here; restated from the source text only.
 #include "oracle_common.h"
 #include <algorithm>
 #include <vector>

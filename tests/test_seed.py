@@ -27,8 +27,28 @@ def test_oracle_comparelists_and_sort_match_reference_golden(oracle):
         assert np.stack([oq, ot], 1).flatten().tolist() == c["pairs"]
 
 
+def test_oracle_minimizers_match_reference_golden(oracle):
+    """Restated StoreMinimizers emits exactly the positions the reference's own MinCount.h (compiled in place, oracle/_ref/minimizers_ref) emitted on the
+    crafted reads of seed_cases.a1_reads -- lengths around the span and the tiles, runs of tied minima, the first-window and last-window quirks, N at every
+    critical offset, lower case, the bytes 0..7 -- and every key is the canonical key (pinned by tuple_ops_golden.json) at its position."""
+    import seed_cases
+    g = json.load(open(os.path.join(HERE, "golden", "minimizers_golden.json")))["cases"]
+    assert len(g) >= 500
+    assert {(c["k"], c["w"]) for c in g} == set(seed_cases.KW)
+    n = 0
+    for c in g:
+        seq = seed_cases.from_text(c["seq"])
+        keys, pos = oracle.store_minimizers(seq, c["k"], c["w"])
+        assert pos.tolist() == c["pos"], (c["k"], c["w"], c["family"], c["seq"])
+        if len(pos):
+            ck, cs = seed_cases.keys_of(seq, c["k"])
+            assert np.array_equal(keys & M63, ck[pos]) and np.array_equal((keys >> np.uint64(63)) == 1, cs[pos]), (c["k"], c["w"], c["seq"])
+        n += len(pos)
+    assert n > 10000
+
+
 def test_oracle_minimizers_basic_properties(oracle):
-    """(parity unpinned for a1) sanity: every emitted tuple is the canonical k-mer at its position and
+    """(a1's parity is pinned by the golden test above) sanity: every emitted tuple is the canonical k-mer at its position and
     is a minimum (by masked key) of some w-window containing it; short / N-only inputs give nothing."""
     rng = np.random.default_rng(5)
     seq = synth.BASES[rng.integers(0, 4, size=5000)].tobytes()
