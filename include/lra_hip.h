@@ -832,6 +832,25 @@ typedef struct lra_svsig_result {
 } lra_svsig_result;
 int lra_sv_signatures_batch(lra_ctx* ctx, int n_aln, const int32_t* d_blocks, const uint64_t* d_block_off, const char* d_qseq, const uint64_t* d_q_off,
                             const int32_t* d_q_len, const char* d_tseq, const uint64_t* d_t_off, int32_t min_len, lra_svsig_result* out);
+/* The text of these signatures (MapRead's svsigstrm), on the device (svsig_text.hip).  sv: a result as lra_sv_signatures_batch leaves it.  Per
+ * alignment: d_aln_read[a] its read, d_chrom[a] its chromosome, d_skip[a] (d_skip NULL: none) 1 when the alignment prints nothing.  The names are two
+ * tables on the device, a blob and offsets each: read r's name is d_read_names[d_read_name_off[r], d_read_name_off[r + 1]), n_reads + 1 offsets; the
+ * chromosomes' the same way (an index outside its table prints an empty name).  One line per signature, alignments in index order, an alignment's
+ * signatures in d_sig order, each exactly what lra_map_svsig_host writes:
+ *     chrom \t readName \t t_start \t end \t len \t INS|DEL \t bases \n
+ * end = t_start for INS, (uint32)(t_start + len - 1) for DEL; decimal without padding; bases = d_seq[seq_off, seq_off + len) as stored.
+ * Output (context-owned, valid until the next call on the context): alignment a's lines are d_text[d_aln_off[a], d_aln_off[a + 1]), n_bytes =
+ * d_aln_off[n_aln]; nothing is written behind d_text + n_bytes.  n_sig == 0 launches nothing (d_aln_off is zeros, d_text NULL).  LRA_ERR_INVALID: a
+ * NULL sv, negative counts, a NULL array or name table with n_sig > 0.  Synchronous.                                                          */
+typedef struct lra_svsig_text_result {
+  int32_t n_aln;
+  uint64_t n_sig, n_bytes;
+  const uint64_t* d_aln_off;        /* [n_aln+1] */
+  const char* d_text;               /* [n_bytes] */
+} lra_svsig_text_result;
+int lra_svsig_text_batch(lra_ctx* ctx, const lra_svsig_result* sv, const uint32_t* d_aln_read, const int32_t* d_chrom, const uint8_t* d_skip, int n_reads,
+                         const char* d_read_names, const uint64_t* d_read_name_off, int n_chrom, const char* d_chrom_names, const uint64_t* d_chrom_name_off,
+                         lra_svsig_text_result* out);
 
 /* ---- a17: the CIGAR strings of every alignment, on the device ----------------------------------------------------------
  * Replaces  the CIGAR field as Alignment::PrintSAM / PrintPAF write it (Alignment.h:640-650, :700-714): the clip in front (preClip, when > 0, and the
@@ -1381,8 +1400,9 @@ int lra_map_records_host_tags(lra_map_host* snap, const lra_map_opts* opts, cons
                               const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough, int n_threads, const char** text,
                               uint64_t* len, const uint64_t** rec_off);
 /* The record text built on the device.  For print formats 's' (SAM), 'P' (PAF with CG:z:) and 'a' (pairwise) *text, *len and (*rec_off)[n_reads + 1] are exactly what
- * lra_map_records_host_tags gives for a snapshot of the same result under the same options (flags & LRA_PACK_MD: with MD:Z, opts.printMD; other flag
- * bits are LRA_ERR_INVALID).  The split of work:
+ * lra_map_records_host_tags gives for a snapshot of the same result under the same options (flags & LRA_PACK_MD: with MD:Z, opts.printMD;
+ * flags & LRA_PACK_SVSIG: the SV signature text is built too, see lra_map_records_device_svsig below; other flag bits are LRA_ERR_INVALID).  The
+ * split of work:
  *   host    SetFromSegAlignment, AlignmentsOrder::Update, SimpleMapQV, the grouping and PrintNumAln, and every SHORT field of a record (name, flag,
  *           chrom, pos, MAPQ, the clips, the tag block with NV:f: through libstdc++, the short parts of SA:Z, passthrough text, the unaligned
  *           prefix), on n_threads threads (0: as lra_map_records_host) from a snapshot packed with LRA_PACK_NORUNS: the per-alignment arrays only --
@@ -1407,7 +1427,16 @@ int lra_map_records_host_tags(lra_map_host* snap, const lra_map_opts* opts, cons
  * Formats 'p' and 'b' have no long per-base field worth moving: the call falls through to lra_map_snapshot + lra_map_records_host_tags and returns that
  * text (in pageable memory).
  * *text / *rec_off are owned by the context and valid until the next lra_map_records_device on it; the result's arrays must still be alive (call it
- * where lra_map_snapshot would be called).  lra_map_records_device_last: where the last call's time and bytes went (zeros after a fall-through). */
+ * where lra_map_snapshot would be called).  lra_map_records_device_last: where the last call's time and bytes went (zeros after a fall-through).
+ * flags & LRA_PACK_SVSIG (opts.Printsvsig; alone or with LRA_PACK_MD; the record text is unchanged by it): the call also builds MapRead's second
+ * stream and keeps it on the context, where lra_map_records_device_svsig returns it until the next lra_map_records_device: *text, *len and
+ * (*rec_off)[n_reads + 1] are byte for byte what lra_map_svsig_host gives for lra_map_snapshot(ctx, res, LRA_PACK_SVSIG) of the same result (length
+ * = lra_ctx_set_svsig_len; a read with a non-zero status word has no lines).  For the device formats it runs lra_sv_signatures_batch on the result's
+ * own blocks, strands and the genome and lra_svsig_text_batch with d_aln_read, d_chrom, a skip byte made from d_read_status and the read and
+ * chromosome names uploaded as blobs (a few tens of bytes per read); rec_off is gathered at the job offsets on the device and the text crosses in one
+ * copy into a page-locked buffer the context keeps -- no signature record, block or base crosses to the host.  The fall-through formats take their
+ * snapshot with the flag and print through lra_map_svsig_host.  LRA_ERR_INVALID when the last call on the context had no LRA_PACK_SVSIG (or there was
+ * none). */
 typedef struct lra_records_device_stats {
   double ms_snapshot;      /* pack without the runs + its device-to-host copy + unpack */
   double ms_cigar_md;      /* lra_cigar_text_batch (+ lra_md_strings_batch); format 'a': lra_pairwise_text_batch */
@@ -1417,12 +1446,15 @@ typedef struct lra_records_device_stats {
   double ms_copy_kernel;   /* of these: the copy pass alone (HIP events) */
   double ms_text_copy;     /* the text, device to host (HIP events) */
   uint64_t bytes_h2d, bytes_d2h, text_bytes, n_pieces;
+  double ms_svsig;         /* LRA_PACK_SVSIG: the signatures, their text, its copy to the host (wall); its bytes are in none of the fields above */
+  uint64_t svsig_bytes_h2d, svsig_bytes_d2h, svsig_text_bytes;   /* the names up; the text, rec_off and the totals down */
 } lra_records_device_stats;
 int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* opts, const char* const* names, const char* const* reads,
                            const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough,
                            const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const char** text, uint64_t* len,
                            const uint64_t** rec_off);
 int lra_map_records_device_last(lra_ctx* ctx, lra_records_device_stats* out);
+int lra_map_records_device_svsig(lra_ctx* ctx, const char** text, uint64_t* len, const uint64_t** rec_off);
 /* the reads of a snapshot whose status word is non-zero: their number; *status (optional) = the snapshot's status array [n_reads], owned by the snapshot */
 uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status);
 /* The record buffer of a batch as ONE device buffer -- what a rank sends to rank 0 in the single exchange step of the multi-GPU path (the

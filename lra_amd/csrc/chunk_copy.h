@@ -1,6 +1,6 @@
 // lra_amd/csrc/chunk_copy.h -- the copy pass of strings that fill an output back to back, cut by OUTPUT bytes: the body of rc_copy (records.hip: the
-// pieces of the record text) and of pk_copy (pack_strings.hip: lra_pack_strings_batch).  The two differ in where a string's bytes come from, which is the
-// one thing the caller passes in.
+// pieces of the record text), of pk_copy (pack_strings.hip: lra_pack_strings_batch) and of svt_copy (svsig_text.hip: the bases of the SV signature lines).
+// They differ in where a string's bytes come from, which the caller passes in, and svt_copy in that only a window of every string is a copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,9 +25,12 @@ __device__ __forceinline__ void wave_copy(unsigned char* dst, const unsigned cha
 // bytes, one wave each (wave `wave` of `n_waves` takes every n_waves-th chunk): the wave finds the first string under its chunk by binary search and
 // copies the strings' parts that lie in it, so a string of 1 MB is 256 waves at CHUNK = 4096 and a chunk of 200-byte strings is one wave.  Empty strings
 // cost a step of the walk and nothing else.  src_of is not called for an empty string.
-template <int CHUNK, typename SrcOf>
+// window(p, b, e), called with string p's range [b, e) of the output when it is not empty, may narrow it to the part src_of(p) fills (its first byte then
+// lands at the new b); the bytes outside the window are the caller's to write.  The default copies every string whole.
+struct chunk_copy_whole { __device__ __forceinline__ void operator()(uint64_t, uint64_t&, uint64_t&) const {} };
+template <int CHUNK, typename SrcOf, typename Window = chunk_copy_whole>
 __device__ __forceinline__ void chunk_copy(unsigned char* out, uint64_t n_out, uint64_t n_items, const uint64_t* __restrict__ at, SrcOf src_of, uint64_t wave,
-                                           uint64_t n_waves, int lane) {
+                                           uint64_t n_waves, int lane, Window window = Window()) {
   const uint64_t n_chunks = (n_out + CHUNK - 1) / CHUNK;
   for (uint64_t c = wave; c < n_chunks; c += n_waves) {
     const uint64_t lo = c * CHUNK, hi = min(lo + (uint64_t)CHUNK, n_out);
@@ -36,8 +39,10 @@ __device__ __forceinline__ void chunk_copy(unsigned char* out, uint64_t n_out, u
     uint64_t b = at[p];
     for (; p < n_items && b < hi; p++) {
       const uint64_t end = at[p + 1];
-      const uint64_t from = max(lo, b), to = min(hi, end);
-      if (to > from) wave_copy(out + from, src_of(p) + (from - b), to - from, lane);
+      uint64_t wb = b, we = end;
+      if (end > b) window(p, wb, we);
+      const uint64_t from = max(lo, wb), to = min(hi, we);
+      if (to > from) wave_copy(out + from, src_of(p) + (from - wb), to - from, lane);
       b = end;
     }
   }

@@ -35,6 +35,7 @@ struct lra_ctx {
   void* out_buf = nullptr; size_t out_bytes = 0;
   void* pin_buf = nullptr; size_t pin_bytes = 0;      // page-locked host staging of the large device-to-host copies (lra_pinned)
   void* rec_pin = nullptr; size_t rec_pin_bytes = 0;  // records.hip: the page-locked buffer the device record stage's text lands in (kept between batches)
+  void* sv_pin = nullptr; size_t sv_pin_bytes = 0;    // map_output.hip: the same for the SV signature text (LRA_PACK_SVSIG), which lives beside the record text
   uint64_t* scan_tmp = nullptr;
   // lra_side_fork / lra_side_join: further streams for kernels that would only extend a stage's tail on the context's own stream
   static constexpr int N_SIDE = 4;

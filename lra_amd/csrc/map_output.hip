@@ -55,6 +55,21 @@ __global__ void k_md_address(uint64_t nA, const uint32_t* __restrict__ aln_read,
   q_off[a] = read_off[aln_read[a]] + (strand[a] ? rc_base : 0);
   t_off[a] = chrom_pos[chrom[a]];
 }
+// lra_map_records_device with LRA_PACK_SVSIG: no alignment of a read with a non-zero status word (flagged or handed back) prints a signature
+__global__ void k_sv_skip(uint64_t nA, int n_reads, const uint32_t* __restrict__ aln_read, const uint32_t* __restrict__ read_status, uint8_t* __restrict__ skip) {
+  const uint64_t a = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= nA) return;
+  const uint32_t r = aln_read[a];
+  skip[a] = r < (uint32_t)n_reads && read_status[r] ? 1 : 0;
+}
+// ... and read r's lines are those of alignments job_aln_off[r * num_aln] .. job_aln_off[(r + 1) * num_aln)
+__global__ void k_sv_rec_off(int n_reads, int num_aln, uint64_t nJ, uint64_t nA, const uint64_t* __restrict__ job_aln_off, const uint64_t* __restrict__ aln_off,
+                             uint64_t* __restrict__ rec_off) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r > n_reads) return;
+  const uint64_t j = min((uint64_t)r * num_aln, nJ);
+  rec_off[r] = aln_off[min(job_aln_off[j], nA)];
+}
 }  // namespace
 
 extern "C" void lra_map_host_free(lra_map_host* h) { delete h; }
@@ -736,14 +751,86 @@ extern "C" int lra_map_records_tags(lra_ctx* ctx, const lra_map_result* res, con
 }
 
 // ---- the record text built on the device (records.hip) ---------------------------------------------------------------------------------------------
+// LRA_PACK_SVSIG of the device formats: the signatures (svsig.hip) and their text (svsig_text.hip) from the result's own arrays; adr = k_md_address's offsets.
+// The host's part is the two name tables, uploaded as one buffer: offsets u64[n_reads + 1] | offsets u64[n_chrom + 1] | the read names | the chromosome names.
+static int records_device_svsig(lra_ctx* ctx, const lra_map_result* res, const uint64_t* adr, const char* const* names, const char* const* chrom_names,
+                                lra_records_device_stats& S) {
+  lra_map_state* m = ctx->map;
+  hipStream_t st = ctx->stream;
+  const int nR = res->n_reads, na = std::max(res->num_aln, 1);
+  const uint64_t nA = res->n_alignments, nJ = res->n_jobs;
+  const double t0 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  m->dev_sv_off.assign((size_t)nR + 1, 0);
+  m->dev_sv_ptr = nullptr; m->dev_sv_len = 0;
+  if (nA && nJ) {
+    if (nJ != (uint64_t)nR * na || !res->d_job_aln_off) return lra_set_err(ctx, LRA_ERR_INVALID, "LRA_PACK_SVSIG: the result's jobs are not its reads'");
+    int rc;
+    lra_svsig_result sv; memset(&sv, 0, sizeof sv);
+    if ((rc = lra_sv_signatures_batch(ctx, (int)nA, res->d_blocks, res->d_block_off, res->d_strands, adr, nullptr, (const char*)ctx->seed->genome, adr + nA + 1,
+                                      ctx->svsig_len, &sv))) return rc;
+    S.svsig_bytes_d2h += 24;                                             // (its block count and two totals)
+    if (sv.n_sig) {
+      const size_t nCh = m->chrom_pos.size() - 1;
+      std::vector<uint64_t> off((size_t)nR + 1 + nCh + 1, 0);
+      for (int r = 0; r < nR; r++) off[(size_t)r + 1] = off[r] + strlen(names[r]);
+      uint64_t* coff = off.data() + nR + 1;
+      for (size_t c = 0; c < nCh; c++) coff[c + 1] = coff[c] + strlen(chrom_names[c]);
+      const size_t offBytes = off.size() * 8, rBytes = (size_t)off[nR], cBytes = (size_t)coff[nCh], up = offBytes + rBytes + cBytes;
+      char* stage = (char*)lra_pinned(ctx, up);
+      // scratch 1 (dead at return; lra_svsig_text_batch works in scratch 0): the name tables, the skip bytes, rec_off
+      const size_t upPad = (up + 64 + 255) & ~(size_t)255, skipPad = (nA + 255) & ~(size_t)255;
+      char* dev = (char*)lra_scratch(ctx, 1, upPad + skipPad + ((size_t)nR + 1) * 8);
+      if (!stage || !dev) return LRA_ERR_NOMEM;
+      char* w = dev + upPad;
+      memcpy(stage, off.data(), offBytes);
+      for (int r = 0; r < nR; r++) memcpy(stage + offBytes + off[r], names[r], (size_t)(off[(size_t)r + 1] - off[r]));
+      for (size_t c = 0; c < nCh; c++) memcpy(stage + offBytes + rBytes + coff[c], chrom_names[c], (size_t)(coff[c + 1] - coff[c]));
+      LRA_HIP_CHECK(ctx, hipMemcpyAsync(dev, stage, up, hipMemcpyHostToDevice, st));
+      S.svsig_bytes_h2d += up;
+      uint8_t* skip = nullptr;
+      if (res->d_read_status) {
+        skip = (uint8_t*)w;
+        hipLaunchKernelGGL(k_sv_skip, dim3((unsigned)((nA + 255) / 256)), dim3(256), 0, st, nA, nR, res->d_aln_read, res->d_read_status, skip);
+      }
+      uint64_t* d_rec_off = (uint64_t*)(w + skipPad);
+      LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));                      // (the staging buffer is free again)
+      const uint64_t* d_roff = (const uint64_t*)dev; const uint64_t* d_coff = d_roff + nR + 1;
+      lra_svsig_text_result tx; memset(&tx, 0, sizeof tx);
+      if ((rc = lra_svsig_text_batch(ctx, &sv, res->d_aln_read, res->d_chrom, skip, nR, dev + offBytes, d_roff, (int)nCh, dev + offBytes + rBytes, d_coff, &tx))) return rc;
+      S.svsig_bytes_d2h += 8;
+      if (tx.n_bytes) {
+        if (ctx->sv_pin_bytes < tx.n_bytes) {                            // kept and grown as the record text's buffer is
+          if (ctx->sv_pin) { (void)hipHostFree(ctx->sv_pin); ctx->sv_pin = nullptr; ctx->sv_pin_bytes = 0; }
+          const size_t want = tx.n_bytes + tx.n_bytes / 4 + 4096;
+          if (hipHostMalloc(&ctx->sv_pin, want, hipHostMallocDefault) != hipSuccess) { ctx->sv_pin = nullptr; return lra_set_err(ctx, LRA_ERR_NOMEM, "hipHostMalloc(%zu) failed", want); }
+          ctx->sv_pin_bytes = want;
+        }
+        hipLaunchKernelGGL(k_sv_rec_off, dim3((unsigned)(((size_t)nR + 1 + 255) / 256)), dim3(256), 0, st, nR, na, nJ, nA, res->d_job_aln_off, tx.d_aln_off, d_rec_off);
+        LRA_HIP_CHECK(ctx, hipMemcpyAsync(m->dev_sv_off.data(), d_rec_off, ((size_t)nR + 1) * 8, hipMemcpyDeviceToHost, st));
+        LRA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->sv_pin, tx.d_text, tx.n_bytes, hipMemcpyDeviceToHost, st));
+        LRA_HIP_CHECK(ctx, hipGetLastError());
+        LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+        S.svsig_bytes_d2h += tx.n_bytes + ((size_t)nR + 1) * 8;
+        m->dev_sv_ptr = (const char*)ctx->sv_pin; m->dev_sv_len = tx.n_bytes;
+      }
+    }
+  }
+  S.svsig_text_bytes = m->dev_sv_len;
+  S.ms_svsig = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0;
+  m->dev_sv = true;
+  return LRA_OK;
+}
+
 // The host half: a snapshot without the runs, the piece table on host threads; the device half: the CIGAR text, MD, the pairwise rows, the assembly.  See lra_hip.h.
 extern "C" int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
                                       const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough,
                                       const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const char** text, uint64_t* len,
                                       const uint64_t** rec_off) {
-  if (!ctx || !res || !o || !names || !read_len || !chrom_names || !len || (flags & ~LRA_PACK_MD) || (d_qual && !d_qual_off)) return LRA_ERR_INVALID;
+  if (!ctx || !res || !o || !names || !read_len || !chrom_names || !len || (flags & ~(LRA_PACK_MD | LRA_PACK_SVSIG)) || (d_qual && !d_qual_off)) return LRA_ERR_INVALID;
   lra_map_state* m = ctx->map;
   if (!m) return LRA_ERR_INVALID;
+  m->dev_sv = false;
+  const bool withSv = (flags & LRA_PACK_SVSIG) != 0;
   m->dev_stats = lra_records_device_stats{};
   lra_records_device_stats& S = m->dev_stats;
   auto wall = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -754,13 +841,19 @@ extern "C" int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, c
   int rc;
   if (!device) {                                                         // 'p', 'b': no long field worth moving -- the host path, its text kept by the context
     if (!reads) return LRA_ERR_INVALID;
-    if ((rc = lra_map_snapshot(ctx, res, flags & LRA_PACK_MD, &h))) return rc;
+    if ((rc = lra_map_snapshot(ctx, res, flags & (LRA_PACK_MD | LRA_PACK_SVSIG), &h))) return rc;
     const char* t = nullptr; const uint64_t* ro = nullptr;
     rc = records_host(h, o, names, reads, quals, read_len, chrom_names, nullptr, passthrough, n_threads, &t, len, &ro);
+    uint64_t svLen = 0;
+    if (!rc && withSv) rc = lra_map_svsig_host(h, names, chrom_names, n_threads, nullptr, &svLen, nullptr);
     if (!rc) {
       m->dev_text.swap(h->text); m->dev_off.swap(h->rec_off);
       if (text) *text = m->dev_text.data();
       if (rec_off) *rec_off = m->dev_off.data();
+      if (withSv) {
+        m->dev_sv_text.swap(h->sv_text); m->dev_sv_off.swap(h->sv_rec_off);
+        m->dev_sv_ptr = m->dev_sv_text.data(); m->dev_sv_len = svLen; m->dev_sv = true;
+      }
     }
     lra_map_host_free(h);
     return rc;
@@ -778,14 +871,15 @@ extern "C" int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, c
   lra_md_result md; memset(&md, 0, sizeof md);
   lra_pairwise_text_result pw; memset(&pw, 0, sizeof pw);
   hipStream_t st = ctx->stream;
+  uint64_t* adr = nullptr;
   if (nA) {
     if (!res->d_run_off || !res->d_strands) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device: the result has no runs / reads to work on");
     if (!pairwise && (rc = lra_cigar_text_batch(ctx, (int)nA, res->d_runs, res->d_run_off, nullptr, nullptr, nullptr, &cg))) return rc;
-    if (withMd || pairwise) {
+    if (withMd || pairwise || withSv) {
       if (!res->d_aln_read || !res->d_strand || !res->d_chrom || !res->d_blocks || !res->d_block_off)
         return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device: the result has no blocks to work on");
-      if (!ctx->seed || !ctx->seed->genome || !m->d_chrom_pos) return lra_set_err(ctx, LRA_ERR_INVALID, "LRA_PACK_MD / print format 'a': genome not loaded");
-      uint64_t* adr = (uint64_t*)lra_ensure(ctx, 187, 2 * (nA + 1) * 8);
+      if (!ctx->seed || !ctx->seed->genome || !m->d_chrom_pos) return lra_set_err(ctx, LRA_ERR_INVALID, "LRA_PACK_MD / LRA_PACK_SVSIG / print format 'a': genome not loaded");
+      adr = (uint64_t*)lra_ensure(ctx, 187, 2 * (nA + 1) * 8);
       if (!adr) return LRA_ERR_NOMEM;
       const uint64_t* ro = (const uint64_t*)(res->d_strands + lra_strands_ro_at(res->rc_base));
       hipLaunchKernelGGL(k_md_address, dim3((unsigned)((nA + 255) / 256)), dim3(256), 0, st, nA, res->d_aln_read, res->d_strand, res->d_chrom, ro, res->rc_base,
@@ -835,6 +929,15 @@ extern "C" int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, c
   m->dev_text.clear();
   if ((rc = lra_records_assemble(ctx, J, text, len, m->dev_off.data(), &S))) return rc;
   if (rec_off) *rec_off = m->dev_off.data();
+  if (withSv && (rc = records_device_svsig(ctx, res, adr, names, chrom_names, S))) return rc;   // (behind the records: their long fields' buffers are done with)
+  return LRA_OK;
+}
+
+extern "C" int lra_map_records_device_svsig(lra_ctx* ctx, const char** text, uint64_t* len, const uint64_t** rec_off) {
+  if (!ctx || !len || !ctx->map || !ctx->map->dev_sv) return LRA_ERR_INVALID;
+  *len = ctx->map->dev_sv_len;
+  if (text) *text = ctx->map->dev_sv_ptr;
+  if (rec_off) *rec_off = ctx->map->dev_sv_off.data();
   return LRA_OK;
 }
 

@@ -56,6 +56,8 @@ struct lra_map_state {
   lra_text_buf last_text; std::vector<uint64_t> last_off; lra_map_sig last_sig;   // lra_map_records: sizing call -> filling call
   lra_text_buf sv_text; std::vector<uint64_t> sv_off;                             // lra_map_svsig: the text and read ranges of its last call
   lra_text_buf dev_text; std::vector<uint64_t> dev_off; lra_records_device_stats dev_stats{};   // lra_map_records_device: rec_off (and a fall-through's text) of its last call
+  bool dev_sv = false; const char* dev_sv_ptr = nullptr; uint64_t dev_sv_len = 0;               // its SV signature text, when it was called with LRA_PACK_SVSIG: in the
+  lra_text_buf dev_sv_text; std::vector<uint64_t> dev_sv_off;                                   // context's page-locked buffer, or (a fall-through's) in dev_sv_text
 };
 
 int lra_map_count_flagged(lra_ctx* ctx, lra_map_result* out);   // mapread.hip: counters.n_flagged_reads of a finished batch

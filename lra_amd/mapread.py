@@ -147,7 +147,8 @@ class MapResult(C.Structure):
 class RecordsDeviceStats(C.Structure):
     """lra_records_device_stats (include/lra_hip.h)"""
     _fields_ = [(k, C.c_double) for k in ("ms_snapshot", "ms_cigar_md", "ms_pieces", "ms_upload", "ms_kernels", "ms_copy_kernel", "ms_text_copy")] + \
-               [(k, C.c_uint64) for k in ("bytes_h2d", "bytes_d2h", "text_bytes", "n_pieces")]
+               [(k, C.c_uint64) for k in ("bytes_h2d", "bytes_d2h", "text_bytes", "n_pieces")] + [("ms_svsig", C.c_double)] + \
+               [(k, C.c_uint64) for k in ("svsig_bytes_h2d", "svsig_bytes_d2h", "svsig_text_bytes")]
 
 
 PACK_NORUNS = 8                                  # LRA_PACK_NORUNS: a pack / snapshot without the CIGAR runs (what lra_map_records_device copies)
@@ -447,12 +448,14 @@ class LowAccMapper:
             lib.lra_map_host_free(snap)
         return out
 
-    def records_device(self, res: MapResult, args, passthrough=None, d_qual=None, d_qual_off=None, md=None, n_threads=0, as_list=True):
+    def records_device(self, res: MapResult, args, passthrough=None, d_qual=None, d_qual_off=None, md=None, n_threads=0, as_list=True, svsig=False):
         """lra_map_records_device: the batch's record text built on the device (formats 's', 'P' and 'a'; the others fall through to the host path) -- the bytes
         records_host gives for a snapshot of the same result.  args: record_args(names, reads, quals); passthrough: None or one text per read (None entries:
         none); d_qual / d_qual_off: the batch's qualities as device tensors or raw device addresses (a device reader's batch["d_qual"] / ["d_qual_off"];
         None: uploaded from args' quals); md (None: opts.printMD): MD:Z in SAM records.
-        Call it where snapshot() would be called: the result's arrays must be alive.  -> list of per-read bytes, or the total bytes when as_list is False."""
+        Call it where snapshot() would be called: the result's arrays must be alive.  -> list of per-read bytes, or the total bytes when as_list is False.
+        svsig: the call builds the SV signature text too (LRA_PACK_SVSIG, net gaps above svsigLen; on the device for the device formats) and returns
+        (records, signatures), the signatures per read as svsig_host returns them (their total bytes when as_list is False); the records do not change."""
         ctx = self.ctx
         n = args["n"]
         tags = None
@@ -460,11 +463,26 @@ class LowAccMapper:
             tags = (C.c_char_p * n)(*[None if t is None else bytes(t) for t in passthrough])
         elif passthrough is not None:
             tags = (C.c_char_p * n)(*[bytes(passthrough)] * n)
-        flags = PACK_MD if (self.print_md if md is None else md) else 0
+        flags = (PACK_MD if (self.print_md if md is None else md) else 0) | (PACK_SVSIG if svsig else 0)
+        if svsig:
+            set_svsig_len(ctx, self.svsig_len)
         text = C.c_void_p(); ln = C.c_uint64(0); roff = C.POINTER(C.c_uint64)()
         ctx.check(ctx.lib.lra_map_records_device(ctx.h, C.byref(res), C.byref(self.copts), args["names"], args["reads"], args["quals"], args["lens"], args["chroms"], tags,
                                                  ptr(d_qual) if d_qual is not None else None, ptr(d_qual_off) if d_qual_off is not None else None, flags,
                                                  int(n_threads), C.byref(text), C.byref(ln), C.byref(roff)))
+        out = ln.value
+        if as_list:
+            raw = C.string_at(text, ln.value) if ln.value else b""
+            out = [raw[roff[i]:roff[i + 1]] for i in range(n)]
+        if not svsig:
+            return out
+        return out, self.records_device_svsig(n, as_list=as_list)
+
+    def records_device_svsig(self, n, as_list=True):
+        """lra_map_records_device_svsig: the SV signature text the last records_device(svsig=True) on this context built -> per read the bytes of its lines."""
+        ctx = self.ctx
+        text = C.c_void_p(); ln = C.c_uint64(0); roff = C.POINTER(C.c_uint64)()
+        ctx.check(ctx.lib.lra_map_records_device_svsig(ctx.h, C.byref(text), C.byref(ln), C.byref(roff)))
         if not as_list:
             return ln.value
         raw = C.string_at(text, ln.value) if ln.value else b""
@@ -691,6 +709,7 @@ class HighAccMapper:
     svsig_len = LowAccMapper.svsig_len
     records_device = LowAccMapper.records_device
     records_device_stats = LowAccMapper.records_device_stats
+    records_device_svsig = LowAccMapper.records_device_svsig
     svsig_host = LowAccMapper.svsig_host
     sv_signatures = LowAccMapper.sv_signatures
     fetch_local_index = LowAccMapper.fetch_local_index

@@ -189,6 +189,42 @@ def sv_signatures_batch(ctx: Context, b: RefineBatch, min_len=25):
     return off, recs, seq
 
 
+class SvSigTextResult(C.Structure):
+    """lra_svsig_text_result (include/lra_hip.h)"""
+    _fields_ = [("n_aln", C.c_int32), ("n_sig", C.c_uint64), ("n_bytes", C.c_uint64), ("d_aln_off", C.c_void_p), ("d_text", C.c_void_p)]
+
+
+SVSIG_TEXT_CHUNK = 4096             # svsig_text.hip's SVT_CHUNK: the output bytes one wave of its copy kernel moves
+
+
+def name_table(ctx: Context, names):
+    """A name table as lra_svsig_text_batch takes it: (the names back to back, uint64 offsets [n + 1]) as device tensors."""
+    import torch
+    off = np.zeros(len(names) + 1, np.int64)
+    off[1:] = np.cumsum([len(x) for x in names])
+    blob = np.frombuffer(b"".join(names) + b"\0" * 8, np.uint8).copy()
+    return torch.from_numpy(blob).to(ctx.device), torch.from_numpy(off).to(ctx.device)
+
+
+def svsig_text_batch(ctx: Context, sv: SvSigResult, aln_read, chrom, read_names, chrom_names, skip=None):
+    """lra_svsig_text_batch: the lines of the signatures `sv` holds (the result of lra_sv_signatures_batch, still alive on the context), on the device.
+    aln_read / chrom / skip: per alignment its read, its chromosome and (optional) 1 to print nothing; the names as lists of bytes.
+    -> (the text, aln_off uint64[n_aln + 1]): alignment a's lines are text[aln_off[a]:aln_off[a + 1]]."""
+    import torch
+    dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(ctx.device)
+    d_read, d_chrom = dev(np.asarray(aln_read, np.uint32).view(np.int32), np.int32), dev(chrom, np.int32)
+    d_skip = dev(skip, np.uint8) if skip is not None else None
+    rn, ro = name_table(ctx, read_names)
+    cn, co = name_table(ctx, chrom_names)
+    res = SvSigTextResult()
+    ctx.check(ctx.lib.lra_svsig_text_batch(ctx.h, C.byref(sv), ptr(d_read), ptr(d_chrom), ptr(d_skip) if d_skip is not None else None, len(read_names), ptr(rn), ptr(ro),
+                                           len(chrom_names), ptr(cn), ptr(co), C.byref(res)))
+    assert int(res.n_aln) == int(sv.n_aln) and int(res.n_sig) == int(sv.n_sig)
+    off = ctx.to_host(res.d_aln_off, int(res.n_aln) + 1, np.uint64)
+    text = ctx.to_host(res.d_text, int(res.n_bytes), np.uint8).tobytes() if res.n_bytes else b""
+    return text, off
+
+
 STAT_NAMES = ["nm", "nmm", "nins", "ndel", "tdel", "tins", "nSmallDel", "nMedDel", "nLargeDel", "nSmallIns", "nMedIns", "nLargeIns",
               "preClip", "sufClip", "qStart", "qEnd", "tStart", "tEnd"]
 

@@ -116,9 +116,9 @@ def main():
              (["-Flag", str(args.flag)] if args.flag else []) + (["--passthrough"] if args.passthrough else []) + (["-SV", *args.sv] if args.sv else [])       # (--device-records is no lra option: the same records)
         out.write(mapread.LowAccMapper.sam_header(mapper, b"lra_amd", " ".join(cl).encode()))   # the lra command line: the same for either reader
     # --device-records with device input: the qualities stay on the device from the reader to the record text; the host copies of bases and qualities
-    # are switched off where nothing reads them (the formats the device builds; -SV prints from a host snapshot)
+    # are switched off where nothing reads them (the formats the device builds; with them -SV is built on the device too, from the result's own arrays)
     dev_quals = args.device_records and not args.host_input
-    no_host = dev_quals and fmt in ("s", "c", "a") and not args.sv
+    no_host = dev_quals and fmt in ("s", "c", "a")
     rf = reads_io.ReadsFile(args.reads, ctx=None if args.host_input else ctx, chunk=None if args.host_input else args.chunk, flag_remove=args.flag, compressed_text=True,
                             passthrough=args.passthrough, device_quals=dev_quals, no_host_copy=no_host)
     sv_out = open(args.sv[1], "wb") if args.sv else None
@@ -139,7 +139,12 @@ def main():
         t_map += time.perf_counter() - t
         t = time.perf_counter()
         tags = b["tags"] if args.passthrough else None
-        if sv_out:                                                          # one snapshot: the records and the signatures of the same batch, both in read order
+        if sv_out and args.device_records:                                  # one call: the records and the signatures of the same batch, both in read order
+            texts, sigs = mapper.records_device(res, mapper.record_args(b["names"], b["seqs"], b["quals"], lens=b.get("read_len")), passthrough=tags,
+                                                d_qual=b.get("d_qual"), d_qual_off=b.get("d_qual_off"), svsig=True)
+            for sig in sigs:
+                sv_out.write(sig)
+        elif sv_out:                                                        # one snapshot: the same from the host
             snap = mapper.snapshot(res, with_blocks=fmt == "a", svsig=True)
             texts = mapper.records_host(snap, mapper.record_args(b["names"], b["seqs"], b["quals"]), passthrough=tags, free=False)
             for sig in mapper.svsig_host(snap, b["names"]):
