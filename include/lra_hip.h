@@ -1330,6 +1330,32 @@ int lra_bgzf_inflate_batch(lra_ctx* ctx, int n_blocks, const uint8_t* d_in, cons
 int lra_bgzf_inflate_lut_batch(lra_ctx* ctx, int n_blocks, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_out_off, uint8_t* d_out,
                                int32_t* d_status);
 int lra_bgzf_inflate_host(int n_blocks, const uint8_t* in, const uint64_t* in_off, const uint64_t* out_off, uint8_t* out, int32_t* status);
+/* BGZF deflate, the inverse stage (additive to ABI 9): member i is the data in[in_off[i], in_off[i + 1]) and becomes one complete BGZF member at
+ * out + i * LRA_BGZF_SLOT -- the 18-byte header with the 'BC' field (BSIZE = the member's length - 1), raw DEFLATE data, CRC-32, ISIZE -- of out_len[i]
+ * (<= 65536) bytes.  Data longer than LRA_BGZF_IN_MAX: status[i] != 0, out_len[i] = 0, nothing else written (a status per member, as inflate gives).
+ * Length 0 gives a valid empty member; n_blocks = 0 is legal.  Nothing outside [slot, slot + out_len[i]) is written and nothing outside the member's
+ * data is read (single bytes and unaligned words inside it: the input needs no alignment and no padding); the device form writes the slot in aligned
+ * dwords, so d_out must be 4-byte aligned (else LRA_ERR_INVALID).  One algorithm, no level: a single-candidate hash of three bytes, greedy parse,
+ * matches of 3 .. 258 at distances up to 32768 inside the member, dynamic Huffman blocks of 4096 positions, each written stored when that is not
+ * smaller (65280 random bytes still fit the slot).  The parse is defined by position (lra_amd/csrc/bgzf_deflate.h states the rule), so _host and _batch
+ * give byte-identical members, whatever a member's place in the batch, its alignment and its neighbours.  _batch: device arrays, on ctx's device and
+ * stream, complete at return (one wave per member). */
+#define LRA_BGZF_IN_MAX 65280   /* bytes of data per member (htslib's block size: a stored member of it still fits 64 KiB) */
+#define LRA_BGZF_SLOT 65536     /* bytes a member may take */
+int lra_bgzf_deflate_batch(lra_ctx* ctx, int n_blocks, const uint8_t* d_in, const uint64_t* d_in_off, uint8_t* d_out, uint32_t* d_out_len,
+                           int32_t* d_status);
+int lra_bgzf_deflate_host(int n_blocks, const uint8_t* in, const uint64_t* in_off, uint8_t* out, uint32_t* out_len, int32_t* status);
+/* The stream stage: the device text d_text[0, len) cut every LRA_BGZF_IN_MAX bytes, deflated in rounds of a bounded number of members (the slots of a
+ * round are the stage's scratch: 2048 members, 128 MiB, and as much for the round's packed members, whatever len is), each round's members packed back
+ * to back (lra_pack_strings_batch's kernel) and copied into a page-locked buffer the context keeps.  *h_data[0, *data_len) holds the members,
+ * member i at (*h_member_off)[i] .. [i + 1] (n_members + 1 entries); both are owned by the context and valid until the next call on it.  len = 0 gives
+ * zero members; no EOF member is appended (the file's writer does that).  On ctx's device and stream, complete at return.
+ *   lra_bgzf_compress_set_round   members per round (0: the default), for tests and for a caller short of device memory.
+ *   lra_bgzf_compress_stats       the last call's wall time in ms and its output bytes (either may be NULL). */
+int lra_bgzf_compress_device(lra_ctx* ctx, const uint8_t* d_text, uint64_t len, const uint8_t** h_data, uint64_t* data_len,
+                             const uint64_t** h_member_off, uint64_t* n_members);
+int lra_bgzf_compress_set_round(lra_ctx* ctx, int members);
+int lra_bgzf_compress_stats(lra_ctx* ctx, double* ms_deflate, uint64_t* bgzf_bytes);
 /* ---- the genome (Genome::Read, Genome.h:115-138) -------------------------------------------------------------------------------------------------
  * A genome FASTA file -- plain text, gzip or BGZF, as gzopen takes them -- into what lra_ctx_load_genome[_device] and lra_ctx_load_chromosomes take: the
  * bases of all records back to back, upper-cased, and header.pos.  The parsing rules are kseq_read's FASTA branch; lra_amd/csrc/genome.hip states them.
@@ -1454,6 +1480,16 @@ int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, const lra_ma
                            const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const char** text, uint64_t* len,
                            const uint64_t** rec_off);
 int lra_map_records_device_last(lra_ctx* ctx, lra_records_device_stats* out);
+/* lra_map_records_device whose record text leaves the device BGZF-compressed (additive to ABI 9): the arguments, the flags, rec_off (in UNCOMPRESSED
+ * bytes) and the SV signature text (plain, through lra_map_records_device_svsig) are those of lra_map_records_device.  Formats 's', 'P' and 'a': the
+ * text's own device-to-host copy is skipped and lra_bgzf_compress_device runs on the text where the assembly left it; the fall-through formats 'p' and
+ * 'b' upload the host text and compress it the same way.  data / data_len / member_off / n_members: as lra_bgzf_compress_device returns them (owned by
+ * the context, valid until its next compress call; no EOF member).  lra_map_records_device_last then has the members' bytes in bytes_d2h instead of the
+ * text's; lra_bgzf_compress_stats gives the compress stage's wall time (ms_deflate) and its output (bgzf_bytes). */
+int lra_map_records_device_bgzf(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* opts, const char* const* names, const char* const* reads,
+                                const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough,
+                                const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const uint8_t** data, uint64_t* data_len,
+                                const uint64_t** rec_off, const uint64_t** member_off, uint64_t* n_members);
 int lra_map_records_device_svsig(lra_ctx* ctx, const char** text, uint64_t* len, const uint64_t** rec_off);
 /* the reads of a snapshot whose status word is non-zero: their number; *status (optional) = the snapshot's status array [n_reads], owned by the snapshot */
 uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status);

@@ -79,6 +79,11 @@ SYMBOLS = {
     "lra_bgzf_inflate_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lra_bgzf_inflate_lut_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lra_bgzf_inflate_host": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "lra_bgzf_deflate_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "lra_bgzf_deflate_host": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "lra_bgzf_compress_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "lra_bgzf_compress_set_round": (C.c_int, [_vp, C.c_int]),
+    "lra_bgzf_compress_stats": (C.c_int, [_vp, _vp, _vp]),
     "lra_genome_open": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),
     "lra_genome_read_host": (C.c_int, [_vp]),
     "lra_genome_read_device": (C.c_int, [_vp, _vp]),
@@ -157,6 +162,7 @@ SYMBOLS = {
     "lra_map_records_host_tags": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "lra_map_records_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "lra_map_records_device_last": (C.c_int, [_vp, _vp]),
+    "lra_map_records_device_bgzf": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lra_map_records_device_svsig": (C.c_int, [_vp, _vp, _vp, _vp]),
     "lra_filter_chains_batch": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "lra_filter_chains_ex_batch": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),

@@ -36,6 +36,10 @@ struct lra_ctx {
   void* pin_buf = nullptr; size_t pin_bytes = 0;      // page-locked host staging of the large device-to-host copies (lra_pinned)
   void* rec_pin = nullptr; size_t rec_pin_bytes = 0;  // records.hip: the page-locked buffer the device record stage's text lands in (kept between batches)
   void* sv_pin = nullptr; size_t sv_pin_bytes = 0;    // map_output.hip: the same for the SV signature text (LRA_PACK_SVSIG), which lives beside the record text
+  void* bgzf_pin = nullptr; size_t bgzf_pin_bytes = 0;   // deflate.hip: the page-locked buffer lra_bgzf_compress_device's members land in (kept between calls)
+  std::vector<uint64_t> bgzf_member_off;             // deflate.hip: where each member of the last lra_bgzf_compress_device starts in it
+  int bgzf_round = 0;                                 // deflate.hip: members per round of lra_bgzf_compress_device (0: its default)
+  double bgzf_ms = 0; uint64_t bgzf_bytes = 0;        // deflate.hip: the last lra_bgzf_compress_device's wall time and output size
   uint64_t* scan_tmp = nullptr;
   // lra_side_fork / lra_side_join: further streams for kernels that would only extend a stage's tail on the context's own stream
   static constexpr int N_SIDE = 4;

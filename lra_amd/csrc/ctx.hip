@@ -141,6 +141,7 @@ extern "C" void lra_ctx_destroy(lra_ctx* ctx) {
   if (ctx->pin_buf) (void)hipHostFree(ctx->pin_buf);
   if (ctx->rec_pin) (void)hipHostFree(ctx->rec_pin);
   if (ctx->sv_pin) (void)hipHostFree(ctx->sv_pin);
+  if (ctx->bgzf_pin) (void)hipHostFree(ctx->bgzf_pin);
   if (ctx->scan_tmp) (void)hipFree(ctx->scan_tmp);
   for (int i = 0; i < 192; i++) if (ctx->gbuf[i]) (void)hipFree(ctx->gbuf[i]);
   for (auto& r : ctx->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }

@@ -822,10 +822,11 @@ static int records_device_svsig(lra_ctx* ctx, const lra_map_result* res, const u
 }
 
 // The host half: a snapshot without the runs, the piece table on host threads; the device half: the CIGAR text, MD, the pairwise rows, the assembly.  See lra_hip.h.
-extern "C" int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
-                                      const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough,
-                                      const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const char** text, uint64_t* len,
-                                      const uint64_t** rec_off) {
+// keep: the device formats' text stays on the device (*text is a device pointer then), for lra_map_records_device_bgzf
+static int records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
+                          const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough,
+                          const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const char** text, uint64_t* len,
+                          const uint64_t** rec_off, bool keep) {
   if (!ctx || !res || !o || !names || !read_len || !chrom_names || !len || (flags & ~(LRA_PACK_MD | LRA_PACK_SVSIG)) || (d_qual && !d_qual_off)) return LRA_ERR_INVALID;
   lra_map_state* m = ctx->map;
   if (!m) return LRA_ERR_INVALID;
@@ -924,12 +925,47 @@ extern "C" int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, c
   J.d_read_off = res->d_strands ? (const uint64_t*)(res->d_strands + lra_strands_ro_at(res->rc_base)) : nullptr;
   J.d_qual = dq; J.d_qual_off = dqo; J.d_cg = cg.d_text; J.d_cg_off = cg.d_off; J.d_md = withMd ? md.d_md : nullptr; J.d_md_off = withMd ? md.d_md_off : nullptr;
   J.d_pw = pw.d_text; J.d_pw_off = pw.d_off;
+  J.keep_on_device = keep;
   if (!J.d_strands && nR) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device: the result has no reads to work on");
   m->dev_off.assign((size_t)nR + 1, 0);
   m->dev_text.clear();
   if ((rc = lra_records_assemble(ctx, J, text, len, m->dev_off.data(), &S))) return rc;
   if (rec_off) *rec_off = m->dev_off.data();
   if (withSv && (rc = records_device_svsig(ctx, res, adr, names, chrom_names, S))) return rc;   // (behind the records: their long fields' buffers are done with)
+  return LRA_OK;
+}
+
+extern "C" int lra_map_records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
+                                      const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough,
+                                      const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const char** text, uint64_t* len,
+                                      const uint64_t** rec_off) {
+  return records_device(ctx, res, o, names, reads, quals, read_len, chrom_names, passthrough, d_qual, d_qual_off, flags, n_threads, text, len, rec_off, false);
+}
+
+// lra_map_records_device whose text leaves the device as BGZF members: formats 's', 'P' and 'a' compress the device text where the assembly left it (work
+// buffer 99; the SV signature text, built behind it, does not touch that buffer), the fall-through formats upload the host text first (work buffer 74)
+extern "C" int lra_map_records_device_bgzf(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
+                                           const char* const* quals, const int32_t* read_len, const char* const* chrom_names,
+                                           const char* const* passthrough, const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads,
+                                           const uint8_t** data, uint64_t* data_len, const uint64_t** rec_off, const uint64_t** member_off,
+                                           uint64_t* n_members) {
+  if (!data || !data_len || !member_off || !n_members || !o) return LRA_ERR_INVALID;
+  const char* text = nullptr;
+  uint64_t len = 0;
+  int rc = records_device(ctx, res, o, names, reads, quals, read_len, chrom_names, passthrough, d_qual, d_qual_off, flags, n_threads, &text, &len, rec_off, true);
+  if (rc) return rc;
+  const bool device = o->printFormat == 's' || o->printFormat == 'P' || o->printFormat == 'a';
+  const uint8_t* d_text = (const uint8_t*)text;
+  if (!device && len) {
+    char* up = (char*)lra_ensure(ctx, 74, len + 64);
+    if (!up) return LRA_ERR_NOMEM;
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(up, text, len, hipMemcpyHostToDevice, ctx->stream));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->map->dev_stats.bytes_h2d += len;
+    d_text = (const uint8_t*)up;
+  }
+  if ((rc = lra_bgzf_compress_device(ctx, d_text, len, data, data_len, member_off, n_members))) return rc;
+  ctx->map->dev_stats.bytes_d2h += *data_len;
   return LRA_OK;
 }
 

@@ -18,5 +18,6 @@ struct lra_rec_job {
   const char* d_cg = nullptr; const uint64_t* d_cg_off = nullptr;
   const char* d_md = nullptr; const uint64_t* d_md_off = nullptr;
   const char* d_pw = nullptr; const uint64_t* d_pw_off = nullptr;
+  bool keep_on_device = false;                                       // lra_map_records_device_bgzf: *text is the device text (work buffer 99), not copied to the host
 };
 int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& job, const char** text, uint64_t* len, uint64_t* h_rec_off, lra_records_device_stats* stats);

@@ -249,7 +249,7 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
   A.out = (unsigned char*)lra_ensure(ctx, 99, sz(total + 64, 1));
   if (!A.out) return LRA_ERR_NOMEM;
   A.n_out = total;
-  if (ctx->rec_pin_bytes < total) {                            // the page-locked buffer the text lands in: kept, grown with a quarter of headroom
+  if (!J.keep_on_device && ctx->rec_pin_bytes < total) {                            // the page-locked buffer the text lands in: kept, grown with a quarter of headroom
     if (ctx->rec_pin) { (void)hipHostFree(ctx->rec_pin); ctx->rec_pin = nullptr; ctx->rec_pin_bytes = 0; }
     const size_t want = total + total / 4 + 4096;
     if (hipHostMalloc(&ctx->rec_pin, want, hipHostMallocDefault) != hipSuccess) { ctx->rec_pin = nullptr; return lra_set_err(ctx, LRA_ERR_NOMEM, "hipHostMalloc(%zu) failed", want); }
@@ -264,7 +264,7 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
     lra_time_end(ctx);
   }
   LRA_HIP_CHECK(ctx, hipEventRecord(e1, st));
-  if (total) LRA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->rec_pin, A.out, total, hipMemcpyDeviceToHost, st));
+  if (total && !J.keep_on_device) LRA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->rec_pin, A.out, total, hipMemcpyDeviceToHost, st));
   LRA_HIP_CHECK(ctx, hipEventRecord(e2, st));
   LRA_HIP_CHECK(ctx, hipGetLastError());
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
@@ -274,11 +274,11 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
     if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) { S->ms_copy_kernel = ms; S->ms_kernels += ms; }
     if (hipEventElapsedTime(&ms, e1, e2) == hipSuccess) S->ms_text_copy = ms;
     S->bytes_h2d += nP * sizeof(lra_rec_piece) + (nR + 1) * 8 + J.blob_bytes;
-    S->bytes_d2h += total + (nR + 1) * 8 + 8;
+    S->bytes_d2h += (J.keep_on_device ? 0 : total) + (nR + 1) * 8 + 8;
     S->text_bytes = total; S->n_pieces = nP;
   }
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
   if (len) *len = total;
-  if (text) *text = (const char*)ctx->rec_pin;
+  if (text) *text = J.keep_on_device ? (const char*)A.out : (const char*)ctx->rec_pin;
   return LRA_OK;
 }

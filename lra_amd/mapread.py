@@ -478,6 +478,31 @@ class LowAccMapper:
             return out
         return out, self.records_device_svsig(n, as_list=as_list)
 
+    def records_device_bgzf(self, res: MapResult, args, passthrough=None, d_qual=None, d_qual_off=None, md=None, n_threads=0, svsig=False):
+        """lra_map_records_device_bgzf: records_device whose text leaves the device as BGZF members (no EOF member) -> (data, rec_off, member_off): the
+        members back to back as bytes, rec_off[n + 1] in UNCOMPRESSED bytes and member_off[n_members + 1] as uint64 arrays.  The arguments are
+        records_device's.  svsig: -> (data, rec_off, member_off, signatures); the signature text stays plain."""
+        from .deflate import compress_result
+        ctx = self.ctx
+        n = args["n"]
+        tags = None
+        if isinstance(passthrough, (list, tuple)):
+            tags = (C.c_char_p * n)(*[None if t is None else bytes(t) for t in passthrough])
+        elif passthrough is not None:
+            tags = (C.c_char_p * n)(*[bytes(passthrough)] * n)
+        flags = (PACK_MD if (self.print_md if md is None else md) else 0) | (PACK_SVSIG if svsig else 0)
+        if svsig:
+            set_svsig_len(ctx, self.svsig_len)
+        data = C.c_void_p(); ln = C.c_uint64(0); roff = C.POINTER(C.c_uint64)(); moff = C.c_void_p(); nm = C.c_uint64(0)
+        rc = ctx.lib.lra_map_records_device_bgzf(ctx.h, C.byref(res), C.byref(self.copts), args["names"], args["reads"], args["quals"], args["lens"], args["chroms"],
+                                                 tags, ptr(d_qual) if d_qual is not None else None, ptr(d_qual_off) if d_qual_off is not None else None, flags,
+                                                 int(n_threads), C.byref(data), C.byref(ln), C.byref(roff), C.byref(moff), C.byref(nm))
+        raw, member_off = compress_result(ctx.lib, ctx, rc, data, ln, moff, nm)
+        rec_off = np.array([roff[i] for i in range(n + 1)], np.uint64)
+        if not svsig:
+            return raw, rec_off, member_off
+        return raw, rec_off, member_off, self.records_device_svsig(n)
+
     def records_device_svsig(self, n, as_list=True):
         """lra_map_records_device_svsig: the SV signature text the last records_device(svsig=True) on this context built -> per read the bytes of its lines."""
         ctx = self.ctx
@@ -710,6 +735,7 @@ class HighAccMapper:
     records_device = LowAccMapper.records_device
     records_device_stats = LowAccMapper.records_device_stats
     records_device_svsig = LowAccMapper.records_device_svsig
+    records_device_bgzf = LowAccMapper.records_device_bgzf
     svsig_host = LowAccMapper.svsig_host
     sv_signatures = LowAccMapper.sv_signatures
     fetch_local_index = LowAccMapper.fetch_local_index

@@ -1,11 +1,12 @@
 """Map read files against a genome FASTA and print the records as `lra align` would (needs the GPU):
 
-    python tools/map_files.py -ONT genome.fa reads.fq [more.fa ...] [-p s|p|pc|b|a] [-H] [--printMD] [-a] [--PrintNumAln N] [--refineBreakpoints] [-o out.sam] [--device-records]
+    python tools/map_files.py -ONT genome.fa reads.fq [more.fa ...] [-p s|p|pc|b|a] [-H] [--printMD] [-a] [--PrintNumAln N] [--refineBreakpoints] [-o out.sam] [--device-records] [--bgzf]
 
 The reads are parsed on the device (lra_reads_next_batch_device) and mapped from the reader's device arrays; --host-input parses them on the host
 (lra_reads_next_batch) and maps through lra_map_reads_host, the same records.  The index: genome.fa.mms / genome.fa.gli when both exist (lra_read_mms /
 lra_read_gli), else built on the device with the preset's `lra index` parameters.  The genome (plain text, gzip or BGZF) is parsed on the device too
-(lra_genome_read_device); --host-genome parses it on the host (lra_genome_read_host).  Per-stage times go to stderr."""
+(lra_genome_read_device); --host-genome parses it on the host (lra_genome_read_host).  --bgzf writes the output BGZF-compressed: the header through
+lra_bgzf_deflate_host, every batch's records deflated on the device, the EOF member at the end.  Per-stage times go to stderr."""
 import argparse
 import os
 import sys
@@ -14,7 +15,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
-from lra_amd import genome_io, index, mapread, reads_io
+from lra_amd import bgzf, deflate, genome_io, index, mapread, reads_io
 from lra_amd.context import Context
 
 INDEX_PARAMS = {"ONT": (17, 10, 150, 15, 1), "CLR": (15, 10, 250, 12, 1), "CCS": (17, 10, 150, 15, 1), "CONTIG": (19, 10, 30, 20, 1)}   # `lra index -<preset>`
@@ -67,6 +68,8 @@ def main():
     ap.add_argument("--passthrough", action="store_true", help="SAM / BAM input: append each read's aux fields to its SAM records")
     ap.add_argument("--device-records", action="store_true",
                     help="build the record text on the device (lra_map_records_device; formats s, pc and a, the others fall through to the host path)")
+    ap.add_argument("--bgzf", action="store_true",
+                    help="write the output as BGZF: the records are deflated on the device (with --device-records before they leave it: lra_map_records_device_bgzf)")
     args = ap.parse_args()
     P = args.preset
     t0 = time.perf_counter()
@@ -114,7 +117,10 @@ def main():
         cl = ["lra", "align", "-" + P, args.genome, *args.reads, "-p", args.fmt] + (["-H"] if args.hard_clip else []) + (["--printMD"] if args.printMD else []) + \
              (["-a"] if args.store_all else []) + ["--PrintNumAln", str(args.PrintNumAln)] + (["--refineBreakpoints"] if args.refineBreakpoints else []) + \
              (["-Flag", str(args.flag)] if args.flag else []) + (["--passthrough"] if args.passthrough else []) + (["-SV", *args.sv] if args.sv else [])       # (--device-records is no lra option: the same records)
-        out.write(mapread.LowAccMapper.sam_header(mapper, b"lra_amd", " ".join(cl).encode()))   # the lra command line: the same for either reader
+        head = mapread.LowAccMapper.sam_header(mapper, b"lra_amd", " ".join(cl).encode())     # the lra command line: the same for either reader
+        if args.bgzf:
+            head = b"".join(deflate.deflate_members([head[a:a + deflate.IN_MAX] for a in range(0, len(head), deflate.IN_MAX)])[0])
+        out.write(head)
     # --device-records with device input: the qualities stay on the device from the reader to the record text; the host copies of bases and qualities
     # are switched off where nothing reads them (the formats the device builds; with them -SV is built on the device too, from the result's own arrays)
     dev_quals = args.device_records and not args.host_input
@@ -139,7 +145,13 @@ def main():
         t_map += time.perf_counter() - t
         t = time.perf_counter()
         tags = b["tags"] if args.passthrough else None
-        if sv_out and args.device_records:                                  # one call: the records and the signatures of the same batch, both in read order
+        if args.bgzf and args.device_records:                               # the text leaves the device as BGZF members; the signatures stay plain
+            r = mapper.records_device_bgzf(res, mapper.record_args(b["names"], b["seqs"], b["quals"], lens=b.get("read_len")), passthrough=tags,
+                                           d_qual=b.get("d_qual"), d_qual_off=b.get("d_qual_off"), svsig=bool(sv_out))
+            texts = [r[0]]
+            for sig in (r[3] if sv_out else []):
+                sv_out.write(sig)
+        elif sv_out and args.device_records:                                # one call: the records and the signatures of the same batch, both in read order
             texts, sigs = mapper.records_device(res, mapper.record_args(b["names"], b["seqs"], b["quals"], lens=b.get("read_len")), passthrough=tags,
                                                 d_qual=b.get("d_qual"), d_qual_off=b.get("d_qual_off"), svsig=True)
             for sig in sigs:
@@ -154,6 +166,8 @@ def main():
                                           d_qual=b.get("d_qual"), d_qual_off=b.get("d_qual_off"))
         else:
             texts = mapper.records(res, b["names"], b["seqs"], quals=b["quals"], passthrough=tags)
+        if args.bgzf and not args.device_records:                           # the host text, deflated on the device
+            texts = [deflate.compress_device(ctx, b"".join(texts))[0]]
         for txt in texts:
             out.write(txt)
         t_rec += time.perf_counter() - t
@@ -161,6 +175,8 @@ def main():
         if failed:
             break
     rf.close()
+    if args.bgzf:
+        out.write(bgzf.EOF_BLOCK)
     if sv_out:
         sv_out.close()
     if args.out:
