@@ -32,7 +32,13 @@
  *     lra_refine_clusters_batch with lra_refine_splitchain_batch;
  *   - a lra_map_reads_*_batch call invalidates every result of the call before it (and a
  *     pending two-call lra_map_records text); lra_map_snapshot / lra_map_pack take what the
- *     record stage needs out of the context first.
+ *     record stage needs out of the context first;
+ *   - lra_map_records_device, _bgzf and _bam share the record stage's buffers (the text or the
+ *     BAM record stream of the last call only); _bam also calls lra_bam_cigar_batch,
+ *     lra_bam_pack_seq_batch and lra_bam_phred_batch, whose results have buffers of their own.
+ * Output: the record stage writes SAM / PAF / BED / pairwise text, the same text as BGZF
+ * members (lra_map_records_device_bgzf) and BAM records (lra_map_records_device_bam with
+ * lra_bam_header), the last two made on the device before anything crosses to the host.
  * The two drivers are the tested orderings of these calls.
  */
 #ifndef LRA_HIP_H_
@@ -1465,7 +1471,7 @@ int lra_map_records_host_tags(lra_map_host* snap, const lra_map_opts* opts, cons
  * none). */
 typedef struct lra_records_device_stats {
   double ms_snapshot;      /* pack without the runs + its device-to-host copy + unpack */
-  double ms_cigar_md;      /* lra_cigar_text_batch (+ lra_md_strings_batch); format 'a': lra_pairwise_text_batch */
+  double ms_cigar_md;      /* lra_cigar_text_batch (+ lra_md_strings_batch); format 'a': lra_pairwise_text_batch; BAM records: + the three lra_bam_* primitives */
   double ms_pieces;        /* the host's piece table (wall) */
   double ms_upload;        /* pieces, blob (+ qualities when they come from the host) */
   double ms_kernels;       /* resolve, scan, copy */
@@ -1491,6 +1497,55 @@ int lra_map_records_device_bgzf(lra_ctx* ctx, const lra_map_result* res, const l
                                 const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const uint8_t** data, uint64_t* data_len,
                                 const uint64_t** rec_off, const uint64_t** member_off, uint64_t* n_members);
 int lra_map_records_device_svsig(lra_ctx* ctx, const char** text, uint64_t* len, const uint64_t** rec_off);
+/* ---- BAM output (additive to ABI 9) ----------------------------------------------------------------------------------------------------------------
+ * lra_map_records_device_bam: the batch's records as BAM alignment records (SAM/BAM specification 4.2: block_size, the 32-byte core, the name, the
+ * CIGAR ops, SEQ as 4-bit codes, QUAL as phred bytes, the typed tags), which say what lra_map_records_device's SAM text (printFormat 's') of the same
+ * result under the same options says: the same grouping, order, MAPQ, flags and clips, the same hardClip rule, PrintNumAln, MD:Z under LRA_PACK_MD,
+ * SA:Z and passthrough tags; unaligned, flagged and handed-back reads follow the same rules.  Arguments and flags are lra_map_records_device's (reads
+ * may be NULL).  printFormat other than 's', a read name above 254 bytes and a passthrough text that is not SAM aux fields (TG:T:value, tab-separated)
+ * are LRA_ERR_INVALID; the last two name the read.  The split is lra_map_records_device's: the host writes the core, the name, the clip ops, the tag
+ * block (integers typed as the smallest of C S I / c s i that holds them, NV:f as the float's bytes, TP:A, MD:Z / SA:Z with a NUL; passthrough text
+ * turned into binary aux) as literals of the piece table; the device makes the CIGAR ops, the packed SEQ and the phred QUAL once each
+ * (lra_bam_cigar_batch, lra_bam_pack_seq_batch, lra_bam_phred_batch) and the copy pass of lra_map_records_device assembles the records; block_size is
+ * written behind it, a lane per record.
+ *   core      refID = the chromosome's index, pos = t_start, bin = reg2bin(t_start, t_end), next_refID = next_pos = -1, tlen = the bits of the SAM's
+ *             column 9 (t_end - t_start); an unaligned record has refID = pos = -1, bin 4680, flag 4 and no CIGAR.
+ *   QUAL      BAM's QUAL has l_seq bytes: where the SAM's QUAL is not as long as its SEQ (hardClip's supplementary records, whose two ranges differ; a
+ *             quality string shorter than its read; "*"; no qualities) the record has none (0xff).  A reverse-strand record's qualities stay as they came.
+ *   CG:B:I    a record with more CIGAR ops than the limit (65535; lra_bam_set_cigar_limit, 1 .. 65535, 0: the default -- for tests) has the CIGAR
+ *             <l_seq>S<t_end - t_start>N and its ops in a CG:B:I tag at the end of the tag block, as the specification says.
+ * bgzf = 0: *data[0, *data_len) is the raw record stream in the context's page-locked record buffer, *member_off = NULL, *n_members = 0.  bgzf = 1: the
+ * stream stays on the device and goes through lra_bgzf_compress_device; data / data_len / member_off / n_members are as lra_map_records_device_bgzf
+ * returns them (no EOF member).  (*rec_off)[n_reads + 1] is per read, in bytes of the uncompressed stream.  The stream is in read order, not coordinate
+ * order: no index and no virtual offsets come with it.  LRA_PACK_SVSIG works as in lra_map_records_device (the signature text is plain);
+ * lra_map_records_device_last reports this call too.  The file's writer puts lra_bam_header's bytes in front and the BGZF EOF member behind.
+ * lra_bam_header (host only, two-call convention): "BAM\1", l_text, the text (lra_format_sam_header's, as it is), n_ref and per reference l_name, the
+ * name with its NUL and l_ref = chrom_pos[i + 1] - chrom_pos[i]. */
+int lra_map_records_device_bam(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* opts, const char* const* names, const char* const* quals,
+                               const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough, const char* d_qual,
+                               const uint64_t* d_qual_off, int flags, int n_threads, int bgzf, const uint8_t** data, uint64_t* data_len,
+                               const uint64_t** rec_off, const uint64_t** member_off, uint64_t* n_members);
+int lra_bam_set_cigar_limit(lra_ctx* ctx, int ops);
+int lra_bam_header(const char* text, uint64_t text_len, int n_chrom, const char* const* chrom_names, const uint64_t* chrom_pos, uint8_t* out, uint64_t cap,
+                   uint64_t* len);
+/* The device primitives behind it (gfx950; device arrays, on ctx's device and stream, complete at return; results owned by the context and valid until
+ * the next call of the same primitive on it; nothing is written behind the last byte or in front of the first).
+ *   lra_bam_cigar_batch     arguments as lra_cigar_text_batch.  One lane per run: (len << 4) | {0 1 2 3} for = X I D becomes BAM's (len << 4) | {7 8 1 2};
+ *                           a positive clip is an S (clip_op 'H': H) op on its side of the alignment's ops.  d_off[n_aln + 1] is in ops.
+ *   lra_bam_pack_seq_batch  range i = d_src[off, off + len) as 4-bit codes, (len + 1) / 2 bytes, the first base in the high nibble, an odd tail's low
+ *                           nibble 0; the ranges back to back at d_off[n + 1] (bytes).  "=ACMGRSVTWYHKDBN" in either case are 0 .. 15, any other byte 15.
+ *                           A range that leaves d_src[0, src_bytes) is not read: its bases are 15.
+ *   lra_bam_phred_batch     request i = len bytes: character - 33 of read's quality string d_qual[d_qual_off[read] + pos ..] where [pos, pos + len) lies
+ *                           inside the string; otherwise (d_qual NULL, read >= n_reads, the string too short, empty or "*") every byte is 0xff. */
+typedef struct lra_bam_cigar_result { int32_t n_aln; uint64_t n_ops; const uint64_t* d_off; const uint32_t* d_ops; } lra_bam_cigar_result;
+typedef struct lra_bam_seq_range { uint64_t off, len; } lra_bam_seq_range;
+typedef struct lra_bam_qual_req { uint32_t read, pos, len, reserved; } lra_bam_qual_req;
+typedef struct lra_bam_bytes_result { uint64_t n, n_bytes; const uint64_t* d_off; const uint8_t* d_data; } lra_bam_bytes_result;
+int lra_bam_cigar_batch(lra_ctx* ctx, int n_aln, const uint32_t* d_runs, const uint64_t* d_run_off, const int32_t* d_pre_clip, const int32_t* d_suf_clip,
+                        const uint8_t* d_clip_op, lra_bam_cigar_result* out);
+int lra_bam_pack_seq_batch(lra_ctx* ctx, uint64_t n, const lra_bam_seq_range* d_ranges, const uint8_t* d_src, uint64_t src_bytes, lra_bam_bytes_result* out);
+int lra_bam_phred_batch(lra_ctx* ctx, uint64_t n, const lra_bam_qual_req* d_req, int n_reads, const char* d_qual, const uint64_t* d_qual_off,
+                        lra_bam_bytes_result* out);
 /* the reads of a snapshot whose status word is non-zero: their number; *status (optional) = the snapshot's status array [n_reads], owned by the snapshot */
 uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status);
 /* The record buffer of a batch as ONE device buffer -- what a rank sends to rank 0 in the single exchange step of the multi-GPU path (the

@@ -164,6 +164,12 @@ SYMBOLS = {
     "lra_map_records_device_last": (C.c_int, [_vp, _vp]),
     "lra_map_records_device_bgzf": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lra_map_records_device_svsig": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "lra_map_records_device_bam": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "lra_bam_set_cigar_limit": (C.c_int, [_vp, C.c_int]),
+    "lra_bam_header": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "lra_bam_cigar_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lra_bam_pack_seq_batch": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp]),
+    "lra_bam_phred_batch": (C.c_int, [_vp, C.c_uint64, _vp, C.c_int, _vp, _vp, _vp]),
     "lra_filter_chains_batch": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "lra_filter_chains_ex_batch": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "lra_calculate_statistics_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),

@@ -27,10 +27,10 @@ __device__ __forceinline__ void wave_copy(unsigned char* dst, const unsigned cha
 // cost a step of the walk and nothing else.  src_of is not called for an empty string.
 // window(p, b, e), called with string p's range [b, e) of the output when it is not empty, may narrow it to the part src_of(p) fills (its first byte then
 // lands at the new b); the bytes outside the window are the caller's to write.  The default copies every string whole.
-struct chunk_copy_whole { __device__ __forceinline__ void operator()(uint64_t, uint64_t&, uint64_t&) const {} };
-template <int CHUNK, typename SrcOf, typename Window = chunk_copy_whole>
-__device__ __forceinline__ void chunk_copy(unsigned char* out, uint64_t n_out, uint64_t n_items, const uint64_t* __restrict__ at, SrcOf src_of, uint64_t wave,
-                                           uint64_t n_waves, int lane, Window window = Window()) {
+// The walk itself: body(p, b, end, lo, hi) is called for every non-empty string p = out[b, end) that has bytes in the wave's chunk [lo, hi).  The packers of
+// bam_encode.hip, whose bytes are made rather than copied, run it too.
+template <int CHUNK, typename Body>
+__device__ __forceinline__ void chunk_walk(uint64_t n_out, uint64_t n_items, const uint64_t* __restrict__ at, uint64_t wave, uint64_t n_waves, Body body) {
   const uint64_t n_chunks = (n_out + CHUNK - 1) / CHUNK;
   for (uint64_t c = wave; c < n_chunks; c += n_waves) {
     const uint64_t lo = c * CHUNK, hi = min(lo + (uint64_t)CHUNK, n_out);
@@ -39,13 +39,22 @@ __device__ __forceinline__ void chunk_copy(unsigned char* out, uint64_t n_out, u
     uint64_t b = at[p];
     for (; p < n_items && b < hi; p++) {
       const uint64_t end = at[p + 1];
-      uint64_t wb = b, we = end;
-      if (end > b) window(p, wb, we);
-      const uint64_t from = max(lo, wb), to = min(hi, we);
-      if (to > from) wave_copy(out + from, src_of(p) + (from - wb), to - from, lane);
+      if (end > b) body(p, b, end, lo, hi);
       b = end;
     }
   }
+}
+
+struct chunk_copy_whole { __device__ __forceinline__ void operator()(uint64_t, uint64_t&, uint64_t&) const {} };
+template <int CHUNK, typename SrcOf, typename Window = chunk_copy_whole>
+__device__ __forceinline__ void chunk_copy(unsigned char* out, uint64_t n_out, uint64_t n_items, const uint64_t* __restrict__ at, SrcOf src_of, uint64_t wave,
+                                           uint64_t n_waves, int lane, Window window = Window()) {
+  chunk_walk<CHUNK>(n_out, n_items, at, wave, n_waves, [&](uint64_t p, uint64_t b, uint64_t end, uint64_t lo, uint64_t hi) {
+    uint64_t wb = b, we = end;
+    window(p, wb, we);
+    const uint64_t from = max(lo, wb), to = min(hi, we);
+    if (to > from) wave_copy(out + from, src_of(p) + (from - wb), to - from, lane);
+  });
 }
 
 // pk_copy on `st` (pack_strings.hip): lra_pack_strings_batch for a caller that knows total = d_dst_off[n] already; nothing is launched for total = 0

@@ -40,6 +40,8 @@ struct lra_ctx {
   std::vector<uint64_t> bgzf_member_off;             // deflate.hip: where each member of the last lra_bgzf_compress_device starts in it
   int bgzf_round = 0;                                 // deflate.hip: members per round of lra_bgzf_compress_device (0: its default)
   double bgzf_ms = 0; uint64_t bgzf_bytes = 0;        // deflate.hip: the last lra_bgzf_compress_device's wall time and output size
+  void* bam_buf[6] = {}; size_t bam_bytes[6] = {};    // bam_encode.hip: the staging arrays of the BAM fields (offsets and data of CIGAR, SEQ, QUAL), which live side by side
+  int bam_cigar_limit = 65535;                        // lra_bam_set_cigar_limit: a record with more CIGAR ops keeps them in a CG:B:I tag
   uint64_t* scan_tmp = nullptr;
   // lra_side_fork / lra_side_join: further streams for kernels that would only extend a stage's tail on the context's own stream
   static constexpr int N_SIDE = 4;

@@ -106,6 +106,7 @@ extern "C" int lra_ctx_release_buffers(lra_ctx* ctx, uint64_t* bytes) {
     for (int i = 0; i < lra_ctx::N_SIDE; i++) if (c->side[i]) (void)hipStreamSynchronize(c->side[i]);
     for (int i = 0; i < 4; i++) if (c->scratch[i]) { (void)hipFree(c->scratch[i]); freed += c->scratch_bytes[i]; c->scratch[i] = nullptr; c->scratch_bytes[i] = 0; }
     for (int i = 0; i < 192; i++) if (c->gbuf[i]) { (void)hipFree(c->gbuf[i]); freed += c->gbytes[i]; c->gbuf[i] = nullptr; c->gbytes[i] = 0; }
+    for (int i = 0; i < 6; i++) if (c->bam_buf[i]) { (void)hipFree(c->bam_buf[i]); freed += c->bam_bytes[i]; c->bam_buf[i] = nullptr; c->bam_bytes[i] = 0; }
     if (c->aux) { (void)hipFree(c->aux); freed += c->aux_bytes; c->aux = nullptr; c->aux_bytes = 0; }
     if (c->out_buf) { (void)hipFree(c->out_buf); freed += c->out_bytes; c->out_buf = nullptr; c->out_bytes = 0; }
     c->ahead.valid = false;                                                // (a seed result adopted ahead of its batch pointed into the side context's arrays: stays valid there, but the pairing is over)
@@ -143,6 +144,7 @@ extern "C" void lra_ctx_destroy(lra_ctx* ctx) {
   if (ctx->sv_pin) (void)hipHostFree(ctx->sv_pin);
   if (ctx->bgzf_pin) (void)hipHostFree(ctx->bgzf_pin);
   if (ctx->scan_tmp) (void)hipFree(ctx->scan_tmp);
+  for (int i = 0; i < 6; i++) if (ctx->bam_buf[i]) (void)hipFree(ctx->bam_buf[i]);
   for (int i = 0; i < 192; i++) if (ctx->gbuf[i]) (void)hipFree(ctx->gbuf[i]);
   for (auto& r : ctx->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   for (auto e : ctx->free_events) (void)hipEventDestroy(e);

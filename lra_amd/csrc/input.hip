@@ -32,6 +32,7 @@
 #include "map_state.h"
 #include "reads_state.h"
 #include "zsource.h"
+#include "sam_aux.h"
 #include <fcntl.h>
 #include <unistd.h>
 #include <cmath>
@@ -266,63 +267,6 @@ int lra_ztext_sniff(const std::string& path, int* zmode) {
 
 namespace {
 
-bool parse_sam_aux(const std::string& f, std::string& aux) {   // "TG:T:value" -> its BAM binary form (sam_parse1)
-  if (f.size() < 5 || f[2] != ':' || f[4] != ':') return false;
-  const char t = f[3];
-  const char* v = f.c_str() + 5;
-  aux.push_back(f[0]); aux.push_back(f[1]);
-  auto put = [&](const void* p, size_t n) { aux.append((const char*)p, n); };
-  auto put_int = [&](long long x, bool typed) {
-    if (x < 0) {
-      if (x >= INT8_MIN) { if (typed) aux.push_back('c'); int8_t y = (int8_t)x; put(&y, 1); }
-      else if (x >= INT16_MIN) { if (typed) aux.push_back('s'); int16_t y = (int16_t)x; put(&y, 2); }
-      else { if (typed) aux.push_back('i'); int32_t y = (int32_t)x; put(&y, 4); }
-    } else {
-      if (x <= UINT8_MAX) { if (typed) aux.push_back('C'); uint8_t y = (uint8_t)x; put(&y, 1); }
-      else if (x <= UINT16_MAX) { if (typed) aux.push_back('S'); uint16_t y = (uint16_t)x; put(&y, 2); }
-      else { if (typed) aux.push_back('I'); uint32_t y = (uint32_t)x; put(&y, 4); }
-    }
-  };
-  char* end = nullptr;
-  switch (t) {
-    case 'A': if (f.size() != 6) return false; aux.push_back('A'); aux.push_back(v[0]); return true;
-    case 'i': {
-      const long long x = strtoll(v, &end, 10);
-      if (end == v || *end || x < INT32_MIN || x > (long long)UINT32_MAX) return false;
-      put_int(x, true);
-      return true;
-    }
-    case 'f': { const float x = strtof(v, &end); if (end == v || *end) return false; aux.push_back('f'); put(&x, 4); return true; }
-    case 'Z': case 'H': aux.push_back(t); aux.append(v); aux.push_back('\0'); return true;
-    case 'B': {
-      const char st = v[0];
-      if (!strchr("cCsSiIf", st) || !st) return false;
-      aux.push_back('B'); aux.push_back(st);
-      const size_t at = aux.size();
-      uint32_t n = 0; put(&n, 4);
-      const char* p = v + 1;
-      while (*p == ',') {
-        p++;
-        if (st == 'f') { const float x = strtof(p, &end); if (end == p) return false; put(&x, 4); }
-        else {
-          const long long x = strtoll(p, &end, 10);
-          if (end == p) return false;
-          switch (st) {
-            case 'c': { int8_t y = (int8_t)x; put(&y, 1); break; } case 'C': { uint8_t y = (uint8_t)x; put(&y, 1); break; }
-            case 's': { int16_t y = (int16_t)x; put(&y, 2); break; } case 'S': { uint16_t y = (uint16_t)x; put(&y, 2); break; }
-            case 'i': { int32_t y = (int32_t)x; put(&y, 4); break; } default: { uint32_t y = (uint32_t)x; put(&y, 4); break; }
-          }
-        }
-        p = end; n++;
-      }
-      if (*p) return false;
-      memcpy(&aux[at], &n, 4);
-      return true;
-    }
-    default: return false;
-  }
-}
-
 int nt16(unsigned char c) {                         // htslib's seq_nt16_table
   switch (toupper(c)) {
     case '=': return 0; case 'A': return 1; case 'C': return 2; case 'M': return 3; case 'G': return 4; case 'R': return 5; case 'S': return 6; case 'V': return 7;
@@ -390,7 +334,7 @@ int lra_hts_next(lra_hts_in* h, lra_hts_rec* rec, std::string* err) {
     if (!rec->has_qual) rec->qual.clear();
   }
   for (size_t i = 11; i < f.size(); i++)
-    if (!parse_sam_aux(f[i], rec->aux)) { *err = where + ": a malformed aux field"; return -1; }
+    if (!lra_parse_sam_aux(f[i], rec->aux)) { *err = where + ": a malformed aux field"; return -1; }
   return 1;
 }
 

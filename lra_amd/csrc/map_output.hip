@@ -7,6 +7,7 @@
 #include "map_state.h"
 #include "records.h"
 #include "emit_fmt.h"
+#include "emit_bam.h"
 #include <chrono>
 #include <math.h>
 #include <stdlib.h>
@@ -366,13 +367,23 @@ extern "C" int lra_map_snapshot(lra_ctx* ctx, const lra_map_result* res, int wit
 
 // ---- lra_map_records_device, the host half: the records as a piece table (records.h) ------------------------------------------------------------
 namespace {
-struct lra_piece_part { std::vector<lra_rec_piece> pieces; std::string blob; std::vector<uint64_t> first; };   // a thread's range of reads; first: every read's first piece
-struct lra_piece_table { std::vector<lra_rec_piece> pieces; std::string blob; std::vector<uint64_t> read_piece; };
+// BAM records: seq = the ranges lra_bam_pack_seq_batch packs, as (reverse strand << 63) | (read << 32) | first base until the read offsets are known; qual = the
+// requests of lra_bam_phred_batch; rec_first = every record's first piece
+struct lra_piece_part {                                                  // a thread's range of reads; first: every read's first piece
+  std::vector<lra_rec_piece> pieces; std::string blob; std::vector<uint64_t> first;
+  std::vector<lra_bam_seq_range> seq; std::vector<lra_bam_qual_req> qual; std::vector<uint64_t> rec_first;
+};
+struct lra_piece_table {
+  std::vector<lra_rec_piece> pieces; std::string blob; std::vector<uint64_t> read_piece;
+  bool bam = false; int cigar_limit = 65535; int bad_read = -1;          // in: BAM records; out: the read whose record could not be written
+  std::vector<lra_bam_seq_range> seq; std::vector<lra_bam_qual_req> qual; std::vector<uint64_t> rec_first;
+};
 // emit_fmt.h's sink: the short fields into the blob (literals that follow each other inside a read are one piece), the long ones as references
 struct lra_piece_sink {
   lra_piece_part& P; size_t barrier;                                     // the read's first piece: no literal is joined across it
   const lra_aln_record* base; const uint64_t* aln;                       // the read's records and their alignments
   uint32_t read; int32_t read_len;
+  const int32_t* chrom = nullptr; const uint64_t* roff = nullptr; int limit = 65535;   // BAM records: per alignment its chromosome and its runs' offsets
   void push(uint32_t kind, uint64_t n, uint64_t src) { P.pieces.push_back(lra_rec_piece{kind, (uint32_t)n, src}); }
   void lit(const std::string& t) {
     if (t.empty()) return;
@@ -392,6 +403,24 @@ struct lra_piece_sink {
   void seq(const lra_aln_record& r, size_t from, size_t n) { range(r.strand ? LRA_PIECE_SEQ_RC : LRA_PIECE_SEQ_FW, from, n); }
   void qual(const lra_aln_record& r) { range(LRA_PIECE_QUAL, 0, (size_t)r.read_len); }   // (an unaligned read's string goes out as it is, a leading '*' too)
   void qual_sub(const lra_aln_record&, size_t pos, size_t n) { range(LRA_PIECE_QUAL, pos, n); }
+  // emit_bam.h's part
+  void rec_begin() { P.rec_first.push_back(P.pieces.size()); barrier = P.pieces.size(); }
+  int32_t ref_id(const lra_aln_record& x) const { return chrom[aln[&x - base]]; }
+  uint64_t n_runs(const lra_aln_record& x) const { const uint64_t a = aln[&x - base]; return roff[a + 1] - roff[a]; }
+  int cigar_limit() const { return limit; }
+  void bam_cigar(const lra_aln_record& x) { push(LRA_PIECE_BAM_CIGAR, 0, aln[&x - base]); }
+  void bam_seq(const lra_aln_record& r, size_t from, size_t n) {
+    const size_t L = (size_t)std::max(read_len, 0);
+    from = std::min(from, L); n = std::min(n, L - from);
+    if (!n) return;
+    push(LRA_PIECE_BAM_SEQ, 0, P.seq.size());
+    P.seq.push_back(lra_bam_seq_range{((uint64_t)(r.strand ? 1 : 0) << 63) | ((uint64_t)read << 32) | (uint64_t)from, (uint64_t)n});
+  }
+  void bam_qual(const lra_aln_record&, size_t pos, size_t n, bool have) {
+    if (!n) return;
+    push(LRA_PIECE_BAM_QUAL, 0, P.qual.size());
+    P.qual.push_back(lra_bam_qual_req{have ? read : 0xffffffffu, (uint32_t)pos, (uint32_t)n, 0});
+  }
 };
 // lra_output_read_str (rank.hip; OUTPUT, Mapping_ultility.h:453-493) for the three formats the device stage writes
 int piece_output_read(const lra_aln_group* groups, const int32_t* index, int n_groups, lra_aln_record* recs, int print_num_aln, char format, int hard_clip,
@@ -403,11 +432,13 @@ int piece_output_read(const lra_aln_group* groups, const int32_t* index, int n_g
       lra_aln_record* S = recs + G.first;
       for (int s = G.count - 1; s >= 0; s--) {
         S[s].order = G.count - 1 - s;
-        const int rc = format == 's' ? lra_fmt_sam(S, G.count, s, hard_clip, passthrough, k) : format == 'a' ? lra_fmt_pairwise(S[s], k) : lra_fmt_paf(&S[s], 1, k);
+        const int rc = format == 's' ? lra_fmt_sam(S, G.count, s, hard_clip, passthrough, k) : format == 'B' ? lra_fmt_bam(S, G.count, s, hard_clip, passthrough, k) :
+                       format == 'a' ? lra_fmt_pairwise(S[s], k) : lra_fmt_paf(&S[s], 1, k);
         if (rc) return rc;
       }
     }
   } else if (format == 's' && unaligned_rec) return lra_fmt_sam_simple_unaligned(*unaligned_rec, passthrough, k);
+  else if (format == 'B' && unaligned_rec) return lra_fmt_bam_unaligned(*unaligned_rec, passthrough, k);
   return LRA_OK;
 }
 }  // namespace
@@ -428,6 +459,7 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
   const bool withMd = (PT ? pieceMd : h->has_md) && o->printFormat == 's';   // (only PrintSAM prints MD; SimplePrintSAM, PrintPAF, PrintBed do not)
   if (withMd && !PT && h->md_off.size() != nA + 1) return LRA_ERR_INVALID;
   if (!PT && nA && roff.size() == nA + 1 && runs.size() < roff[nA]) return LRA_ERR_INVALID;   // a snapshot packed with LRA_PACK_NORUNS has no CIGAR to print
+  const char pieceFormat = (PT && PT->bam) ? 'B' : (char)o->printFormat;  // ('B': the BAM form of 's', emit_bam.h)
   const bool hi = !o->bypassClustering;                                   // MapRead_highacc's tail (Map_highacc.h:733-789)
   if (pairwise && h->segText.size() != h->nA) return LRA_ERR_INVALID;
   // every read is independent: host threads take contiguous ranges of reads, each builds its own text; ranges are joined in read order
@@ -438,7 +470,7 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
   std::vector<std::string> part(T);
   std::vector<lra_piece_part> ppart(PT ? T : 0);                         // lra_map_records_device: the threads write pieces, not text
   std::vector<std::vector<uint64_t>> plen(T);
-  std::vector<int> prc(T, LRA_OK);
+  std::vector<int> prc(T, LRA_OK), pbad(T, -1);
   auto work = [&](int tix) {
     const int lo = (int)((long)n_reads * tix / T), hi = (int)((long)n_reads * (tix + 1) / T);
     std::string& text = part[tix];
@@ -455,8 +487,8 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
     std::vector<lra_aln_group> groups;
     std::vector<char> buf;
     std::string rcRead;
-    int rc = LRA_OK;
-    for (int r = lo; r < hi; r++) {
+    int rc = LRA_OK, r = lo;
+    for (; r < hi; r++) {
       recs.clear(); cigars.clear(); mds.clear(); seg_off.assign(1, 0); rcRead.clear(); alnOf.clear();
       if (PT) ppart[tix].first.push_back(ppart[tix].pieces.size());
       const bool flagged = !rstat.empty() && rstat[r];
@@ -545,7 +577,7 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
         const size_t before = text.size();
         if (PT) {
           lra_piece_sink k{ppart[tix], ppart[tix].pieces.size(), nullptr, nullptr, (uint32_t)r, read_len[r]};
-          if ((rc = piece_output_read(nullptr, nullptr, 0, nullptr, o->PrintNumAln, (char)o->printFormat, o->hardClip, tags ? tags[r] : passthrough, &un, k))) break;
+          if ((rc = piece_output_read(nullptr, nullptr, 0, nullptr, o->PrintNumAln, pieceFormat, o->hardClip, tags ? tags[r] : passthrough, &un, k))) break;
         } else
         if ((rc = lra_output_read_str(nullptr, nullptr, 0, nullptr, o->PrintNumAln, (char)o->printFormat, o->hardClip, tags ? tags[r] : passthrough, 1, &un, text))) break;
         need = text.size() - before;
@@ -559,8 +591,8 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
         // (the records' text goes straight into the thread's part, written once: the sizing-then-filling calls of the C entry points formatted every record four times)
         const size_t before = text.size();
         if (PT) {
-          lra_piece_sink k{ppart[tix], ppart[tix].pieces.size(), recs.data(), alnOf.data(), (uint32_t)r, read_len[r]};
-          if ((rc = piece_output_read(groups.data(), index.data(), n, recs.data(), o->PrintNumAln, (char)o->printFormat, o->hardClip, tags ? tags[r] : passthrough, nullptr, k))) break;
+          lra_piece_sink k{ppart[tix], ppart[tix].pieces.size(), recs.data(), alnOf.data(), (uint32_t)r, read_len[r], chrom.data(), roff.data(), PT->cigar_limit};
+          if ((rc = piece_output_read(groups.data(), index.data(), n, recs.data(), o->PrintNumAln, pieceFormat, o->hardClip, tags ? tags[r] : passthrough, nullptr, k))) break;
         } else
         if ((rc = lra_output_read_str(groups.data(), index.data(), n, recs.data(), o->PrintNumAln, (char)o->printFormat, o->hardClip, tags ? tags[r] : passthrough, 0, nullptr, text))) break;
         need = text.size() - before;
@@ -568,6 +600,7 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
       plen[tix].push_back(need);
     }
     prc[tix] = rc;
+    if (rc) pbad[tix] = r;
   };
   const bool rdbg = getenv("LRA_RECORD_DBG") != nullptr;
   auto wallr = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -579,7 +612,7 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
     for (auto& x : th) x.join();
   }
   if (rdbg) fprintf(stderr, "[records] %d threads: per-read work %.0f ms\n", T, wallr() - tr0);
-  for (int t = 0; t < T; t++) if (prc[t]) return prc[t];
+  for (int t = 0; t < T; t++) if (prc[t]) { if (PT) PT->bad_read = pbad[t]; return prc[t]; }
   if (PT) {                                                              // the ranges' pieces joined in read order; a literal's place moves with its range's blob
     size_t np = 0, nb = 0;
     for (int t = 0; t < T; t++) { np += ppart[t].pieces.size(); nb += ppart[t].blob.size(); }
@@ -587,10 +620,18 @@ static int records_host(lra_map_host* h, const lra_map_opts* o, const char* cons
     for (int t = 0; t < T; t++) {
       const uint64_t p0 = PT->pieces.size(), b0 = PT->blob.size();
       for (uint64_t f : ppart[t].first) PT->read_piece.push_back(p0 + f);
-      for (lra_rec_piece q : ppart[t].pieces) { if (q.kind == LRA_PIECE_LIT) q.src += b0; PT->pieces.push_back(q); }
+      const uint64_t s0 = PT->seq.size(), q0 = PT->qual.size();
+      for (lra_rec_piece q : ppart[t].pieces) {
+        if (q.kind == LRA_PIECE_LIT) q.src += b0; else if (q.kind == LRA_PIECE_BAM_SEQ) q.src += s0; else if (q.kind == LRA_PIECE_BAM_QUAL) q.src += q0;
+        PT->pieces.push_back(q);
+      }
       PT->blob += ppart[t].blob;
+      for (uint64_t f : ppart[t].rec_first) PT->rec_first.push_back(p0 + f);
+      PT->seq.insert(PT->seq.end(), ppart[t].seq.begin(), ppart[t].seq.end());
+      PT->qual.insert(PT->qual.end(), ppart[t].qual.begin(), ppart[t].qual.end());
     }
     PT->read_piece.push_back(PT->pieces.size());
+    PT->rec_first.push_back(PT->pieces.size());
     *len = 0;
     return LRA_OK;
   }
@@ -826,10 +867,11 @@ static int records_device_svsig(lra_ctx* ctx, const lra_map_result* res, const u
 static int records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
                           const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough,
                           const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const char** text, uint64_t* len,
-                          const uint64_t** rec_off, bool keep) {
+                          const uint64_t** rec_off, bool keep, bool bam = false) {
   if (!ctx || !res || !o || !names || !read_len || !chrom_names || !len || (flags & ~(LRA_PACK_MD | LRA_PACK_SVSIG)) || (d_qual && !d_qual_off)) return LRA_ERR_INVALID;
   lra_map_state* m = ctx->map;
   if (!m) return LRA_ERR_INVALID;
+  if (bam && o->printFormat != 's') return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device_bam: print format '%c' has no BAM form (only 's')", (char)o->printFormat);
   m->dev_sv = false;
   const bool withSv = (flags & LRA_PACK_SVSIG) != 0;
   m->dev_stats = lra_records_device_stats{};
@@ -875,7 +917,8 @@ static int records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map
   uint64_t* adr = nullptr;
   if (nA) {
     if (!res->d_run_off || !res->d_strands) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device: the result has no runs / reads to work on");
-    if (!pairwise && (rc = lra_cigar_text_batch(ctx, (int)nA, res->d_runs, res->d_run_off, nullptr, nullptr, nullptr, &cg))) return rc;
+    // (BAM records: the CIGAR text is SA:Z's only -- made below, once the piece table says a record names it)
+    if (!pairwise && !bam && (rc = lra_cigar_text_batch(ctx, (int)nA, res->d_runs, res->d_run_off, nullptr, nullptr, nullptr, &cg))) return rc;
     if (withMd || pairwise || withSv) {
       if (!res->d_aln_read || !res->d_strand || !res->d_chrom || !res->d_blocks || !res->d_block_off)
         return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device: the result has no blocks to work on");
@@ -892,10 +935,51 @@ static int records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map
   double t2 = wall();
   S.ms_cigar_md = t2 - t1;
   lra_piece_table PT;
+  PT.bam = bam; PT.cigar_limit = ctx->bam_cigar_limit;
   uint64_t dummy = 0;
-  if ((rc = records_host(h, o, names, reads, quals, read_len, chrom_names, nullptr, passthrough, n_threads, nullptr, &dummy, nullptr, &PT, withMd))) return rc;
+  if ((rc = records_host(h, o, names, reads, quals, read_len, chrom_names, nullptr, passthrough, n_threads, nullptr, &dummy, nullptr, &PT, withMd))) {
+    if (bam && rc == LRA_ERR_INVALID && PT.bad_read >= 0 && PT.bad_read < nR)
+      return lra_set_err(ctx, rc, "lra_map_records_device_bam: read %d (%.64s): %s", PT.bad_read, names[PT.bad_read],
+                         strlen(names[PT.bad_read]) > 254 ? "a name above 254 bytes" : "its passthrough text is not SAM aux fields");
+    return rc;
+  }
   double t3 = wall();
   S.ms_pieces = t3 - t2;
+  // BAM records: the three staging arrays.  The ranges and requests go up in work buffer 75, the ranges with the device's own read offsets.
+  lra_bam_cigar_result bcg; memset(&bcg, 0, sizeof bcg);
+  lra_bam_bytes_result bsq; memset(&bsq, 0, sizeof bsq);
+  lra_bam_bytes_result bph; memset(&bph, 0, sizeof bph);
+  const lra_bam_qual_req* d_req = nullptr;
+  if (bam) {
+    const size_t nS = PT.seq.size(), nQ = PT.qual.size();
+    bool saCigar = false;
+    for (const lra_rec_piece& p : PT.pieces) if (p.kind == LRA_PIECE_CIGAR) { saCigar = true; break; }
+    if (nA && saCigar && (rc = lra_cigar_text_batch(ctx, (int)nA, res->d_runs, res->d_run_off, nullptr, nullptr, nullptr, &cg))) return rc;
+    if (nA && (rc = lra_bam_cigar_batch(ctx, (int)nA, res->d_runs, res->d_run_off, nullptr, nullptr, nullptr, &bcg))) return rc;
+    if (nS && !res->d_strands) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device_bam: the result has no reads to work on");
+    const size_t sBytes = (nS * sizeof(lra_bam_seq_range) + 255) & ~(size_t)255, qBytes = nQ * sizeof(lra_bam_qual_req);
+    char* up = (char*)lra_ensure(ctx, 75, sBytes + qBytes + 64);
+    if (!up) return LRA_ERR_NOMEM;
+    if (nS) {
+      std::vector<uint64_t> ro((size_t)nR + 1);
+      LRA_HIP_CHECK(ctx, hipMemcpyAsync(ro.data(), res->d_strands + lra_strands_ro_at(res->rc_base), ((size_t)nR + 1) * 8, hipMemcpyDeviceToHost, st));
+      LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+      S.bytes_d2h += ((size_t)nR + 1) * 8;
+      for (lra_bam_seq_range& q : PT.seq) {
+        const uint64_t r = (q.off >> 32) & 0x7fffffffu, from = q.off & 0xffffffffu;
+        q.off = ro[r] + from + ((q.off >> 63) ? res->rc_base : 0);
+      }
+      LRA_HIP_CHECK(ctx, hipMemcpyAsync(up, PT.seq.data(), nS * sizeof(lra_bam_seq_range), hipMemcpyHostToDevice, st));
+    }
+    if (nQ) LRA_HIP_CHECK(ctx, hipMemcpyAsync(up + sBytes, PT.qual.data(), qBytes, hipMemcpyHostToDevice, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    S.bytes_h2d += nS * sizeof(lra_bam_seq_range) + qBytes;
+    d_req = (const lra_bam_qual_req*)(up + sBytes);
+    // (both strands of the batch lie in [0, 2 * rc_base): a range is cut to the read on the host, so it lies inside)
+    if ((rc = lra_bam_pack_seq_batch(ctx, nS, (const lra_bam_seq_range*)up, (const uint8_t*)res->d_strands, 2 * res->rc_base, &bsq))) return rc;
+    S.ms_cigar_md += wall() - t3;
+    t3 = wall();
+  }
   // the qualities: the caller's device copy, or the strings of the reads that print them, uploaded through the context's page-locked staging
   const char* dq = d_qual; const uint64_t* dqo = d_qual_off;
   if (!dq) {
@@ -903,6 +987,8 @@ static int records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map
     bool any = false;
     for (const lra_rec_piece& p : PT.pieces)                             // (a string shorter than its read -- "*" -- is uploaded as far as it goes; the device cuts the piece to it)
       if (p.kind == LRA_PIECE_QUAL) { const size_t r = (size_t)(p.src >> 32); qo[r + 1] = strnlen(quals[r], (size_t)std::max(read_len[r], 0)); any = true; }
+    for (const lra_bam_qual_req& q : PT.qual)                            // (BAM records: the same strings, named by the requests)
+      if (q.read < (uint32_t)nR && quals && quals[q.read]) { qo[(size_t)q.read + 1] = strnlen(quals[q.read], (size_t)std::max(read_len[q.read], 0)); any = true; }
     if (any) {
       for (int r = 0; r < nR; r++) qo[(size_t)r + 1] += qo[r];
       const size_t offBytes = ((size_t)nR + 1) * 8, total = (size_t)qo[nR];
@@ -918,6 +1004,11 @@ static int records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map
     }
   }
   S.ms_upload = wall() - t3;
+  if (bam) {
+    const double tq = wall();
+    if ((rc = lra_bam_phred_batch(ctx, PT.qual.size(), d_req, nR, dq, dqo, &bph))) return rc;
+    S.ms_cigar_md += wall() - tq;
+  }
   lra_rec_job J;
   J.n_reads = nR; J.n_aln = nA; J.pieces = PT.pieces.data(); J.n_pieces = PT.pieces.size(); J.read_piece = PT.read_piece.data();
   J.blob = PT.blob.data(); J.blob_bytes = PT.blob.size();
@@ -925,6 +1016,11 @@ static int records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map
   J.d_read_off = res->d_strands ? (const uint64_t*)(res->d_strands + lra_strands_ro_at(res->rc_base)) : nullptr;
   J.d_qual = dq; J.d_qual_off = dqo; J.d_cg = cg.d_text; J.d_cg_off = cg.d_off; J.d_md = withMd ? md.d_md : nullptr; J.d_md_off = withMd ? md.d_md_off : nullptr;
   J.d_pw = pw.d_text; J.d_pw_off = pw.d_off;
+  if (bam) {
+    J.d_bcg = bcg.d_ops; J.d_bcg_off = bcg.d_off; J.d_pseq = bsq.d_data; J.d_pseq_off = bsq.d_off; J.n_pseq = bsq.n;
+    J.d_phred = bph.d_data; J.d_phred_off = bph.d_off; J.n_phred = bph.n;
+    J.rec_first = PT.rec_first.data(); J.n_rec = PT.rec_first.size() - 1;
+  }
   J.keep_on_device = keep;
   if (!J.d_strands && nR) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device: the result has no reads to work on");
   m->dev_off.assign((size_t)nR + 1, 0);
@@ -966,6 +1062,36 @@ extern "C" int lra_map_records_device_bgzf(lra_ctx* ctx, const lra_map_result* r
   }
   if ((rc = lra_bgzf_compress_device(ctx, d_text, len, data, data_len, member_off, n_members))) return rc;
   ctx->map->dev_stats.bytes_d2h += *data_len;
+  return LRA_OK;
+}
+
+// lra_map_records_device's SAM records as BAM records (emit_bam.h, bam_encode.hip): raw in the page-locked record buffer, or through the BGZF stream stage
+extern "C" int lra_map_records_device_bam(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* quals,
+                                          const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough, const char* d_qual,
+                                          const uint64_t* d_qual_off, int flags, int n_threads, int bgzf, const uint8_t** data, uint64_t* data_len,
+                                          const uint64_t** rec_off, const uint64_t** member_off, uint64_t* n_members) {
+  if (!data || !data_len || !member_off || !n_members || !o) return LRA_ERR_INVALID;
+  *member_off = nullptr; *n_members = 0;
+  const char* text = nullptr;
+  uint64_t len = 0;
+  int rc = records_device(ctx, res, o, names, nullptr, quals, read_len, chrom_names, passthrough, d_qual, d_qual_off, flags, n_threads, &text, &len, rec_off, bgzf != 0, true);
+  if (rc) return rc;
+  if (!bgzf) { *data = (const uint8_t*)text; *data_len = len; return LRA_OK; }
+  if ((rc = lra_bgzf_compress_device(ctx, (const uint8_t*)text, len, data, data_len, member_off, n_members))) return rc;
+  ctx->map->dev_stats.bytes_d2h += *data_len;
+  return LRA_OK;
+}
+
+// the head of a BAM file: magic, the header text, the reference table (host only; two-call convention)
+extern "C" int lra_bam_header(const char* text, uint64_t text_len, int n_chrom, const char* const* chrom_names, const uint64_t* chrom_pos, uint8_t* out, uint64_t cap,
+                              uint64_t* len) {
+  if (!len || n_chrom < 0 || (text_len && !text) || text_len > 0x7fffffffu || (n_chrom && (!chrom_names || !chrom_pos))) return LRA_ERR_INVALID;
+  std::string s;
+  if (lra_bam_header_str(text, text_len, n_chrom, chrom_names, chrom_pos, s)) return LRA_ERR_INVALID;
+  *len = s.size();
+  if (!out) return LRA_OK;
+  if (cap < s.size()) return LRA_ERR_INVALID;
+  memcpy(out, s.data(), s.size());
   return LRA_OK;
 }
 

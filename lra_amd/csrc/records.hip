@@ -14,6 +14,9 @@
 // dwords (a lane's dword is put together from the two aligned source dwords around it), bytes at a part's ragged ends.  The loop is chunk_copy.h's, which
 // lra_pack_strings_batch (pack_strings.hip) runs too.  rc_rec_off reads every read's
 // first byte off the scan.  The host reads one number (the text's bytes), then the text and rec_off in one copy each.
+// BAM records (lra_map_records_device_bam) are assembled the same way: three more piece kinds point into the staging arrays bam_encode.hip wrote (an
+// alignment's ops, a range's packed bases, a request's phred bytes), and behind the copy rc_block_size writes every record's block_size, which the host
+// cannot know (MD and SA:Z are the device's), from the host's list of first pieces and the scan.
 #include "common.h"
 #include "chunk_copy.h"
 #include "records.h"
@@ -88,6 +91,10 @@ struct RcArgs {
   const unsigned char* cg; const uint64_t* cg_off;
   const unsigned char* md; const uint64_t* md_off;             // NULL: no MD pieces
   const unsigned char* pw; const uint64_t* pw_off;             // NULL: no PAIRWISE pieces
+  const uint32_t* bcg; const uint64_t* bcg_off;                // NULL: no BAM_CIGAR pieces
+  const unsigned char* pseq; const uint64_t* pseq_off; uint64_t n_pseq;      // NULL: no BAM_SEQ pieces
+  const unsigned char* phred; const uint64_t* phred_off; uint64_t n_phred;   // NULL: no BAM_QUAL pieces
+  const uint64_t* rec_first; uint64_t n_rec;                   // BAM records: every record's first piece [n_rec + 1]
   uint32_t* len; const unsigned char** src;                    // per piece
   const uint64_t* at;                                          // the lengths' exclusive prefix [n_pieces + 1]
   unsigned char* out; uint64_t n_out; uint64_t* rec_off;
@@ -125,6 +132,15 @@ __global__ void __launch_bounds__(256) rc_resolve(RcArgs A) {
     case LRA_PIECE_PAIRWISE:
       if (A.pw && p.src < A.n_aln) { n = A.pw_off[p.src + 1] - A.pw_off[p.src]; s = A.pw + A.pw_off[p.src]; }
       break;
+    case LRA_PIECE_BAM_CIGAR:
+      if (A.bcg && p.src < A.n_aln) { n = 4 * (A.bcg_off[p.src + 1] - A.bcg_off[p.src]); s = (const unsigned char*)(A.bcg + A.bcg_off[p.src]); }
+      break;
+    case LRA_PIECE_BAM_SEQ:
+      if (A.pseq && p.src < A.n_pseq) { n = A.pseq_off[p.src + 1] - A.pseq_off[p.src]; s = A.pseq + A.pseq_off[p.src]; }
+      break;
+    case LRA_PIECE_BAM_QUAL:
+      if (A.phred && p.src < A.n_phred) { n = A.phred_off[p.src + 1] - A.phred_off[p.src]; s = A.phred + A.phred_off[p.src]; }
+      break;
     default: break;
   }
   A.len[i] = (uint32_t)n;
@@ -134,6 +150,16 @@ __global__ void __launch_bounds__(256) rc_resolve(RcArgs A) {
 __global__ void __launch_bounds__(256) rc_rec_off(RcArgs A) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r <= A.n_reads) A.rec_off[r] = A.at[A.read_piece[r]];
+}
+
+// BAM records, behind the copy: lane i writes record i's block_size, its bytes less the field's own four, at the record's first byte (any alignment: by bytes)
+__global__ void __launch_bounds__(256) rc_block_size(RcArgs A) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n_rec) return;
+  const uint64_t b = A.at[A.rec_first[i]], e = A.at[A.rec_first[i + 1]];
+  if (e < b + 4 || e > A.n_out) return;
+  const uint32_t v = (uint32_t)(e - b - 4);
+  for (int k = 0; k < 4; k++) A.out[b + k] = (unsigned char)(v >> (8 * k));
 }
 
 // one wave per chunk of the output bytes (chunk_copy.h)
@@ -211,7 +237,8 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
   auto wall = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t0 = wall();
   // 30: what the host wrote -- the pieces, every read's first piece, the literal blob (+ 64 bytes: aligned dwords are read)
-  char* u = (char*)lra_ensure(ctx, 30, sz(nP, sizeof(lra_rec_piece)) + sz(nR + 1, 8) + sz(J.blob_bytes + 64, 1));
+  const size_t nRec = J.rec_first ? (size_t)J.n_rec : 0;
+  char* u = (char*)lra_ensure(ctx, 30, sz(nP, sizeof(lra_rec_piece)) + sz(nR + 1, 8) + sz(J.blob_bytes + 64, 1) + sz(nRec + 1, 8));
   // 31: per piece -- its length, its source, the lengths' prefix; rec_off; the text's bytes
   char* w = (char*)lra_ensure(ctx, 31, sz(nP, 4) + sz(nP, 8) + 2 * sz(nP + 1, 8) + sz(nR + 1, 8) + 256);
   if (!u || !w) return LRA_ERR_NOMEM;
@@ -219,7 +246,11 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
   A.n_pieces = nP; A.n_reads = J.n_reads; A.n_aln = J.n_aln;
   A.piece = (const lra_rec_piece*)u; u += sz(nP, sizeof(lra_rec_piece));
   A.read_piece = (const uint64_t*)u; u += sz(nR + 1, 8);
-  A.blob = (const unsigned char*)u; A.blob_bytes = J.blob_bytes;
+  A.blob = (const unsigned char*)u; A.blob_bytes = J.blob_bytes; u += sz(J.blob_bytes + 64, 1);
+  if (nRec) {
+    A.rec_first = (const uint64_t*)u; A.n_rec = nRec;
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync((void*)A.rec_first, J.rec_first, (nRec + 1) * 8, hipMemcpyHostToDevice, st));
+  }
   LRA_HIP_CHECK(ctx, hipMemcpyAsync((void*)A.piece, J.pieces, nP * sizeof(lra_rec_piece), hipMemcpyHostToDevice, st));
   LRA_HIP_CHECK(ctx, hipMemcpyAsync((void*)A.read_piece, J.read_piece, (nR + 1) * 8, hipMemcpyHostToDevice, st));
   if (J.blob_bytes) LRA_HIP_CHECK(ctx, hipMemcpyAsync((void*)A.blob, J.blob, J.blob_bytes, hipMemcpyHostToDevice, st));
@@ -229,6 +260,8 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
   A.qual = (const unsigned char*)J.d_qual; A.qual_off = J.d_qual_off;
   A.cg = (const unsigned char*)J.d_cg; A.cg_off = J.d_cg_off; A.md = (const unsigned char*)J.d_md; A.md_off = J.d_md_off;
   A.pw = (const unsigned char*)J.d_pw; A.pw_off = J.d_pw_off;
+  A.bcg = J.d_bcg; A.bcg_off = J.d_bcg_off; A.pseq = J.d_pseq; A.pseq_off = J.d_pseq_off; A.n_pseq = J.n_pseq;
+  A.phred = J.d_phred; A.phred_off = J.d_phred_off; A.n_phred = J.n_phred;
   A.len = (uint32_t*)w; w += sz(nP, 4);
   A.src = (const unsigned char**)w; w += sz(nP, 8);
   uint64_t* at = (uint64_t*)w; w += sz(nP + 1, 8);
@@ -261,6 +294,7 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
     const uint64_t n_chunks = (total + RC_CHUNK - 1) / RC_CHUNK;
     lra_time_begin(ctx, "records_copy");
     hipLaunchKernelGGL(rc_copy, dim3((unsigned)std::min<uint64_t>((n_chunks + 3) / 4, (uint64_t)ctx->num_cu * 32)), dim3(256), 0, st, A);
+    if (nRec) hipLaunchKernelGGL(rc_block_size, dim3((unsigned)((nRec + 255) / 256)), dim3(256), 0, st, A);
     lra_time_end(ctx);
   }
   LRA_HIP_CHECK(ctx, hipEventRecord(e1, st));
@@ -273,7 +307,7 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
     S->ms_upload += t1 - t0; S->ms_kernels += t2 - t1;
     if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) { S->ms_copy_kernel = ms; S->ms_kernels += ms; }
     if (hipEventElapsedTime(&ms, e1, e2) == hipSuccess) S->ms_text_copy = ms;
-    S->bytes_h2d += nP * sizeof(lra_rec_piece) + (nR + 1) * 8 + J.blob_bytes;
+    S->bytes_h2d += nP * sizeof(lra_rec_piece) + (nR + 1) * 8 + J.blob_bytes + (nRec ? (nRec + 1) * 8 : 0);
     S->bytes_d2h += (J.keep_on_device ? 0 : total) + (nR + 1) * 8 + 8;
     S->text_bytes = total; S->n_pieces = nP;
   }

@@ -94,6 +94,31 @@ def set_store_all(ctx: Context, on):
     ctx.check(ctx.lib.lra_ctx_set_store_all(ctx.h, 1 if on else 0))
 
 
+def bam_header(text, chrom_names, chrom_pos):
+    """lra_bam_header (host only): "BAM\\1", l_text, the header text, n_ref and per chromosome l_name, the name with its NUL, l_ref -> bytes.
+    chrom_pos has one entry more than chrom_names."""
+    from ._lib import load_library
+    lib = load_library()
+    nm = [x if isinstance(x, bytes) else str(x).encode() for x in chrom_names]
+    if len(chrom_pos) != len(nm) + 1:
+        raise ValueError("chrom_pos has %d entries for %d chromosomes" % (len(chrom_pos), len(nm)))
+    names = (C.c_char_p * max(len(nm), 1))(*nm)
+    pos = (C.c_uint64 * len(chrom_pos))(*[int(x) for x in chrom_pos])
+    text = bytes(text)
+    ln = C.c_uint64(0)
+    if lib.lra_bam_header(text, len(text), len(nm), names, pos, None, 0, C.byref(ln)) != 0:
+        raise ValueError("lra_bam_header: invalid arguments")
+    buf = (C.c_uint8 * max(int(ln.value), 1))()
+    if lib.lra_bam_header(text, len(text), len(nm), names, pos, buf, ln.value, C.byref(ln)) != 0:
+        raise ValueError("lra_bam_header: invalid arguments")
+    return bytes(buf[:ln.value])
+
+
+def set_bam_cigar_limit(ctx: Context, ops=0):
+    """lra_bam_set_cigar_limit: a BAM record with more CIGAR ops keeps them in a CG:B:I tag (0: the default, 65535)."""
+    ctx.check(ctx.lib.lra_bam_set_cigar_limit(ctx.h, int(ops)))
+
+
 def set_svsig_len(ctx: Context, n):
     """lra_ctx_set_svsig_len: the record stage on this context emits an SV signature for every net gap longer than n (opts.svsigLen)."""
     ctx.check(ctx.lib.lra_ctx_set_svsig_len(ctx.h, int(n)))
@@ -503,6 +528,39 @@ class LowAccMapper:
             return raw, rec_off, member_off
         return raw, rec_off, member_off, self.records_device_svsig(n)
 
+    def records_device_bam(self, res: MapResult, args, passthrough=None, d_qual=None, d_qual_off=None, md=None, n_threads=0, svsig=False, bgzf=False):
+        """lra_map_records_device_bam: the batch's records as BAM alignment records, which say what records_device's SAM text (format 's') says.  The
+        arguments are records_device's (args' reads are not read).  bgzf False -> (stream, rec_off): the raw record stream as bytes and rec_off[n + 1];
+        bgzf True -> (data, rec_off, member_off) as records_device_bgzf (no EOF member; rec_off in bytes of the uncompressed stream).  svsig: the
+        signatures (plain text) are appended to the tuple.  A file is bam_header() (BGZF-compressed), the batches' members, bgzf.EOF_BLOCK."""
+        from .deflate import compress_result
+        ctx = self.ctx
+        n = args["n"]
+        tags = None
+        if isinstance(passthrough, (list, tuple)):
+            tags = (C.c_char_p * n)(*[None if t is None else bytes(t) for t in passthrough])
+        elif passthrough is not None:
+            tags = (C.c_char_p * n)(*[bytes(passthrough)] * n)
+        flags = (PACK_MD if (self.print_md if md is None else md) else 0) | (PACK_SVSIG if svsig else 0)
+        if svsig:
+            set_svsig_len(ctx, self.svsig_len)
+        data = C.c_void_p(); ln = C.c_uint64(0); roff = C.POINTER(C.c_uint64)(); moff = C.c_void_p(); nm = C.c_uint64(0)
+        rc = ctx.lib.lra_map_records_device_bam(ctx.h, C.byref(res), C.byref(self.copts), args["names"], args["quals"], args["lens"], args["chroms"], tags,
+                                                ptr(d_qual) if d_qual is not None else None, ptr(d_qual_off) if d_qual_off is not None else None, flags,
+                                                int(n_threads), 1 if bgzf else 0, C.byref(data), C.byref(ln), C.byref(roff), C.byref(moff), C.byref(nm))
+        if bgzf:
+            raw, member_off = compress_result(ctx.lib, ctx, rc, data, ln, moff, nm)
+        else:
+            ctx.check(rc)
+            raw = C.string_at(data, ln.value) if ln.value else b""
+        rec_off = np.array([roff[i] for i in range(n + 1)], np.uint64)
+        out = (raw, rec_off, member_off) if bgzf else (raw, rec_off)
+        return out + (self.records_device_svsig(n),) if svsig else out
+
+    def bam_header(self, text=None):
+        """lra_bam_header: the head of a BAM file (magic, the header text, the reference table) for this mapper's chromosomes; text None: sam_header()."""
+        return bam_header(self.sam_header() if text is None else bytes(text), self.chrom_names, self.chrom_pos)
+
     def records_device_svsig(self, n, as_list=True):
         """lra_map_records_device_svsig: the SV signature text the last records_device(svsig=True) on this context built -> per read the bytes of its lines."""
         ctx = self.ctx
@@ -736,6 +794,9 @@ class HighAccMapper:
     records_device_stats = LowAccMapper.records_device_stats
     records_device_svsig = LowAccMapper.records_device_svsig
     records_device_bgzf = LowAccMapper.records_device_bgzf
+    records_device_bam = LowAccMapper.records_device_bam
+    bam_header = LowAccMapper.bam_header
+    sam_header = LowAccMapper.sam_header
     svsig_host = LowAccMapper.svsig_host
     sv_signatures = LowAccMapper.sv_signatures
     fetch_local_index = LowAccMapper.fetch_local_index

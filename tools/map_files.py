@@ -1,12 +1,14 @@
 """Map read files against a genome FASTA and print the records as `lra align` would (needs the GPU):
 
-    python tools/map_files.py -ONT genome.fa reads.fq [more.fa ...] [-p s|p|pc|b|a] [-H] [--printMD] [-a] [--PrintNumAln N] [--refineBreakpoints] [-o out.sam] [--device-records] [--bgzf]
+    python tools/map_files.py -ONT genome.fa reads.fq [more.fa ...] [-p s|p|pc|b|a] [-H] [--printMD] [-a] [--PrintNumAln N] [--refineBreakpoints] [-o out.sam] [--device-records] [--bgzf | --bam]
 
 The reads are parsed on the device (lra_reads_next_batch_device) and mapped from the reader's device arrays; --host-input parses them on the host
 (lra_reads_next_batch) and maps through lra_map_reads_host, the same records.  The index: genome.fa.mms / genome.fa.gli when both exist (lra_read_mms /
 lra_read_gli), else built on the device with the preset's `lra index` parameters.  The genome (plain text, gzip or BGZF) is parsed on the device too
 (lra_genome_read_device); --host-genome parses it on the host (lra_genome_read_host).  --bgzf writes the output BGZF-compressed: the header through
-lra_bgzf_deflate_host, every batch's records deflated on the device, the EOF member at the end.  Per-stage times go to stderr."""
+lra_bgzf_deflate_host, every batch's records deflated on the device, the EOF member at the end.  --bam writes a BAM file (in read order, not indexed):
+lra_bam_header's bytes as BGZF members, every batch's BAM records encoded and deflated on the device (lra_map_records_device_bam), the EOF member.
+Per-stage times go to stderr."""
 import argparse
 import os
 import sys
@@ -70,7 +72,13 @@ def main():
                     help="build the record text on the device (lra_map_records_device; formats s, pc and a, the others fall through to the host path)")
     ap.add_argument("--bgzf", action="store_true",
                     help="write the output as BGZF: the records are deflated on the device (with --device-records before they leave it: lra_map_records_device_bgzf)")
+    ap.add_argument("--bam", action="store_true",
+                    help="write BAM: the records are encoded and deflated on the device (lra_map_records_device_bam); implies --device-records and -p s")
     args = ap.parse_args()
+    if args.bam:
+        if args.fmt != "s" or args.bgzf:
+            ap.error("--bam writes SAM records (-p s) as BAM; it does not go with another format or with --bgzf")
+        args.device_records = True
     P = args.preset
     t0 = time.perf_counter()
     ctx = Context(0)
@@ -118,7 +126,9 @@ def main():
              (["-a"] if args.store_all else []) + ["--PrintNumAln", str(args.PrintNumAln)] + (["--refineBreakpoints"] if args.refineBreakpoints else []) + \
              (["-Flag", str(args.flag)] if args.flag else []) + (["--passthrough"] if args.passthrough else []) + (["-SV", *args.sv] if args.sv else [])       # (--device-records is no lra option: the same records)
         head = mapread.LowAccMapper.sam_header(mapper, b"lra_amd", " ".join(cl).encode())     # the lra command line: the same for either reader
-        if args.bgzf:
+        if args.bam:
+            head = mapper.bam_header(head)
+        if args.bgzf or args.bam:
             head = b"".join(deflate.deflate_members([head[a:a + deflate.IN_MAX] for a in range(0, len(head), deflate.IN_MAX)])[0])
         out.write(head)
     # --device-records with device input: the qualities stay on the device from the reader to the record text; the host copies of bases and qualities
@@ -145,7 +155,13 @@ def main():
         t_map += time.perf_counter() - t
         t = time.perf_counter()
         tags = b["tags"] if args.passthrough else None
-        if args.bgzf and args.device_records:                               # the text leaves the device as BGZF members; the signatures stay plain
+        if args.bam:                                                        # BAM records, BGZF members when they leave the device; the signatures stay plain
+            r = mapper.records_device_bam(res, mapper.record_args(b["names"], b["seqs"], b["quals"], lens=b.get("read_len")), passthrough=tags,
+                                          d_qual=b.get("d_qual"), d_qual_off=b.get("d_qual_off"), svsig=bool(sv_out), bgzf=True)
+            texts = [r[0]]
+            for sig in (r[3] if sv_out else []):
+                sv_out.write(sig)
+        elif args.bgzf and args.device_records:                             # the text leaves the device as BGZF members; the signatures stay plain
             r = mapper.records_device_bgzf(res, mapper.record_args(b["names"], b["seqs"], b["quals"], lens=b.get("read_len")), passthrough=tags,
                                            d_qual=b.get("d_qual"), d_qual_off=b.get("d_qual_off"), svsig=bool(sv_out))
             texts = [r[0]]
@@ -175,7 +191,7 @@ def main():
         if failed:
             break
     rf.close()
-    if args.bgzf:
+    if args.bgzf or args.bam:
         out.write(bgzf.EOF_BLOCK)
     if sv_out:
         sv_out.close()
