@@ -5,9 +5,11 @@
 //   otherwise:          StoreMinimizers_noncanonical<GenomeTuple,Tuple> (MinCount.h:182-338) of both spans, std::sort (the library's
 //                       libstdc++-exact sort), CompareLists<GenomeTuple,Tuple> with the diagonal band        :305-311
 //   then "+= qs", "+= ts - lrts" and the reverse-strand flip                                                  :313-323
-// Mapping: the short-gap branch (the common one: gaps between chained anchors) is the batched AffineOneGapAlign plus one lane per gap
-// for the K-mer scan; the long-gap branch runs one lane per (gap, side) for the sketch and one lane per gap for the list walk --
-// literal serial code, it is rare and bounded by refineSpaceDist.  Algorithmic bytes: qLen + tLen + 12 per block + 8 per pair.
+// Mapping: the short-gap branch (gaps between chained anchors) is the batched AffineOneGapAlign plus one lane per gap for the K-mer scan.
+// The long-gap branch is not rare: Refine_Btwnsplitchain sends it about a thousand gaps of 2-4 k tuples each in every round, and each launch
+// is as long as its longest gap.  It runs a wave per (gap, side) for the sketch, and for the list walk a bounds pass over every key of the
+// call (rs_bounds), a wave per gap that walks on those bounds without a search of its own (rs_compare), and the band count and the pairs of
+// the rectangles it recorded (rs_count, rs_emit).  Algorithmic bytes: qLen + tLen + 12 per block + 8 per pair; 28 per long-gap tuple.
 #include "common.h"
 #include <stdlib.h>
 #include "scan.h"
@@ -41,15 +43,29 @@ struct RsArgs {
   // large branch: lists 2*j (target), 2*j+1 (query) of large problem j
   uint32_t* lcnt; const uint64_t* loff; uint64_t* lkey; uint32_t* lpos;
   int4* rects; uint32_t* nrect;              // the (target run x query run) rectangles the list walk emits, per large problem
+  uint4* tab;                                // per key of lkey: its bounds in the gap's target and query lists (rs_bounds)
+  unsigned long long* totals;                // [0] short gaps, [1] their block capacity, [2] the long gaps' raw list capacity: one read-back for the three
   // output
   uint32_t* cnt; const uint64_t* pair_off; uint32_t* outQ; uint32_t* outT; float* identity; uint32_t* status;
 };
 
-__global__ void rs_classify(RsArgs a) {
+__device__ __forceinline__ uint32_t rs_list_cap(long len, long k) { return (uint32_t)(len >= k && k >= 1 ? len - k + 1 : 0); }   // a list cannot hold more tuples than k-mer positions
+__global__ void __launch_bounds__(256) rs_classify(RsArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.n) return;
-  a.isSmall[i] = (a.q_len[i] < 1000 && a.t_len[i] < 1000) ? 1u : 0u;   // querySeq.size() < 1000 and refSeq.size() < 1000  :262
-  a.status[i] = 0; a.identity[i] = -1.f; a.cnt[i] = 0;
+  unsigned long long nS = 0, capS = 0, capL = 0;
+  if (i < a.n) {
+    const bool small = a.q_len[i] < 1000 && a.t_len[i] < 1000;          // querySeq.size() < 1000 and refSeq.size() < 1000  :262
+    a.isSmall[i] = small ? 1u : 0u;
+    a.status[i] = 0; a.identity[i] = -1.f; a.cnt[i] = 0;
+    if (small) { nS = 1; capS = (unsigned long long)(uint32_t)(a.q_len[i] + a.t_len[i] + 8); }   // rs_split's bcap
+    else capL = (unsigned long long)rs_list_cap(a.t_len[i], a.K[i]) + rs_list_cap(a.q_len[i], a.K[i]);   // rs_caps' two lists
+  }
+  for (int o = 32; o > 0; o >>= 1) { nS += __shfl_xor(nS, o); capS += __shfl_xor(capS, o); capL += __shfl_xor(capL, o); }
+  if ((threadIdx.x & 63) == 0) {
+    if (nS) atomicAdd(&a.totals[0], nS);
+    if (capS) atomicAdd(&a.totals[1], capS);
+    if (capL) atomicAdd(&a.totals[2], capL);
+  }
 }
 
 __global__ void rs_split(RsArgs a) {
@@ -290,9 +306,7 @@ __global__ void rs_caps(RsArgs a, int nLarge, uint32_t* cap) {
   const int l = blockIdx.x * blockDim.x + threadIdx.x;
   if (l >= 2 * nLarge) return;
   const uint32_t i = a.largeIdx[l >> 1];
-  const long len = (l & 1) ? a.q_len[i] : a.t_len[i];
-  const long k = a.K[i];
-  cap[l] = (uint32_t)(len >= k && k >= 1 ? len - k + 1 : 0);
+  cap[l] = rs_list_cap((l & 1) ? a.q_len[i] : a.t_len[i], a.K[i]);
 }
 // one wave per list: raw (capacity-spaced) tuples -> the CSR lists
 __global__ void __launch_bounds__(64) rs_compact(int nLists, const uint64_t* __restrict__ capOff, const uint64_t* __restrict__ loff, const uint64_t* __restrict__ rk,
@@ -304,13 +318,18 @@ __global__ void __launch_bounds__(64) rs_compact(int nLists, const uint64_t* __r
 }
 
 // long gaps: CompareLists<GenomeTuple,Tuple>(query, target, ..., Global = false, maxDiagNum, minDiagNum, canonical = false)  CompareLists.h:9-146
-// One WAVE per gap, the walk on uniform values as in rs_sketch; the two sorted key lists are staged in LDS (when they fit) so that the
-// searches and run scans of the walk never wait on HBM.  The walk runs once: every emission of the reference is a rectangle (a run of
-// equal target keys x a run of equal query keys, target-major); the walk records the rectangle and counts its cells that pass the
-// diagonal band with all lanes, rs_emit then writes the pairs of all rectangles in the same order.
-// Keys staged per wave: 12 KB of LDS (measured, headline batch, lists of 2-4 k keys per gap: 7168 keys of LDS per wave 54 ms, 3072: 50, 1536: 49, 512: 52 -- the
-// waves per CU matter more than where the keys sit).
-constexpr int CMP_LDS_KEYS = 1536;
+// The walk is a serial state machine over four cursors (qs, qe, ts, te) and sets the length of the launch, so it does no search of its own (as seed.hip's
+// bounds_kernel / compare_kernel do for the same function at tier 1):
+//   rs_bounds   one lane per key of every list of the call: the key's lower and upper bound in its gap's target list and in its gap's query list.  For a key of the
+//               other list these are what the walk's std::lower_bound / upper_bound and its "skip what cannot match" loops look for; for a key of the list itself they
+//               are the start and the end of its run of equal keys.  The lists are sorted, so a bound over any sub-range [from, to) is the global bound clamped.
+//   rs_compare     one wave per gap, every lane on the same (uniform) cursors.  Each fwd / bwd / lower of the literal walk is a clamp of a table entry.  The 64 lanes hold
+//               the keys and table entries of the 64 list places from each cursor on in the direction it moves, and a place is read with v_readlane: memory is
+//               touched only when a cursor leaves its window, not in every iteration.  Every emission of the reference is a rectangle (a run of equal target keys x a
+//               run of equal query keys, target-major); the walk records the rectangles and looks at no position.
+//   rs_count    the cells of the rectangles that pass the diagonal band, a lane per rectangle (the wave together on a large one); rs_emit writes the pairs in order.
+// The long-gap sketches clear the top bit of every key (rs_sketch: "& FOR_MASK" on both of its paths), so the raw compares of :101-102 and the masked ones everywhere
+// else agree: one table serves both.
 struct RsBand { long long minDiag, maxDiag; };
 __device__ __forceinline__ RsBand rs_band(const RsArgs& a, uint32_t i) {
   const long long diag2 = (long long)a.t_span[i] - (long long)(uint32_t)a.q_len[i];
@@ -323,115 +342,153 @@ __device__ __forceinline__ bool rs_pass(const RsBand& bd, const uint32_t* tp, co
   }
   return true;
 }
-__global__ void __launch_bounds__(64) rs_compare(RsArgs a, int nLarge, int ldsKeys) {
-  extern __shared__ uint64_t skeys[];
+
+// [first index with key >= v, first index with key > v) of a sorted list
+__device__ __forceinline__ uint2 rs_equal_range(const uint64_t* __restrict__ k, uint32_t n, uint64_t v) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if ((k[mid] & FOR_MASK) < v) lo = mid + 1; else hi = mid; }
+  const uint32_t l = lo;
+  int steps = 0;                                                         // the equal run is short but for tandem arrays: a few steps, then the search on what is left
+  while (lo < n && steps < 4 && (k[lo] & FOR_MASK) == v) { lo++; steps++; }
+  if (steps == 4) { hi = n; while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (!(v < (k[mid] & FOR_MASK))) lo = mid + 1; else hi = mid; } }
+  return make_uint2(l, lo);
+}
+// the run of equal keys around place x of a sorted list
+__device__ __forceinline__ uint2 rs_own_run(const uint64_t* __restrict__ k, uint32_t n, uint32_t x, uint64_t v) {
+  uint32_t l = x, u = x + 1;
+  int steps = 0;
+  while (l > 0 && steps < 4 && (k[l - 1] & FOR_MASK) == v) { l--; steps++; }
+  if (steps == 4) { uint32_t lo = 0, hi = l; while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if ((k[mid] & FOR_MASK) < v) lo = mid + 1; else hi = mid; } l = lo; }
+  steps = 0;
+  while (u < n && steps < 4 && (k[u] & FOR_MASK) == v) { u++; steps++; }
+  if (steps == 4) { uint32_t lo = u, hi = n; while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (!(v < (k[mid] & FOR_MASK))) lo = mid + 1; else hi = mid; } u = lo; }
+  return make_uint2(l, u);
+}
+// tab[g] of the key v at place g of lkey: (lbT, ubT, lbQ, ubQ), places within the gap's two lists.  One workgroup per list.
+__global__ void __launch_bounds__(256) rs_bounds(RsArgs a, int nLarge) {
+  const int l = blockIdx.x;
+  if (l >= 2 * nLarge) return;
+  const int j = l >> 1;
+  const uint64_t* tk = a.lkey + a.loff[2 * j]; const uint64_t* qk = a.lkey + a.loff[2 * j + 1];
+  const uint32_t nt = (uint32_t)(a.loff[2 * j + 1] - a.loff[2 * j]), nq = (uint32_t)(a.loff[2 * j + 2] - a.loff[2 * j + 1]);
+  const bool isQ = l & 1;
+  const uint64_t* own = isQ ? qk : tk; const uint64_t* oth = isQ ? tk : qk;
+  const uint32_t nOwn = isQ ? nq : nt, nOth = isQ ? nt : nq;
+  uint4* tab = a.tab + a.loff[l];
+  for (uint32_t x = threadIdx.x; x < nOwn; x += 256) {
+    const uint64_t v = own[x] & FOR_MASK;
+    const uint2 o = rs_equal_range(oth, nOth, v), s = rs_own_run(own, nOwn, x, v);
+    tab[x] = isQ ? make_uint4(o.x, o.y, s.x, s.y) : make_uint4(s.x, s.y, o.x, o.y);
+  }
+}
+
+// 64 places of a list (key and table entry) from a cursor on, upwards (DIR = 1) or downwards (DIR = -1): lane d holds place base + DIR * d
+// (32-bit cursors and entries: a list holds fewer than 2^31 tuples, and the walk is bound by instruction issue, where a 64-bit compare or add is two: 1041 -> 683 us
+// per launch)
+struct RsWin { uint64_t k; uint4 e; int base; };
+struct RsAt { uint64_t k; int lbT, ubT, lbQ, ubQ; };
+__device__ __forceinline__ uint32_t rs_lane_u32(uint32_t v, int d) { return (uint32_t)__builtin_amdgcn_readlane((int)v, d); }
+template <int DIR>
+__device__ __forceinline__ RsAt rs_at(RsWin& w, const uint64_t* __restrict__ keys, const uint4* __restrict__ tab, int n, int c, int lane) {   // 0 <= c < n, c uniform
+  int d = DIR > 0 ? c - w.base : w.base - c;
+  if (d < 0 || d >= 64) {
+    w.base = c; d = 0;
+    const int idx = c + DIR * lane;
+    if (idx >= 0 && idx < n) { w.k = keys[idx]; w.e = tab[idx]; }
+  }
+  const int dl = (int)d;
+  RsAt r;
+  r.k = ((uint64_t)rs_lane_u32((uint32_t)(w.k >> 32), dl) << 32 | rs_lane_u32((uint32_t)w.k, dl)) & FOR_MASK;
+  r.lbT = rs_lane_u32(w.e.x, dl); r.ubT = rs_lane_u32(w.e.y, dl); r.lbQ = rs_lane_u32(w.e.z, dl); r.ubQ = rs_lane_u32(w.e.w, dl);
+  return r;
+}
+__global__ void __launch_bounds__(64) rs_compare(RsArgs a, int nLarge) {
   const int j = blockIdx.x, lane = threadIdx.x;
   if (j >= nLarge) return;
   const uint32_t i = a.largeIdx[j];
-  const uint64_t* tkG = a.lkey + a.loff[2 * j]; const uint32_t* tp = a.lpos + a.loff[2 * j];
-  const uint64_t* qkG = a.lkey + a.loff[2 * j + 1]; const uint32_t* qp = a.lpos + a.loff[2 * j + 1];
-  const long nt = (long)(a.loff[2 * j + 1] - a.loff[2 * j]), nq = (long)(a.loff[2 * j + 2] - a.loff[2 * j + 1]);
-  const bool staged = nt + nq <= ldsKeys;
-  if (staged) {                                                          // the two lists are adjacent in lkey: one copy
-    for (long x = lane; x < nt + nq; x += 64) skeys[x] = tkG[x];
-    rs_wave_sync();
-  }
-  const RsBand bd = rs_band(a, i);
-  const long maxFreq = a.maxFreqArr ? (long)a.maxFreqArr[i] : a.maxFreq;
+  const uint64_t* tk = a.lkey + a.loff[2 * j]; const uint64_t* qk = a.lkey + a.loff[2 * j + 1];
+  const uint4* tt = a.tab + a.loff[2 * j]; const uint4* qt = a.tab + a.loff[2 * j + 1];
+  const int nt = (int)(a.loff[2 * j + 1] - a.loff[2 * j]), nq = (int)(a.loff[2 * j + 2] - a.loff[2 * j + 1]);
+  const int maxFreq = a.maxFreqArr ? a.maxFreqArr[i] : (int)a.maxFreq;   // (the entry points take it as an int)
   int4* rects = a.rects + a.loff[2 * j] + 2 * (uint64_t)j;               // nt + nq + 2 slots: every iteration of the walk emits at most one
-  const long rcap = nt + nq + 2;
-  uint32_t n = 0, nrect = 0;
-  // The walk, once for keys staged in LDS and once for keys left in HBM: through one pointer that may be either, every read would be a flat_load.
-  auto walk = [&](const uint64_t* tk, const uint64_t* qk) __attribute__((always_inline)) {
-  auto rect = [&](long t0, long t1, long q0, long q1) {                   // ti in [t0, t1), qi in [q0, q1]
+  const uint32_t rcap = (uint32_t)(nt + nq + 2);
+  uint32_t nrect = 0;
+  auto rect = [&](int t0, int t1, int q0, int q1) {                   // ti in [t0, t1), qi in [q0, q1]
     if (nrect < rcap) { if (lane == 0) rects[nrect] = make_int4((int)t0, (int)t1, (int)q0, (int)q1); }
     else if (lane == 0) atomicOr(&a.status[i], (uint32_t)LRA_ST_CAPACITY);
     nrect++;
-    const long w = q1 - q0 + 1, cells = (t1 - t0) * w;
-    uint32_t c = 0;
-    for (long x = lane; x < cells; x += 64) c += rs_pass(bd, tp, qp, q0 + x % w, t0 + x / w) ? 1u : 0u;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    n += c;
-  };
-#define Qk(x) (qk[x] & FOR_MASK)
-#define Tk(x) (tk[x] & FOR_MASK)
-  // The walk's loops, 64 list entries per round (every lane holds the same cursors; the lists are sorted, the predicates of the searches monotone):
-  // fwd(from, to, pred): the smallest x in [from, to) with !pred(x), else to  == `while (x < to && pred(x)) x++`
-  auto fwd = [&](long from, long to, auto pred) -> long {
-    long x = from;
-    while (x < to) {
-      const long idx = x + lane;
-      const unsigned long long m = __ballot(!(idx < to && pred(idx)));
-      if (m) return min(x + (long)(__ffsll((long long)m) - 1), to);
-      x += 64;
-    }
-    return to;
-  };
-  // bwd(from, stop, pred): the largest x in (stop, from] with !pred(x), else stop  == `while (x > stop && pred(x)) x--`
-  auto bwd = [&](long from, long stop, auto pred) -> long {
-    long x = from;
-    while (x > stop) {
-      const long idx = x - lane;
-      const unsigned long long m = __ballot(!(idx > stop && pred(idx)));
-      if (m) return max(x - (long)(__ffsll((long long)m) - 1), stop);
-      x -= 64;
-    }
-    return stop;
-  };
-  // lower(lo, hi, pred): the binary search `while (lo < hi) { mid; if (pred(mid)) lo = mid + 1; else hi = mid; }` for a monotone pred, 64 probes per round
-  auto lower = [&](long lo, long hi, auto pred) -> long {
-    while (hi - lo > 64) {
-      const long step = (hi - lo + 63) / 64;
-      const long idx = lo + step * (lane + 1) - 1;
-      const int c = __popcll(__ballot(idx < hi && pred(idx)));            // the probes that hold: a prefix
-      const long idxC = lo + step * (c + 1) - 1;                           // the first probe that does not (or lies past hi)
-      lo = lo + step * c; hi = min(hi, idxC);
-    }
-    return fwd(lo, hi, pred);
   };
   if (nq > 0 && nt > 0) {
-    long qs = 0, qe = nq - 1, ts = 0, te = nt;
+    RsWin wts, wte, wqs, wqe;
+    wts.k = wte.k = wqs.k = wqe.k = 0; wts.e = wte.e = wqs.e = wqe.e = make_uint4(0, 0, 0, 0);
+    wts.base = wqs.base = -128; wte.base = wqe.base = -128;               // no place is in a window yet
+    int qs = 0, qe = nq - 1, ts = 0, te = nt;
     do {
-      { const uint64_t t0 = Tk(ts); qs = fwd(qs, qe + 1, [&](long x) { return Qk(x) < t0; }); }   // :47-49
+      const RsAt Ts = rs_at<1>(wts, tk, tt, nt, ts, lane);
+      qs = min(max(Ts.lbQ, qs), qe + 1);                                  // :47-49  while (qs <= qe && Q[qs] < T[ts]) qs++
       if (qs >= qe) break;                                               // :51-53
-      const uint64_t startGap = Qk(qs) - Tk(ts);
-      if (te > ts) { const uint64_t t1 = Tk(te - 1); qe = bwd(qe, qs, [&](long x) { return Qk(x) > t1; }); }
-      const uint64_t endGap = Tk(te - 1) - Qk(qe);
+      const RsAt Qs = rs_at<1>(wqs, qk, qt, nq, qs, lane);
+      const uint64_t startGap = Qs.k - Ts.k;
+      const RsAt Te = rs_at<-1>(wte, tk, tt, nt, te - 1, lane);
+      qe = max(qs, min(qe, Te.ubQ - 1));                                  // :63-65  while (qe > qs && Q[qe] > T[te-1]) qe--   (te > ts holds here)
+      const RsAt Qe = rs_at<-1>(wqe, qk, qt, nq, qe, lane);
+      const uint64_t endGap = Te.k - Qe.k;
       if (startGap == 0 || (startGap & FOR_MASK) > (endGap & FOR_MASK)) {
-        const long tsOrig = ts, qsOrig = qs;
-        const uint64_t qv = Qk(qs);
-        ts = lower(ts, te, [&](long x) { return Tk(x) < qv; });
-        if (ts < te && Tk(ts) == qv) {
-          const long tsStart = ts;
-          const long tsi = fwd(ts, te, [&](long x) { return Tk(x) == qv; });
-          const long qsStart = qs;
-          qs = fwd(qs + 1, qe + 1, [&](long x) { return Qk(x) == qv; }) - 1;   // while (qs < qe && Qk(qs + 1) == Qk(qs)) qs++
-          if (qs - qsStart < maxFreq && tsi > tsStart) rect(tsStart, tsi, qsStart, qs);   // for ti .. if (..) for qi .. emit(qi, ti)
+        ts = min(max(Qs.lbT, ts), te);                                    // :76  lower_bound(T + ts, T + te, Q[qs])
+        if (ts < te && ts < Qs.ubT) {                                     // T[ts] == Q[qs]  (ts is at or past the key's lower bound)
+          const int tsStart = ts, tsi = min(Qs.ubT, te);                 // :81
+          const int qsStart = qs;
+          qs = min(Qs.ubQ, qe + 1) - 1;                                   // :83  while (qs < qe && Q[qs + 1] == Q[qs]) qs++
+          if (qs - qsStart < maxFreq && tsi > tsStart) rect(tsStart, tsi, qsStart, qs);
         }
-        { const uint64_t r = tk[tsOrig]; ts = fwd(ts, te, [&](long x) { return tk[x] == r; }); }   // :101 raw compare
-        { const uint64_t r = qk[qsOrig]; qs = fwd(qs, qe, [&](long x) { return qk[x] == r; }); }   // :102
+        if (ts < te && ts < Ts.ubT) ts = min(Ts.ubT, te);                 // :101  while (ts < te && T[ts] == T[tsOrig]) ts++   (raw compare: the same, see above)
+        if (qs < qe && qs < Qs.ubQ) qs = min(Qs.ubQ, qe);                 // :102  while (qs < qe && Q[qs] == Q[qsOrig]) qs++
       } else {
-        const uint64_t qv = Qk(qe);
-        if (te != nt && Tk(te - 1) == qv) {
+        if (te != nt && Te.k == Qe.k) {                                   // :110-112
         } else {
-          te = lower(ts, te, [&](long x) { return !(qv < Tk(x)); });
+          te = min(max(Qe.ubT, ts), te);                                  // :114  upper_bound(T + ts, T + te, Q[qe])
         }
-        const long teStart = te;
-        const long tei = bwd(te - 1, ts - 1, [&](long x) { return Tk(x) == qv; }) + 1;   // while (tei > ts && Tk(tei - 1) == Qk(qe)) tei--
+        const int teStart = te;
+        const int tei = (te > ts && Qe.lbT <= te - 1 && te - 1 < Qe.ubT) ? max(Qe.lbT, ts) : te;   // :119  while (tei > ts && T[tei - 1] == Q[qe]) tei--
         if (tei < teStart && teStart > 0) {
-          const long qeStart = qe;
-          qe = bwd(qe - 1, qs - 1, [&](long x) { return Qk(x) == qv; }) + 1;             // while (qe > qs && Qk(qe) == Qk(qe - 1)) qe--
+          const int qeStart = qe;
+          if (qe > qs && Qe.lbQ <= qe - 1) qe = max(Qe.lbQ, qs);          // :124  while (qe > qs && Q[qe] == Q[qe - 1]) qe--
           if (qeStart - qe < maxFreq) rect(tei, teStart, qe, qeStart);
         }
         te = tei;
       }
     } while (qs < qe && ts < te);
   }
-#undef Qk
-#undef Tk
-  };
-  if (staged) walk(skeys, skeys + nt); else walk(tkG, qkG);
-  if (lane == 0) { a.cnt[i] = n; a.nrect[j] = nrect < rcap ? nrect : (uint32_t)rcap; }
+  if (lane == 0) a.nrect[j] = nrect < rcap ? nrect : rcap;
+}
+
+// the cells of a gap's rectangles that pass the band: a lane per rectangle, the wave together on one of more than 32 cells
+__global__ void __launch_bounds__(64) rs_count(RsArgs a, int nLarge) {
+  const int j = blockIdx.x, lane = threadIdx.x;
+  if (j >= nLarge) return;
+  const uint32_t i = a.largeIdx[j];
+  const uint32_t* tp = a.lpos + a.loff[2 * j]; const uint32_t* qp = a.lpos + a.loff[2 * j + 1];
+  const RsBand bd = rs_band(a, i);
+  const bool band = bd.maxDiag != 0 && bd.minDiag != 0;
+  const int4* rects = a.rects + a.loff[2 * j] + 2 * (uint64_t)j;
+  const uint32_t nrect = a.nrect[j];
+  uint32_t c = 0;
+  for (uint32_t r0 = 0; r0 < nrect; r0 += 64) {
+    int4 R = make_int4(0, 0, 0, -1);
+    if (r0 + lane < nrect) R = rects[r0 + lane];
+    const long w = (long)R.w - R.z + 1, cells = ((long)R.y - R.x) * w;
+    const bool big = band && cells > 32;
+    if (!band) c += (uint32_t)cells;
+    else if (!big) for (long x = 0; x < cells; x++) c += rs_pass(bd, tp, qp, R.z + x % w, R.x + x / w) ? 1u : 0u;
+    unsigned long long m = __ballot(big);
+    while (m) {
+      const int src = __ffsll((long long)m) - 1; m &= m - 1;
+      const long t0 = __shfl(R.x, src), q0 = __shfl(R.z, src), wB = __shfl((int)w, src), cellsB = ((long)__shfl(R.y, src) - t0) * wB;
+      for (long x = lane; x < cellsB; x += 64) c += rs_pass(bd, tp, qp, q0 + x % wB, t0 + x / wB) ? 1u : 0u;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  if (lane == 0) a.cnt[i] = c;
 }
 
 // the pairs of the recorded rectangles, in the reference's order (rectangle by rectangle, target-major)
@@ -483,7 +540,7 @@ static int refine_space_impl(lra_ctx* ctx, int n, const char* d_qseq, const uint
   hipStream_t st = ctx->stream;
   const size_t n1 = (size_t)n + 2;
   auto take = [](char*& p, size_t cnt, size_t e) { char* r = p; p += sz(cnt, e); return r; };
-  size_t needW = sz(n1, 4) * 8 + sz(n1, 8) * 6 + 2 * (sz(2 * n1, 4) + sz(2 * n1 + 2, 8)) + 4096;
+  size_t needW = sz(n1, 4) * 8 + sz(n1, 8) * 6 + 2 * (sz(2 * n1, 4) + sz(2 * n1 + 2, 8)) + sz(4, 8) + 4096;
   char* w = (char*)lra_ensure(ctx, 14, needW);
   if (!w) return LRA_ERR_NOMEM;
   RsArgs a;
@@ -495,6 +552,7 @@ static int refine_space_impl(lra_ctx* ctx, int n, const char* d_qseq, const uint
   a.smallPos = (uint64_t*)take(w, n1, 8); a.sq_off = (uint64_t*)take(w, n1, 8); a.st_off = (uint64_t*)take(w, n1, 8);
   uint64_t* boff = (uint64_t*)take(w, n1, 8); uint64_t* pair_off = (uint64_t*)take(w, n1, 8); uint64_t* spare8 = (uint64_t*)take(w, n1, 8); (void)spare8;
   a.lcnt = (uint32_t*)take(w, 2 * n1, 4); uint64_t* loff = (uint64_t*)take(w, 2 * n1 + 2, 8);
+  a.totals = (unsigned long long*)take(w, 4, 8);
   // results that outlive the call
   size_t needR = sz(n1, 8) + sz(n1, 4) * 2 + 4096;
   const unsigned g = (unsigned)((n + 255) / 256);
@@ -505,22 +563,23 @@ static int refine_space_impl(lra_ctx* ctx, int n, const char* d_qseq, const uint
     pairOffOut = (uint64_t*)take(r0, n1, 8); identity = (float*)take(r0, n1, 4); status = (uint32_t*)take(r0, n1, 4);
   }
   a.identity = identity; a.status = status;
+  // the three sizes the host needs before the sketch (short gaps, their block capacity, the long gaps' raw list capacity) are sums over lengths that are known
+  // here: rs_classify adds them up and one copy brings them back
+  LRA_HIP_CHECK(ctx, hipMemsetAsync(a.totals, 0, 4 * 8, st));
   lra_time_begin(ctx, "refine_space");
   hipLaunchKernelGGL(rs_classify, dim3(g), dim3(256), 0, st, a);
   lra_time_end(ctx);
+  unsigned long long totals[3] = {0, 0, 0};
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(totals, a.totals, sizeof totals, hipMemcpyDeviceToHost, st));
   { int rc = lra_exclusive_scan<uint32_t>(ctx, n, a.isSmall, a.smallPos); if (rc) return rc; }
-  uint64_t nSmall64 = 0;
-  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&nSmall64, a.smallPos + n, 8, hipMemcpyDeviceToHost, st));
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  const int nSmall = (int)nSmall64, nLarge = n - nSmall;
+  const int nSmall = (int)totals[0], nLarge = n - nSmall;
   hipLaunchKernelGGL(rs_split, dim3(g), dim3(256), 0, st, a);
   // ---- short gaps
   int32_t* blocks = nullptr;
   if (nSmall > 0) {
     { int rc = lra_exclusive_scan<uint32_t>(ctx, nSmall, a.bcap, boff); if (rc) return rc; }
-    uint64_t totalCap = 0;
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&totalCap, boff + nSmall, 8, hipMemcpyDeviceToHost, st));
-    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    const uint64_t totalCap = totals[1];
     size_t needB = sz(3 * totalCap + 3, 4) + sz((size_t)nSmall + 1, 4) * 3 + 4096;
     char* wb = (char*)lra_ensure(ctx, 16, needB);
     if (!wb) return LRA_ERR_NOMEM;
@@ -541,9 +600,7 @@ static int refine_space_impl(lra_ctx* ctx, int n, const char* d_qseq, const uint
     uint32_t* lcap = (uint32_t*)take(w, 2 * n1, 4); uint64_t* capOff = (uint64_t*)take(w, 2 * n1 + 2, 8);
     hipLaunchKernelGGL(rs_caps, dim3((2 * nLarge + 255) / 256), dim3(256), 0, st, a, nLarge, lcap);
     { int rc = lra_exclusive_scan<uint32_t>(ctx, 2 * nLarge, lcap, capOff); if (rc) return rc; }
-    uint64_t totalCap = 0;
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&totalCap, capOff + 2 * nLarge, 8, hipMemcpyDeviceToHost, st));
-    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    const uint64_t totalCap = totals[2];
     char* wr = (char*)lra_ensure(ctx, 66, sz(totalCap + 1, 8) + sz(totalCap + 1, 4) + 4096);
     if (!wr) return LRA_ERR_NOMEM;
     uint64_t* rawKey = (uint64_t*)take(wr, totalCap + 1, 8); uint32_t* rawPos = (uint32_t*)take(wr, totalCap + 1, 4);
@@ -556,14 +613,18 @@ static int refine_space_impl(lra_ctx* ctx, int n, const char* d_qseq, const uint
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(&totalMm, loff + 2 * nLarge, 8, hipMemcpyDeviceToHost, st));
     LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     if (getenv("LRA_RS_DBG")) fprintf(stderr, "[rs] n %d nLarge %d minimizers %llu\n", n, nLarge, (unsigned long long)totalMm);
-    char* wl = (char*)lra_ensure(ctx, 17, sz(totalMm + 1, 8) + sz(totalMm + 1, 4) + sz(totalMm + 2 * (size_t)nLarge + 4, 16) + sz((size_t)nLarge + 1, 4) + 4096);
+    char* wl = (char*)lra_ensure(ctx, 17, sz(totalMm + 1, 8) + sz(totalMm + 1, 4) + sz(totalMm + 2 * (size_t)nLarge + 4, 16) + sz((size_t)nLarge + 1, 4) +
+                                          sz(totalMm + 1, 16) + 4096);
     if (!wl) return LRA_ERR_NOMEM;
     a.lkey = (uint64_t*)take(wl, totalMm + 1, 8); a.lpos = (uint32_t*)take(wl, totalMm + 1, 4); a.loff = loff;
     a.rects = (int4*)take(wl, totalMm + 2 * (size_t)nLarge + 4, 16); a.nrect = (uint32_t*)take(wl, (size_t)nLarge + 1, 4);
+    a.tab = (uint4*)take(wl, totalMm + 1, 16);
     hipLaunchKernelGGL(rs_compact, dim3(2 * nLarge), dim3(64), 0, st, 2 * nLarge, capOff, loff, rawKey, rawPos, a.lkey, a.lpos);
     { int rc = lra_sort_minimizers_batch(ctx, 2 * nLarge, loff, a.lkey, a.lpos); if (rc) return rc; }   // sort(EndGenomeTup), sort(EndReadTup)  :306,:308
     lra_time_begin(ctx, "rs_long_compare");
-    hipLaunchKernelGGL(rs_compare, dim3(nLarge), dim3(64), (size_t)CMP_LDS_KEYS * 8, st, a, nLarge, CMP_LDS_KEYS);
+    hipLaunchKernelGGL(rs_bounds, dim3(2 * nLarge), dim3(256), 0, st, a, nLarge);
+    hipLaunchKernelGGL(rs_compare, dim3(nLarge), dim3(64), 0, st, a, nLarge);
+    hipLaunchKernelGGL(rs_count, dim3(nLarge), dim3(64), 0, st, a, nLarge);
     lra_time_end(ctx);
   }
   // ---- pairs

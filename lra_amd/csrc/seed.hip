@@ -52,19 +52,21 @@ __device__ __forceinline__ uint64_t code2(unsigned char c) {  // SeqUtils.h:7 (s
 
 // ------------------------------------------------------------------------------------ a1
 // One lane per read; the state machine of MinCount.h:8-179 verbatim in behaviour.
-// EMIT=false only counts.  The w-entry ring lives in LDS, lane-interleaved.
+// EMIT=false only counts.  The w-entry ring lives in LDS, lane-interleaved.  The reads are those of `list` (the reads with a non-ACGT byte, which the wave kernel
+// below leaves to this one): the kernel is launched over them alone, and not at all when there are none.
 template <bool EMIT>
 __global__ void __launch_bounds__(64) sketch_kernel(int n_reads, const unsigned char* __restrict__ seq_all,
                                                     const uint64_t* __restrict__ read_off, int k, int w,
                                                     const uint64_t* __restrict__ mm_off, uint64_t* __restrict__ mm_key,
                                                     uint32_t* __restrict__ mm_pos, uint32_t* __restrict__ counts,
-                                                    const int* __restrict__ only_flagged) {
+                                                    const int* __restrict__ list, int n_list) {
   __shared__ uint64_t ringT[MAX_W * 64];
   __shared__ uint32_t ringP[MAX_W * 64];
   const int lane = threadIdx.x;
-  const int r = blockIdx.x * 64 + lane;
-  if (r >= n_reads) return;
-  if (only_flagged && !only_flagged[r]) return;
+  const int x = blockIdx.x * 64 + lane;
+  if (x >= n_list) return;
+  const int r = list[x];
+  if (r < 0 || r >= n_reads) return;
   const unsigned char* seq = seq_all + read_off[r];
   const uint32_t seqLen = (uint32_t)(read_off[r + 1] - read_off[r]);
   uint64_t* okey = EMIT ? mm_key + mm_off[r] : nullptr;
@@ -176,7 +178,8 @@ template <bool EMIT>
 __global__ void __launch_bounds__(64) sketch_wave_kernel(int n_reads, const unsigned char* __restrict__ seq_all,
                                                          const uint64_t* __restrict__ read_off, int k, int w,
                                                          const uint64_t* __restrict__ mm_off, uint64_t* __restrict__ mm_key,
-                                                         uint32_t* __restrict__ mm_pos, uint32_t* __restrict__ counts, int* flagN) {
+                                                         uint32_t* __restrict__ mm_pos, uint32_t* __restrict__ counts, int* flagN,
+                                                         int* __restrict__ n_flagged, int* __restrict__ flagged) {
   __shared__ uint64_t kbuf[128];
   const int lane = threadIdx.x;
   const uint64_t kbits = (k >= 32) ? 0xFFFFFFFFULL : ((1ULL << k) - 1);
@@ -292,7 +295,11 @@ __global__ void __launch_bounds__(64) sketch_wave_kernel(int n_reads, const unsi
       __builtin_amdgcn_wave_barrier();
     }
     const bool anyN = __ballot(hasN) != 0;
-    if (lane == 0) { counts[r] = nout; flagN[r] = anyN ? 1 : 0; }
+    if (lane == 0) {
+      counts[r] = anyN ? 0 : nout;                                     // (a flagged read's count comes from the serial kernel, after the first scan)
+      flagN[r] = anyN ? 1 : 0;
+      if (anyN) flagged[atomicAdd(n_flagged, 1)] = r;                  // in any order: every read's tuples go to the read's own places
+    }
   }
 }
 
@@ -1337,10 +1344,11 @@ static int grow_mm(lra_ctx* ctx, lra_seed_state* s, uint64_t total_mm) {
   return LRA_OK;
 }
 
-// a1 for w > 1: the window machine, a wave per read (sketch_wave_kernel), the reads with a non-ACGT byte a lane per read (sketch_kernel)
+// a1 for w > 1: the window machine, a wave per read (sketch_wave_kernel), the reads with a non-ACGT byte a lane per read (sketch_kernel).  The wave kernel lists the
+// reads it leaves to the serial one; how many there are comes back with the minimizer total, so a batch without such reads (the usual one) launches nothing for them
+// and waits no more often than before.  A batch with some counts them, scans again and reads the total a second time.
 static int sketch_windows(lra_ctx* ctx, lra_seed_state* s, int n_reads, const unsigned char* seq, const uint64_t* d_read_off, int k, int w, uint64_t& total_mm) {
   hipStream_t st = ctx->stream;
-  const int nb = (n_reads + 63) / 64;
   // ---- a1: count, scan, emit
   const int gridW = n_reads < ctx->num_cu * 32 ? n_reads : ctx->num_cu * 32;
   int* flagN = (int*)s->n_forward;   // reused before a4 writes it
@@ -1349,30 +1357,44 @@ static int sketch_windows(lra_ctx* ctx, lra_seed_state* s, int n_reads, const un
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
   // (the staging arrays -- 12 bytes per base of the batch -- live in the sparse DP's arena, slot 12: the seed stage comes first in a batch, the arena is dead until the
   // first sparse DP, and what the batch before left there -- IndelRefine's and CalculateStatistics' arrays -- belonged to a result that ends with this call)
-  char* stg = (char*)lra_ensure(ctx, 12, (size_t)total_bases * 12 + 1024);
+  const size_t key_b = ((size_t)total_bases * 8 + 255) & ~(size_t)255, pos_b = ((size_t)total_bases * 4 + 255) & ~(size_t)255;
+  char* stg = (char*)lra_ensure(ctx, 12, key_b + pos_b + ((size_t)n_reads + 1) * 4 + 1024);
   if (!stg) return LRA_ERR_NOMEM;
   uint64_t* wkey = (uint64_t*)stg;
-  uint32_t* wpos = (uint32_t*)(stg + (((size_t)total_bases * 8 + 255) & ~(size_t)255));
+  uint32_t* wpos = (uint32_t*)(stg + key_b);
+  int* n_flagged = (int*)(stg + key_b + pos_b); int* flagged = n_flagged + 1;   // the reads left to the serial kernel: their number, then the reads
+  LRA_HIP_CHECK(ctx, hipMemsetAsync(n_flagged, 0, 4, st));
   lra_time_begin(ctx, "sketch_emit");
-  hipLaunchKernelGGL(sketch_wave_kernel<true>, dim3(gridW), dim3(64), 0, st, n_reads, seq, d_read_off, k, w, d_read_off, wkey, wpos, s->counts32, flagN);
+  hipLaunchKernelGGL(sketch_wave_kernel<true>, dim3(gridW), dim3(64), 0, st, n_reads, seq, d_read_off, k, w, d_read_off, wkey, wpos, s->counts32, flagN, n_flagged, flagged);
   lra_time_end(ctx);
-  lra_time_begin(ctx, "sketch_serial");
-  hipLaunchKernelGGL(sketch_kernel<false>, dim3(nb), dim3(64), 0, st, n_reads, seq, d_read_off, k, w, (const uint64_t*)nullptr,
-                     (uint64_t*)nullptr, (uint32_t*)nullptr, s->counts32, (const int*)flagN);
-  lra_time_end(ctx);
+  int n_flag = 0;
+  LRA_HIP_CHECK(ctx, hipMemcpyAsync(&n_flag, n_flagged, 4, hipMemcpyDeviceToHost, st));
   if (lra_exclusive_scan<uint32_t>(ctx, (long)n_reads, s->counts32, s->mm_off)) return LRA_ERR_HIP;
   total_mm = 0;
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(&total_mm, s->mm_off + n_reads, 8, hipMemcpyDeviceToHost, st));
   LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  if (n_flag < 0 || n_flag > n_reads) return lra_set_err(ctx, LRA_ERR_INVALID, "sketch: flagged read count");
+  const int nb = (n_flag + 63) / 64;
+  if (n_flag) {
+    lra_time_begin(ctx, "sketch_serial");
+    hipLaunchKernelGGL(sketch_kernel<false>, dim3(nb), dim3(64), 0, st, n_reads, seq, d_read_off, k, w, (const uint64_t*)nullptr,
+                       (uint64_t*)nullptr, (uint32_t*)nullptr, s->counts32, (const int*)flagged, n_flag);
+    lra_time_end(ctx);
+    if (lra_exclusive_scan<uint32_t>(ctx, (long)n_reads, s->counts32, s->mm_off)) return LRA_ERR_HIP;
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&total_mm, s->mm_off + n_reads, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  }
   { int rc = grow_mm(ctx, s, total_mm); if (rc) return rc; }
   lra_time_begin(ctx, "sketch_compact");
   hipLaunchKernelGGL(sketch_compact, dim3(std::min((n_reads + 3) / 4, ctx->num_cu * 32)), dim3(256), 0, st, n_reads, d_read_off, (const uint64_t*)s->mm_off, (const int*)flagN,
                      (const uint64_t*)wkey, (const uint32_t*)wpos, s->mm_key, s->mm_pos);
   lra_time_end(ctx);
-  lra_time_begin(ctx, "sketch_serial");
-  hipLaunchKernelGGL(sketch_kernel<true>, dim3(nb), dim3(64), 0, st, n_reads, seq, d_read_off, k, w, s->mm_off, s->mm_key, s->mm_pos,
-                     (uint32_t*)nullptr, (const int*)flagN);
-  lra_time_end(ctx);
+  if (n_flag) {
+    lra_time_begin(ctx, "sketch_serial");
+    hipLaunchKernelGGL(sketch_kernel<true>, dim3(nb), dim3(64), 0, st, n_reads, seq, d_read_off, k, w, s->mm_off, s->mm_key, s->mm_pos,
+                       (uint32_t*)nullptr, (const int*)flagged, n_flag);
+    lra_time_end(ctx);
+  }
   return LRA_OK;
 }
 
