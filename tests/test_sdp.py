@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from sdp_inputs import _MIX_OPTS, _compare, _load_jobs, _random_clusters, _random_read_mix, _run_hip
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "sdp_parts_golden.json")
 
@@ -51,94 +52,6 @@ def test_oracle_maximization_matches_reference(gold):
 
 
 # ---------------------------------------------------------------- GPU: HIP SDP#A vs. oracle ---------------------------
-def _random_clusters(rng, n_clusters, per_cluster, span, ties):
-    offs = [0]; strands = []; Q = []; T = []; L = []
-    for c in range(n_clusters):
-        strand = int(rng.random() < 0.4)
-        q = int(rng.integers(0, span)); t = int(rng.integers(0, span)) + (span if strand else 0)
-        m = int(rng.integers(1, per_cluster + 1))
-        for i in range(m):
-            ln = int(rng.choice([1, 2, 3])) if ties else int(rng.choice([17, 17, 20, 30, 60, 150]))
-            Q.append(q); T.append(t); L.append(ln)
-            step = int(rng.integers(0, 3)) if ties else int(rng.integers(0, 200))
-            q += ln + step
-            if strand:
-                t = max(0, t - ln - (int(rng.integers(0, 3)) if ties else int(rng.integers(0, 200))))
-            else:
-                t += ln + (int(rng.integers(0, 3)) if ties else int(rng.integers(0, 200)))
-        strands.append(strand); offs.append(len(Q))
-    return (np.array(offs, np.int32), np.array(strands, np.uint8), np.array(Q, np.uint32), np.array(T, np.uint32), np.array(L, np.int32))
-
-
-def _run_hip(ctx, reads_in, read_lens, opts_kw):
-    """reads_in: list of (cluster_off, strands, q, t, len) per read -> fetched result dict"""
-    import torch
-    from lra_amd import chain
-    dev = ctx.device
-    coff = [0]; cstart = []; ccount = []; cstrand = []; Q = []; T = []; L = []
-    pad = 0
-    for (offs, st, q, t, ln) in reads_in:
-        for c in range(len(st)):
-            a, b = int(offs[c]), int(offs[c + 1])
-            Q.extend([7] * pad); T.extend([9] * pad); L.extend([1] * pad)          # gaps between clusters, as lra_linear_extend_batch leaves them
-            cstart.append(len(Q)); ccount.append(b - a); cstrand.append(int(st[c]))
-            Q.extend(q[a:b].tolist()); T.extend(t[a:b].tolist()); L.extend(ln[a:b].tolist())
-            pad = (pad + 1) % 3
-        coff.append(len(cstart))
-    roff = np.concatenate([[0], np.cumsum(read_lens)]).astype(np.int64)
-    tt = lambda a, dt: torch.tensor(np.asarray(a, dtype=dt), device=dev)
-    d = dict(cluster_off=tt(coff, np.int64), c_start=tt(cstart if cstart else [0], np.int64), c_count=tt(ccount if ccount else [0], np.int32),
-             c_strand=tt(cstrand if cstrand else [0], np.int32), q=tt(Q if Q else [0], np.int64).to(torch.int32),
-             t=tt(T if T else [0], np.int64).to(torch.int32), ln=tt(L if L else [0], np.int32), roff=tt(roff, np.int64))
-    res = chain.sparse_dp_batch(ctx, len(reads_in), d["cluster_off"], d["c_start"], d["c_count"], d["c_strand"], d["q"], d["t"], d["ln"], d["roff"],
-                                chain.sdp_opts(**opts_kw))
-    return res, chain.fetch(ctx, res)
-
-
-def _compare(out, num_aln, reads_in, read_lens, opts_kw):
-    n_ok = 0
-    for r, (offs, st, q, t, ln) in enumerate(reads_in):
-        exp = O.sdp_chain(offs, st, q, t, ln, O.sdp_opts(read_lens[r], **opts_kw))
-        if exp["status"] < 0:
-            assert out["status"][r] != 0, r
-            continue
-        assert out["status"][r] == 0, (r, out["status"][r])
-        f0, f1 = int(out["frag_off"][r]), int(out["frag_off"][r + 1])
-        assert f1 - f0 == len(q)
-        assert np.array_equal(out["frag_val"][f0:f1].view(np.uint32), exp["val"].view(np.uint32)), r
-        assert int(out["n_chains"][r]) == len(exp["chains"]), (r, out["n_chains"][r], len(exp["chains"]))
-        for c, ch in enumerate(exp["chains"]):
-            s = r * num_aln + c
-            a = int(out["chain_start"][s]); m = int(out["chain_len"][s])
-            assert m == len(ch["frags"]), (r, c)
-            cl = np.searchsorted(offs, ch["frags"], side="right") - 1
-            assert np.array_equal(out["chain_cluster"][a:a + m], cl), (r, c)
-            assert np.array_equal(out["chain_anchor"][a:a + m], ch["frags"] - offs[cl]), (r, c)
-            assert np.array_equal(out["chain_link"][a:a + m - 1], ch["link"]), (r, c)
-            assert out["chain_box"][s].tolist() == ch["box"].tolist(), (r, c)
-            assert np.float32(out["chain_value"][s]) == np.float32(ch["value"]), (r, c)
-            n_ok += 1
-    return n_ok
-
-
-def _random_read_mix():
-    """162 reads of 0 .. 599 anchors (0 .. 1298 points; 90 of them below 40 points): the oracle accepts every one under each of _MIX_OPTS"""
-    rng = np.random.default_rng(77)
-    reads_in = []
-    for k in range(160):
-        if k < 40: reads_in.append(_random_clusters(rng, int(rng.integers(1, 4)), 3, 12, True))        # heavy coordinate ties
-        elif k < 80: reads_in.append(_random_clusters(rng, int(rng.integers(1, 5)), 6, 40, True))
-        elif k < 140: reads_in.append(_random_clusters(rng, int(rng.integers(1, 8)), 12, 3000, False))
-        else: reads_in.append(_random_clusters(rng, int(rng.integers(4, 30)), 40, 30000, False))
-    reads_in.insert(5, (np.array([0], np.int32), np.zeros(0, np.uint8), np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.int32)))   # read without clusters
-    reads_in.insert(9, (np.array([0, 1], np.int32), np.array([1], np.uint8), np.array([5], np.uint32), np.array([100], np.uint32), np.array([17], np.int32)))
-    read_lens = [max(300, int(q.max()) + 200) if len(q) else 300 for (_, _, q, _, _) in reads_in]
-    return reads_in, read_lens
-
-
-_MIX_OPTS = (dict(), dict(NumAln=3, alnthres=0.3, rate=3.0), dict(gapopen=4.0, gapextend=20.0, gapCeiling1=3000, gapCeiling2=5000, rate=1.0))
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("sizes", ["estimated", "outgrown", "counted"])
 def test_hip_sdp_random_clusters(ctx, sizes, monkeypatch):
@@ -345,21 +258,6 @@ def test_hip_sdp_workgroup_reads_only(ctx, monkeypatch):
     res, out = _run_hip(ctx, reads_in, read_lens, {})
     assert _compare(out, int(res.num_aln), reads_in, read_lens, {}) == 2   # (the oracle's chains, counted on the CPU)
     assert int((out["status"][:3] == 0).sum()) >= 3                        # the oracle has a result for all three reads: none skipped
-
-
-def _load_jobs(path):
-    """jobs written by LRA_SDP_DUMP (lra_amd/csrc/sdp_diag.hip, diag_dump): header (mode, clusters, anchors, read length), rate, cluster offsets, strands, q, t, len"""
-    b = open(path, "rb").read(); at = 0; jobs = []
-    while at < len(b):
-        mode, nc, total, rl = (int(x) for x in np.frombuffer(b, np.int32, 4, at)); at += 16
-        rate = float(np.frombuffer(b, np.float32, 1, at)[0]); at += 4
-        off = np.frombuffer(b, np.int32, nc + 1, at).copy(); at += 4 * (nc + 1)
-        st = np.frombuffer(b, np.uint8, nc, at).copy(); at += nc
-        q = np.frombuffer(b, np.uint32, total, at).copy(); at += 4 * total
-        t = np.frombuffer(b, np.uint32, total, at).copy(); at += 4 * total
-        ln = np.frombuffer(b, np.int32, total, at).copy(); at += 4 * total
-        jobs.append((mode, rate, (off, st, q, t, ln)))
-    return jobs
 
 
 @pytest.mark.gpu
