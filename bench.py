@@ -10,8 +10,12 @@ record buffer packed (lra_map_pack) and gathered to rank 0 (RCCL; the single exc
 text: lra_map_records_host) of every rank's reads in input order -- the host tail of batch i runs beside the device side of batch i + 1.
 
 Contract: python bench.py --gpus N --steps K --warmup W  -> rank 0 prints ONE JSON line (ms_per_step: one timed step).  --dump-outputs DIR also writes
-what the last timed step computed, for a seeded sample of its reads, as DIR/<name>.npy.
+what the last timed step computed, for a seeded sample of its reads, as DIR/<name>.npy.  Such a plain run does what the headline figure needs and no more: set up,
+warm up, the timed steps, the dump, the line.  --full adds, behind the timed steps, what else the benchmark measures or checks (cpu_baseline: the oracle on the
+host's cores on a sample of the batch, and whether its alignments equal the last step's).
 """
+import time
+T_START = time.perf_counter()    # (LRA_BENCH_DBG: where a run's time outside its steps goes)
 import argparse
 import ctypes as C
 import json
@@ -19,13 +23,18 @@ import os
 import sys
 import contextlib
 import threading
-import time
 import zlib
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+
+def phase(what):
+    """LRA_BENCH_DBG: how long into the run `what` is reached (a plain run's time outside its steps is part of what every measurement of it costs)"""
+    if os.environ.get("LRA_BENCH_DBG"):
+        sys.stderr.write("[bench] %7.2f s: %s\n" % (time.perf_counter() - T_START, what))
 
 
 def host_cpus():
@@ -233,7 +242,10 @@ def main():
     ap.add_argument("--refine-band", type=int, default=7)
     ap.add_argument("--local-window", type=int, default=int(os.environ.get("LRA_BENCH_LOCAL_WINDOW", 2048)),
                     help="glIndex.localIndexWindow: 2048 = the .gli file `lra index` writes (LocalIndex(0), MMIndex.h:110-127), 256 = `lra align` without a .gli file (opts.localIndexWindow)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed steps, also what the headline figure does not need: cpu_baseline (the same stages through the oracle on the host's cores, on a sample "
+                         "of the batch, and whether its alignments equal the last step's).  Off by default: a plain run sets up, warms up, times its steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave cpu_baseline out all the same (without --full there is none)")
     ap.add_argument("--no-records", action="store_true", help="leave the host tail (SAM text) out of the step")
     ap.add_argument("--satellite-frac", type=float, default=0.03, help="fraction of every chromosome in its satellite array")
     ap.add_argument("--genome-seed", type=int, default=3, help="seed of the synthetic reference (3 = the one every recorded figure is on)")
@@ -271,6 +283,7 @@ def main():
 
     import torch
     import torch.distributed as dist
+    phase("torch imported")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -299,11 +312,13 @@ def main():
     torch.cuda.synchronize()
     torch.cuda.empty_cache()                                               # (the generator's scratch, the deterministic write's sort included, back before the index build)
     gen_s = time.time() - t0
+    phase("reference generated")
     ctx = Context(dev_index)
     t0 = time.time()
     mapper = mapread.LowAccMapper(ctx, genome, None, None, chrom_names, chrom_pos, mopts, index_params=(args.k, args.w, args.max_freq, 15, 1), staged=False)
     torch.cuda.synchronize()
     index_s = time.time() - t0
+    phase("reference indexed")
     G = mapper.G
     # ---- this rank's reads (hash partition of the job's ordinals; weak scaling: args.reads per GPU), cut into args.lanes sub-batches
     t0 = time.time()
@@ -367,6 +382,7 @@ def main():
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
     sim_s = time.time() - t0
+    phase("reads simulated, batches and record arguments ready")
 
     worker = [None]
     text_bytes = [0]
@@ -698,6 +714,7 @@ def main():
     tw = time.perf_counter()
     run_steps(min(n_warm, 1), 0.0)
     step_guess = (time.perf_counter() - tw) if n_warm > 1 else 0.0
+    phase("warm-up steps done")
     ahead_on = ahead["on"]
     timed = lanes + ([heavy["lane"]] if defer_T and args.heavy_lane else [])
     if ahead_on:
@@ -713,6 +730,7 @@ def main():
     run_steps(args.steps, step_guess if args.lanes > 1 else 0.0)
     sync()
     dt = time.perf_counter() - t0
+    phase("timed steps done")
     t_dev = dt
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -820,7 +838,7 @@ def main():
         }
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 if len(lanes) > 1 or defer_T:                              # (untimed: the sample is the head of sub-batch 0, whichever lane mapped it last -- and in ONE batch, nothing handed back)
                     mapper.copts.defer_seed_matches = 0
@@ -837,6 +855,7 @@ def main():
         out["hbm_used_gb"] = round((total_b - free_b) / 1e9, 1)               # everything resident at the end of the run: reference, reads, work buffers
         out["hbm_torch_reserved_gb"] = round(torch.cuda.memory_reserved(dev_index) / 1e9, 1)
         print(json.dumps(out))
+        phase("result line printed")
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

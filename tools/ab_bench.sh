@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of two builds of the library: ab_base/liblra_hip.so (A) against lra_amd/liblra_hip.so (B), alternating, bench.py's own flags behind "--".
-# usage (on the GPU box): bash tools/ab_bench.sh <tag> <pairs> -- <bench flags>
+# usage (on the GPU box): bash tools/ab_bench.sh <tag> <pairs> -- <bench flags>   (--full among them: every run's cpu_baseline.sample_equals_gpu is printed too, else None)
 tag=$1; pairs=$2; shift 3
 cp lra_amd/liblra_hip.so /tmp/ab_new.so
 for i in $(seq 1 $pairs); do

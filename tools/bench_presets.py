@@ -2,7 +2,7 @@
   --preset ccs     configs[1]: a chr20-sized reference (64 Mb) + 15 kb CCS reads (1 % error), -CCS       -> lra_map_reads_highacc_batch
   --preset clr     configs[3]: the GRCh38-like reference + 20 kb CLR reads (15 % error), -CLR            -> lra_map_reads_lowacc_batch
   --preset contig  configs[4]: the GRCh38-like reference + long assembly contigs (0.2 % error), -CONTIG  -> lra_map_reads_highacc_batch
-One JSON line per run: whole-step throughput (device side + record text), inputs resident in HBM, no CPU baseline (bench.py carries that for the headline).
+One JSON line per run: whole-step throughput (device side + record text), inputs resident in HBM, no CPU baseline (bench.py --full carries that for the headline).
 Results are kept under profiles/ (r02_<preset>_bench.json)."""
 import argparse
 import json
