@@ -1546,6 +1546,63 @@ int lra_bam_cigar_batch(lra_ctx* ctx, int n_aln, const uint32_t* d_runs, const u
 int lra_bam_pack_seq_batch(lra_ctx* ctx, uint64_t n, const lra_bam_seq_range* d_ranges, const uint8_t* d_src, uint64_t src_bytes, lra_bam_bytes_result* out);
 int lra_bam_phred_batch(lra_ctx* ctx, uint64_t n, const lra_bam_qual_req* d_req, int n_reads, const char* d_qual, const uint64_t* d_qual_off,
                         lra_bam_bytes_result* out);
+/* ---- Coordinate-sorted BAM with a .bai index (additive to ABI 9) -----------------------------------------------------------------------------------
+ * lra_bam_sorter holds the raw BAM alignment records of any number of batches in device memory of its own (no work buffer of the context), sorts them
+ * on the device and gives them back as BGZF members together with the bytes of the .bai file (SAM specification 5.2).  One sorter serves one context.
+ *   create    max_bytes bounds everything the sorter allocates on the device, finish and index included (>= 1; nothing is allocated yet).
+ *   add       records d_stream[d_rec_start[i], d_rec_start[i + 1]), i < n_rec: complete records (block_size, core, ...) back to back, device arrays,
+ *             copied into an allocation of the batch's own.  LRA_ERR_NOMEM, with nothing changed, when held + the batch + need(held + batch) exceeds
+ *             max_bytes: the caller finishes a run and adds again.  More than 2^32 - 1 held records: LRA_ERR_INVALID.  Not between finish and index.
+ *   need(N records, B bytes), what finish and index allocate:
+ *             the sorted copy of the stream (B + 64) and its record offsets (8 (N + 1)); per sorted record refID, pos, end and bin | unmapped (16 N);
+ *             the larger of  the sort's arena -- keys and ordinals twice for rocprim's double buffer (24 N), rocprim's temporary storage, per record
+ *             its address and length, and both in sorted order (24 N) --  and  the index's arena -- run heads and their scan (12 N + 8), the run
+ *             records and their sort (48 per run, at most N runs, + rocprim's temporary storage), the members' offsets (8 per member), per reference
+ *             five counters and (ref_len + 16383) / 16384 + 1 linear-index windows of 8 bytes (known at finish: LRA_ERR_NOMEM there, nothing
+ *             changed, if they do not fit) --;  and the compress stage's round (lra_bgzf_compress_device: 2 x 65536 + 32 bytes per member of a
+ *             round, lra_bgzf_compress_set_round; these two buffers are the context's and stay with it).
+ *   finish    sorts what is held.  Order (samtools sort's default): refID as an unsigned number (-1 last), pos, forward before reverse (flag & 16),
+ *             ties in the order added.  One 64-bit key: (refID, -1 as 0x7fffffff) << 33 | (uint32)(pos + 1) << 1 | reverse; rocprim's radix sort runs
+ *             over the bits in which the held keys differ.  A record shorter than its core, or a refID >= n_ref: LRA_ERR_INVALID, nothing changed.
+ *   next      successive pieces of whole BGZF members (host memory of the context's, valid until the next call): the sorted stream goes through
+ *             lra_bgzf_compress_device in slices of (members per round) x LRA_BGZF_IN_MAX bytes, so the members are those of ONE call on the whole
+ *             stream.  *len = 0: done.  No EOF member.
+ *   index     after the last piece (before: LRA_ERR_INVALID): the .bai bytes (owned by the sorter, valid until its next finish or its destruction).
+ *             Afterwards the sorter is empty and takes the next run.  A reference above 2^29 bases: LRA_ERR_INVALID with the reason (BAI cannot
+ *             address it; the members were delivered, the sorter is empty; CSI is out of scope).
+ * Virtual offsets.  Byte u of the sorted stream is ((first_member_file_offset + member_off[u / 65280]) << 16) | (u % 65280); a record that ends on a cut
+ * ends at the next member's start with offset 0, behind the last member that is the EOF member the writer appends.
+ * The .bai rules (lra_bam_index_host states them as code; both forms write the same bytes):
+ *   - only records with refID >= 0 are indexed, under the bin of their own core field;
+ *   - a run is a maximal sequence of consecutive records in file order with the same (refID, bin); each run is one chunk [voff(start of its first
+ *     record), voff(end of its last)); a bin's chunks are in file order; nothing is merged further;
+ *   - a reference's bins ascend by number; a reference with records also gets the pseudo-bin 37450, last and counted in n_bin, with the two chunks
+ *     (voff of its first record, voff end of its last) and (n_mapped, n_unmapped by flag & 4);
+ *   - a record's end is pos + max(1, the lengths of its CIGAR ops M D N = X); window w (16384 bases) of the linear index holds the smallest start
+ *     offset of a record with pos >> 14 <= w <= (end - 1) >> 14 (a record that reaches past its reference's end counts up to the window of that end);
+ *     n_intv = the last touched window + 1; an untouched window takes the value of the next touched one behind it; pos < 0 counts as 0;
+ *   - a reference without records has n_bin = n_intv = 0; the trailing n_no_coor counts the records with refID = -1.
+ * lra_bam_index_host (host only, two-call convention: out NULL sets *len; cap < *len is LRA_ERR_INVALID): the same bytes from a sorted raw stream and
+ * the member table ((n_members + 1) offsets), walked serially.  A record cut short, a refID outside [-1, n_ref) or a reference above 2^29 bases:
+ * LRA_ERR_INVALID.
+ * lra_map_records_device_bam_to_sorter: lra_map_records_device_bam's encoding, with nothing copied to the host and nothing compressed: the stream and
+ * the record starts (the assembly's piece-length scan at every record's first piece) go to the sorter.  rec_off as lra_map_records_device_bam. */
+typedef struct lra_bam_sorter lra_bam_sorter;
+int lra_bam_sorter_create(lra_ctx* ctx, uint64_t max_bytes, lra_bam_sorter** out);
+void lra_bam_sorter_destroy(lra_bam_sorter* s);
+int lra_bam_sorter_add_device(lra_bam_sorter* s, const uint8_t* d_stream, const uint64_t* d_rec_start, uint64_t n_rec);
+int lra_bam_sorter_held(lra_bam_sorter* s, uint64_t* n_rec, uint64_t* bytes);
+int lra_bam_sorter_finish(lra_bam_sorter* s, uint64_t first_member_file_offset, int n_ref, const uint64_t* ref_len);
+int lra_bam_sorter_next(lra_bam_sorter* s, const uint8_t** h_data, uint64_t* len);
+int lra_bam_sorter_index(lra_bam_sorter* s, const uint8_t** h_bai, uint64_t* len);
+/* per stage of the last finish / next / index, HIP events (ms): keys + span, the sort, the gather, the compress stage (wall), the index */
+int lra_bam_sorter_stats(lra_bam_sorter* s, double ms[5]);
+int lra_bam_index_host(const uint8_t* stream, uint64_t len, int n_ref, const uint64_t* ref_len, const uint64_t* member_off, uint64_t n_members,
+                       uint64_t first_member_file_offset, uint8_t* out, uint64_t cap, uint64_t* out_len);
+int lra_map_records_device_bam_to_sorter(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* opts, const char* const* names,
+                                         const char* const* quals, const int32_t* read_len, const char* const* chrom_names,
+                                         const char* const* passthrough, const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads,
+                                         lra_bam_sorter* sorter, const uint64_t** rec_off);
 /* the reads of a snapshot whose status word is non-zero: their number; *status (optional) = the snapshot's status array [n_reads], owned by the snapshot */
 uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status);
 /* The record buffer of a batch as ONE device buffer -- what a rank sends to rank 0 in the single exchange step of the multi-GPU path (the

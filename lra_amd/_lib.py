@@ -165,6 +165,16 @@ SYMBOLS = {
     "lra_map_records_device_bgzf": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lra_map_records_device_svsig": (C.c_int, [_vp, _vp, _vp, _vp]),
     "lra_map_records_device_bam": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "lra_map_records_device_bam_to_sorter": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "lra_bam_sorter_create": (C.c_int, [_vp, C.c_uint64, C.POINTER(_vp)]),
+    "lra_bam_sorter_destroy": (None, [_vp]),
+    "lra_bam_sorter_add_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
+    "lra_bam_sorter_held": (C.c_int, [_vp, _u64p, _u64p]),
+    "lra_bam_sorter_finish": (C.c_int, [_vp, C.c_uint64, C.c_int, _vp]),
+    "lra_bam_sorter_next": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
+    "lra_bam_sorter_index": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
+    "lra_bam_sorter_stats": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "lra_bam_index_host": (C.c_int, [_vp, C.c_uint64, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _u64p]),
     "lra_bam_set_cigar_limit": (C.c_int, [_vp, C.c_int]),
     "lra_bam_header": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int, _vp, _vp, _vp, C.c_uint64, _vp]),
     "lra_bam_cigar_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),

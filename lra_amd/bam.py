@@ -1,5 +1,6 @@
 """The device primitives behind BAM output (bam_encode.hip): an alignment's CIGAR as BAM ops, ranges of bases as 4-bit codes, ranges of quality strings
-as phred bytes.  Inputs are device tensors; results are copied to numpy."""
+as phred bytes.  Inputs are device tensors; results are copied to numpy.  Behind them: BamSorter (bam_sort.hip), which sorts the records of several
+batches by coordinate on the device and gives back BGZF members and the .bai bytes, and index_host, the same index from a sorted stream on the host."""
 import ctypes as C
 
 import numpy as np
@@ -58,3 +59,98 @@ def bam_phred_batch(ctx: Context, reqs, n_reads, qual, qual_off, raw=False):
     ctx.check(ctx.lib.lra_bam_phred_batch(ctx.h, C.c_uint64(n), _p(reqs), int(n_reads), C.c_void_p(qual.data_ptr()) if qual is not None else None,
                                           C.c_void_p(qual_off.data_ptr()) if qual_off is not None else None, C.byref(res)))
     return res if raw else _split(ctx, res, n)
+
+
+# ---- coordinate-sorted BAM with a .bai index (bam_sort.hip) -------------------------------------------------------------------------------------------
+ERR_INVALID, ERR_NOMEM = -1, -3
+
+
+class SorterFull(MemoryError):
+    """lra_bam_sorter_add_device's LRA_ERR_NOMEM: the batch does not fit the sorter's budget; nothing changed.  Finish a run and add again."""
+
+
+class BamSorter:
+    """lra_bam_sorter: raw BAM records of any number of batches, held in device memory of the sorter's own (at most max_bytes, finish included), given back
+    sorted by coordinate as BGZF members, with the bytes of the .bai file."""
+
+    def __init__(self, ctx: Context, max_bytes):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        ctx.check(ctx.lib.lra_bam_sorter_create(ctx.h, C.c_uint64(int(max_bytes)), C.byref(self.h)))
+
+    def add(self, stream, rec_start):
+        """stream: uint8 device tensor (or raw address); rec_start: uint64 device tensor [n + 1] of record starts.  SorterFull when the budget is short."""
+        n = int(rec_start.numel()) - 1
+        rc = self.ctx.lib.lra_bam_sorter_add_device(self.h, C.c_void_p(stream if isinstance(stream, int) else stream.data_ptr()), C.c_void_p(rec_start.data_ptr()),
+                                                    C.c_uint64(max(n, 0)))
+        if rc == ERR_NOMEM:
+            raise SorterFull(self.ctx.lib.lra_ctx_last_error(self.ctx.h).decode())
+        self.ctx.check(rc)
+
+    def held(self):
+        """-> (records, bytes) held"""
+        n, b = C.c_uint64(0), C.c_uint64(0)
+        self.ctx.check(self.ctx.lib.lra_bam_sorter_held(self.h, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
+
+    def finish(self, first_member_file_offset, ref_len):
+        """sorts what is held; ref_len: the references' lengths.  Then pieces() / next(), then index()."""
+        a = np.ascontiguousarray(ref_len, np.uint64)
+        self.ctx.check(self.ctx.lib.lra_bam_sorter_finish(self.h, C.c_uint64(int(first_member_file_offset)), len(a), C.c_void_p(a.ctypes.data) if len(a) else None))
+
+    def next(self):
+        """the next piece of whole BGZF members as bytes; b"": done"""
+        p, n = C.c_void_p(), C.c_uint64(0)
+        self.ctx.check(self.ctx.lib.lra_bam_sorter_next(self.h, C.byref(p), C.byref(n)))
+        return C.string_at(p, n.value) if n.value else b""
+
+    def pieces(self):
+        while True:
+            b = self.next()
+            if not b:
+                return
+            yield b
+
+    def index(self):
+        """the .bai bytes of the run whose last piece has been taken; the sorter is empty afterwards"""
+        p, n = C.c_void_p(), C.c_uint64(0)
+        self.ctx.check(self.ctx.lib.lra_bam_sorter_index(self.h, C.byref(p), C.byref(n)))
+        return C.string_at(p, n.value)
+
+    def stats(self):
+        """ms of the last run: keys + span, the sort, the gather, the compress stage, the index"""
+        a = (C.c_double * 5)()
+        self.ctx.check(self.ctx.lib.lra_bam_sorter_stats(self.h, a))
+        return dict(zip(("keys_span", "sort", "gather", "compress", "index"), a))
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:                                                      # (a sorter that outlives its context is left alone: destroy needs the context's device)
+                self.ctx.lib.lra_bam_sorter_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def index_host(stream, ref_len, member_off, first_member_file_offset=0, lib=None):
+    """lra_bam_index_host (no GPU): the .bai bytes of the sorted raw record stream `stream` (bytes) whose BGZF members start at member_off[n_members + 1]
+    behind first_member_file_offset.  ValueError for LRA_ERR_INVALID (a record cut short, a refID outside the table, a reference above 2^29 bases)."""
+    if lib is None:
+        from ._lib import load_library
+        lib = load_library()
+    s = np.frombuffer(bytes(stream), np.uint8)
+    r = np.ascontiguousarray(ref_len, np.uint64)
+    m = np.ascontiguousarray(member_off, np.uint64)
+    q = lambda a: C.c_void_p(a.ctypes.data) if len(a) else None
+    n = C.c_uint64(0)
+    args = (q(s), C.c_uint64(len(s)), len(r), q(r), C.c_void_p(m.ctypes.data), C.c_uint64(len(m) - 1), C.c_uint64(int(first_member_file_offset)))
+    if lib.lra_bam_index_host(*args, None, C.c_uint64(0), C.byref(n)) != 0:
+        raise ValueError("lra_bam_index_host: not a sorted BAM record stream this index can hold")
+    out = np.empty(int(n.value), np.uint8)
+    if lib.lra_bam_index_host(*args, C.c_void_p(out.ctypes.data), C.c_uint64(len(out)), C.byref(n)) != 0:
+        raise ValueError("lra_bam_index_host failed")
+    return out.tobytes()

@@ -867,7 +867,7 @@ static int records_device_svsig(lra_ctx* ctx, const lra_map_result* res, const u
 static int records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names, const char* const* reads,
                           const char* const* quals, const int32_t* read_len, const char* const* chrom_names, const char* const* passthrough,
                           const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads, const char** text, uint64_t* len,
-                          const uint64_t** rec_off, bool keep, bool bam = false) {
+                          const uint64_t** rec_off, bool keep, bool bam = false, const uint64_t** d_rec_start = nullptr, uint64_t* n_rec = nullptr) {
   if (!ctx || !res || !o || !names || !read_len || !chrom_names || !len || (flags & ~(LRA_PACK_MD | LRA_PACK_SVSIG)) || (d_qual && !d_qual_off)) return LRA_ERR_INVALID;
   lra_map_state* m = ctx->map;
   if (!m) return LRA_ERR_INVALID;
@@ -1022,6 +1022,8 @@ static int records_device(lra_ctx* ctx, const lra_map_result* res, const lra_map
     J.rec_first = PT.rec_first.data(); J.n_rec = PT.rec_first.size() - 1;
   }
   J.keep_on_device = keep;
+  if (bam && d_rec_start) { *d_rec_start = nullptr; J.d_rec_start = d_rec_start; }
+  if (n_rec) *n_rec = bam ? PT.rec_first.size() - 1 : 0;
   if (!J.d_strands && nR) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device: the result has no reads to work on");
   m->dev_off.assign((size_t)nR + 1, 0);
   m->dev_text.clear();
@@ -1079,6 +1081,25 @@ extern "C" int lra_map_records_device_bam(lra_ctx* ctx, const lra_map_result* re
   if (!bgzf) { *data = (const uint8_t*)text; *data_len = len; return LRA_OK; }
   if ((rc = lra_bgzf_compress_device(ctx, (const uint8_t*)text, len, data, data_len, member_off, n_members))) return rc;
   ctx->map->dev_stats.bytes_d2h += *data_len;
+  return LRA_OK;
+}
+
+// lra_map_records_device_bam's stream, left on the device and handed to a sorter (bam_sort.hip) with the record starts the assembly knows
+extern "C" int lra_map_records_device_bam_to_sorter(lra_ctx* ctx, const lra_map_result* res, const lra_map_opts* o, const char* const* names,
+                                                    const char* const* quals, const int32_t* read_len, const char* const* chrom_names,
+                                                    const char* const* passthrough, const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads,
+                                                    lra_bam_sorter* sorter, const uint64_t** rec_off) {
+  if (!sorter || !o) return LRA_ERR_INVALID;
+  const char* text = nullptr;
+  uint64_t len = 0, nRec = 0;
+  const uint64_t* d_start = nullptr;
+  int rc = records_device(ctx, res, o, names, nullptr, quals, read_len, chrom_names, passthrough, d_qual, d_qual_off, flags, n_threads, &text, &len, rec_off, true, true,
+                          &d_start, &nRec);
+  if (rc) return rc;
+  if (!len || !nRec) return LRA_OK;
+  if (!d_start) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_map_records_device_bam_to_sorter: the assembly gave no record starts");
+  if ((rc = lra_bam_sorter_add_device(sorter, (const uint8_t*)text, d_start, nRec)))
+    return rc == LRA_ERR_NOMEM ? lra_set_err(ctx, rc, "lra_map_records_device_bam_to_sorter: the batch does not fit the sorter's budget") : rc;
   return LRA_OK;
 }
 

@@ -27,6 +27,8 @@ struct lra_rec_job {
   const uint8_t* d_pseq = nullptr; const uint64_t* d_pseq_off = nullptr; uint64_t n_pseq = 0;
   const uint8_t* d_phred = nullptr; const uint64_t* d_phred_off = nullptr; uint64_t n_phred = 0;
   const uint64_t* rec_first = nullptr; uint64_t n_rec = 0;
+  const uint64_t** d_rec_start = nullptr;                            // BAM records, when not NULL: *d_rec_start = the records' starts in the text [n_rec + 1], on the device (work
+                                                                     // buffer 31, valid until the next assembly): the piece-length scan at every record's first piece
   bool keep_on_device = false;                                       // lra_map_records_device_bgzf: *text is the device text (work buffer 99), not copied to the host
 };
 int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& job, const char** text, uint64_t* len, uint64_t* h_rec_off, lra_records_device_stats* stats);

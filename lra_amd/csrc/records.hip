@@ -98,6 +98,7 @@ struct RcArgs {
   uint32_t* len; const unsigned char** src;                    // per piece
   const uint64_t* at;                                          // the lengths' exclusive prefix [n_pieces + 1]
   unsigned char* out; uint64_t n_out; uint64_t* rec_off;
+  uint64_t* rec_start;                                         // BAM records for the sorter: every record's first byte [n_rec + 1]
 };
 
 // lane i: the length and the source of piece i.  A reference outside what it names gives an empty piece (the host clamps them already).
@@ -150,6 +151,11 @@ __global__ void __launch_bounds__(256) rc_resolve(RcArgs A) {
 __global__ void __launch_bounds__(256) rc_rec_off(RcArgs A) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r <= A.n_reads) A.rec_off[r] = A.at[A.read_piece[r]];
+}
+
+__global__ void __launch_bounds__(256) rc_rec_start(RcArgs A) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i <= A.n_rec) A.rec_start[i] = A.at[A.rec_first[i]];
 }
 
 // BAM records, behind the copy: lane i writes record i's block_size, its bytes less the field's own four, at the record's first byte (any alignment: by bytes)
@@ -240,7 +246,8 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
   const size_t nRec = J.rec_first ? (size_t)J.n_rec : 0;
   char* u = (char*)lra_ensure(ctx, 30, sz(nP, sizeof(lra_rec_piece)) + sz(nR + 1, 8) + sz(J.blob_bytes + 64, 1) + sz(nRec + 1, 8));
   // 31: per piece -- its length, its source, the lengths' prefix; rec_off; the text's bytes
-  char* w = (char*)lra_ensure(ctx, 31, sz(nP, 4) + sz(nP, 8) + 2 * sz(nP + 1, 8) + sz(nR + 1, 8) + 256);
+  const bool starts = nRec && J.d_rec_start;
+  char* w = (char*)lra_ensure(ctx, 31, sz(nP, 4) + sz(nP, 8) + 2 * sz(nP + 1, 8) + sz(nR + 1, 8) + 256 + (starts ? sz(nRec + 1, 8) : 0));
   if (!u || !w) return LRA_ERR_NOMEM;
   RcArgs A; memset(&A, 0, sizeof A);
   A.n_pieces = nP; A.n_reads = J.n_reads; A.n_aln = J.n_aln;
@@ -267,6 +274,7 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
   uint64_t* at = (uint64_t*)w; w += sz(nP + 1, 8);
   A.at = at;
   A.rec_off = (uint64_t*)w; w += sz(nR + 1, 8);
+  if (starts) A.rec_start = (uint64_t*)(w + 256);
   uint64_t total = 0;
   hipEvent_t e0, e1, e2;
   LRA_HIP_CHECK(ctx, hipEventCreate(&e0)); LRA_HIP_CHECK(ctx, hipEventCreate(&e1)); LRA_HIP_CHECK(ctx, hipEventCreate(&e2));
@@ -274,6 +282,7 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
   hipLaunchKernelGGL(rc_resolve, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, st, A);
   if (lra_exclusive_scan<uint32_t>(ctx, (long)nP, A.len, at)) return LRA_ERR_HIP;
   hipLaunchKernelGGL(rc_rec_off, dim3((unsigned)((nR + 1 + 255) / 256)), dim3(256), 0, st, A);
+  if (starts) hipLaunchKernelGGL(rc_rec_start, dim3((unsigned)((nRec + 1 + 255) / 256)), dim3(256), 0, st, A);
   lra_time_end(ctx);
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(&total, at + nP, 8, hipMemcpyDeviceToHost, st));
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(h_rec_off, A.rec_off, (nR + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -314,5 +323,6 @@ int lra_records_assemble(lra_ctx* ctx, const lra_rec_job& J, const char** text, 
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
   if (len) *len = total;
   if (text) *text = J.keep_on_device ? (const char*)A.out : (const char*)ctx->rec_pin;
+  if (J.d_rec_start) *J.d_rec_start = A.rec_start;
   return LRA_OK;
 }

@@ -557,6 +557,31 @@ class LowAccMapper:
         out = (raw, rec_off, member_off) if bgzf else (raw, rec_off)
         return out + (self.records_device_svsig(n),) if svsig else out
 
+    def records_device_bam_to_sorter(self, res: MapResult, args, sorter, passthrough=None, d_qual=None, d_qual_off=None, md=None, n_threads=0, svsig=False):
+        """lra_map_records_device_bam_to_sorter: records_device_bam's records, left on the device and handed to a bam.BamSorter; nothing is compressed or
+        copied to the host.  -> rec_off[n + 1] (bytes of the batch's stream), with svsig (rec_off, signatures).  bam.SorterFull when the batch does
+        not fit the sorter's budget (nothing was added): finish a run and call again."""
+        ctx = self.ctx
+        n = args["n"]
+        tags = None
+        if isinstance(passthrough, (list, tuple)):
+            tags = (C.c_char_p * n)(*[None if t is None else bytes(t) for t in passthrough])
+        elif passthrough is not None:
+            tags = (C.c_char_p * n)(*[bytes(passthrough)] * n)
+        flags = (PACK_MD if (self.print_md if md is None else md) else 0) | (PACK_SVSIG if svsig else 0)
+        if svsig:
+            set_svsig_len(ctx, self.svsig_len)
+        roff = C.POINTER(C.c_uint64)()
+        rc = ctx.lib.lra_map_records_device_bam_to_sorter(ctx.h, C.byref(res), C.byref(self.copts), args["names"], args["quals"], args["lens"], args["chroms"], tags,
+                                                          ptr(d_qual) if d_qual is not None else None, ptr(d_qual_off) if d_qual_off is not None else None, flags,
+                                                          int(n_threads), sorter.h, C.byref(roff))
+        if rc == -3:
+            from .bam import SorterFull
+            raise SorterFull(ctx.lib.lra_ctx_last_error(ctx.h).decode())
+        ctx.check(rc)
+        rec_off = np.array([roff[i] for i in range(n + 1)], np.uint64)
+        return (rec_off, self.records_device_svsig(n)) if svsig else rec_off
+
     def bam_header(self, text=None):
         """lra_bam_header: the head of a BAM file (magic, the header text, the reference table) for this mapper's chromosomes; text None: sam_header()."""
         return bam_header(self.sam_header() if text is None else bytes(text), self.chrom_names, self.chrom_pos)

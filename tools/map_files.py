@@ -1,6 +1,6 @@
 """Map read files against a genome FASTA and print the records as `lra align` would (needs the GPU):
 
-    python tools/map_files.py -ONT genome.fa reads.fq [more.fa ...] [-p s|p|pc|b|a] [-H] [--printMD] [-a] [--PrintNumAln N] [--refineBreakpoints] [-o out.sam] [--device-records] [--bgzf | --bam]
+    python tools/map_files.py -ONT genome.fa reads.fq [more.fa ...] [-p s|p|pc|b|a] [-H] [--printMD] [-a] [--PrintNumAln N] [--refineBreakpoints] [-o out.sam] [--device-records] [--bgzf | --bam [--sort [--sort-mem BYTES]]]
 
 The reads are parsed on the device (lra_reads_next_batch_device) and mapped from the reader's device arrays; --host-input parses them on the host
 (lra_reads_next_batch) and maps through lra_map_reads_host, the same records.  The index: genome.fa.mms / genome.fa.gli when both exist (lra_read_mms /
@@ -8,6 +8,10 @@ lra_read_gli), else built on the device with the preset's `lra index` parameters
 (lra_genome_read_device); --host-genome parses it on the host (lra_genome_read_host).  --bgzf writes the output BGZF-compressed: the header through
 lra_bgzf_deflate_host, every batch's records deflated on the device, the EOF member at the end.  --bam writes a BAM file (in read order, not indexed):
 lra_bam_header's bytes as BGZF members, every batch's BAM records encoded and deflated on the device (lra_map_records_device_bam), the EOF member.
+--bam --sort writes a coordinate-sorted BAM file and its index, out.bam and out.bam.bai (-o is required): the header text gets "@HD VN:1.6 SO:coordinate"
+in front, every batch's records go to a device sorter (lra_bam_sorter, at most --sort-mem bytes of device memory), which gives back the sorted members and
+the .bai bytes.  When the records do not fit one run, every run becomes a complete sorted, indexed file of its own -- out.run0000.bam, out.run0000.bam.bai,
+out.run0001.bam, ... -- and the tool says so on stderr; merging them is left to the user.  The SV signatures (-SV) stay per batch, in read order.
 Per-stage times go to stderr."""
 import argparse
 import os
@@ -74,7 +78,11 @@ def main():
                     help="write the output as BGZF: the records are deflated on the device (with --device-records before they leave it: lra_map_records_device_bgzf)")
     ap.add_argument("--bam", action="store_true",
                     help="write BAM: the records are encoded and deflated on the device (lra_map_records_device_bam); implies --device-records and -p s")
+    ap.add_argument("--sort", action="store_true", help="with --bam and -o: sort the records by coordinate on the device and write out.bam.bai beside the file")
+    ap.add_argument("--sort-mem", type=int, default=8 << 30, metavar="BYTES", help="device memory the sorter may use (default 8 GiB); more records make several sorted files")
     args = ap.parse_args()
+    if args.sort and not (args.bam and args.out):
+        ap.error("--sort sorts BAM output into a file and its index: it needs --bam and -o")
     if args.bam:
         if args.fmt != "s" or args.bgzf:
             ap.error("--bam writes SAM records (-p s) as BAM; it does not go with another format or with --bgzf")
@@ -120,17 +128,51 @@ def main():
             ov["svsigLen"] = int(args.sv[0])
         mapper = mapread.HighAccMapper(ctx, genome, ik, ipos, names, chrom_pos, preset=P.lower(), index_params=INDEX_PARAMS[P], gli=gli_params, **ov)
     t_index = time.perf_counter() - t0
-    out = open(args.out, "wb") if args.out else sys.stdout.buffer
+    out = None if args.sort else open(args.out, "wb") if args.out else sys.stdout.buffer
     if fmt == "s":
         cl = ["lra", "align", "-" + P, args.genome, *args.reads, "-p", args.fmt] + (["-H"] if args.hard_clip else []) + (["--printMD"] if args.printMD else []) + \
              (["-a"] if args.store_all else []) + ["--PrintNumAln", str(args.PrintNumAln)] + (["--refineBreakpoints"] if args.refineBreakpoints else []) + \
              (["-Flag", str(args.flag)] if args.flag else []) + (["--passthrough"] if args.passthrough else []) + (["-SV", *args.sv] if args.sv else [])       # (--device-records is no lra option: the same records)
         head = mapread.LowAccMapper.sam_header(mapper, b"lra_amd", " ".join(cl).encode())     # the lra command line: the same for either reader
+        if args.sort:
+            head = b"@HD\tVN:1.6\tSO:coordinate\n" + head
         if args.bam:
             head = mapper.bam_header(head)
         if args.bgzf or args.bam:
             head = b"".join(deflate.deflate_members([head[a:a + deflate.IN_MAX] for a in range(0, len(head), deflate.IN_MAX)])[0])
-        out.write(head)
+        if out:
+            out.write(head)
+    sorter = run_no = None
+    if args.sort:
+        from lra_amd.bam import BamSorter, SorterFull
+        from lra_amd._lib import LraError
+        sorter, run_no = BamSorter(ctx, args.sort_mem), 0
+        stem = args.out[:-4] if args.out.endswith(".bam") else args.out
+
+        def write_run(last):
+            """the sorter's records as a sorted file with its index: args.out when everything fitted one run, else stem.runNNNN.bam"""
+            nonlocal run_no
+            path = args.out if last and run_no == 0 else "%s.run%04d.bam" % (stem, run_no)
+            n_held = sorter.held()[0]
+            try:
+                sorter.finish(len(head), np.diff(np.asarray(chrom_pos, np.int64)))
+            except LraError as e:
+                raise SystemExit("map_files: --sort-mem %d is too small to sort and index the %d records held: %s" % (args.sort_mem, n_held, e))
+            with open(path, "wb") as f:
+                f.write(head)
+                for piece in sorter.pieces():
+                    f.write(piece)
+                f.write(bgzf.EOF_BLOCK)
+            try:
+                bai = sorter.index()
+                with open(path + ".bai", "wb") as f:
+                    f.write(bai)
+            except LraError as e:
+                sys.stderr.write("map_files: %s is not indexed: %s\n" % (path, e))
+            if path != args.out:
+                sys.stderr.write("map_files: the records do not fit one sorted run of %d bytes (--sort-mem): %s holds %d records, sorted and indexed on its own; "
+                                 "the runs are not merged\n" % (args.sort_mem, path, n_held))
+            run_no += 1
     # --device-records with device input: the qualities stay on the device from the reader to the record text; the host copies of bases and qualities
     # are switched off where nothing reads them (the formats the device builds; with them -SV is built on the device too, from the result's own arrays)
     dev_quals = args.device_records and not args.host_input
@@ -155,7 +197,20 @@ def main():
         t_map += time.perf_counter() - t
         t = time.perf_counter()
         tags = b["tags"] if args.passthrough else None
-        if args.bam:                                                        # BAM records, BGZF members when they leave the device; the signatures stay plain
+        if args.sort:                                                       # BAM records that stay on the device, in the sorter; the signatures stay plain, per batch
+            rargs = mapper.record_args(b["names"], b["seqs"], b["quals"], lens=b.get("read_len"))
+            while True:
+                try:
+                    r = mapper.records_device_bam_to_sorter(res, rargs, sorter, passthrough=tags, d_qual=b.get("d_qual"), d_qual_off=b.get("d_qual_off"), svsig=bool(sv_out))
+                    break
+                except SorterFull as e:
+                    if sorter.held()[0] == 0:
+                        raise SystemExit("map_files: --sort-mem %d does not hold one batch: %s" % (args.sort_mem, e))
+                    write_run(False)
+            texts = []
+            for sig in (r[1] if sv_out else []):
+                sv_out.write(sig)
+        elif args.bam:                                                      # BAM records, BGZF members when they leave the device; the signatures stay plain
             r = mapper.records_device_bam(res, mapper.record_args(b["names"], b["seqs"], b["quals"], lens=b.get("read_len")), passthrough=tags,
                                           d_qual=b.get("d_qual"), d_qual_off=b.get("d_qual_off"), svsig=bool(sv_out), bgzf=True)
             texts = [r[0]]
@@ -191,13 +246,16 @@ def main():
         if failed:
             break
     rf.close()
-    if args.bgzf or args.bam:
+    if sorter:
+        write_run(True)
+        sorter.close()
+    elif args.bgzf or args.bam:
         out.write(bgzf.EOF_BLOCK)
     if sv_out:
         sv_out.close()
-    if args.out:
+    if out and args.out:
         out.close()
-    else:
+    elif out:
         out.flush()
     sys.stderr.write("map_files: %d reads, %d bases, %d batches; genome + index %.2f s, %s %.2f s (%.1f Mbases/s), map %.2f s, records %.2f s\n"
                      % (n_reads, n_bases, n_batches, t_index, "read+parse (host)" if args.host_input else "read+parse (device)", t_read,
