@@ -9,7 +9,7 @@
 //
 // Pipeline on the GPU (all device-resident, CSR arrays; sizes come back to the host between
 // phases only to size the next buffers):
-//   ir_segment  one lane per alignment : the block-grouping state machine -> segment
+//   ir_segment  one wave per alignment : the block-grouping state machine -> segment
 //               descriptors + an ordered item list (pass-through block | segment)
 //   ir_band     one wave per segment   : the row-window construction, event by event (the
 //               k look-ahead / look-back updates of one event are done by k lanes; a
@@ -86,25 +86,49 @@ struct IRArgs {
 // The grouping loop of IndelRefine.h:79-211 / :761-767.  Only blocks[startBlock] and
 // blocks[endBlock] are ever modified by the reference, and only the "alt" remainder survives
 // an iteration, so one override record replaces the in-place edits.
-constexpr int SEG_LANES = 16;             // one lane per alignment walks its blocks: fewer lanes per wave, more waves
+// A wave per alignment, SEG_TILE blocks at a time, one per lane.  Whether the grouping loop moves on from a block depends on that block and the next one alone: the gap
+// behind it and its length (the "alt" remainder the loop leaves in blocks[endBlock] keeps the block's end, so no gap ever changes).  Every lane decides that for its
+// own block and two ballots hold the answers of the round.  The loop then steps from segment to segment, not from block to block: a segment ends at the first block
+// behind its start that it does not move on from (one count-trailing-zeros), and the two blocks a segment reads, its first and its last, come out of the lanes'
+// registers.  One irregularity of the reference is kept: a segment that reaches the block before the last moves on to the last whatever the gap, because the gaps are
+// refreshed only while endBlock + 1 < n - 1 (IndelRefine.h:158) -- the values still held are those of the gap before, which has just passed the test.
+// The copy into ab[] is wave-wide, with the two optional end blocks placed by lane 0; items are collected in LDS and written 64 at a time.
+constexpr int SEG_TILE = 64;
 template <bool EMIT>
 __global__ void __launch_bounds__(64) ir_segment(IRArgs A) {
-  if (threadIdx.x >= SEG_LANES) return;
-  const int a = blockIdx.x * SEG_LANES + threadIdx.x;
-  if (a >= A.n_aln) return;
-  const long nIn = (long)(A.block_off[a + 1] - A.block_off[a]);
+  __shared__ int32_t itemBuf[4 * 64];     // kind and the three data words of the items not written yet
+  const int lane = threadIdx.x;
+  const int a = blockIdx.x;
+  const int nIn = (int)(A.block_off[a + 1] - A.block_off[a]);          // (block indices are ints throughout the pipeline: s_b0, s_b1)
   const int32_t* bin = A.blocks_in + 3 * A.block_off[a];
   int32_t* ab = A.ab + 3 * (A.block_off[a] + 2 * (uint64_t)a);
   const int k = A.k, maxGap = k - 1;
   uint32_t nseg = 0, nitem = 0;
   const uint64_t so = EMIT ? A.seg_off[a] : 0, io = EMIT ? A.item_off[a] : 0;
-  auto pass = [&](long q, long t, long l) {
-    if (EMIT) { A.i_kind[io + nitem] = 0; int32_t* d = A.i_data + 3 * (io + nitem); d[0] = (int)q; d[1] = (int)t; d[2] = (int)l; }
+  auto flush = [&](uint32_t upto) {                                     // items [upto - count, upto), count = 1..64: the buffer's content
+    wave_sync_lds();
+    const uint32_t count = ((upto - 1) & 63) + 1, first = upto - count;
+    if ((uint32_t)lane < count) {
+      const int kind = itemBuf[4 * lane];
+      int32_t* d = A.i_data + 3 * (io + first + lane);
+      A.i_kind[io + first + lane] = kind; d[0] = itemBuf[4 * lane + 1];
+      if (kind == 0) { d[1] = itemBuf[4 * lane + 2]; d[2] = itemBuf[4 * lane + 3]; }   // (a segment item has one word)
+    }
+    wave_sync_lds();
+  };
+  auto item = [&](int kind, int d0, int d1, int d2) {
+    if (EMIT) {
+      const uint32_t slot = nitem & 63;
+      if (lane == 0) { itemBuf[4 * slot] = kind; itemBuf[4 * slot + 1] = d0; itemBuf[4 * slot + 2] = d1; itemBuf[4 * slot + 3] = d2; }
+      if (slot == 63) flush(nitem + 1);
+    }
     nitem++;
   };
+  auto pass = [&](long q, long t, long l) { item(0, (int)q, (int)t, (int)l); };
   if (nIn <= 1) {                                                       // :79
-    for (long i = 0; i < nIn; i++) pass(bin[3 * i], bin[3 * i + 1], bin[3 * i + 2]);
-    if (!EMIT) { A.a_nseg[a] = 0; A.a_nitem[a] = nitem; A.a_status[a] = 0; }
+    for (int i = 0; i < nIn; i++) pass(bin[3 * i], bin[3 * i + 1], bin[3 * i + 2]);
+    if (EMIT && (nitem & 63)) flush(nitem);
+    if (!EMIT && lane == 0) { A.a_nseg[a] = 0; A.a_nitem[a] = nitem; A.a_status[a] = 0; }
     return;
   }
   int addStart = 0, addEnd = 0;
@@ -113,43 +137,65 @@ __global__ void __launch_bounds__(64) ir_segment(IRArgs A) {
     long qS0 = bin[0], tS0 = bin[1];
     int minStart = (int)min(qS0, tS0);
     if (minStart < 40) { sQ = qS0 - minStart; sT = tS0 - minStart; sL = minStart; addStart = 1; }
-    long qAE = (long)bin[3 * (nIn - 1)] + bin[3 * (nIn - 1) + 2], tAE = (long)bin[3 * (nIn - 1) + 1] + bin[3 * (nIn - 1) + 2];
+    const int32_t* lb = bin + 3 * (long)(nIn - 1);
+    long qAE = (long)lb[0] + lb[2], tAE = (long)lb[1] + lb[2];
     int minEnd = (int)min((long)A.q_len[a] - qAE, (long)A.t_len[a] - tAE);
     if (minEnd < 40) { eQ = qAE; eT = tAE; eL = minEnd; addEnd = 1; }
   }
-  const long nB = nIn + addStart + addEnd;
-  auto getRaw = [&](long i, long& q, long& t, long& l) {
+  const int nB = nIn + addStart + addEnd;
+  auto getRaw = [&](int i, long& q, long& t, long& l) {
     if (addStart && i == 0) { q = sQ; t = sT; l = sL; }
     else if (addEnd && i == nB - 1) { q = eQ; t = eT; l = eL; }
-    else { const int32_t* p = bin + 3 * (i - addStart); q = p[0]; t = p[1]; l = p[2]; }
+    else { const int32_t* p = bin + 3 * (long)(i - addStart); q = p[0]; t = p[1]; l = p[2]; }
   };
-  if (EMIT)
-    for (long i = 0; i < nB; i++) { long q, t, l; getRaw(i, q, t, l); ab[3 * i] = (int)q; ab[3 * i + 1] = (int)t; ab[3 * i + 2] = (int)l; }
-  long ovIdx = -1, ovQ = 0, ovT = 0, ovL = 0;                           // surviving "alt" block
-  auto get = [&](long i, long& q, long& t, long& l) {
-    if (i == ovIdx) { q = ovQ; t = ovT; l = ovL; } else getRaw(i, q, t, l);
-  };
-  long startBlock = 0, endBlock = 0;
-  while (endBlock < nB) {                                               // :132
-    long q0, t0, l0;
-    get(startBlock, q0, t0, l0);
-    long qStart = q0, tStart = t0;
-    long qPos = q0 + l0, tPos = t0 + l0;
-    int tGap = 0, qGap = 0;
-    long nq, nt, nl;
-    if (endBlock < nB - 1) { get(endBlock + 1, nq, nt, nl); tGap = (int)(nt - tPos); qGap = (int)(nq - qPos); }
-    long el = l0, eq = q0, et = t0;                                     // blocks[endBlock]
-    while (endBlock < nB - 1 && qGap < maxGap && tGap < maxGap && (startBlock == endBlock || el < 100)) {   // :148-162
-      endBlock++;
-      get(endBlock, eq, et, el);
-      qPos = eq + el; tPos = et + el;
-      if (endBlock + 1 < nB - 1) { get(endBlock + 1, nq, nt, nl); tGap = (int)(nt - tPos); qGap = (int)(nq - qPos); }
+  if (EMIT) {
+    for (long x = lane; x < 3 * (long)nIn; x += 64) ab[3 * addStart + x] = bin[x];
+    if (lane == 0 && addStart) { ab[0] = (int)sQ; ab[1] = (int)sT; ab[2] = (int)sL; }
+    if (lane == 0 && addEnd) { int32_t* d = ab + 3 * (long)(nB - 1); d[0] = (int)eQ; d[1] = (int)eT; d[2] = (int)eL; }
+  }
+  int ovIdx = -1; long ovQ = 0, ovT = 0, ovL = 0;                       // surviving "alt" block
+  int startBlock = 0, from = 0;
+  bool open = false;                                                    // a segment has left startBlock and looks for its end from block `from` on
+  long q0 = 0, t0 = 0, l0 = 0;                                          // blocks[startBlock]
+  for (int base = 0; base < nB; base += SEG_TILE) {
+    const int i = base + lane;
+    long bq = 0, bt = 0, bl = 0;
+    bool leaveFirst = false, moveOn = false;                            // the loop's test (:148) at endBlock == i, as the segment's first block and as a later one
+    if (i < nB) {
+      getRaw(i, bq, bt, bl);
+      if (i < nB - 1) {
+        long nq, nt, nl;
+        getRaw(i + 1, nq, nt, nl);
+        const int tGap = (int)(nt - (bt + bl)), qGap = (int)(nq - (bq + bl));
+        leaveFirst = qGap < maxGap && tGap < maxGap;
+        moveOn = (i == nB - 2 || leaveFirst) && bl < 100;
+      }
     }
-    bool usedAlt = false;
-    long altQ = 0, altT = 0, altL = 0;
-    if (endBlock == startBlock) {
-      pass(q0, t0, l0);                                                 // :170-173
-    } else {
+    const uint64_t mFirst = __ballot(leaveFirst), mOn = __ballot(moveOn);
+    const int vq = (int)bq, vt = (int)bt, vl = (int)bl;                 // (all but the two added blocks are ints)
+    auto blockAt = [&](int b, long& q, long& t, long& l) {              // a block of this round, out of its lane
+      if (addStart && b == 0) { q = sQ; t = sT; l = sL; }
+      else if (addEnd && b == nB - 1) { q = eQ; t = eT; l = eL; }
+      else { q = __builtin_amdgcn_readlane(vq, b - base); t = __builtin_amdgcn_readlane(vt, b - base); l = __builtin_amdgcn_readlane(vl, b - base); }
+    };
+    const int lim = min(nB, base + SEG_TILE);
+    while (true) {
+      if (!open) {
+        if (startBlock >= lim) break;
+        if (startBlock == ovIdx) { q0 = ovQ; t0 = ovT; l0 = ovL; } else blockAt(startBlock, q0, t0, l0);
+        if (!((mFirst >> (startBlock - base)) & 1)) { pass(q0, t0, l0); startBlock++; continue; }   // :170-173
+        open = true; from = startBlock + 1;
+      }
+      const int sh = from - base;                                       // 0 .. 64
+      const uint64_t stop = sh >= 64 ? 0 : ((~mOn >> sh) << sh);        // (the last block never moves on: a stop bit at or before it)
+      if (stop == 0) { from = base + SEG_TILE; break; }
+      const int endBlock = base + (int)__builtin_ctzll(stop);
+      long eq, et, el;                                                  // blocks[endBlock]
+      blockAt(endBlock, eq, et, el);
+      long qStart = q0, tStart = t0;
+      long tPos = et + el;
+      bool usedAlt = false;
+      long altQ = 0, altT = 0, altL = 0;
       long fq = q0, ft = t0, fl = l0;                                   // first block as the segment sees it
       if (l0 > maxGap) {                                                // :178-196
         long advanced = l0 - maxGap;
@@ -162,30 +208,31 @@ __global__ void __launch_bounds__(64) ir_segment(IRArgs A) {
         usedAlt = true;
         altQ = eq + maxGap; altT = et + maxGap; altL = el - maxGap;
         ll = maxGap;
-        qPos = eq + maxGap; tPos = et + maxGap;
+        tPos = et + maxGap;
       }
       const long qEnd = eq + ll, tEnd = et + ll;
       const long tLen = tPos - tStart;
       const long tSeqLen = tEnd - tStart, qSeqLen = qEnd - qStart;
       const bool aog = (tSeqLen < k || qSeqLen < k);                    // :344
-      if (EMIT) {
+      if (EMIT && lane == 0) {
         const uint64_t s = so + nseg;
         A.s_aln[s] = a; A.s_kind[s] = aog ? 1 : 0;
         A.s_qStart[s] = (int)qStart; A.s_tStart[s] = (int)tStart; A.s_qEnd[s] = (int)qEnd; A.s_tEnd[s] = (int)tEnd;
-        A.s_b0[s] = (int)startBlock; A.s_b1[s] = (int)endBlock;
+        A.s_b0[s] = startBlock; A.s_b1[s] = endBlock;
         A.s_first[3 * s] = (int)fq; A.s_first[3 * s + 1] = (int)ft; A.s_first[3 * s + 2] = (int)fl;
         A.s_lastLen[s] = (int)ll;
         A.s_rows[s] = aog ? 0 : (uint64_t)(tLen > 0 ? tLen : 0);
         A.s_isAog[s] = aog ? 1u : 0u;
-        A.i_kind[io + nitem] = 1; A.i_data[3 * (io + nitem)] = (int)(nseg);   // segment index local to the alignment
       }
-      nitem++; nseg++;
+      item(1, (int)nseg, 0, 0);                                          // segment index local to the alignment
+      nseg++;
+      if (!usedAlt) startBlock = endBlock + 1;                          // :761-766
+      else { ovIdx = endBlock; ovQ = altQ; ovT = altT; ovL = altL; startBlock = endBlock; }
+      open = false;
     }
-    if (!usedAlt) endBlock++;                                           // :761-766
-    else { ovIdx = endBlock; ovQ = altQ; ovT = altT; ovL = altL; }
-    startBlock = endBlock;
   }
-  if (!EMIT) { A.a_nseg[a] = nseg; A.a_nitem[a] = nitem; A.a_status[a] = 0; }
+  if (EMIT && (nitem & 63)) flush(nitem);
+  if (!EMIT && lane == 0) { A.a_nseg[a] = nseg; A.a_nitem[a] = nitem; A.a_status[a] = 0; }
 }
 
 // ---------------------------------------------------------------------------------- band
@@ -1142,7 +1189,7 @@ extern "C" int lra_indel_refine_batch(lra_ctx* ctx, int n_aln, const int32_t* d_
   uint64_t* seg_off = ap.get<uint64_t>(nA + 1); uint64_t* item_off = ap.get<uint64_t>(nA + 1); uint64_t* out_block_off = ap.get<uint64_t>(nA + 1);
   if (!out_block_off) return lra_set_err(ctx, LRA_ERR_NOMEM, "arena accounting");
   A.seg_off = seg_off; A.item_off = item_off;
-  const int nbA = (n_aln + SEG_LANES - 1) / SEG_LANES;
+  const int nbA = n_aln;                                                 // a wave per alignment
   lra_time_begin(ctx, "ir_segment");
   hipLaunchKernelGGL(ir_segment<false>, dim3(nbA), dim3(64), 0, st, A);
   lra_time_end(ctx);

@@ -18,6 +18,7 @@ constexpr int LV = 18;                    // levels per decomposition (distinct 
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr int MAXALN = 16;
 constexpr int PEN_TAB_WG = 4096, PEN_TAB_WAVE = 2048;   // entries of the gap-cost table (k_pen_table) the workgroup / the wave kernel keeps in LDS
+constexpr int TRACE_CAP = 2560;          // sdp_trace walks reads of up to this many anchors in LDS (16-bit fpred, chain, value order + a `used` bit: 15680 bytes a wave)
 
 struct PwlTab { long long stops[25]; float slope[25], inter[25]; int c1, c2; };
 
