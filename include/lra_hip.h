@@ -225,6 +225,9 @@ int lra_create_rc_batch(lra_ctx* ctx, int n_reads, const char* d_seq, const uint
  * GenomeTuple::operator<, TupleOps.h:76) would, including the order it leaves equal keys in.
  * Asynchronous.                                                                               */
 int lra_sort_minimizers_batch(lra_ctx* ctx, int n_lists, const uint64_t* d_off, uint64_t* d_key, uint32_t* d_pos);
+/* The same sort of ONE list of n (key,pos) tuples in HOST memory, in place, on the calling thread (additive to ABI 9; no context, no device): the host
+ * instantiation of the library's restatement of std::sort, whose device instantiation takes the lists beyond 2^26 tuples.  Synchronous.             */
+int lra_sort_minimizers_host(uint64_t n, uint64_t* h_key, uint32_t* h_pos);
 
 /* The path's other sorts -- DiagonalSort / AntiDiagonalSort / CartesianSort of a read's (a cluster's, a gap's) matches (Sorting.h:50-150; called from
  * Clustering.h:1840 CleanMatches, ChainRefine.h:767 MergeChain's LinearExtend, LocalRefineAlignment.h:364), the sparse DP's point orders where no two

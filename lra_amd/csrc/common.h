@@ -50,8 +50,6 @@ struct lra_ctx {
   size_t gbytes[192] = {};
   // kernel timing
   bool sdp_inner = false;                    // local_refine.hip: its small inner sparse DP is timed under "sdp_inner_*"
-  bool sort_short = false;                   // the exact sort: a launch of its own for the short lists (set by the sparse DP around its sorts: hundreds of tuples per list)
-  const char* sort_tag = "sort"; const char* sort_fb_tag = "sort_fallback";   // timing names of the exact-sort kernels (sdp.hip's Retag renames them for the length of a call)
   bool timing = false;
   std::vector<lra_time_rec> recs;
   std::vector<hipEvent_t> free_events;
@@ -74,6 +72,9 @@ void lra_side_join(lra_ctx* ctx, int i = 0);
 // segsort.hip: rocprim::segmented_radix_sort_pairs' interface for (uint64 key, uint32 value) pairs; segments of 257 .. 8192 pairs are sorted by one workgroup in LDS
 hipError_t lra_segsort_pairs(lra_ctx* ctx, void* temp, size_t& temp_bytes, const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout, unsigned int total,
                              unsigned int nseg, const uint64_t* b, const uint64_t* e, int begin_bit, int end_bit, hipStream_t st);
+// the same on the context's stream with the temporary storage in scratch slot 2 -> LRA_* code
+int lra_segsort_pairs_scratch(lra_ctx* ctx, const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout, uint64_t total, uint64_t nseg, const uint64_t* b,
+                              const uint64_t* e, int begin_bit, int end_bit);
 // timing records (lra_ctx_timing_get); stream = nullptr: the context's stream
 void lra_time_begin(lra_ctx* ctx, const char* name, hipStream_t stream = nullptr);
 void lra_time_end(lra_ctx* ctx, hipStream_t stream = nullptr);
@@ -95,9 +96,13 @@ void* lra_pinned(lra_ctx* ctx, size_t bytes);
 // growable buffer `idx` of at least `bytes` (contents NOT preserved on growth)
 void* lra_ensure(lra_ctx* ctx, int idx, size_t bytes);
 
-// seed.hip: std::sort-identical segmented sort of (key, payload) lists whose keys rarely repeat inside a list
+// exact_sort.hip: the std::sort-identical sort of (key, payload) lists (what lra_sort_minimizers_batch does), and the same for lists whose keys rarely repeat inside
+// a list.  The options: the names its kernels' time is recorded under, and whether the short lists (hundreds of tuples: the sparse DP's) get a launch of their own.
+struct lra_sort_opts { const char* tag = "sort"; const char* fb_tag = "sort_fallback"; bool short_lists = false; };
+int lra_sort_exact_batch(lra_ctx* ctx, int n_lists, const uint64_t* d_off, uint64_t* d_key, uint32_t* d_pos, const lra_sort_opts& o = lra_sort_opts(),
+                         const int* only = nullptr);   // only != null: the lists with only[i] != 0
 int lra_sort_mostly_unique_batch(lra_ctx* ctx, int n_lists, const uint64_t* d_off, uint64_t total, uint64_t* d_key, uint32_t* d_pos,
-                                 uint64_t* tmp_key, uint32_t* tmp_pos, int end_bit);
+                                 uint64_t* tmp_key, uint32_t* tmp_pos, int end_bit, const lra_sort_opts& o = lra_sort_opts());
 
 // cluster.hip: LinearExtend (pair version, LinearExtend.h:658) + DecideCoordinates box on caller-supplied clusters of diagonal-sorted matches
 int lra_launch_linear_extend(lra_ctx* ctx, uint64_t n_clusters, int K, const uint64_t* c_start, const uint64_t* c_end, const int* c_strand, const int* c_chrom,

@@ -14,6 +14,7 @@
 #include "common.h"
 #include <vector>
 #include "scan.h"
+#include "std_sort.h"
 #include <algorithm>
 #include <hipcub/hipcub.hpp>
 
@@ -177,77 +178,8 @@ __global__ void __launch_bounds__(64) local_sketch(uint64_t n_win, const unsigne
 #undef LS_DONE
 }
 
-// ---- libstdc++ std::sort on a list of LocalTuple words (comparison on t only), one lane per list
-__device__ __forceinline__ bool wlt(uint32_t a, uint32_t b) { return T_(a) < T_(b); }
-
-__device__ void w_adjust_heap(uint32_t* v, long first, long hole, long len, uint32_t val) {
-  const long top = hole;
-  long child = hole;
-  while (child < (len - 1) / 2) {
-    child = 2 * (child + 1);
-    if (wlt(v[first + child], v[first + child - 1])) child--;
-    v[first + hole] = v[first + child];
-    hole = child;
-  }
-  if ((len & 1) == 0 && child == (len - 2) / 2) {
-    child = 2 * (child + 1);
-    v[first + hole] = v[first + child - 1];
-    hole = child - 1;
-  }
-  long parent = (hole - 1) / 2;
-  while (hole > top && wlt(v[first + parent], val)) { v[first + hole] = v[first + parent]; hole = parent; parent = (hole - 1) / 2; }
-  v[first + hole] = val;
-}
-
-__device__ void w_std_sort(uint32_t* v, long n) {
-  if (n < 2) return;
-  long stF[40], stL[40]; int stD[40];
-  int sp = 0;
-  stF[0] = 0; stL[0] = n; stD[0] = 2 * (63 - __clzll((unsigned long long)n)); sp = 1;
-  while (sp > 0) {
-    --sp;
-    long first = stF[sp], last = stL[sp]; int depth = stD[sp];
-    while (last - first > 16) {
-      if (depth == 0) {                                                  // __partial_sort(first,last,last)
-        long len = last - first;
-        for (long parent = (len - 2) / 2;; parent--) { w_adjust_heap(v, first, parent, len, v[first + parent]); if (parent == 0) break; }
-        long l2 = last;
-        while (l2 - first > 1) { --l2; uint32_t val = v[l2]; v[l2] = v[first]; w_adjust_heap(v, first, 0, l2 - first, val); }
-        break;
-      }
-      --depth;
-      const long a = first + 1, b = first + (last - first) / 2, c = last - 1;
-      auto sw = [&](long x, long y) { uint32_t t = v[x]; v[x] = v[y]; v[y] = t; };
-      if (wlt(v[a], v[b])) { if (wlt(v[b], v[c])) sw(first, b); else if (wlt(v[a], v[c])) sw(first, c); else sw(first, a); }
-      else if (wlt(v[a], v[c])) sw(first, a);
-      else if (wlt(v[b], v[c])) sw(first, c);
-      else sw(first, b);
-      long f = first + 1, l = last;
-      const uint32_t pv = v[first];
-      while (true) {
-        while (wlt(v[f], pv)) ++f;
-        --l;
-        while (wlt(pv, v[l])) --l;
-        if (!(f < l)) break;
-        sw(f, l);
-        ++f;
-      }
-      if (sp < 40) { stF[sp] = f; stL[sp] = last; stD[sp] = depth; sp++; }
-      last = f;
-    }
-  }
-  auto ins = [&](long first, long last) {                                // __insertion_sort
-    for (long i = first + 1; i < last; ++i) {
-      uint32_t val = v[i];
-      if (wlt(val, v[first])) { for (long x = i; x > first; --x) v[x] = v[x - 1]; v[first] = val; }
-      else { long j = i; while (wlt(val, v[j - 1])) { v[j] = v[j - 1]; --j; } v[j] = val; }
-    }
-  };
-  if (n > 16) {
-    ins(0, 16);
-    for (long i = 16; i < n; ++i) { uint32_t val = v[i]; long j = i; while (wlt(val, v[j - 1])) { v[j] = v[j - 1]; --j; } v[j] = val; }
-  } else ins(0, n);
-}
+// ---- libstdc++ std::sort (std_sort.h) on a list of LocalTuple words: the comparison is on t only
+struct WLess { __device__ __forceinline__ bool operator()(uint32_t a, uint32_t b) const { return T_(a) < T_(b); } };
 
 // sort + RemoveFrequent in place; counts[wi] = surviving tuples.  Lists of <= LCAP tuples are sorted in a
 // lane-private LDS row (copied in and out with coalesced accesses); longer ones in HBM.
@@ -287,7 +219,7 @@ __global__ void __launch_bounds__(STAGE_NT) local_sort_filter(uint64_t n_win_all
       const bool staged = myFits;
       // (once per address space, so that the list in LDS is read with ds_read and the one in HBM with global_load instead of flat_load through an either-or pointer)
       auto work = [&](uint32_t* v) __attribute__((always_inline)) {
-        w_std_sort(v, n);                                                // MMIndex.h:219
+        lra_std_sort::std_sort<40>(v, n, WLess());                       // MMIndex.h:219
         long x = 0;                                                      // RemoveFrequent MMIndex.h:69-84
         while (x < n) {
           long ne = x;
@@ -392,7 +324,7 @@ __global__ void __launch_bounds__(NT) local_sort_radix(uint64_t n_win, uint64_t 
 }
 
 // ---- the exact sort of the long lists with a repeated key, a WAVE per list (local_sort_filter walks such a list with one lane: 52-62 ms per batch at windows of 2048
-// bases, a third of the windows).  libstdc++'s introsort is data-parallel as it stands (seed.hip, sort_wg_kernel): the segments the loop recurses into are disjoint,
+// bases, a third of the windows).  libstdc++'s introsort is data-parallel as it stands (exact_sort.hip, sort_wg_kernel): the segments the loop recurses into are disjoint,
 // and the unguarded Hoare partition of [first + 1, last) around *first is a closed form -- with a_0 < a_1 < .. the positions holding x >= pivot and b_0 > b_1 > .. those
 // holding x <= pivot it swaps (a_i, b_i) for i < m = #{i: a_i < b_i} and returns cut = min(a_m, b_(m-1)); the final insertion sort equals a stable insertion sort of
 // every block between two cuts.  Here the list lies in the wave's LDS; a segment is taken from a stack, its stoppers ranked by ballots into two position lists, m counted
@@ -430,12 +362,7 @@ __global__ void __launch_bounds__(64) local_sort_exact_wave(uint64_t stride, uin
       const int first = stF[sp], last = stL[sp]; int depth = stD[sp];
       wave_sync_lds();                                                     // (everyone has read the entry before it is overwritten)
       if (depth == 0) {                                                    // __partial_sort(first, last, last): heap sort, one lane
-        if (lane == 0) {
-          const long len = last - first;
-          for (long parent = (len - 2) / 2;; parent--) { w_adjust_heap(v, first, parent, len, v[first + parent]); if (parent == 0) break; }
-          long l2 = last;
-          while (l2 - first > 1) { --l2; const uint32_t val = v[l2]; v[l2] = v[first]; w_adjust_heap(v, first, 0, l2 - first, val); }
-        }
+        if (lane == 0) lra_std_sort::heap_sort(lra_std_sort::Ptr<uint32_t>{v}, first, last, WLess());
         wave_sync_lds();
         continue;
       }
@@ -494,12 +421,7 @@ __global__ void __launch_bounds__(64) local_sort_exact_wave(uint64_t stride, uin
       if ((sbits[p >> 5] >> (p & 31)) & 1u) {
         int q = p + 1;
         while (q < n && !((sbits[q >> 5] >> (q & 31)) & 1u)) q++;
-        for (int i = p + 1; i < q; ++i) {
-          const uint32_t val = v[i];
-          int j = i;
-          while (j > p && T_(val) < T_(v[j - 1])) { v[j] = v[j - 1]; --j; }
-          v[j] = val;
-        }
+        lra_std_sort::insertion_sort(lra_std_sort::Ptr<uint32_t>{v}, p, q, WLess());
       }
     }
     wave_sync_lds();

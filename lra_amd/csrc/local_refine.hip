@@ -610,12 +610,7 @@ static int local_refine_impl(lra_ctx* ctx, uint64_t n_jobs, const uint64_t* d_jo
     const unsigned gw = (unsigned)std::min<uint64_t>(nJ, (uint64_t)ctx->num_cu * 32);
     hipLaunchKernelGGL(lr_job_pairs, dim3(gw), dim3(64), 0, st, a, key, val);
     if (nJP) {
-      size_t temp_bytes = 0;
-      (void)lra_segsort_pairs(ctx, nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, (unsigned int)nJP, (unsigned int)nJ, nullptr, nullptr, 0, 64, st);
-      void* temp = lra_scratch(ctx, 2, temp_bytes + 256);
-      if (!temp) return LRA_ERR_NOMEM;
-      hipError_t e = lra_segsort_pairs(ctx, temp, temp_bytes, key, key2, val, val2, (unsigned int)nJP, (unsigned int)nJ, a.cStart, a.cEnd, 0, 64, st);
-      if (e != hipSuccess) return lra_set_err(ctx, LRA_ERR_HIP, "segmented sort: %s", hipGetErrorString(e));
+      { int rc = lra_segsort_pairs_scratch(ctx, key, key2, val, val2, nJP, nJ, a.cStart, a.cEnd, 0, 64); if (rc) return rc; }
       hipLaunchKernelGGL(lr_sorted, grid(nJP), dim3(256), 0, st, nJP, (const uint32_t*)val2, (const uint32_t*)a.jq, (const uint32_t*)a.jt, (const uint64_t*)key2, sq, stt);
       hipLaunchKernelGGL(lr_add_coff, dim3(gw), dim3(64), 0, st, a, stt);
     }

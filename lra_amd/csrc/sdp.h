@@ -143,6 +143,7 @@ struct Call {                                  // one call of sdp_run
   const int32_t* d_len; const uint64_t* d_read_off; const float* d_rate; const uint32_t* d_qe; const uint32_t* d_te; const int32_t* d_num_anchors;
   bool boxes;                                  // box mode (d_qe != null): clusters are the fragments; d_c_start / d_c_count are null, d_q/d_t/d_qe/d_te/d_len(=Val)/d_c_strand are per box
   PwlTab pw; short* d_penTab; int penN;        // InitPWL; -w as a table for small distances (slot 190), penN = 0: none
+  lra_sort_opts sort;                          // the exact sorts of the call (point orders, value order): timed as "sdp_sort" / "sdp_inner_sort", short lists launched apart
   std::vector<uint64_t> h_off, h_frag, h_pt;   // cluster / fragment / point offsets of the reads
   uint64_t NC, NF, NP; size_t nslot;           // clusters, fragments, points; n_reads * NumAln
   // slot 7: clusters and reads

@@ -13,7 +13,7 @@
 // literally; what is re-designed is how it is laid out and scheduled:
 //
 //  * points, sorts: one thread per cluster writes the points; the two std::sorts are the library's libstdc++-exact
-//    workgroup sort (seed.hip) on packed 63-bit keys (q,t,ind / t,q,ind) -- the permutation of tied points is part
+//    workgroup sort (exact_sort.hip) on packed 63-bit keys (q,t,ind / t,q,ind) -- the permutation of tied points is part
 //    of the result because it fixes the processing order;
 //  * decompositions: the sub-problem numbering is internal to the reference (prev_sub is only an index), so the trees
 //    are built level by level instead of depth first: per family the points are kept sorted by diagonal and stably
@@ -174,30 +174,22 @@ void make_points(const Call& c) {
   lra_time_end(ctx);
 }
 
-// The exact sorts' timing names and their launch for short lists, for as long as the call lasts (the value order's sort in the trace included)
-struct Retag { lra_ctx* c; Retag(lra_ctx* x) : c(x) { c->sort_tag = c->sdp_inner ? "sdp_inner_sort" : "sdp_sort"; c->sort_fb_tag = c->sdp_inner ? "sdp_inner_sort_fallback" : "sdp_sort_fallback"; c->sort_short = true; } ~Retag() { c->sort_tag = "sort"; c->sort_fb_tag = "sort_fallback"; c->sort_short = false; } };
 // The three point orders: by row (H1), by column (H2), by diagonal per point class
 int sort_points(const Call& c) {
   lra_ctx* ctx = c.ctx; hipStream_t st = c.st; const int n_reads = c.n_reads; const uint64_t NP = c.NP;
   // the two point orders: (q, t, ind) / (t, q, ind) keys repeat only where two anchors share a corner, so the radix path takes nearly all lists
-  SDP_TRY(lra_sort_mostly_unique_batch(ctx, n_reads, c.ptOff, NP, c.key1, c.pay1, c.key3, c.pay3, 64));   // sort(H1, SortByRowOp)  :2171
+  SDP_TRY(lra_sort_mostly_unique_batch(ctx, n_reads, c.ptOff, NP, c.key1, c.pay1, c.key3, c.pay3, 64, c.sort));   // sort(H1, SortByRowOp)  :2171
   lra_time_begin(ctx, ctx->sdp_inner ? "sdp_inner_points" : "sdp_points");
   // after the row sort: the point attributes in H1 order, the column-sort and diagonal-sort keys
   launch_gather(st, NP, c.ptRead, c.ptOff, c.pay1, c.iq, c.it, c.ifl, c.ifr, c.hq, c.ht, c.hfl, c.hfr, c.key2, c.pay2, c.key3, c.pay3);
   lra_time_end(ctx);
-  SDP_TRY(lra_sort_mostly_unique_batch(ctx, n_reads, c.ptOff, NP, c.key2, c.pay2, c.key1, c.pay1, 63));   // sort(H2, SortByColOp)  :2174
+  SDP_TRY(lra_sort_mostly_unique_batch(ctx, n_reads, c.ptOff, NP, c.key2, c.pay2, c.key1, c.pay1, 63, c.sort));   // sort(H2, SortByColOp)  :2174
   // diagonal order per point class: any sorted order serves (ties are the same diagonal), so this one is a segmented radix sort -- the
   // exact introsort degenerates on the long runs of equal diagonals.  Sorted into the (now free) key1 / pay1 buffers.
-  {
-    size_t temp_bytes = 0;
-    (void)lra_segsort_pairs(ctx, nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, (unsigned int)NP, (unsigned int)n_reads, nullptr, nullptr, 0, 42, st);
-    void* temp = lra_scratch(ctx, 2, temp_bytes + 256);
-    if (!temp) return LRA_ERR_NOMEM;
-    lra_time_begin(ctx, ctx->sdp_inner ? "sdp_inner_sort" : "sdp_sort");
-    hipError_t e = lra_segsort_pairs(ctx, temp, temp_bytes, c.key3, c.key1, c.pay3, c.pay1, (unsigned int)NP, (unsigned int)n_reads, c.ptOff, c.ptOff + 1, 0, 42, st);
-    lra_time_end(ctx);
-    if (e != hipSuccess) return lra_set_err(ctx, LRA_ERR_HIP, "segmented sort: %s", hipGetErrorString(e));
-  }
+  lra_time_begin(ctx, c.sort.tag);
+  const int rc = lra_segsort_pairs_scratch(ctx, c.key3, c.key1, c.pay3, c.pay1, NP, (uint64_t)n_reads, c.ptOff, c.ptOff + 1, 0, 42);
+  lra_time_end(ctx);
+  if (rc) return rc;
   LRA_HIP_CHECK(ctx, hipGetLastError());
   return LRA_OK;
 }
@@ -471,7 +463,7 @@ int trace_chains(const Call& c, const Chunk& k) {
   if (needOrder) launch_valkeys(st, cf0, cfn, c.fval, c.fragRead, c.fragOff, c.okey, c.opay);
   launch_pred(st, cf0, cfn, r0, c.fragRead, c.fprevNode, c.fprevInd, c.status, k.ra, c.spare);
   lra_time_end(ctx);
-  if (needOrder) SDP_TRY(lra_sort_minimizers_batch(ctx, nr, c.fragOff + r0, c.okey, c.opay));   // Fragment_valueOrder::Sort (Fragment_Info.h:88)
+  if (needOrder) SDP_TRY(lra_sort_exact_batch(ctx, nr, c.fragOff + r0, c.okey, c.opay, c.sort));   // Fragment_valueOrder::Sort (Fragment_Info.h:88)
   TraceArgs ta;
   ta.r0 = r0; ta.n = nr; ta.numAln = opts->NumAln; ta.single = opts->mode == LRA_SDP_SINGLE_CLUSTER; ta.alnthres = opts->alnthres; ta.fragOff = c.fragOff; ta.read_off = c.d_read_off; ta.fq = c.fq; ta.ft = c.ft;
   ta.flen = c.flen; ta.fcl = c.fcl; ta.fai = c.fai; ta.fval = c.fval; ta.fpred = c.spare; ta.fflags = c.fflags; ta.opay = c.opay; ta.used = c.used;
@@ -499,12 +491,12 @@ int sdp_run(lra_ctx* ctx, int n_reads, const uint64_t* d_cluster_off, const uint
   c.ctx = ctx; c.st = ctx->stream; c.opts = opts; c.out = out; c.n_reads = n_reads; c.n1 = (size_t)n_reads + 1;
   c.d_cluster_off = d_cluster_off; c.d_c_start = d_c_start; c.d_c_count = d_c_count; c.d_c_strand = d_c_strand; c.d_q = d_q; c.d_t = d_t; c.d_len = d_len;
   c.d_read_off = d_read_off; c.d_rate = d_rate; c.d_qe = d_qe; c.d_te = d_te; c.d_num_anchors = d_num_anchors; c.boxes = d_qe != nullptr;
+  c.sort = ctx->sdp_inner ? lra_sort_opts{"sdp_inner_sort", "sdp_inner_sort_fallback", true} : lra_sort_opts{"sdp_sort", "sdp_sort_fallback", true};
   SDP_TRY(pwl_table(c));
   SDP_TRY(batch_buffers(c));
   if (c.NF == 0) { LRA_HIP_CHECK(ctx, hipStreamSynchronize(c.st)); return LRA_OK; }
   make_points(c);
   SDP_TRY(diag_dump(c));
-  Retag retag(ctx);
   SDP_TRY(sort_points(c));
   // ---- chunks of reads: decompositions, ProcessPoint, trace
   // one chunk if it fits: the kernels' duration is set by the longest read once the chip is no longer full, so few large launches

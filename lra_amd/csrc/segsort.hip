@@ -1,5 +1,5 @@
 // lra_amd/csrc/segsort.hip -- the path's segmented sorts of (64-bit key, 32-bit value) pairs: DiagonalSort / CartesianSort of a read's (a cluster's, a job's) matches
-// (Sorting.h:50-150: any stable order by the packed key), the sparse DP's point orders where the keys of a list are all different (seed.hip: lra_sort_mostly_unique_batch),
+// (Sorting.h:50-150: any stable order by the packed key), the sparse DP's point orders where the keys of a list are all different (exact_sort.hip: lra_sort_mostly_unique_batch),
 // its diagonal order.  gfx950 only.
 //
 // rocprim::segmented_radix_sort_pairs sorts a segment of a few thousand pairs in ~10 digit passes THROUGH MEMORY (key / value arrays read and written per pass: 10-15 G
@@ -79,6 +79,18 @@ hipError_t lra_segsort_pairs(lra_ctx* ctx, void* temp, size_t& temp_bytes, const
   return rocprim::segmented_radix_sort_pairs(temp, rb, kin, kout, vin, vout, total, nseg, (const uint64_t*)mb, (const uint64_t*)me, begin_bit, end_bit, st);
 }
 
+int lra_segsort_pairs_scratch(lra_ctx* ctx, const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout, uint64_t total, uint64_t nseg, const uint64_t* b,
+                              const uint64_t* e, int begin_bit, int end_bit) {
+  size_t tb = 0;
+  hipError_t rc = lra_segsort_pairs(ctx, nullptr, tb, nullptr, nullptr, nullptr, nullptr, (unsigned int)total, (unsigned int)nseg, nullptr, nullptr, begin_bit, end_bit, ctx->stream);
+  if (rc == hipSuccess) {
+    void* temp = lra_scratch(ctx, 2, tb + 256);
+    if (!temp) return LRA_ERR_NOMEM;
+    rc = lra_segsort_pairs(ctx, temp, tb, kin, kout, vin, vout, (unsigned int)total, (unsigned int)nseg, b, e, begin_bit, end_bit, ctx->stream);
+  }
+  return rc == hipSuccess ? LRA_OK : lra_set_err(ctx, LRA_ERR_HIP, "segmented sort: %s", hipGetErrorString(rc));
+}
+
 extern "C" int lra_sort_pairs_batch(lra_ctx* ctx, uint64_t n_pairs, uint64_t n_segments, const uint64_t* d_begin, const uint64_t* d_end, const uint64_t* d_key_in,
                                     uint64_t* d_key_out, const uint32_t* d_val_in, uint32_t* d_val_out, int begin_bit, int end_bit) {
   if (!ctx || begin_bit < 0 || end_bit > 64 || begin_bit >= end_bit) return LRA_ERR_INVALID;
@@ -86,14 +98,8 @@ extern "C" int lra_sort_pairs_batch(lra_ctx* ctx, uint64_t n_pairs, uint64_t n_s
   if (n_pairs == 0 || n_segments == 0) return LRA_OK;
   if (!d_begin || !d_end || !d_key_in || !d_key_out || !d_val_in || !d_val_out || d_key_in == d_key_out || d_val_in == d_val_out) return LRA_ERR_INVALID;
   LRA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  size_t tb = 0;
-  if (lra_segsort_pairs(ctx, nullptr, tb, nullptr, nullptr, nullptr, nullptr, (unsigned int)n_pairs, (unsigned int)n_segments, nullptr, nullptr, begin_bit, end_bit, ctx->stream) != hipSuccess)
-    return lra_set_err(ctx, LRA_ERR_HIP, "segmented sort: sizing");
-  void* temp = lra_scratch(ctx, 2, tb + 256);
-  if (!temp) return LRA_ERR_NOMEM;
-  const hipError_t e = lra_segsort_pairs(ctx, temp, tb, d_key_in, d_key_out, d_val_in, d_val_out, (unsigned int)n_pairs, (unsigned int)n_segments, d_begin, d_end, begin_bit, end_bit,
-                                         ctx->stream);
-  if (e != hipSuccess) return lra_set_err(ctx, LRA_ERR_HIP, "segmented sort: %s", hipGetErrorString(e));
+  const int rc = lra_segsort_pairs_scratch(ctx, d_key_in, d_key_out, d_val_in, d_val_out, n_pairs, n_segments, d_begin, d_end, begin_bit, end_bit);
+  if (rc) return rc;
   LRA_HIP_CHECK(ctx, hipGetLastError());
   return LRA_OK;
 }

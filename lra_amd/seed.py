@@ -116,6 +116,17 @@ def sort_minimizers_batch(ctx: Context, keys_list, pos_list):
     return [(K2[off[i]:off[i + 1]].copy(), P2[off[i]:off[i + 1]].copy()) for i in range(n)]
 
 
+def sort_minimizers_host(keys, pos, lib=None):
+    """lra_sort_minimizers_host (no GPU): the library's std::sort on one list of (keys uint64, pos uint32) in host memory; returns sorted copies."""
+    if lib is None:
+        from ._lib import load_library
+        lib = load_library()
+    K = np.array(keys, dtype=np.uint64); P = np.array(pos, dtype=np.uint32)
+    if lib.lra_sort_minimizers_host(len(K), K.ctypes.data, P.ctypes.data) != 0:
+        raise ValueError("lra_sort_minimizers_host failed")
+    return K, P
+
+
 def sort_pairs_batch(ctx: Context, keys, vals, begin, end, begin_bit=0, end_bit=64):
     """lra_sort_pairs_batch: every segment [begin[i], end[i]) of (uint64 key, uint32 value) pairs sorted stably by the key bits [begin_bit, end_bit); returns
     (keys_out, vals_out) -- positions outside every segment are left as the output buffers were (zero here)."""

@@ -78,4 +78,4 @@ def test_work_buffer_slots_have_one_owner():
     assert max(owners) < 192                                     # lra_ctx::gbuf
     bad = {k: sorted(v) for k, v in owners.items() if len(v) > 1 and k not in _SHARED_SLOTS}
     assert not bad, bad
-    assert owners[97] == {"seed.hip"} and owners[98] == {"seed.hip"} and owners[86] == {"fine_clusters.hip"} and owners[87] == {"fine_clusters.hip"}
+    assert owners[97] == {"exact_sort.hip"} and owners[98] == {"exact_sort.hip"} and owners[86] == {"fine_clusters.hip"} and owners[87] == {"fine_clusters.hip"}

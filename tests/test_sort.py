@@ -26,6 +26,21 @@ def test_oracle_sort_is_std_sort_and_adversary_hits_depth_limit(oracle):
     assert np.all(np.diff(sk.astype(np.int64)) >= 0) and sorted(sp.tolist()) == list(range(5000))
 
 
+def test_host_sort_matches_std_sort(oracle):
+    """lra_sort_minimizers_host: the host instantiation of std_sort.h's serial sort on (key, pos) pairs with the masked comparison -- the text every device sort is
+    built from, and the one whose device instantiation (sort_kernel: lists beyond 2^26 tuples) no device test reaches.  The adversaries force its heap-sort fall-back."""
+    import __graft_entry__ as g
+    g.build()
+    from lra_amd import seed
+    cs = _cases() + [oracle.antiqsort_keys(n) for n in (300, 3000, 7000)]
+    for i, k in enumerate(cs):
+        p = np.arange(len(k), dtype=np.uint32)
+        gk, gp = seed.sort_minimizers_host(k, p)
+        ek, ep = oracle.sort_minimizers(k, p)
+        assert np.array_equal(gk, ek), (i, len(k))
+        assert np.array_equal(gp, ep), (i, len(k))
+
+
 @pytest.mark.gpu
 def test_hip_sort_matches_std_sort(ctx, oracle):
     from lra_amd import seed
@@ -42,8 +57,8 @@ def test_hip_sort_matches_std_sort(ctx, oracle):
 
 @pytest.mark.gpu
 def test_hip_sort_big_lists(ctx, oracle):
-    """Lists beyond the LDS capacity (9000 tuples): the global-memory workgroup sort up to 65534 tuples, the serial kernel beyond; heavy ties,
-    the depth-limit adversary, sizes around both limits."""
+    """Lists beyond the LDS capacity (9000 tuples): the global-memory workgroup sort up to 65534 tuples, the one with 32-bit indices beyond (65535, 70000);
+    heavy ties, the depth-limit adversary, sizes around both limits."""
     from lra_amd import seed
     rng = np.random.default_rng(3)
     cs = [rng.integers(0, 1 << 34, 9001).astype(np.uint64), rng.integers(0, 50, 20000).astype(np.uint64), rng.integers(0, 1 << 20, 65534).astype(np.uint64),
