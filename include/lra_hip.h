@@ -1606,6 +1606,61 @@ int lra_map_records_device_bam_to_sorter(lra_ctx* ctx, const lra_map_result* res
                                          const char* const* quals, const int32_t* read_len, const char* const* chrom_names,
                                          const char* const* passthrough, const char* d_qual, const uint64_t* d_qual_off, int flags, int n_threads,
                                          lra_bam_sorter* sorter, const uint64_t** rec_off);
+/* ---- Merging coordinate-sorted BAM files (additive to ABI 9) ---------------------------------------------------------------------------------------
+ * lra_bam_merger streams n_runs (1 .. 256) coordinate-sorted BAM files -- each a complete file: header, records that may begin in the middle of a
+ * member, an optional EOF member; all with the same reference table -- into one sorted stream, given back as BGZF members with the bytes of the .bai
+ * file.  The order is the sorter's key, computed by the sorter's code; ties keep run order, then file order within a run: runs that a sorter made from
+ * successive batches merge into the stream one sorter with an unbounded budget gives, member for member and index byte for index byte.
+ *   create    sniffs every file and parses its header on the host; a file that is no BAM file, or whose n_ref, names or lengths differ from the first
+ *             run's: LRA_ERR_INVALID naming the file and the first difference.  n_runs outside 1 .. 256: LRA_ERR_INVALID (256 runs is the limit; a
+ *             merge of merges is not built).  window_bytes: the compressed bytes a run reads per refill, at least 65536 (smaller values are raised to
+ *             it) and never more than the file still holds; 0: max_bytes / (24 n_runs), within [65536, 2^28] -- a window, its decoded bytes twice, its
+ *             arrays and its share of the round take about twenty times its compressed bytes at BAM's usual ratios.
+ *   header    the first run's uncompressed header bytes and the reference lengths (owned by the merger).  The caller writes the header and passes
+ *             the length of what it wrote in front of the first member as first_member_file_offset.
+ *   next      pieces of whole BGZF members, at most (members per round of the compress stage) x LRA_BGZF_IN_MAX bytes of the stream each; *len = 0:
+ *             done.  No EOF member.
+ *   index     after the last piece (before: LRA_ERR_INVALID): the .bai bytes, by the sorter's rules.  A reference above 2^29 bases: LRA_ERR_INVALID
+ *             with the reason, after the members were delivered.
+ * A round.  Every run owns a window: the whole records of its last refill, framed and keyed once.  The bound is the smallest (key of the window's last
+ * record, run) over the runs that have bytes behind their window; a run emits its records with (key, run) <= bound, every run everything when no run
+ * sets a bound.  The bound's run emits its whole window, so every round makes progress; a record not yet seen is never smaller than an emitted one,
+ * and one of the bound's own run that equals the bound sorts behind everything emitted by the tie rule.  A record's place in the round is its ordinal
+ * among its run's emitted records + the emitted records of every earlier run with key <= its own + those of every later run with key < its own (a
+ * merge by ranks: binary searches, no second sort).  The round is gathered behind what the last round left, its whole multiples of LRA_BGZF_IN_MAX
+ * bytes are compressed and the rest waits, so the members are those of ONE lra_bgzf_compress_device call on the merged stream and the sorter's formula
+ * for virtual offsets holds.  Only windows a round emptied are refilled; the others keep their records and keys.
+ * Refusals (LRA_ERR_INVALID naming the file; the merger then only refuses): keys that descend, with the record's ordinal in its file; a record shorter
+ * than its fields or a refID >= n_ref; a bad BGZF member; a file that ends inside a record.
+ * Budget.  max_bytes bounds the device memory of the merger (the compress stage's round is the context's, as for the sorter).  With, per run r that
+ * still reads, C_r the compressed bytes of its refill, M_r their members, D_r the decoded bytes of its window with the carried tail and N_r its records:
+ *     need = sum over r of [ C_r + 1  +  2 (D_r rounded up to 4096 + 64)  +  20 (M_r + 1)  +  8 (D_r / 36 + 2)  +  24 N_r ]          (the windows)
+ *          + 80 n_runs + 128  +  (B + 65280 + 64) + 65280  +  72 E + 16                                    (a round of E records, B bytes)
+ *          + 8 (5 n_ref + 1) + 8 (n_ref + 1) + 8 (sum((ref_len + 16383) / 16384 + 1) + 1)                  (the index, resident)
+ * The step's own buffers (the first three terms of a window) have a floor of 4096 items and are never shrunk; the merger's arrays are allocated an
+ * eighth larger than asked and never shrunk.  A run whose file is wholly in its window keeps the decoded bytes, the starts and the keys only, and
+ * nothing once its last record is emitted.  The members of a refill are walked on the host before anything is allocated for them, and a refill or a
+ * round that would pass max_bytes is LRA_ERR_NOMEM with the figure needed (the merger then holds nothing on the device); a record larger than its
+ * window doubles the window's refill under the same check.  At index the window buffers are gone and each reference's chunks are sorted by bin in 24
+ * bytes per chunk + rocprim's temporary storage.
+ * Index.  Kept in stream-offset space while the rounds run: chunk boundaries as byte offsets u, the linear index's windows as the minimum u (64-bit
+ * atomicMin, resident on the device), per reference first / last / counters; a chunk that continues over a round's edge is extended on the host.  The
+ * virtual offset is monotone in u, so index converts with the complete member table and writes through the sorter's writer.
+ * lra_bam_merger_stats: rounds, records and bytes delivered, refills per run, the peak of the merger's device bytes, ms per stage (read + inflate and
+ * compress: wall; the others: HIP events). */
+typedef struct lra_bam_merger lra_bam_merger;
+struct lra_bam_merger_stats {
+  uint64_t rounds, records, bytes, peak_device_bytes;
+  uint64_t refills[256];
+  double ms_read_inflate, ms_frame_keys, ms_bound_rank, ms_gather_span, ms_compress, ms_index;
+};
+int lra_bam_merger_create(lra_ctx* ctx, uint64_t max_bytes, uint64_t window_bytes, int n_runs, const char* const* paths,
+                          uint64_t first_member_file_offset, lra_bam_merger** out);
+int lra_bam_merger_header(lra_bam_merger* m, const uint8_t** h_bytes, uint64_t* len, int* n_ref, const uint64_t** ref_len);
+int lra_bam_merger_next(lra_bam_merger* m, const uint8_t** h_data, uint64_t* len);
+int lra_bam_merger_index(lra_bam_merger* m, const uint8_t** h_bai, uint64_t* len);
+int lra_bam_merger_stats(lra_bam_merger* m, struct lra_bam_merger_stats* out);
+void lra_bam_merger_destroy(lra_bam_merger* m);
 /* the reads of a snapshot whose status word is non-zero: their number; *status (optional) = the snapshot's status array [n_reads], owned by the snapshot */
 uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status);
 /* The record buffer of a batch as ONE device buffer -- what a rank sends to rank 0 in the single exchange step of the multi-GPU path (the

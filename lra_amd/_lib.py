@@ -175,6 +175,12 @@ SYMBOLS = {
     "lra_bam_sorter_next": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
     "lra_bam_sorter_index": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
     "lra_bam_sorter_stats": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "lra_bam_merger_create": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(_vp)]),
+    "lra_bam_merger_header": (C.c_int, [_vp, C.POINTER(_vp), _u64p, C.POINTER(C.c_int), C.POINTER(_vp)]),
+    "lra_bam_merger_next": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
+    "lra_bam_merger_index": (C.c_int, [_vp, C.POINTER(_vp), _u64p]),
+    "lra_bam_merger_stats": (C.c_int, [_vp, _vp]),
+    "lra_bam_merger_destroy": (None, [_vp]),
     "lra_bam_index_host": (C.c_int, [_vp, C.c_uint64, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _u64p]),
     "lra_bam_set_cigar_limit": (C.c_int, [_vp, C.c_int]),
     "lra_bam_header": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int, _vp, _vp, _vp, C.c_uint64, _vp]),

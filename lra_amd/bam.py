@@ -1,7 +1,9 @@
 """The device primitives behind BAM output (bam_encode.hip): an alignment's CIGAR as BAM ops, ranges of bases as 4-bit codes, ranges of quality strings
 as phred bytes.  Inputs are device tensors; results are copied to numpy.  Behind them: BamSorter (bam_sort.hip), which sorts the records of several
-batches by coordinate on the device and gives back BGZF members and the .bai bytes, and index_host, the same index from a sorted stream on the host."""
+batches by coordinate on the device and gives back BGZF members and the .bai bytes, BamMerger (bam_merge.hip), which streams several sorted BAM files
+into one under a bounded device budget, and index_host, the same index from a sorted stream on the host."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -127,6 +129,74 @@ class BamSorter:
         if self.h:
             if self.ctx.h:                                                      # (a sorter that outlives its context is left alone: destroy needs the context's device)
                 self.ctx.lib.lra_bam_sorter_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MergerStats(C.Structure):
+    """struct lra_bam_merger_stats (include/lra_hip.h)"""
+    _fields_ = [("rounds", C.c_uint64), ("records", C.c_uint64), ("bytes", C.c_uint64), ("peak_device_bytes", C.c_uint64), ("refills", C.c_uint64 * 256),
+                ("ms_read_inflate", C.c_double), ("ms_frame_keys", C.c_double), ("ms_bound_rank", C.c_double), ("ms_gather_span", C.c_double),
+                ("ms_compress", C.c_double), ("ms_index", C.c_double)]
+
+
+class BamMerger:
+    """lra_bam_merger: 1 .. 256 coordinate-sorted BAM files with one reference table, merged on the device in at most max_bytes of device memory into
+    BGZF members and the .bai bytes.  The caller writes header()'s bytes (compressed as it likes), passes the length of what it wrote as
+    first_member_file_offset, writes pieces() behind it, then the EOF member; index() gives the .bai.  window_bytes: compressed bytes per refill of a run
+    (0: from the budget)."""
+
+    def __init__(self, ctx: Context, paths, max_bytes, first_member_file_offset, window_bytes=0):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        self.n_runs = len(paths)
+        arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        ctx.check(ctx.lib.lra_bam_merger_create(ctx.h, C.c_uint64(int(max_bytes)), C.c_uint64(int(window_bytes)), len(paths), arr,
+                                                C.c_uint64(int(first_member_file_offset)), C.byref(self.h)))
+
+    def header(self):
+        """-> (the first run's uncompressed header bytes, the references' lengths)"""
+        p, n, n_ref, rl = C.c_void_p(), C.c_uint64(0), C.c_int(0), C.c_void_p()
+        self.ctx.check(self.ctx.lib.lra_bam_merger_header(self.h, C.byref(p), C.byref(n), C.byref(n_ref), C.byref(rl)))
+        lens = list((C.c_uint64 * n_ref.value).from_address(rl.value)) if n_ref.value else []
+        return C.string_at(p, n.value), lens
+
+    def next(self):
+        """the next piece of whole BGZF members as bytes; b"": done"""
+        p, n = C.c_void_p(), C.c_uint64(0)
+        self.ctx.check(self.ctx.lib.lra_bam_merger_next(self.h, C.byref(p), C.byref(n)))
+        return C.string_at(p, n.value) if n.value else b""
+
+    def pieces(self):
+        while True:
+            b = self.next()
+            if not b:
+                return
+            yield b
+
+    def index(self):
+        """the .bai bytes, after the last piece"""
+        p, n = C.c_void_p(), C.c_uint64(0)
+        self.ctx.check(self.ctx.lib.lra_bam_merger_index(self.h, C.byref(p), C.byref(n)))
+        return C.string_at(p, n.value)
+
+    def stats(self):
+        """rounds, records, bytes, refills per run, the peak of the merger's device bytes, ms per stage"""
+        s = MergerStats()
+        self.ctx.check(self.ctx.lib.lra_bam_merger_stats(self.h, C.byref(s)))
+        d = {k: getattr(s, k) for k, _ in MergerStats._fields_ if k != "refills"}
+        d["refills"] = list(s.refills)[:self.n_runs]
+        return d
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:
+                self.ctx.lib.lra_bam_merger_destroy(self.h)
             self.h = None
 
     def __del__(self):

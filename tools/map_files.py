@@ -1,6 +1,6 @@
 """Map read files against a genome FASTA and print the records as `lra align` would (needs the GPU):
 
-    python tools/map_files.py -ONT genome.fa reads.fq [more.fa ...] [-p s|p|pc|b|a] [-H] [--printMD] [-a] [--PrintNumAln N] [--refineBreakpoints] [-o out.sam] [--device-records] [--bgzf | --bam [--sort [--sort-mem BYTES]]]
+    python tools/map_files.py -ONT genome.fa reads.fq [more.fa ...] [-p s|p|pc|b|a] [-H] [--printMD] [-a] [--PrintNumAln N] [--refineBreakpoints] [-o out.sam] [--device-records] [--bgzf | --bam [--sort [--sort-mem BYTES] [--merge-runs]]]
 
 The reads are parsed on the device (lra_reads_next_batch_device) and mapped from the reader's device arrays; --host-input parses them on the host
 (lra_reads_next_batch) and maps through lra_map_reads_host, the same records.  The index: genome.fa.mms / genome.fa.gli when both exist (lra_read_mms /
@@ -11,7 +11,9 @@ lra_bam_header's bytes as BGZF members, every batch's BAM records encoded and de
 --bam --sort writes a coordinate-sorted BAM file and its index, out.bam and out.bam.bai (-o is required): the header text gets "@HD VN:1.6 SO:coordinate"
 in front, every batch's records go to a device sorter (lra_bam_sorter, at most --sort-mem bytes of device memory), which gives back the sorted members and
 the .bai bytes.  When the records do not fit one run, every run becomes a complete sorted, indexed file of its own -- out.run0000.bam, out.run0000.bam.bai,
-out.run0001.bam, ... -- and the tool says so on stderr; merging them is left to the user.  The SV signatures (-SV) stay per batch, in read order.
+out.run0001.bam, ... -- and the tool says so on stderr.  --merge-runs then merges the runs on the device (lra_bam_merger, under the same --sort-mem) into
+out.bam and out.bam.bai, the bytes one run of a large enough budget would have given, and removes the run files; if the merge fails they stay and the
+tool says why.  The SV signatures (-SV) stay per batch, in read order.
 Per-stage times go to stderr."""
 import argparse
 import os
@@ -80,7 +82,10 @@ def main():
                     help="write BAM: the records are encoded and deflated on the device (lra_map_records_device_bam); implies --device-records and -p s")
     ap.add_argument("--sort", action="store_true", help="with --bam and -o: sort the records by coordinate on the device and write out.bam.bai beside the file")
     ap.add_argument("--sort-mem", type=int, default=8 << 30, metavar="BYTES", help="device memory the sorter may use (default 8 GiB); more records make several sorted files")
+    ap.add_argument("--merge-runs", action="store_true", help="with --sort: when the records made several sorted runs, merge them on the device into -o and its index")
     args = ap.parse_args()
+    if args.merge_runs and not args.sort:
+        ap.error("--merge-runs merges the runs --sort made: it needs --sort")
     if args.sort and not (args.bam and args.out):
         ap.error("--sort sorts BAM output into a file and its index: it needs --bam and -o")
     if args.bam:
@@ -171,8 +176,37 @@ def main():
                 sys.stderr.write("map_files: %s is not indexed: %s\n" % (path, e))
             if path != args.out:
                 sys.stderr.write("map_files: the records do not fit one sorted run of %d bytes (--sort-mem): %s holds %d records, sorted and indexed on its own; "
-                                 "the runs are not merged\n" % (args.sort_mem, path, n_held))
+                                 "%s\n" % (args.sort_mem, path, n_held, "--merge-runs merges the runs at the end" if args.merge_runs else "the runs are not merged"))
             run_no += 1
+
+        def merge_runs():
+            """the runs into args.out and its index, under the sorter's budget; the run files go when that worked"""
+            from lra_amd.bam import BamMerger
+            paths = ["%s.run%04d.bam" % (stem, i) for i in range(run_no)]
+            try:
+                m = BamMerger(ctx, paths, args.sort_mem, len(head))
+                try:
+                    with open(args.out, "wb") as f:
+                        f.write(head)
+                        for piece in m.pieces():
+                            f.write(piece)
+                        f.write(bgzf.EOF_BLOCK)
+                    bai = m.index()
+                    with open(args.out + ".bai", "wb") as f:
+                        f.write(bai)
+                finally:
+                    m.close()
+            except LraError as e:
+                for p in (args.out, args.out + ".bai"):
+                    if os.path.exists(p):
+                        os.remove(p)
+                sys.stderr.write("map_files: the %d runs are not merged and stay as they are: %s\n" % (run_no, e))
+                return
+            for p in paths:
+                for q in (p, p + ".bai"):
+                    if os.path.exists(q):
+                        os.remove(q)
+            sys.stderr.write("map_files: %d runs merged into %s\n" % (run_no, args.out))
     # --device-records with device input: the qualities stay on the device from the reader to the record text; the host copies of bases and qualities
     # are switched off where nothing reads them (the formats the device builds; with them -SV is built on the device too, from the result's own arrays)
     dev_quals = args.device_records and not args.host_input
@@ -249,6 +283,8 @@ def main():
     if sorter:
         write_run(True)
         sorter.close()
+        if args.merge_runs and run_no > 1:
+            merge_runs()
     elif args.bgzf or args.bam:
         out.write(bgzf.EOF_BLOCK)
     if sv_out:
