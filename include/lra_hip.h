@@ -1661,6 +1661,64 @@ int lra_bam_merger_next(lra_bam_merger* m, const uint8_t** h_data, uint64_t* len
 int lra_bam_merger_index(lra_bam_merger* m, const uint8_t** h_bai, uint64_t* len);
 int lra_bam_merger_stats(lra_bam_merger* m, struct lra_bam_merger_stats* out);
 void lra_bam_merger_destroy(lra_bam_merger* m);
+/* ---- BAM to SAM text, whole or by region through the .bai (additive to ABI 9) -----------------------------------------------------------------------
+ * lra_bam_view prints the alignment records of a BAM file -- this project's or any other's -- as SAM lines on the device: the inverse of the BAM
+ * encoder and the reader of the index the sorter and the merger write.  One view serves one context and owns its device memory (no work buffer).
+ *   create    sniffs the file (not BAM: LRA_ERR_INVALID), inflates and parses the header on the host.  bai_path (NULL: none) is read and checked whole:
+ *             every count and length against the bytes that remain; a negative n_bin / n_chunk / n_intv, a chunk with end < beg, an n_ref other than
+ *             the BAM header's, bytes behind n_no_coor: LRA_ERR_INVALID with the reason.  The pseudo-bin 37450 is no bin; n_no_coor may be absent.
+ *             window_bytes: the compressed bytes a step reads, at least 65536 (smaller values are raised); 0: 16 MiB.
+ *   header    the header text (not NUL-terminated), the reference names and lengths; owned by the view.
+ *   set_flags a record is kept if (flag & require) == require && (flag & exclude) == 0; holds for the passes started afterwards and the one running.
+ *   all       starts a pass over every record of the file, from the first one behind the header, in windows.
+ *   region    starts a pass over the records that overlap [beg, end) of reference ref_id (0-based, half-open; end is clamped to the reference's
+ *             length): refID == ref_id && pos < end && pos + max(1, span) > beg, span = the reference bases of the core CIGAR (the index's rule; the N
+ *             op of the CG:B:I form carries it).  Without an index, ref_id outside [0, n_ref) or beg > end: LRA_ERR_INVALID.  Either call may be
+ *             repeated on one view; each starts a new pass.
+ *   next      the next piece: whole SAM lines, each ending in '\n', in file order, each record once; page-locked memory of the view, valid until the
+ *             next call on it.  *len = 0: the pass is over.  *n_records (optional): the lines of the piece.
+ *   stats     windows, records, bytes read / inflated / printed, ms per stage (read + inflate: wall, one figure -- the step reads and inflates in one
+ *             call --; frame + select, tags + lengths, the floats' round trip, emit, the copy to the host: HIP events), summed over the view's life.
+ * The plan of a region (lra_bai_query_host states it as code, on the host, without a GPU: index bytes in, chunks out as (beg, end) pairs of virtual
+ * offsets, owned by the library and valid until the calling thread's next call): the chunks of reg2bins(beg, end)'s bins; min_off = lin[beg >> 14] (a
+ * window behind the last one: no record reaches beg, the plan is empty); each chunk's start raised to min_off, a chunk this empties dropped; sorted by
+ * start, chunks that overlap or touch merged: ascending, disjoint, no record read twice.  beg == end gives an empty plan.  n_ref < 0: not compared.
+ * A chunk [vb, ve) is read from file offset vb >> 16 with a fresh BGZF step, framed from decoded offset vb & 0xffff; records that start in front of ve are
+ * taken (the step's member table maps ve to a decoded position).  At the first record with refID > ref_id, or refID == ref_id && pos >= end, the chunk is
+ * over: the file is sorted (the view does not verify it).  A record larger than the window makes the step read on with twice the window.  Planned
+ * chunks that lie less than window_bytes apart in the file are read as one chunk from the first's start to the last's end: the records between them
+ * are in file order too and fail the overlap test, and a step per chunk costs a member's inflate latency (about 10 ms) each.
+ * The text.  QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL and the tags in the file's order, tab-separated.  RNAME '*' for refID < 0; POS and
+ * PNEXT the stored value + 1; CIGAR '*' with 0 ops; a core CIGAR <l_seq>S<n>N with a CG:B:I tag prints the tag's ops and not the tag; RNEXT '*' for
+ * next_refID < 0 (or outside the table), '=' when it equals refID, else the name; SEQ '*' for l_seq = 0, else through "=ACMGRSVTWYHKDBN"; QUAL '*' for
+ * l_seq = 0 or a first byte of 0xff, else + 33.  Tags: c C s S i I print as TAG:i:value; A, Z, H their bytes; B as B:<subtype> and ,value per element;
+ * f (and the elements of B:f) as printf("%.6g", (double)v) -- printed on the host: one array of floats out, their text back, per window.
+ * Refusals (LRA_ERR_INVALID naming the file and the record's ordinal -- in a region pass its ordinal among the records read from a compressed
+ * offset --; the records in front of the fault are delivered first, the next call refuses, and the view takes another pass): a BGZF fault (the
+ * readers' text); a block_size below 32; a record with l_read_name = 0, no NUL behind its name, 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 +
+ * l_seq > block_size or a refID outside [-1, n_ref); a CIGAR op code above 8; an aux block that ends inside a tag or names a type outside
+ * A c C s S i I f Z H B (B: c C s S i I f); a file that ends inside a record.
+ * Memory.  With C = the compressed bytes of a window (window_bytes, or more for a larger record), M its members, D its decoded bytes with the carried
+ * tail, N its framed records, T their printed tags, E their array elements and single floats, F the floats among them, O their CIGAR ops and X the
+ * bytes of their text, a window allocates on the device
+ *     C + 1 + 2 (D rounded up to 4096 + 64) + 20 (M + 1)                                        (the step; C + 1 more page-locked on the host)
+ *   + 8 (D / 36 + 2) + 92 N (region passes: + 16 N) + 40 T + 12 E + 12 O + 20 F + the floats' text + 22 (7 N + T) + X + 64
+ * each array an eighth larger than asked and never shrunk; X + 1 bytes of page-locked host memory take the text. */
+typedef struct lra_bam_view lra_bam_view;
+struct lra_bam_view_stats {
+  uint64_t windows, records, bytes_read, bytes_inflated, bytes_text;
+  double ms_read_inflate, ms_frame_select, ms_tags_lengths, ms_floats, ms_emit, ms_copy;
+};
+int lra_bam_view_create(lra_ctx* ctx, const char* bam_path, const char* bai_path, uint64_t window_bytes, lra_bam_view** out);
+int lra_bam_view_header(lra_bam_view* v, const char** text, uint64_t* text_len, int* n_ref, const char* const** names, const uint64_t** ref_len);
+int lra_bam_view_set_flags(lra_bam_view* v, uint32_t require, uint32_t exclude);
+int lra_bam_view_all(lra_bam_view* v);
+int lra_bam_view_region(lra_bam_view* v, int32_t ref_id, int64_t beg, int64_t end);
+int lra_bam_view_next(lra_bam_view* v, const char** h_text, uint64_t* len, uint64_t* n_records);
+int lra_bam_view_stats(lra_bam_view* v, struct lra_bam_view_stats* out);
+void lra_bam_view_destroy(lra_bam_view* v);
+int lra_bai_query_host(const uint8_t* bai, uint64_t bai_len, int n_ref, int32_t ref_id, int64_t beg, int64_t end, const uint64_t** chunks,
+                       uint64_t* n_chunks);
 /* the reads of a snapshot whose status word is non-zero: their number; *status (optional) = the snapshot's status array [n_reads], owned by the snapshot */
 uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status);
 /* The record buffer of a batch as ONE device buffer -- what a rank sends to rank 0 in the single exchange step of the multi-GPU path (the

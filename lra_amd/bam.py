@@ -1,7 +1,8 @@
 """The device primitives behind BAM output (bam_encode.hip): an alignment's CIGAR as BAM ops, ranges of bases as 4-bit codes, ranges of quality strings
 as phred bytes.  Inputs are device tensors; results are copied to numpy.  Behind them: BamSorter (bam_sort.hip), which sorts the records of several
 batches by coordinate on the device and gives back BGZF members and the .bai bytes, BamMerger (bam_merge.hip), which streams several sorted BAM files
-into one under a bounded device budget, and index_host, the same index from a sorted stream on the host."""
+into one under a bounded device budget, index_host, the same index from a sorted stream on the host, BamView (bam_view.hip), which prints a BAM file
+as SAM text on the device, whole or for a region reached through the .bai, and bai_query, the region planner alone on the host."""
 import ctypes as C
 import os
 
@@ -204,6 +205,115 @@ class BamMerger:
             self.close()
         except Exception:
             pass
+
+
+class ViewStats(C.Structure):
+    """struct lra_bam_view_stats (include/lra_hip.h)"""
+    _fields_ = [("windows", C.c_uint64), ("records", C.c_uint64), ("bytes_read", C.c_uint64), ("bytes_inflated", C.c_uint64), ("bytes_text", C.c_uint64),
+                ("ms_read_inflate", C.c_double), ("ms_frame_select", C.c_double), ("ms_tags_lengths", C.c_double), ("ms_floats", C.c_double),
+                ("ms_emit", C.c_double), ("ms_copy", C.c_double)]
+
+
+def parse_region(text, names, ref_len):
+    """a region as samtools view takes it -- `name` or `name:beg-end`, 1-based and inclusive, commas in the numbers allowed; `name:beg` runs to the
+    reference's end -- -> (ref_id, beg, end), 0-based and half-open.  A name that holds a colon is matched whole first.  ValueError otherwise."""
+    names = [n.decode() if isinstance(n, bytes) else n for n in names]
+    if text in names:
+        r = names.index(text)
+        return r, 0, int(ref_len[r])
+    name, sep, span = text.rpartition(":")
+    if not sep or name not in names:
+        raise ValueError("region %r names no reference of the file" % text)
+    r = names.index(name)
+    lo, dash, hi = span.replace(",", "").partition("-")
+    try:
+        beg = int(lo) - 1 if lo else 0
+        end = int(hi) if hi else int(ref_len[r])
+    except ValueError:
+        raise ValueError("region %r: not name:beg-end" % text)
+    if beg < 0 or end < beg:
+        raise ValueError("region %r: not a 1-based inclusive interval" % text)
+    return r, beg, end
+
+
+class BamView:
+    """lra_bam_view: the records of a BAM file as SAM text, printed on the device; bai: the path of its .bai index (None: whole-file passes only);
+    window_bytes: compressed bytes per step (0: the library's default)."""
+
+    def __init__(self, ctx: Context, path, bai=None, window_bytes=0):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        ctx.check(ctx.lib.lra_bam_view_create(ctx.h, os.fsencode(path), os.fsencode(bai) if bai is not None else None, C.c_uint64(int(window_bytes)),
+                                              C.byref(self.h)))
+
+    def header(self):
+        """-> (header text as bytes, the reference names as bytes, their lengths)"""
+        t, n, n_ref, nm, rl = C.c_void_p(), C.c_uint64(0), C.c_int(0), C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.ctx.lib.lra_bam_view_header(self.h, C.byref(t), C.byref(n), C.byref(n_ref), C.byref(nm), C.byref(rl)))
+        k = n_ref.value
+        names = [C.string_at(q) for q in (C.c_char_p * k).from_address(nm.value)] if k else []
+        lens = list((C.c_uint64 * k).from_address(rl.value)) if k else []
+        return (C.string_at(t, n.value) if n.value else b""), names, lens
+
+    def set_flags(self, require=0, exclude=0):
+        self.ctx.check(self.ctx.lib.lra_bam_view_set_flags(self.h, C.c_uint32(int(require)), C.c_uint32(int(exclude))))
+
+    def fetch(self, ref=None, beg=0, end=None):
+        """yields the pieces (bytes: whole SAM lines) of a pass: ref None: every record; ref: a reference's index or name, [beg, end) 0-based half-open
+        (end None: the reference's end).  self.last_records counts the pass's lines."""
+        lib = self.ctx.lib
+        if ref is None:
+            self.ctx.check(lib.lra_bam_view_all(self.h))
+        else:
+            _, names, lens = self.header()
+            if not isinstance(ref, int):
+                key = ref.encode() if isinstance(ref, str) else ref
+                if key not in names:
+                    raise ValueError("no reference %r in the file" % ref)
+                ref = names.index(key)
+            if end is None:
+                end = lens[ref] if 0 <= ref < len(lens) else 0
+            self.ctx.check(lib.lra_bam_view_region(self.h, C.c_int32(ref), C.c_int64(int(beg)), C.c_int64(int(end))))
+        self.last_records = 0
+        while True:
+            p, n, k = C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+            self.ctx.check(lib.lra_bam_view_next(self.h, C.byref(p), C.byref(n), C.byref(k)))
+            if not n.value:
+                return
+            self.last_records += k.value
+            yield C.string_at(p, n.value)
+
+    def stats(self):
+        s = ViewStats()
+        self.ctx.check(self.ctx.lib.lra_bam_view_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in ViewStats._fields_}
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:
+                self.ctx.lib.lra_bam_view_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bai_query(bai, n_ref, ref_id, beg, end, lib=None):
+    """lra_bai_query_host (no GPU): the chunks [(beg, end)] of virtual offsets a region pass reads, from the .bai bytes.  n_ref: the BAM header's
+    reference count (-1: not compared).  ValueError for LRA_ERR_INVALID (an index the reader refuses, ref_id outside it, beg > end)."""
+    if lib is None:
+        from ._lib import load_library
+        lib = load_library()
+    b = np.frombuffer(bytes(bai), np.uint8)
+    p, n = C.c_void_p(), C.c_uint64(0)
+    if lib.lra_bai_query_host(C.c_void_p(b.ctypes.data) if len(b) else None, C.c_uint64(len(b)), int(n_ref), C.c_int32(int(ref_id)), C.c_int64(int(beg)),
+                              C.c_int64(int(end)), C.byref(p), C.byref(n)) != 0:
+        raise ValueError("lra_bai_query_host: the index or the region is refused")
+    a = np.ctypeslib.as_array((C.c_uint64 * (2 * n.value)).from_address(p.value)).copy() if n.value else np.zeros(0, np.uint64)
+    return [(int(a[2 * i]), int(a[2 * i + 1])) for i in range(n.value)]
 
 
 def index_host(stream, ref_len, member_off, first_member_file_offset=0, lib=None):

@@ -1,0 +1,867 @@
+// lra_amd/csrc/bam_view.hip -- lra_bam_view: a BAM file printed as SAM text on the device, whole or for a region reached through its .bai index (gfx950).
+// include/lra_hip.h has the interface, the text's rules and what a window allocates; bam_view_host.h reads the index and plans a region's chunks.
+//
+// window.  One lra_bgzf_step (zsource.h) reads `window_bytes` compressed bytes, inflates their whole members on the device behind the carried tail and
+// lra_bam_launch_frame chains the block_size fields.  A region's chunk [vb, ve) seeks to vb >> 16, resets the step and frames from vb & 0xffff; the
+// step's member table turns ve into a decoded position, the limit behind which no record of the chunk starts.  Planned chunks less than a window
+// apart in the file are read as one (the overlap test drops what lies between them): a step costs a member's inflate latency, about 10 ms.
+// records.  bv_check, a lane per framed record: the record's arithmetic, the lowest bad index through atomicMin.  bs_span (bam_keys.h, the index's own
+// code) gives a region pass every record's reference span; bv_select, a lane per record: the flag filter, the overlap test, the first record at or behind
+// the region's end (nothing behind it is taken: bv_cut).  bv_tags, a lane per kept record, walks the aux block: every type and length against the
+// record's end, the counts of tags, array elements, floats and CIGAR ops (those of a CG:B:I tag when the core CIGAR is <l_seq>S<n>N); after the scans
+// bv_items writes one item per printed tag.
+// lengths.  A line is a row of pieces: name | flag .. MAPQ | CIGAR | RNEXT .. TLEN | SEQ | QUAL | one per tag | newline.  bv_oplen, a lane per CIGAR op,
+// and bv_elemlen, a lane per array element (and per single float), give the digits of the variable-width bulk; floats go to the host in one array, are
+// printed there with "%.6g" and come back as text (one copy each way per window).  bv_pieces, a lane per record, sizes the pieces; one scan places them.
+// emit.  bv_small, a lane per record: the fields a lane prints (numbers, RNAME, tag prefixes, scalars).  bv_ops / bv_elems, a lane per op / element at
+// its scanned offset.  bv_bulk, chunk_copy.h's walk: the output cut into 4 KiB chunks, a wave each, aligned dword stores; names and Z / H strings are
+// copies, SEQ is expanded eight bases per source dword through the 16-entry table, QUAL is + 33.  The text is one device buffer, one copy to the host.
+#include "common.h"
+#include "chunk_copy.h"
+#include "scan.h"
+#include "bam_view_host.h"
+#include "bam_merge_host.h"
+#include "bam_keys.h"
+#include "zsource.h"
+#include <fcntl.h>
+#include <unistd.h>
+#include <stdarg.h>
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+namespace {
+
+constexpr uint64_t MIN_WINDOW = 65536, DEFAULT_WINDOW = 16ull << 20;
+constexpr int CHUNK = 4096;
+constexpr unsigned long long NONE = ~0ull;
+enum { K_NONE = 0, K_COPY = 1, K_SEQ = 2, K_QUAL = 3, K_ELEM = 4 };
+
+struct Item {                                                 // one printed tag
+  uint64_t src;                                               // its value's offset in the window's data (B: the first element)
+  uint64_t e0, f0;                                            // its first element / float in the window's flat arrays
+  uint32_t count, rec;                                        // elements (B, f: 1), bytes (Z, H)
+  uint8_t type, sub, t0, t1;
+  uint32_t pad;
+};
+static_assert(sizeof(Item) == 40, "Item");
+
+struct View {                                                 // what the kernels of a window see
+  const uint8_t* data; const uint64_t* pos; uint64_t n;       // record i is data[pos[i], pos[i + 1])
+  int n_ref; uint32_t req, excl;
+  int region; int32_t ref_id; int64_t beg, end; uint64_t limit;
+  const char* rname; const uint64_t* rname_off;
+  uint32_t* keep; Meta M;
+  uint32_t* c_item; uint32_t* c_elem; uint32_t* c_float; uint32_t* c_op;
+  uint64_t* item_off; uint64_t* elem_off; uint64_t* float_off; uint64_t* op_off;
+  uint64_t* ops_src; uint64_t* cg_at;                         // where the record's ops are; the CG:B:I tag that is not printed (NONE: none)
+  Item* item; uint64_t n_item;
+  uint32_t* elen; uint64_t* eoff; uint64_t n_elem;
+  uint32_t* oplen; uint64_t* ooff; uint64_t n_op;
+  float* fval; uint64_t* felem; uint64_t n_float; const uint32_t* ftoff; const char* ftext;
+  uint32_t* plen; uint64_t* poff; uint8_t* pkind; uint8_t* ppre; uint64_t* psrc; uint64_t n_piece;
+  unsigned char* text; uint64_t n_text;
+  unsigned long long* bad;                                    // [0] bv_check, [1] bv_tags, [2] bv_oplen: the lowest bad record; [3] the first record at or behind the region's end
+};
+
+__device__ __forceinline__ uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
+__device__ __forceinline__ int ndig(uint64_t v) { int d = 1; while (v >= 10) { v /= 10; d++; } return d; }
+__device__ __forceinline__ int slen(int64_t v) { return v < 0 ? 1 + ndig((uint64_t)(-v)) : ndig((uint64_t)v); }
+__device__ __forceinline__ unsigned char* put_u(unsigned char* d, uint64_t v) {
+  const int k = ndig(v);
+  for (int i = k - 1; i >= 0; i--) { d[i] = (unsigned char)('0' + v % 10); v /= 10; }
+  return d + k;
+}
+__device__ __forceinline__ unsigned char* put_s(unsigned char* d, int64_t v) {
+  if (v < 0) { *d++ = '-'; return put_u(d, (uint64_t)(-v)); }
+  return put_u(d, (uint64_t)v);
+}
+// the last index i < n with a[i] <= x (a ascends, a[0] <= x)
+__device__ __forceinline__ uint64_t last_le(const uint64_t* __restrict__ a, uint64_t n, uint64_t x) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (a[mid] <= x) lo = mid + 1; else hi = mid; }
+  return lo - 1;
+}
+__device__ __forceinline__ int type_size(uint8_t t) {
+  switch (t) { case 'c': case 'C': case 'A': return 1; case 's': case 'S': return 2; case 'i': case 'I': case 'f': return 4; default: return 0; }
+}
+__device__ __forceinline__ int64_t int_value(const uint8_t* p, uint8_t t) {
+  switch (t) {
+    case 'c': return (int8_t)p[0];
+    case 'C': return p[0];
+    case 's': return (int16_t)le16(p);
+    case 'S': return le16(p);
+    case 'i': return (int32_t)le32(p);
+    default: return le32(p);
+  }
+}
+
+struct Core { int32_t ref, pos, next_ref, next_pos, tlen; uint32_t bs, l_name, mapq, n_cig, flag, l_seq; uint64_t fixed; };
+__device__ __forceinline__ Core core_of(const uint8_t* p) {
+  Core c;
+  c.bs = le32(p); c.ref = (int32_t)le32(p + 4); c.pos = (int32_t)le32(p + 8); c.l_name = p[12]; c.mapq = p[13]; c.n_cig = le16(p + 16); c.flag = le16(p + 18);
+  c.l_seq = le32(p + 20); c.next_ref = (int32_t)le32(p + 24); c.next_pos = (int32_t)le32(p + 28); c.tlen = (int32_t)le32(p + 32);
+  c.fixed = 32 + (uint64_t)c.l_name + 4ull * c.n_cig + ((uint64_t)c.l_seq + 1) / 2 + (uint64_t)c.l_seq;
+  return c;
+}
+
+__global__ void __launch_bounds__(256) bv_check(View V) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= V.n) return;
+  const uint8_t* p = V.data + V.pos[i];
+  const Core c = core_of(p);
+  const bool ok = (uint64_t)c.bs + 4 == V.pos[i + 1] - V.pos[i] && c.l_name >= 1 && c.fixed <= c.bs && p[36 + c.l_name - 1] == 0 && c.ref >= -1 && c.ref < V.n_ref;
+  if (!ok) atomicMin(&V.bad[0], (unsigned long long)i);
+}
+
+__global__ void __launch_bounds__(256) bv_select(View V) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= V.n) return;
+  const uint8_t* p = V.data + V.pos[i];
+  const uint32_t flag = le16(p + 18);
+  bool keep = (flag & V.req) == V.req && (flag & V.excl) == 0;
+  if (V.region) {
+    const int32_t ref = V.M.ref[i], pos = V.M.pos[i];
+    const bool inside = V.pos[i] < V.limit;
+    keep = keep && inside && ref == V.ref_id && (int64_t)pos < V.end && (int64_t)pos + (int64_t)V.M.span[i] > V.beg;
+    if (inside && ((uint32_t)ref > (uint32_t)V.ref_id || (ref == V.ref_id && (int64_t)pos >= V.end))) atomicMin(&V.bad[3], (unsigned long long)i);   // (refID -1 sorts last)
+  }
+  V.keep[i] = keep ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(256) bv_cut(View V) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < V.n && i >= V.bad[3]) V.keep[i] = 0;
+}
+
+// The tag at data[at, end): false when it ends behind `end` or names an unknown type.  *val = its value's offset (B: the first element), *count = elements (B),
+// bytes in front of the NUL (Z, H) or 1; *next = the byte behind it.
+__device__ __forceinline__ bool tag_at(const uint8_t* d, uint64_t at, uint64_t end, uint8_t* type, uint8_t* sub, uint64_t* val, uint32_t* count, uint64_t* next) {
+  if (end - at < 3) return false;
+  const uint8_t t = d[at + 2];
+  *type = t; *sub = 0; *val = at + 3; *count = 1;
+  const int sz = type_size(t);
+  if (sz) {
+    if (end - at < 3 + (uint64_t)sz) return false;
+    *next = at + 3 + sz;
+    return true;
+  }
+  if (t == 'Z' || t == 'H') {
+    uint64_t e = at + 3;
+    while (e < end && d[e]) e++;
+    if (e >= end) return false;
+    *count = (uint32_t)(e - (at + 3)); *next = e + 1;
+    return true;
+  }
+  if (t == 'B') {
+    if (end - at < 8) return false;
+    const uint8_t s = d[at + 3];
+    const int es = s == 'A' ? 0 : type_size(s);
+    if (!es) return false;
+    const uint32_t n = le32(d + at + 4);
+    if ((uint64_t)n * es > end - at - 8) return false;
+    *sub = s; *val = at + 8; *count = n; *next = at + 8 + (uint64_t)n * es;
+    return true;
+  }
+  return false;
+}
+
+__global__ void __launch_bounds__(256) bv_tags(View V) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= V.n) return;
+  uint32_t n_item = 0, n_elem = 0, n_float = 0, n_op = 0;
+  uint64_t ops = 0, cg = NONE;
+  if (V.keep[i]) {
+    const uint64_t at0 = V.pos[i];
+    const uint8_t* p = V.data + at0;
+    const Core c = core_of(p);
+    ops = at0 + 36 + c.l_name; n_op = c.n_cig;
+    const bool cg_form = c.n_cig == 2 && le32(V.data + ops) == ((c.l_seq << 4) | 4u) && (le32(V.data + ops + 4) & 15u) == 3u;
+    const uint64_t end = V.pos[i + 1];
+    uint64_t at = at0 + 4 + c.fixed;
+    bool ok = true;
+    while (at < end) {
+      uint8_t t, s; uint64_t val, next; uint32_t cnt;
+      if (!tag_at(V.data, at, end, &t, &s, &val, &cnt, &next)) { ok = false; break; }
+      if (cg_form && cg == NONE && V.data[at] == 'C' && V.data[at + 1] == 'G' && t == 'B' && s == 'I') { cg = at; ops = val; n_op = cnt; }
+      else {
+        n_item++;
+        if (t == 'f') { n_elem++; n_float++; }
+        else if (t == 'B') { n_elem += cnt; if (s == 'f') n_float += cnt; }
+      }
+      at = next;
+    }
+    if (!ok) { atomicMin(&V.bad[1], (unsigned long long)i); n_item = n_elem = n_float = n_op = 0; }
+  }
+  V.c_item[i] = n_item; V.c_elem[i] = n_elem; V.c_float[i] = n_float; V.c_op[i] = n_op;
+  V.ops_src[i] = ops; V.cg_at[i] = cg;
+}
+
+__global__ void __launch_bounds__(256) bv_items(View V) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= V.n || !V.keep[i] || V.item_off[i + 1] == V.item_off[i]) return;
+  const uint64_t at0 = V.pos[i], end = V.pos[i + 1], cg = V.cg_at[i];
+  const Core c = core_of(V.data + at0);
+  uint64_t at = at0 + 4 + c.fixed, j = V.item_off[i], e = V.elem_off[i], f = V.float_off[i];
+  while (at < end) {
+    uint8_t t, s; uint64_t val, next; uint32_t cnt;
+    if (!tag_at(V.data, at, end, &t, &s, &val, &cnt, &next)) break;   // (bv_tags walked the same bytes)
+    if (at != cg) {
+      Item I;
+      I.src = val; I.e0 = e; I.f0 = f; I.count = cnt; I.rec = (uint32_t)i; I.type = t; I.sub = s; I.t0 = V.data[at]; I.t1 = V.data[at + 1]; I.pad = 0;
+      V.item[j++] = I;
+      if (t == 'f') { e++; f++; }
+      else if (t == 'B') { e += cnt; if (s == 'f') f += cnt; }
+    }
+    at = next;
+  }
+}
+
+__global__ void __launch_bounds__(256) bv_oplen(View V) {
+  const uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= V.n_op) return;
+  const uint64_t r = last_le(V.op_off, V.n, o);
+  const uint32_t op = le32(V.data + V.ops_src[r] + 4 * (o - V.op_off[r]));
+  if ((op & 15u) > 8u) atomicMin(&V.bad[2], (unsigned long long)r);
+  V.oplen[o] = (uint32_t)ndig(op >> 4) + 1u;
+}
+
+// a lane per element: an integer's width; a float goes to the array the host prints
+__global__ void __launch_bounds__(256) bv_elemlen(View V) {
+  const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= V.n_elem) return;
+  uint64_t lo = 0, hi = V.n_item;                             // the last item with e0 <= e (items without elements share their e0 with the next)
+  while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (V.item[mid].e0 <= e) lo = mid + 1; else hi = mid; }
+  const Item I = V.item[lo - 1];
+  const uint64_t k = e - I.e0;
+  const uint8_t t = I.type == 'B' ? I.sub : I.type;
+  const uint8_t* p = V.data + I.src + k * type_size(t);
+  if (t == 'f') {
+    V.fval[I.f0 + k] = __uint_as_float(le32(p));
+    V.felem[I.f0 + k] = e | (I.type == 'B' ? 1ull << 63 : 0);
+    V.elen[e] = 0;
+  } else V.elen[e] = 1u + (uint32_t)slen(int_value(p, t));
+}
+
+__global__ void __launch_bounds__(256) bv_floatlen(View V) {
+  const uint64_t f = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= V.n_float) return;
+  const uint64_t x = V.felem[f];
+  V.elen[x & ~(1ull << 63)] = V.ftoff[f + 1] - V.ftoff[f] + (uint32_t)(x >> 63);
+}
+
+__device__ __forceinline__ uint32_t name_len(const View& V, int32_t ref) { return ref < 0 ? 1u : (uint32_t)(V.rname_off[ref + 1] - V.rname_off[ref]); }
+__device__ __forceinline__ unsigned char* put_name(const View& V, unsigned char* d, int32_t ref) {
+  if (ref < 0) { *d++ = '*'; return d; }
+  const uint64_t a = V.rname_off[ref], b = V.rname_off[ref + 1];
+  for (uint64_t k = a; k < b; k++) *d++ = (unsigned char)V.rname[k];
+  return d;
+}
+// RNEXT: a reference outside the table prints as '*' (only refID is checked: a mate's reference is not this record's to refuse)
+__device__ __forceinline__ int32_t next_ref_of(const View& V, const Core& c) { return c.next_ref >= V.n_ref ? -1 : c.next_ref; }
+
+// a lane per record: the lengths and kinds of its pieces
+__global__ void __launch_bounds__(256) bv_pieces(View V) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= V.n) return;
+  const uint64_t pb = 7 * i + V.item_off[i];
+  if (!V.keep[i]) {
+    for (int k = 0; k < 7; k++) { V.plen[pb + k] = 0; V.pkind[pb + k] = K_NONE; V.ppre[pb + k] = 0; V.psrc[pb + k] = 0; }
+    return;
+  }
+  const uint64_t at0 = V.pos[i];
+  const uint8_t* p = V.data + at0;
+  const Core c = core_of(p);
+  auto set = [&](uint64_t q, uint32_t len, uint8_t kind, uint8_t pre, uint64_t src) { V.plen[q] = len; V.pkind[q] = kind; V.ppre[q] = pre; V.psrc[q] = src; };
+  set(pb, c.l_name - 1, K_COPY, 0, at0 + 36);
+  set(pb + 1, 5u + ndig(c.flag) + name_len(V, c.ref) + slen((int64_t)c.pos + 1) + ndig(c.mapq), K_NONE, 0, 0);
+  const uint64_t o0 = V.op_off[i], o1 = V.op_off[i + 1];
+  set(pb + 2, o1 > o0 ? (uint32_t)(V.ooff[o1] - V.ooff[o0]) : 1u, o1 > o0 ? K_ELEM : K_NONE, 0, 0);
+  const int32_t nr = next_ref_of(V, c);
+  set(pb + 3, 4u + (nr >= 0 && nr == c.ref ? 1u : name_len(V, nr)) + slen((int64_t)c.next_pos + 1) + slen(c.tlen), K_NONE, 0, 0);
+  const uint64_t sq = at0 + 36 + c.l_name + 4ull * c.n_cig, ql = sq + ((uint64_t)c.l_seq + 1) / 2;
+  set(pb + 4, c.l_seq ? c.l_seq : 1u, c.l_seq ? K_SEQ : K_NONE, 0, sq);
+  const bool has_q = c.l_seq && V.data[ql] != 0xff;
+  set(pb + 5, 1u + (has_q ? c.l_seq : 1u), has_q ? K_QUAL : K_NONE, 1, ql);
+  const uint64_t j0 = V.item_off[i], j1 = V.item_off[i + 1];
+  for (uint64_t j = j0; j < j1; j++) {
+    const Item I = V.item[j];
+    const uint64_t q = pb + 6 + (j - j0);
+    if (I.type == 'A') set(q, 7, K_NONE, 7, 0);
+    else if (I.type == 'Z' || I.type == 'H') set(q, 6u + I.count, K_COPY, 6, I.src);
+    else if (I.type == 'f') set(q, 6u + (uint32_t)(V.eoff[I.e0 + 1] - V.eoff[I.e0]), K_ELEM, 6, 0);
+    else if (I.type == 'B') set(q, 7u + (uint32_t)(V.eoff[I.e0 + I.count] - V.eoff[I.e0]), K_ELEM, 7, 0);
+    else set(q, 6u + (uint32_t)slen(int_value(V.data + I.src, I.type)), K_NONE, 6, 0);
+  }
+  set(pb + 6 + (j1 - j0), 1, K_NONE, 1, 0);
+}
+
+// a lane per record: everything a lane prints
+__global__ void __launch_bounds__(256) bv_small(View V) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= V.n || !V.keep[i]) return;
+  const uint64_t pb = 7 * i + V.item_off[i];
+  const uint8_t* p = V.data + V.pos[i];
+  const Core c = core_of(p);
+  unsigned char* d = V.text + V.poff[pb + 1];
+  *d++ = '\t'; d = put_u(d, c.flag);
+  *d++ = '\t'; d = put_name(V, d, c.ref);
+  *d++ = '\t'; d = put_s(d, (int64_t)c.pos + 1);
+  *d++ = '\t'; d = put_u(d, c.mapq);
+  *d++ = '\t';
+  if (V.pkind[pb + 2] == K_NONE) V.text[V.poff[pb + 2]] = '*';
+  d = V.text + V.poff[pb + 3];
+  const int32_t nr = next_ref_of(V, c);
+  *d++ = '\t';
+  if (nr >= 0 && nr == c.ref) *d++ = '='; else d = put_name(V, d, nr);
+  *d++ = '\t'; d = put_s(d, (int64_t)c.next_pos + 1);
+  *d++ = '\t'; d = put_s(d, c.tlen);
+  *d++ = '\t';
+  if (V.pkind[pb + 4] == K_NONE) V.text[V.poff[pb + 4]] = '*';
+  d = V.text + V.poff[pb + 5];
+  *d++ = '\t';
+  if (V.pkind[pb + 5] == K_NONE) *d = '*';
+  const uint64_t j0 = V.item_off[i], j1 = V.item_off[i + 1];
+  for (uint64_t j = j0; j < j1; j++) {
+    const Item I = V.item[j];
+    d = V.text + V.poff[pb + 6 + (j - j0)];
+    const bool integer = I.type != 'A' && I.type != 'Z' && I.type != 'H' && I.type != 'f' && I.type != 'B';
+    *d++ = '\t'; *d++ = I.t0; *d++ = I.t1; *d++ = ':'; *d++ = integer ? 'i' : I.type; *d++ = ':';
+    if (I.type == 'A') *d = V.data[I.src];
+    else if (I.type == 'B') *d = I.sub;
+    else if (integer) put_s(d, int_value(V.data + I.src, I.type));
+  }
+  V.text[V.poff[pb + 6 + (j1 - j0)]] = '\n';
+}
+
+__global__ void __launch_bounds__(256) bv_ops(View V) {
+  const uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= V.n_op) return;
+  const uint64_t r = last_le(V.op_off, V.n, o), o0 = V.op_off[r];
+  const uint32_t op = le32(V.data + V.ops_src[r] + 4 * (o - o0));
+  unsigned char* d = put_u(V.text + V.poff[7 * r + V.item_off[r] + 2] + (V.ooff[o] - V.ooff[o0]), op >> 4);
+  *d = (unsigned char)"MIDNSHP=X???????"[op & 15u];
+}
+
+__global__ void __launch_bounds__(256) bv_elems(View V) {
+  const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= V.n_elem) return;
+  uint64_t lo = 0, hi = V.n_item;
+  while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (V.item[mid].e0 <= e) lo = mid + 1; else hi = mid; }
+  const uint64_t j = lo - 1;
+  const Item I = V.item[j];
+  const uint64_t k = e - I.e0;
+  const bool arr = I.type == 'B';
+  const uint8_t t = arr ? I.sub : I.type;
+  unsigned char* d = V.text + V.poff[7 * (uint64_t)I.rec + j + 6] + (arr ? 7 : 6) + (V.eoff[e] - V.eoff[I.e0]);
+  if (arr) *d++ = ',';
+  if (t == 'f') {
+    const uint64_t f = I.f0 + k;
+    for (uint32_t q = V.ftoff[f]; q < V.ftoff[f + 1]; q++) *d++ = (unsigned char)V.ftext[q];
+  } else put_s(d, int_value(V.data + I.src + k * type_size(t), t));
+}
+
+// n bases of the packed sequence `seq` from base j0 on to dst, by one wave: dst in aligned dwords, each lane two of them (eight bases) from one source
+// dword (and the byte behind it when the eight start in a byte's low nibble); bytes in front of the first aligned dword and behind the last whole eight.
+// A byte holds its first base in the high nibble: with the nibbles of every byte swapped, nibble m of the source is base m.
+__device__ __forceinline__ uint32_t four_bases(uint32_t v) {   // the four nibbles of v's low 16 bits, the first base lowest
+  const char* T = "=ACMGRSVTWYHKDBN";
+  return (uint32_t)(uint8_t)T[v & 15] | ((uint32_t)(uint8_t)T[(v >> 4) & 15] << 8) | ((uint32_t)(uint8_t)T[(v >> 8) & 15] << 16) | ((uint32_t)(uint8_t)T[(v >> 12) & 15] << 24);
+}
+__device__ __forceinline__ unsigned char base_at(const uint8_t* seq, uint64_t j) { return (unsigned char)"=ACMGRSVTWYHKDBN"[(seq[j >> 1] >> ((~j & 1) << 2)) & 15]; }
+__device__ __forceinline__ void wave_seq(unsigned char* dst, const uint8_t* seq, uint64_t j0, uint64_t n, int lane) {
+  const uint64_t head = min(n, (uint64_t)((4 - ((uintptr_t)dst & 3)) & 3));
+  if ((uint64_t)lane < head) dst[lane] = base_at(seq, j0 + lane);
+  dst += head; j0 += head; n -= head;
+  const uint64_t n8 = n >> 3;
+  uint32_t* d32 = (uint32_t*)dst;
+  for (uint64_t i = lane; i < n8; i += 64) {
+    const uint64_t j = j0 + 8 * i;
+    const uint8_t* s = seq + (j >> 1);
+    uint64_t w = ld32(s);
+    if (j & 1) w |= (uint64_t)s[4] << 32;                      // (base j + 7 is the high nibble of s[4]: inside the sequence)
+    uint64_t x = ((w & 0x0f0f0f0f0full) << 4) | ((w >> 4) & 0x0f0f0f0f0full);
+    if (j & 1) x >>= 4;
+    d32[2 * i] = four_bases((uint32_t)x & 0xffffu); d32[2 * i + 1] = four_bases((uint32_t)(x >> 16) & 0xffffu);
+  }
+  const uint64_t done = 8 * n8, tail = n - done;              // at most 7 bases
+  if ((uint64_t)lane < tail) dst[done + lane] = base_at(seq, j0 + done + lane);
+}
+
+// n qualities from src to dst, + 33, by one wave (wave_copy's shape)
+__device__ __forceinline__ void wave_qual(unsigned char* dst, const unsigned char* src, uint64_t n, int lane) {
+  const uint64_t head = min(n, (uint64_t)((4 - ((uintptr_t)dst & 3)) & 3));
+  if ((uint64_t)lane < head) dst[lane] = (unsigned char)(src[lane] + 33);
+  dst += head; src += head; n -= head;
+  const uint64_t nd = n >> 2;
+  uint32_t* d32 = (uint32_t*)dst;
+  for (uint64_t i = lane; i < nd; i += 64) {
+    const uint32_t v = ld32(src + 4 * i);
+    d32[i] = ((v & 0x7f7f7f7fu) + 0x21212121u) ^ (v & 0x80808080u);   // a byte-wise add: no carry leaves its byte
+  }
+  const uint64_t tail = n & 3;
+  if ((uint64_t)lane < tail) dst[4 * nd + lane] = (unsigned char)(src[4 * nd + lane] + 33);
+}
+
+__global__ void __launch_bounds__(256) bv_bulk(View V) {
+  const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  chunk_walk<CHUNK>(V.n_text, V.n_piece, V.poff, wave, n_waves, [&](uint64_t q, uint64_t b, uint64_t end, uint64_t lo, uint64_t hi) {
+    const int kind = V.pkind[q];
+    if (kind == K_NONE || kind == K_ELEM) return;
+    const uint64_t wb = b + V.ppre[q], from = max(lo, wb), to = min(hi, end);
+    if (to <= from) return;
+    const uint8_t* src = V.data + V.psrc[q];
+    if (kind == K_COPY) wave_copy(V.text + from, src + (from - wb), to - from, lane);
+    else if (kind == K_QUAL) wave_qual(V.text + from, src + (from - wb), to - from, lane);
+    else wave_seq(V.text + from, src, from - wb, to - from, lane);
+  });
+}
+
+struct Timer {
+  hipEvent_t a = nullptr, b = nullptr; hipStream_t st;
+  explicit Timer(hipStream_t s) : st(s) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, st); }
+  double stop() { float ms = 0; (void)hipEventRecord(b, st); (void)hipEventSynchronize(b); (void)hipEventElapsedTime(&ms, a, b); return ms; }
+  ~Timer() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
+};
+unsigned blocks_of(uint64_t lanes) { return (unsigned)((lanes + 255) / 256); }
+unsigned wave_blocks(lra_ctx* ctx, uint64_t waves) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((waves + 3) / 4, (uint64_t)ctx->num_cu * 32)); }
+// the view's own arrays: an eighth of slack so that windows of about one size do not allocate anew; contents are not kept
+template <typename T> struct Buf {
+  T* p = nullptr; size_t n = 0;
+  bool ensure(size_t want) {
+    if (want <= n) return true;
+    if (p) (void)hipFree(p);
+    p = nullptr; n = 0;
+    const size_t m = want + want / 8 + 16;
+    if (hipMalloc((void**)&p, m * sizeof(T)) != hipSuccess) return false;
+    n = m;
+    return true;
+  }
+  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+};
+double wall_ms(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+bool read_header(const std::string& path, uint64_t hdr, std::vector<uint8_t>& out, std::string& why) {
+  lra_bgzf_source src;
+  src.fd = open(path.c_str(), O_RDONLY);
+  if (src.fd < 0) { why = "cannot open it"; return false; }
+  out.clear();
+  bool ok = true;
+  while (ok && out.size() < hdr) {
+    uint32_t isize = 0;
+    if (!src.peek(&isize)) { why = src.err.empty() ? "the file ends inside the header" : src.err; ok = false; break; }
+    const size_t at = out.size();
+    out.resize(at + isize);
+    if (!src.take(out.data() + at)) { why = src.err; ok = false; }
+  }
+  close(src.fd);
+  if (ok) out.resize(hdr);
+  return ok;
+}
+
+}  // namespace
+
+struct lra_bam_view {
+  lra_ctx* ctx = nullptr;
+  std::string path, bai_path;
+  int fd = -1;
+  uint64_t window = 0, hdr = 0;
+  std::vector<uint8_t> header; lra_merge_refs refs; std::vector<const char*> name_ptr;
+  bool has_index = false; lra_bai_file bai;
+  uint32_t req = 0, excl = 0;
+  lra_bgzf_step z;
+  // the pass
+  int mode = 0;                                               // 0: none, 1: the whole file, 2: a region
+  int32_t ref_id = 0; int64_t beg = 0, end = 0;
+  std::vector<lra_bai_chunk> plan; size_t ci = 0; bool chunk_open = false, over = true;
+  uint64_t skip = 0, want = 0, rec_base = 0, carry_voff = 0;
+  std::string pend_err;
+  // the window
+  Buf<uint8_t> rname, pkind, ppre, text, ftext; Buf<uint64_t> rname_off, pos, misc, item_off, elem_off, float_off, op_off, ops_src, cg_at, eoff, ooff, felem, poff, psrc;
+  Buf<uint32_t> keep, mspan, mbf, c_item, c_elem, c_float, c_op, elen, oplen, ftoff, plen; Buf<int32_t> mref, mpos; Buf<Item> item; Buf<float> fval;
+  PinBuf<char> h_text;
+  struct lra_bam_view_stats S{};
+
+  void release_all() {
+    z.release();
+    rname.release(); pkind.release(); ppre.release(); text.release(); ftext.release(); rname_off.release(); pos.release(); misc.release(); item_off.release();
+    elem_off.release(); float_off.release(); op_off.release(); ops_src.release(); cg_at.release(); eoff.release(); ooff.release(); felem.release(); poff.release();
+    psrc.release(); keep.release(); mspan.release(); mbf.release(); c_item.release(); c_elem.release(); c_float.release(); c_op.release(); elen.release();
+    oplen.release(); ftoff.release(); plen.release(); mref.release(); mpos.release(); item.release(); fval.release(); h_text.release();
+  }
+  // a refusal ends the pass; the view takes another
+  int fail(int code, const char* fmt, ...) __attribute__((format(printf, 3, 4))) {
+    char buf[1024];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    (void)hipStreamSynchronize(ctx->stream);
+    over = true; chunk_open = false; pend_err.clear();
+    return lra_set_err(ctx, code, "%s", buf);
+  }
+  template <class T> bool grab(Buf<T>& b, size_t want_items) { if (b.ensure(want_items)) return true; (void)hipGetLastError(); return false; }
+  std::string where(uint64_t idx) const {                     // a record of the window, for a refusal's text
+    if (mode == 1) return "record " + std::to_string(rec_base + idx);
+    return "record " + std::to_string(idx) + " of the records read from compressed offset " + std::to_string(z.file_off);
+  }
+  uint64_t voff(uint64_t p) const {                           // the virtual offset of decoded position p (at or behind the carry) of the step's data
+    const std::vector<uint64_t>& o = z.out_off;
+    const size_t m = (size_t)(std::upper_bound(o.begin(), o.end(), p) - o.begin()) - 1;
+    return ((z.file_off + z.in_off[m]) << 16) | (p - o[m]);
+  }
+  uint64_t limit_of(uint64_t ve) const;
+  int start_pass();
+  int window_text(uint64_t n, uint64_t limit, uint64_t* len, uint64_t* n_rec, uint64_t* bad_idx, uint64_t* bad_pos, std::string* bad_why, uint64_t* stop_idx);
+  int next(const char** h_text_out, uint64_t* len, uint64_t* n_records);
+};
+
+// the decoded position in front of which the records of a chunk that ends at virtual offset ve start
+uint64_t lra_bam_view::limit_of(uint64_t ve) const {
+  const uint64_t ce = ve >> 16, ue = ve & 0xffff, base = z.file_off, carry = z.out_off[0];
+  if (ce < base) return carry && carry_voff < ve ? 1 : 0;      // the chunk ends in the members before: only the carried record can start inside it
+  const std::vector<uint64_t>& in = z.in_off;
+  const size_t m = (size_t)(std::lower_bound(in.begin(), in.end(), ce - base) - in.begin());
+  if (m == in.size()) return ~0ull;
+  return in[m] == ce - base ? z.out_off[m] + ue : z.out_off[m];
+}
+
+int lra_bam_view::start_pass() {
+  (void)hipStreamSynchronize(ctx->stream);
+  over = false; chunk_open = false; ci = 0; pend_err.clear(); rec_base = 0; carry_voff = 0;
+  if (mode == 1) {
+    if (lseek(fd, 0, SEEK_SET) != 0) return fail(LRA_ERR_INVALID, "lra_bam_view: cannot seek in %s", path.c_str());
+    z.reset(); skip = hdr; want = window; chunk_open = true;
+  }
+  return LRA_OK;
+}
+
+// The text of the window's records [0, n): the first n of the framed ones.  *bad_idx < n: that record is refused (*bad_why) and nothing was printed.
+int lra_bam_view::window_text(uint64_t n, uint64_t limit, uint64_t* len, uint64_t* n_rec, uint64_t* bad_idx, uint64_t* bad_pos, std::string* bad_why, uint64_t* stop_idx) {
+  hipStream_t st = ctx->stream;
+  *len = 0; *n_rec = 0; *bad_idx = NONE; *stop_idx = NONE;
+  const int n_ref = refs.n_ref;
+  View V; memset(&V, 0, sizeof V);
+  V.data = z.data; V.pos = pos.p; V.n = n; V.n_ref = n_ref; V.req = req; V.excl = excl;
+  V.region = mode == 2; V.ref_id = ref_id; V.beg = beg; V.end = end; V.limit = limit;
+  V.rname = (const char*)rname.p; V.rname_off = rname_off.p;
+  bool ok = grab(keep, n) && grab(c_item, n) && grab(c_elem, n) && grab(c_float, n) && grab(c_op, n) && grab(item_off, n + 1) && grab(elem_off, n + 1) &&
+            grab(float_off, n + 1) && grab(op_off, n + 1) && grab(ops_src, n) && grab(cg_at, n);
+  if (ok && V.region) ok = grab(mref, n) && grab(mpos, n) && grab(mspan, n) && grab(mbf, n);
+  if (!ok) return fail(LRA_ERR_NOMEM, "lra_bam_view: hipMalloc failed for the arrays of %llu records", (unsigned long long)n);
+  V.keep = keep.p; V.M = Meta{mref.p, mpos.p, mspan.p, mbf.p};
+  V.c_item = c_item.p; V.c_elem = c_elem.p; V.c_float = c_float.p; V.c_op = c_op.p;
+  V.item_off = item_off.p; V.elem_off = elem_off.p; V.float_off = float_off.p; V.op_off = op_off.p; V.ops_src = ops_src.p; V.cg_at = cg_at.p;
+  V.bad = (unsigned long long*)(misc.p + 8);
+  unsigned long long res[4];
+  {
+    Timer T(st);
+    LRA_HIP_CHECK(ctx, hipMemsetAsync(V.bad, 0xff, 32, st));
+    hipLaunchKernelGGL(bv_check, dim3(blocks_of(n)), dim3(256), 0, st, V);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.bad, 32, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (res[0] < n) {
+      S.ms_frame_select += T.stop();
+      *bad_idx = res[0];
+      LRA_HIP_CHECK(ctx, hipMemcpyAsync(bad_pos, pos.p + res[0], 8, hipMemcpyDeviceToHost, st));
+      LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+      *bad_why = "is shorter than its fields say, has no NUL behind its name, or names a reference outside [-1, " + std::to_string(n_ref) + ")";
+      return LRA_OK;
+    }
+    if (V.region) hipLaunchKernelGGL(bs_span, dim3(wave_blocks(ctx, n)), dim3(256), 0, st, n, V.data, V.pos, V.M);
+    hipLaunchKernelGGL(bv_select, dim3(blocks_of(n)), dim3(256), 0, st, V);
+    if (V.region) hipLaunchKernelGGL(bv_cut, dim3(blocks_of(n)), dim3(256), 0, st, V);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    S.ms_frame_select += T.stop();
+  }
+  uint64_t tot[4] = {0, 0, 0, 0};                             // items, elements, floats, ops
+  {
+    Timer T(st);
+    hipLaunchKernelGGL(bv_tags, dim3(blocks_of(n)), dim3(256), 0, st, V);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    if (lra_exclusive_scan<uint32_t>(ctx, (long)n, c_item.p, item_off.p) || lra_exclusive_scan<uint32_t>(ctx, (long)n, c_elem.p, elem_off.p) ||
+        lra_exclusive_scan<uint32_t>(ctx, (long)n, c_float.p, float_off.p) || lra_exclusive_scan<uint32_t>(ctx, (long)n, c_op.p, op_off.p))
+      return fail(LRA_ERR_HIP, "lra_bam_view: a scan failed");
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&tot[0], item_off.p + n, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&tot[1], elem_off.p + n, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&tot[2], float_off.p + n, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&tot[3], op_off.p + n, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.bad, 32, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    *stop_idx = res[3];
+    if (res[1] < n) {
+      S.ms_tags_lengths += T.stop();
+      *bad_idx = res[1]; *bad_why = "has an aux block that ends inside a tag or names an unknown type";
+      return LRA_OK;
+    }
+    V.n_item = tot[0]; V.n_elem = tot[1]; V.n_float = tot[2]; V.n_op = tot[3];
+    V.n_piece = 7 * n + V.n_item;
+    if (!(grab(item, V.n_item) && grab(elen, V.n_elem) && grab(eoff, V.n_elem + 1) && grab(oplen, V.n_op) && grab(ooff, V.n_op + 1) && grab(fval, V.n_float) &&
+          grab(felem, V.n_float) && grab(ftoff, V.n_float + 1) && grab(plen, V.n_piece) && grab(poff, V.n_piece + 1) && grab(pkind, V.n_piece) &&
+          grab(ppre, V.n_piece) && grab(psrc, V.n_piece)))
+      return fail(LRA_ERR_NOMEM, "lra_bam_view: hipMalloc failed for the pieces of %llu records (%llu tags, %llu array elements, %llu CIGAR ops)", (unsigned long long)n,
+                  (unsigned long long)V.n_item, (unsigned long long)V.n_elem, (unsigned long long)V.n_op);
+    V.item = item.p; V.elen = elen.p; V.eoff = eoff.p; V.oplen = oplen.p; V.ooff = ooff.p; V.fval = fval.p; V.felem = felem.p; V.ftoff = ftoff.p;
+    V.plen = plen.p; V.poff = poff.p; V.pkind = pkind.p; V.ppre = ppre.p; V.psrc = psrc.p;
+    if (V.n_item) hipLaunchKernelGGL(bv_items, dim3(blocks_of(n)), dim3(256), 0, st, V);
+    if (V.n_op) hipLaunchKernelGGL(bv_oplen, dim3(blocks_of(V.n_op)), dim3(256), 0, st, V);
+    if (V.n_elem) hipLaunchKernelGGL(bv_elemlen, dim3(blocks_of(V.n_elem)), dim3(256), 0, st, V);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    if (lra_exclusive_scan<uint32_t>(ctx, (long)V.n_op, oplen.p, ooff.p)) return fail(LRA_ERR_HIP, "lra_bam_view: a scan failed");
+    S.ms_tags_lengths += T.stop();
+  }
+  if (V.n_float) {                                             // the floats' round trip: one array out, their text back
+    Timer T(st);
+    std::vector<float> hv((size_t)V.n_float);
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(hv.data(), fval.p, 4 * V.n_float, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    std::vector<uint32_t> to((size_t)V.n_float + 1, 0);
+    std::string txt;
+    char b[64];
+    for (uint64_t f = 0; f < V.n_float; f++) { const int k = snprintf(b, sizeof b, "%.6g", (double)hv[(size_t)f]); txt.append(b, (size_t)k); to[(size_t)f + 1] = (uint32_t)txt.size(); }
+    if (!grab(ftext, txt.size() + 1)) return fail(LRA_ERR_NOMEM, "lra_bam_view: hipMalloc failed for the text of %llu floats", (unsigned long long)V.n_float);
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(ftoff.p, to.data(), 4 * (V.n_float + 1), hipMemcpyHostToDevice, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(ftext.p, txt.data(), txt.size(), hipMemcpyHostToDevice, st));
+    V.ftext = (const char*)ftext.p;
+    hipLaunchKernelGGL(bv_floatlen, dim3(blocks_of(V.n_float)), dim3(256), 0, st, V);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));              // (the host arrays leave scope)
+    S.ms_floats += T.stop();
+  }
+  uint64_t total = 0, kept = 0;
+  {
+    Timer T(st);
+    if (lra_exclusive_scan<uint32_t>(ctx, (long)V.n_elem, elen.p, eoff.p)) return fail(LRA_ERR_HIP, "lra_bam_view: a scan failed");
+    hipLaunchKernelGGL(bv_pieces, dim3(blocks_of(n)), dim3(256), 0, st, V);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    if (lra_exclusive_scan<uint32_t>(ctx, (long)V.n_piece, plen.p, poff.p)) return fail(LRA_ERR_HIP, "lra_bam_view: a scan failed");
+    if (lra_exclusive_scan<uint32_t>(ctx, (long)n, keep.p, float_off.p)) return fail(LRA_ERR_HIP, "lra_bam_view: a scan failed");   // (float_off is done with: the kept records)
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&total, poff.p + V.n_piece, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&kept, float_off.p + n, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.bad, 32, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    S.ms_tags_lengths += T.stop();
+    if (res[2] < n) { *bad_idx = res[2]; *bad_why = "has a CIGAR op code above 8"; return LRA_OK; }
+  }
+  if (!total) return LRA_OK;
+  if (!grab(text, total + 64)) return fail(LRA_ERR_NOMEM, "lra_bam_view: hipMalloc of %llu bytes for a window's text failed", (unsigned long long)total);
+  V.text = text.p; V.n_text = total;
+  {
+    Timer T(st);
+    hipLaunchKernelGGL(bv_small, dim3(blocks_of(n)), dim3(256), 0, st, V);
+    if (V.n_op) hipLaunchKernelGGL(bv_ops, dim3(blocks_of(V.n_op)), dim3(256), 0, st, V);
+    if (V.n_elem) hipLaunchKernelGGL(bv_elems, dim3(blocks_of(V.n_elem)), dim3(256), 0, st, V);
+    hipLaunchKernelGGL(bv_bulk, dim3(wave_blocks(ctx, (total + CHUNK - 1) / CHUNK)), dim3(256), 0, st, V);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    S.ms_emit += T.stop();
+  }
+  {
+    Timer T(st);
+    if (!h_text.ensure(total + 1, 0, st)) return fail(LRA_ERR_NOMEM, "lra_bam_view: hipHostMalloc of %llu bytes for a window's text failed", (unsigned long long)total);
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(h_text.p, text.p, total, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    S.ms_copy += T.stop();
+  }
+  *len = total; *n_rec = kept;
+  return LRA_OK;
+}
+
+int lra_bam_view::next(const char** out, uint64_t* len, uint64_t* n_records) {
+  hipStream_t st = ctx->stream;
+  *out = nullptr; *len = 0; if (n_records) *n_records = 0;
+  for (;;) {
+    if (over) return LRA_OK;
+    if (!pend_err.empty()) { const std::string e = pend_err; return fail(LRA_ERR_INVALID, "%s", e.c_str()); }
+    if (!chunk_open) {
+      if (mode != 2 || ci >= plan.size()) { over = true; return LRA_OK; }
+      const uint64_t vb = plan[ci].beg;
+      if (lseek(fd, (off_t)(vb >> 16), SEEK_SET) < 0) return fail(LRA_ERR_INVALID, "lra_bam_view: cannot seek in %s", path.c_str());
+      z.reset(); z.file_off = vb >> 16; skip = vb & 0xffff; carry_voff = 0; chunk_open = true;
+      want = std::min(window, (plan[ci].end >> 16) - (vb >> 16) + 65536);   // the chunk's members and the one its end lies in: a short chunk is a short read
+    }
+    // the window
+    const auto t0 = std::chrono::steady_clock::now();
+    const off_t f0 = lseek(fd, 0, SEEK_CUR);
+    const uint64_t carry = z.dec_len - z.dec_used;
+    uint64_t w = want;
+    const int rc = z.fill(ctx, fd, &w, lra_bgzf_launch_inflate_lut, "view_h2d", "view_inflate");
+    want = w;
+    if (rc == LRA_ERR_NOMEM) return fail(rc, "lra_bam_view: %s failed for a window of %s", z.nomem_pinned ? "hipHostMalloc" : "hipMalloc", path.c_str());
+    if (rc == LRA_ERR_INVALID) return fail(rc, "lra_bam_view: read of %s failed", path.c_str());
+    if (rc) { over = true; return rc; }
+    S.ms_read_inflate += wall_ms(t0);
+    S.windows++;
+    S.bytes_read += (uint64_t)std::max<off_t>(lseek(fd, 0, SEEK_CUR) - f0, 0);
+    S.bytes_inflated += z.dlen - std::min(carry, z.dlen);
+    const uint64_t dlen = z.dlen, start = std::min(skip, dlen);
+    const bool fault = !z.err.empty();
+    if (dlen == start && !z.at_end) { z.commit(dlen); skip -= start; continue; }   // nothing but the header (or the bytes in front of the chunk) so far
+    const uint64_t limit = mode == 2 ? limit_of(plan[ci].end) : ~0ull;
+    const uint64_t cap = (dlen - start) / 36 + 1;
+    if (!grab(pos, cap + 1) || !grab(misc, 64)) return fail(LRA_ERR_NOMEM, "lra_bam_view: hipMalloc failed for the record starts of a window");
+    uint64_t fr[4] = {0, start, 0, 0};
+    if (dlen > start) {
+      Timer T(st);
+      lra_bam_launch_frame(st, z.data, start, dlen, pos.p, cap, misc.p);
+      LRA_HIP_CHECK(ctx, hipGetLastError());
+      LRA_HIP_CHECK(ctx, hipMemcpyAsync(fr, misc.p, 32, hipMemcpyDeviceToHost, st));
+      LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+      S.ms_frame_select += T.stop();
+    }
+    uint64_t n = fr[0];
+    const uint64_t used = fr[1];
+    const bool more_in_chunk = limit > used;                   // the record that starts at `used`, if there is one, belongs to the chunk
+    if (n == 0 && !fr[2] && !z.at_end && more_in_chunk) { want = std::max(want, z.comp_len) * 2; continue; }   // a record larger than the window: read on, twice as much
+    bool last = z.at_end;
+    std::string tail_err, rec_err;                             // what is wrong behind the window's whole records; a record among them that is refused
+    if (more_in_chunk) {
+      if (fr[2]) tail_err = "lra_bam_view: " + path + ": " + where(n) + " is a bad record (block_size " + std::to_string(fr[3]) + ")";
+      else if (fault) tail_err = "lra_bam_view: " + path + ": " + z.err;
+      else if (z.at_end && used < dlen) tail_err = "lra_bam_view: " + path + ": " + where(n) + " is cut by the end of the file";
+    }
+    uint64_t tlen = 0, nrec = 0, stop_idx = NONE;
+    if (n) {
+      LRA_HIP_CHECK(ctx, hipMemcpyAsync(pos.p + n, misc.p + 1, 8, hipMemcpyDeviceToDevice, st));
+      for (;;) {
+        uint64_t bad_idx = NONE, bad_pos = 0; std::string why;
+        if (int r2 = window_text(n, limit, &tlen, &nrec, &bad_idx, &bad_pos, &why, &stop_idx)) return r2;
+        if (bad_idx >= n) break;
+        if (!(mode == 2 && bad_pos >= limit)) rec_err = "lra_bam_view: " + path + ": " + where(bad_idx) + " " + why;   // (a record behind the chunk's end is not this pass's to refuse)
+        n = bad_idx; tlen = nrec = 0;                          // the records in front of it go first
+        if (!n) break;
+      }
+    }
+    if (stop_idx != NONE) { tail_err.clear(); rec_err.clear(); }   // the pass ends in front of both
+    pend_err = !rec_err.empty() ? rec_err : tail_err;
+    const bool ended = mode == 2 && (stop_idx != NONE || !more_in_chunk);
+    if (ended || last || fr[2] || !pend_err.empty()) {
+      chunk_open = false;
+      if (mode == 2) ci++; else if (pend_err.empty()) over = true;
+    } else {
+      carry_voff = voff(used);
+      z.commit(used); rec_base += n; skip = 0; want = window;
+    }
+    S.records += nrec; S.bytes_text += tlen;
+    if (tlen) { *out = h_text.p; *len = tlen; if (n_records) *n_records = nrec; return LRA_OK; }
+  }
+}
+
+extern "C" int lra_bam_view_create(lra_ctx* ctx, const char* bam_path, const char* bai_path, uint64_t window_bytes, lra_bam_view** out) {
+  if (!ctx || !bam_path || !out) return LRA_ERR_INVALID;
+  *out = nullptr;
+  std::unique_ptr<lra_bam_view> v(new lra_bam_view());
+  v->ctx = ctx; v->path = bam_path;
+  v->window = window_bytes ? std::max(window_bytes, MIN_WINDOW) : DEFAULT_WINDOW;
+  if (lra_hts_sniff(v->path, &v->hdr) != LRA_IN_BAM) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: %s is not a BAM file", bam_path);
+  std::string why;
+  if (!read_header(v->path, v->hdr, v->header, why)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: %s: %s", bam_path, why.c_str());
+  if (!lra_merge_parse_refs(v->header.data(), v->header.size(), v->refs)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: %s: not a valid BAM header", bam_path);
+  for (const std::string& s : v->refs.name) v->name_ptr.push_back(s.c_str());
+  if (bai_path) {
+    v->bai_path = bai_path;
+    const int fd = open(bai_path, O_RDONLY);
+    if (fd < 0) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: cannot open %s", bai_path);
+    std::vector<uint8_t> b;
+    const off_t sz = lseek(fd, 0, SEEK_END);
+    bool ok = sz >= 0 && lseek(fd, 0, SEEK_SET) == 0;
+    uint64_t got = 0;
+    if (ok) { b.resize((size_t)sz); ok = lra_read_all(fd, b.data(), (uint64_t)sz, &got) && got == (uint64_t)sz; }
+    close(fd);
+    if (!ok) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: read of %s failed", bai_path);
+    if (!lra_bai_read(b.data(), b.size(), v->refs.n_ref, v->bai, why)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: %s: %s", bai_path, why.c_str());
+    v->has_index = true;
+  }
+  v->fd = open(bam_path, O_RDONLY);
+  if (v->fd < 0) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: cannot open %s", bam_path);
+  // the reference names, on the device: RNAME and RNEXT are copies of them
+  LRA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  std::string names; std::vector<uint64_t> off(1, 0);
+  for (const std::string& s : v->refs.name) { names += s; off.push_back(names.size()); }
+  if (!v->rname.ensure(names.size() + 1) || !v->rname_off.ensure(off.size())) {
+    (void)hipGetLastError(); close(v->fd); v->release_all();
+    return lra_set_err(ctx, LRA_ERR_NOMEM, "lra_bam_view_create: hipMalloc failed for the reference names");
+  }
+  hipError_t e = hipMemcpyAsync(v->rname_off.p, off.data(), 8 * off.size(), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && !names.empty()) e = hipMemcpyAsync(v->rname.p, names.data(), names.size(), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) { close(v->fd); v->release_all(); return lra_set_err(ctx, LRA_ERR_HIP, "lra_bam_view_create: %s", hipGetErrorString(e)); }
+  *out = v.release();
+  return LRA_OK;
+}
+
+extern "C" void lra_bam_view_destroy(lra_bam_view* v) {
+  if (!v) return;
+  (void)hipSetDevice(v->ctx->device);
+  (void)hipStreamSynchronize(v->ctx->stream);
+  v->release_all();
+  if (v->fd >= 0) close(v->fd);
+  delete v;
+}
+
+extern "C" int lra_bam_view_header(lra_bam_view* v, const char** text, uint64_t* text_len, int* n_ref, const char* const** names, const uint64_t** ref_len) {
+  if (!v) return LRA_ERR_INVALID;
+  if (text) *text = (const char*)v->header.data() + 8;
+  if (text_len) *text_len = lra_bai_le32(v->header.data() + 4);
+  if (n_ref) *n_ref = v->refs.n_ref;
+  if (names) *names = v->name_ptr.data();
+  if (ref_len) *ref_len = v->refs.len.data();
+  return LRA_OK;
+}
+
+extern "C" int lra_bam_view_set_flags(lra_bam_view* v, uint32_t require, uint32_t exclude) {
+  if (!v) return LRA_ERR_INVALID;
+  v->req = require; v->excl = exclude;
+  return LRA_OK;
+}
+
+extern "C" int lra_bam_view_all(lra_bam_view* v) {
+  if (!v) return LRA_ERR_INVALID;
+  LRA_HIP_CHECK(v->ctx, hipSetDevice(v->ctx->device));
+  v->mode = 1; v->plan.clear();
+  return v->start_pass();
+}
+
+extern "C" int lra_bam_view_region(lra_bam_view* v, int32_t ref_id, int64_t beg, int64_t end) {
+  if (!v) return LRA_ERR_INVALID;
+  lra_ctx* ctx = v->ctx;
+  LRA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  v->over = true;
+  if (!v->has_index) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_region: %s was opened without an index", v->path.c_str());
+  std::string why;
+  if (ref_id >= 0 && ref_id < v->refs.n_ref && end > (int64_t)v->refs.len[(size_t)ref_id]) end = std::max<int64_t>((int64_t)v->refs.len[(size_t)ref_id], std::min(beg, end));
+  std::vector<lra_bai_chunk> plan;
+  if (!lra_bai_plan(v->bai, ref_id, beg, end, plan, why)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_region: %s: %s", v->path.c_str(), why.c_str());
+  // Chunks that lie less than a window of compressed bytes apart are read as one: a member inflates in about 10 ms whatever else the device does, so a
+  // step per chunk costs more than the bytes between two chunks.  The records between them are in file order like the rest and fail the overlap test.
+  size_t o = 0;
+  for (size_t i = 0; i < plan.size(); i++) {
+    if (o && (plan[i].beg >> 16) - (plan[o - 1].end >> 16) < v->window) plan[o - 1].end = plan[i].end;
+    else plan[o++] = plan[i];
+  }
+  plan.resize(o);
+  v->mode = 2; v->ref_id = ref_id; v->beg = beg; v->end = end; v->plan.swap(plan);
+  return v->start_pass();
+}
+
+extern "C" int lra_bam_view_next(lra_bam_view* v, const char** h_text, uint64_t* len, uint64_t* n_records) {
+  if (!v || !h_text || !len) return LRA_ERR_INVALID;
+  LRA_HIP_CHECK(v->ctx, hipSetDevice(v->ctx->device));
+  return v->next(h_text, len, n_records);
+}
+
+extern "C" int lra_bam_view_stats(lra_bam_view* v, struct lra_bam_view_stats* out) {
+  if (!v || !out) return LRA_ERR_INVALID;
+  *out = v->S;
+  return LRA_OK;
+}
+
+extern "C" int lra_bai_query_host(const uint8_t* bai, uint64_t bai_len, int n_ref, int32_t ref_id, int64_t beg, int64_t end, const uint64_t** chunks, uint64_t* n_chunks) {
+  static thread_local std::vector<uint64_t> flat;
+  if (!chunks || !n_chunks) return LRA_ERR_INVALID;
+  *chunks = nullptr; *n_chunks = 0;
+  std::vector<lra_bai_chunk> plan; std::string why;
+  if (lra_bai_query(bai, bai_len, n_ref, ref_id, beg, end, plan, why)) return LRA_ERR_INVALID;
+  flat.clear();
+  for (const lra_bai_chunk& c : plan) { flat.push_back(c.beg); flat.push_back(c.end); }
+  *chunks = flat.data(); *n_chunks = plan.size();
+  return LRA_OK;
+}

@@ -40,6 +40,7 @@ struct lra_bgzf_step {
   // what fill() found
   const uint8_t* data = nullptr; uint64_t dlen = 0;   // the step's data: the carry, then the members in front of the first fault; zeros up to padded_tiles(dlen)
   uint64_t stop = 0;                               // the compressed bytes the step's members take
+  std::vector<uint64_t> in_off, out_off;           // the step's member table (lra_bgzf_members'): compressed offsets from file_off, decoded offsets in data
   bool at_end = false;                             // no byte of the file's data is behind this step: the end of the file, or a fault (err)
   std::string err;                                 // the BGZF fault text (zsource.hip: offset and reason): a member's status wins over the walk's stop
   size_t nomem_pinned = 0;                         // fill() returned LRA_ERR_NOMEM: the page-locked bytes it asked for (0: a device allocation failed)

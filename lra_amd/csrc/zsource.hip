@@ -126,6 +126,7 @@ int lra_bgzf_step::fill(lra_ctx* ctx, int fd, uint64_t* want, lra_inflate_launch
   if (good < nb) err = block_error(file_off + m.in_off[good], lra_bgzf_reason(bst[good]));
   else if (m.block_err) err = block_error(file_off + m.p, m.block_err);
   data = d_dec[dst].p; dlen = m.out_off[good]; stop = m.p;
+  in_off.swap(m.in_off); out_off.swap(m.out_off);
   at_end = !err.empty() || (file_eof && m.p == comp_len);
   LRA_HIP_CHECK(ctx, hipMemsetAsync(d_dec[dst].p + dlen, 0, padded_tiles(dlen) - dlen, st));
   return LRA_OK;
