@@ -702,7 +702,8 @@ int lra_between_anchors_batch(lra_ctx* ctx, int n, const char* d_qseq, const uin
  * (is_ont: clr / ont vs contig / ccs), and the PWL parameters of the sparse DP.
  * Output (context-owned): the SegAlignments each job pushes, in order: alignments d_job_aln_off[j] .. d_job_aln_off[j+1], each with strand,
  * Supplymentary, ISsecondary, NumOfAnchors0 / 1, chromIndex, value and its blocks (qPos, tPos, length) d_block_off[a] .. d_block_off[a+1].
- * d_status[j] != 0: the reference would read outside an array on that job.  Synchronous.                                             */
+ * d_status[j] != 0: the reference would read outside an array on that job (LRA_ST_OOB_SLOT: an empty inner chain; LRA_ST_RANGE: two anchors
+ * that overlap on the read by two or more bases, a string of negative length in the reference); its alignments are then not defined.  Synchronous. */
 typedef struct lra_lra_opts {
   int32_t localW, globalW, localMaxFreq, match, mismatch, indel, localBand, refineBySDP, isOnt;
   float gapopen, gapextend, gaproot; int32_t gapCeiling1, gapCeiling2;

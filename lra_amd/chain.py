@@ -270,6 +270,22 @@ def local_refine_batch(ctx: Context, job_chain_off, job_read, job_h, chain_ancho
     return res
 
 
+def local_refine_highacc_batch(ctx: Context, job_chain_off, job_read, job_h, job_lsc, chain_anchor_off, chain_strand, chain_chrom, chain_value, chain_n0, chain_n1, q, t,
+                               length, read_off, strands, rc_base, genome, chrom_pos, **kw):
+    """The walk of the high-accuracy overload (LocalRefineAlignment.h:552-766): the caller gives each job's LSC (job_lsc, uint32 per job), a chain of one
+    anchor still makes an alignment, empty chains are skipped; otherwise as local_refine_batch."""
+    cp = np.ascontiguousarray(chrom_pos, dtype=np.uint64)
+    d = dict(ONT_LRA); d.update(kw)
+    o = LraOpts(*[d[n] for n, _ in LraOpts._fields_])
+    res = AlignmentsResult()
+    nj, nc, na = int(job_read.numel()), int(chain_strand.numel()), int(q.numel())
+    ctx.check(ctx.lib.lra_local_refine_highacc_batch(ctx.h, C.c_uint64(nj), ptr(job_chain_off), ptr(job_read), ptr(job_h), ptr(job_lsc), C.c_uint64(nc), ptr(chain_anchor_off),
+                                                     ptr(chain_strand), ptr(chain_chrom), ptr(chain_value), ptr(chain_n0), ptr(chain_n1), C.c_uint64(na), ptr(q), ptr(t),
+                                                     ptr(length), ptr(read_off), ptr(strands), C.c_uint64(int(rc_base)), ptr(genome), C.c_void_p(cp.ctypes.data), len(cp) - 1,
+                                                     C.byref(o), C.byref(res)))
+    return res
+
+
 def fetch_alignments(ctx: Context, res: AlignmentsResult):
     nj, na, nb = res.n_jobs, res.n_alignments, res.n_blocks
     d = {"job_aln_off": ctx.to_host(res.d_job_aln_off, nj + 1, np.uint64), "block_off": ctx.to_host(res.d_block_off, na + 1, np.uint64),

@@ -4,7 +4,8 @@
 // how many blocks the current alignment holds (:288), everything else is a function of the anchor pair alone.  So all candidate work is
 // done up front in batches, and a last pass (one lane per primary chain) walks the chains, takes the reference's decisions with the block
 // counts in hand and copies the precomputed pieces into place:
-//   1 classify every consecutive anchor pair: nothing between / direct (RefineByLinearAlignment) / large space (RefineBySDP, both sides >= 300)
+//   1 classify every consecutive anchor pair: nothing between / direct (RefineByLinearAlignment) / large space (RefineBySDP, both sides >= 300) /
+//     undefined (the anchors overlap on the read: no work, the job is flagged LRA_ST_RANGE; so is a job whose walk uses a piece lra_between_anchors_batch flagged)
 //   2 lra_between_anchors_batch on the direct pairs
 //   3 lra_refine_space_batch_mf on the large spaces, read strand; 4 again on the other strand where the first result is sparse (:287-289 without
 //     the block-count clause: a superset of the spaces the reference tries)
@@ -41,7 +42,7 @@ struct LrArgs {
   uint32_t* chainJob; uint32_t* anchChain;
   uint8_t* type; uint32_t* cre; uint32_t* nrs; uint32_t* cge; uint32_t* ngs; uint32_t* isDir; uint32_t* isBig; const uint64_t* dirId; const uint64_t* bigId;
   // direct results
-  const uint64_t* d1Off; const int32_t* d1Blk;
+  const uint64_t* d1Off; const int32_t* d1Blk; const uint32_t* d1St;
   // big spaces
   uint64_t nBig;
   uint32_t* bPair; int32_t* bK; int32_t* bW; int32_t* bMf; int32_t* bDiag; float* bMinRatio; int32_t* bMinDist; int32_t* bSv;
@@ -63,7 +64,7 @@ struct LrArgs {
   uint32_t* pCnt; const uint64_t* pOff;      // AOG problems of the second batch: per job, then one per seedless space
   uint32_t* wholeNeed; const uint64_t* wholeId; uint64_t nJobProb;
   uint64_t* p2QB; uint32_t* p2cre; uint32_t* p2nrs; uint64_t* p2TB; uint32_t* p2cge; uint32_t* p2ngs; uint8_t* jFinal;
-  const uint64_t* d2Off; const int32_t* d2Blk;
+  const uint64_t* d2Off; const int32_t* d2Blk; const uint32_t* d2St;
   // output
   uint32_t* nAln; uint32_t* nBlk; const uint64_t* alnOff; const uint64_t* blkOff;
   int32_t* oStrand; int32_t* oSupp; int32_t* oSec; int32_t* oN0; int32_t* oN1; int32_t* oChrom; float* oValue; uint64_t* oBlockOff; int32_t* oBlocks; uint32_t* status;
@@ -96,7 +97,12 @@ __global__ void lr_classify(LrArgs a) {
   a.cre[p] = cre; a.nrs[p] = nrs; a.cge[p] = cge; a.ngs[p] = ngs;
   if (!(cge <= ngs)) { a.type[p] = 3; return; }
   const long long rd = (long long)(uint32_t)(nrs - cre), gd = (long long)(uint32_t)(ngs - cge);
-  if (a.o.refineBySDP && min(rd, gd) >= 300) { a.type[p] = 2; a.isBig[p] = 1; }
+  const bool big = a.o.refineBySDP && min(rd, gd) >= 300;
+  // The next anchor starts before this one ends on the read.  By one base RefineByLinearAlignment aligns nothing (Matched is 0); by more, or by one on the way to
+  // RefineSpace, the reference builds a string of negative length: the pair gets no work and the walk flags its job (type 4).
+  const int32_t span = (int32_t)(nrs - cre);
+  if (span < -1 || (span < 0 && big)) { a.type[p] = 4; return; }
+  if (big) { a.type[p] = 2; a.isBig[p] = 1; }
   else { a.type[p] = 1; a.isDir[p] = 1; }
 }
 
@@ -348,7 +354,8 @@ __global__ void lr_walk(LrArgs a) {
     ai++; nAln++; curBlocks = 0;
   };
   auto blk = [&](int q, int t, int l) { if (PASS) { a.oBlocks[3 * bi] = q; a.oBlocks[3 * bi + 1] = t; a.oBlocks[3 * bi + 2] = l; } bi++; nBlk++; curBlocks++; };
-  auto copy = [&](const uint64_t* off, const int32_t* B, uint64_t id) {
+  auto copy = [&](const uint64_t* off, const int32_t* B, const uint32_t* S, uint64_t id) {    // a piece the walk uses; a negative span in it (:103-104) flags the job
+    if (PASS == 0 && (S[id] & LRA_ST_RANGE)) a.status[job] |= LRA_ST_RANGE;
     for (uint64_t k = off[id]; k < off[id + 1]; k++) blk(B[3 * k], B[3 * k + 1], B[3 * k + 2]);
   };
   auto run_job = [&](uint64_t j) {                                        // :468-497 with the precomputed pieces
@@ -356,11 +363,11 @@ __global__ void lr_walk(LrArgs a) {
     const uint32_t* XQ = a.xq + a.xOff[j]; const uint32_t* XT = a.xt + a.xOff[j]; const int32_t* XL = a.xl + a.xOff[j];
     uint64_t w = a.pOff[j];
     for (int btc = a.jEnd[j]; btc >= a.jStart[j]; btc--) {
-      copy(a.d2Off, a.d2Blk, w); w++;
+      copy(a.d2Off, a.d2Blk, a.d2St, w); w++;
       const uint32_t x = kept[btc];
       blk((int)XQ[x], (int)XT[x], XL[x]);
     }
-    if (a.jFinal[j]) copy(a.d2Off, a.d2Blk, w);
+    if (a.jFinal[j]) copy(a.d2Off, a.d2Blk, a.d2St, w);
   };
   for (uint64_t c = c0; c < c1; c++) {
     const uint64_t a0 = a.aOff[c];
@@ -377,19 +384,20 @@ __global__ void lr_walk(LrArgs a) {
       if (str == 0) blk((int)a.AQ[p], (int)a.AT[p], a.AL[p]); else blk((int)(L - a.AQ[p] - (uint32_t)a.AL[p]), (int)a.AT[p], a.AL[p]);
       const int ty = a.type[p];
       bool inversion = false, brk = false;
-      if (ty == 1) copy(a.d1Off, a.d1Blk, a.dirId[p]);
+      if (ty == 1) copy(a.d1Off, a.d1Blk, a.d1St, a.dirId[p]);
+      else if (ty == 4) { if (PASS == 0) a.status[job] |= LRA_ST_RANGE; }
       else if (ty == 2) {
         const uint64_t b = a.bigId[p];
         const bool tried = a.needRev[b] && curBlocks >= 5;
         const int oc = tried ? a.outcome[b] : 1;
         if (oc == 0) brk = true;
         else if (oc == 1) {
-          if (a.needJob[2 * b]) { const uint64_t j = a.jobId[2 * b]; if (a.keptCnt[j] == 0) { if (PASS == 0) a.status[job] = LRA_ST_OOB_SLOT; } else run_job(j); }
-          else copy(a.d2Off, a.d2Blk, a.nJobProb + a.wholeId[b]);
+          if (a.needJob[2 * b]) { const uint64_t j = a.jobId[2 * b]; if (a.keptCnt[j] == 0) { if (PASS == 0) a.status[job] |= LRA_ST_OOB_SLOT; } else run_job(j); }
+          else copy(a.d2Off, a.d2Blk, a.d2St, a.nJobProb + a.wholeId[b]);
         } else {
           const uint64_t j = a.jobId[2 * b + 1];
           inversion = true;
-          if (a.keptCnt[j] == 0) { if (PASS == 0) a.status[job] = LRA_ST_OOB_SLOT; }
+          if (a.keptCnt[j] == 0) { if (PASS == 0) a.status[job] |= LRA_ST_OOB_SLOT; }
           open(inv_str, 1, 0, (int)a.keptCnt[j], (int)a.keptCnt[j], chrom, a.sValue[j]);    // inv_alignment :474-480
           if (a.keptCnt[j]) run_job(j);
         }
@@ -501,12 +509,13 @@ static int local_refine_impl(lra_ctx* ctx, uint64_t n_jobs, const uint64_t* d_jo
   // ---- 2: direct pairs
   uint64_t d1Blocks = 0;
   {
-    char* wd = (char*)lra_ensure(ctx, 41, sz(nDir + 1, 8) * 3 + sz(nDir + 1, 4) * 4 + 4096);
+    char* wd = (char*)lra_ensure(ctx, 41, sz(nDir + 2, 8) * 3 + sz(nDir + 1, 4) * 5 + 4096);
     if (!wd) return LRA_ERR_NOMEM;
     Carver c{wd};
     uint64_t* qB = c.take<uint64_t>(nDir + 1); uint64_t* tB = c.take<uint64_t>(nDir + 1); uint64_t* d1Off = c.take<uint64_t>(nDir + 2);
     uint32_t* cre = c.take<uint32_t>(nDir + 1); uint32_t* nrs = c.take<uint32_t>(nDir + 1); uint32_t* cge = c.take<uint32_t>(nDir + 1); uint32_t* ngs = c.take<uint32_t>(nDir + 1);
-    a.d1Off = d1Off;
+    uint32_t* d1St = c.take<uint32_t>(nDir + 1);                          // (the second lra_between_anchors_batch reuses the first one's result buffers)
+    a.d1Off = d1Off; a.d1St = d1St;
     if (nDir) {
       hipLaunchKernelGGL(lr_direct_gather, grid(NA), dim3(256), 0, st, a, qB, cre, nrs, tB, cge, ngs);
       lra_between_result br;
@@ -517,6 +526,7 @@ static int local_refine_impl(lra_ctx* ctx, uint64_t n_jobs, const uint64_t* d_jo
       if (!d1Blk) return LRA_ERR_NOMEM;
       LRA_HIP_CHECK(ctx, hipMemcpyAsync(d1Off, br.d_block_off, (nDir + 1) * 8, hipMemcpyDeviceToDevice, st));
       LRA_HIP_CHECK(ctx, hipMemcpyAsync(d1Blk, br.d_blocks, 3 * d1Blocks * 4, hipMemcpyDeviceToDevice, st));
+      LRA_HIP_CHECK(ctx, hipMemcpyAsync(d1St, br.d_status, nDir * 4, hipMemcpyDeviceToDevice, st));
       a.d1Blk = d1Blk;
     } else LRA_HIP_CHECK(ctx, hipMemsetAsync(d1Off, 0, 16, st));
   }
@@ -664,7 +674,7 @@ static int local_refine_impl(lra_ctx* ctx, uint64_t n_jobs, const uint64_t* d_jo
       lra_between_result b2;
       { int rc = lra_between_anchors_batch(ctx, (int)nP2, d_strands, a.p2QB, a.p2cre, a.p2nrs, d_genome, a.p2TB, a.p2cge, a.p2ngs, opts->match, opts->mismatch, opts->indel,
                                            opts->localBand, 1, &b2); if (rc) return rc; }
-      a.d2Off = b2.d_block_off; a.d2Blk = b2.d_blocks;
+      a.d2Off = b2.d_block_off; a.d2Blk = b2.d_blocks; a.d2St = (const uint32_t*)b2.d_status;
     }
   }
   LR_DBG("second AOG done: nP2 %llu", (unsigned long long)nP2);

@@ -629,9 +629,19 @@ class LraOpts(C.Structure):
         ("gapopen", C.c_float), ("gapextend", C.c_float), ("gaproot", C.c_float), ("gapCeiling1", C.c_int), ("gapCeiling2", C.c_int)]
 
 
+# one record of the walk's trace (oracle/local_refine.cpp, the T_* enum): per anchor pair in walk order; -1 where a field does not apply.
+# type 0 nothing between / 1 direct / 2 large space; outcome 0 break / 1 forward seeds / 2 inverted seeds / 3 whole space aligned (no seed);
+# super: the ratio and identity clauses of the reverse try hold (whatever the block count); spec: the outcome if it were tried;
+# rm_max / kept_min: the longest anchor RemovePairedIndels took from the inner chain, the shortest it left;
+# jobs / np2: the seed sets and second-batch alignment problems the device plans for the space.
+LR_TRACE_FIELDS = ("chain", "cur", "type", "rd", "gd", "K", "W", "maxFreq", "diag", "sv", "nf", "idF", "super", "blocks", "tried", "nr", "idR", "outcome", "inner_before",
+                   "inner_after", "btc_start", "btc_end", "final", "rm_max", "kept_min", "spec", "jobs", "np2")
+
+
 def local_refine_alignment(chain_off, aq, at, alen, chain_strand, chain_chrom, first_sdp, n0, n1, h, fwd: bytes, rc: bytes, genome: bytes, chrom_pos, lsc=None,
-                           min_anchors=2, **kw):
-    """LocalRefineAlignment (LocalRefineAlignment.h:885) for one primary chain -> list of dict(strand, supp, secondary, n0, n1, value, chrom, blocks) or None (UB)."""
+                           min_anchors=2, trace=False, **kw):
+    """LocalRefineAlignment (LocalRefineAlignment.h:885) for one primary chain -> list of dict(strand, supp, secondary, n0, n1, value, chrom, blocks) or None (UB).
+    trace=True: (that, the trace: one dict of LR_TRACE_FIELDS per anchor pair walked)."""
     L = lib()
     d = dict(localW=5, globalW=5, localMaxFreq=15, match=4, mismatch=-1, indel=-2, localBand=15, refineBySDP=1, isOnt=1, gapopen=7.0, gapextend=10.0, gaproot=1.5,
              gapCeiling1=1500, gapCeiling2=3000)
@@ -647,18 +657,29 @@ def local_refine_alignment(chain_off, aq, at, alen, chain_strand, chain_chrom, f
     max_seg = 4 * len(aq) + 8; cap = 4 * (len(aq) + len(fwd)) + 64
     seg = [np.zeros(max_seg, np.int32) for _ in range(5)]; sv = np.zeros(max_seg, np.float32); sc = np.zeros(max_seg, np.int32)
     sbo = np.zeros(max_seg + 1, np.int32); blk = np.zeros(3 * cap, np.int32)
-    L.oracle_local_refine_alignment_ex.restype = C.c_int
-    n = L.oracle_local_refine_alignment_ex(C.c_int(nch), _p(co, C.c_int), _p(aq, C.c_uint32), _p(at, C.c_uint32), _p(al, C.c_int), _p(cs, C.c_uint8), _p(cc, C.c_int),
-                                        _p(fs, C.c_float), _p(a0, C.c_int), _p(a1, C.c_int), C.c_int(lsc), C.c_int(int(h)), C.c_int(int(min_anchors)), C.c_char_p(fwd), C.c_char_p(rc),
-                                        C.c_uint32(len(fwd)), C.c_char_p(genome), _p(pos, C.c_uint64), C.byref(o), C.c_int(max_seg), _p(seg[0], C.c_int),
-                                        _p(seg[1], C.c_int), _p(seg[2], C.c_int), _p(seg[3], C.c_int), _p(seg[4], C.c_int), _p(sv, C.c_float), _p(sc, C.c_int),
-                                        _p(sbo, C.c_int), _p(blk, C.c_int), C.c_long(cap))
+    args = (C.c_int(nch), _p(co, C.c_int), _p(aq, C.c_uint32), _p(at, C.c_uint32), _p(al, C.c_int), _p(cs, C.c_uint8), _p(cc, C.c_int),
+            _p(fs, C.c_float), _p(a0, C.c_int), _p(a1, C.c_int), C.c_int(lsc), C.c_int(int(h)), C.c_int(int(min_anchors)), C.c_char_p(fwd), C.c_char_p(rc),
+            C.c_uint32(len(fwd)), C.c_char_p(genome), _p(pos, C.c_uint64), C.byref(o), C.c_int(max_seg), _p(seg[0], C.c_int),
+            _p(seg[1], C.c_int), _p(seg[2], C.c_int), _p(seg[3], C.c_int), _p(seg[4], C.c_int), _p(sv, C.c_float), _p(sc, C.c_int),
+            _p(sbo, C.c_int), _p(blk, C.c_int), C.c_long(cap))
+    rows = None
+    if trace:
+        nf = L.oracle_lr_trace_fields()
+        assert nf == len(LR_TRACE_FIELDS)
+        tcap = len(aq) + 1; tr = np.zeros(tcap * nf, np.float64); nt = C.c_int(0)
+        L.oracle_local_refine_alignment_trace.restype = C.c_int
+        n = L.oracle_local_refine_alignment_trace(*args, _p(tr, C.c_double), C.c_int(tcap), C.byref(nt))
+        rows = [dict(zip(LR_TRACE_FIELDS, tr[i * nf:(i + 1) * nf].tolist())) for i in range(nt.value)]
+    else:
+        L.oracle_local_refine_alignment_ex.restype = C.c_int
+        n = L.oracle_local_refine_alignment_ex(*args)
     if n == -1:
-        return None
+        return (None, rows) if trace else None
     assert n >= 0, n
     B = blk.reshape(-1, 3)
-    return [dict(strand=int(seg[0][i]), supp=int(seg[1][i]), secondary=int(seg[2][i]), n0=int(seg[3][i]), n1=int(seg[4][i]), value=float(sv[i]), chrom=int(sc[i]),
-                 blocks=B[sbo[i]:sbo[i + 1]].copy()) for i in range(n)]
+    res = [dict(strand=int(seg[0][i]), supp=int(seg[1][i]), secondary=int(seg[2][i]), n0=int(seg[3][i]), n1=int(seg[4][i]), value=float(sv[i]), chrom=int(sc[i]),
+                blocks=B[sbo[i]:sbo[i + 1]].copy()) for i in range(n)]
+    return (res, rows) if trace else res
 
 
 # ---- chain post-filters + SPLITChain (a9, low-accuracy path) ----------------------------------------------------------
