@@ -1720,6 +1720,57 @@ int lra_bam_view_stats(lra_bam_view* v, struct lra_bam_view_stats* out);
 void lra_bam_view_destroy(lra_bam_view* v);
 int lra_bai_query_host(const uint8_t* bai, uint64_t bai_len, int n_ref, int32_t ref_id, int64_t beg, int64_t end, const uint64_t** chunks,
                        uint64_t* n_chunks);
+/* ---- BAM depth: per-base and binned coverage, whole or by region through the .bai (additive to ABI 9) ----------------------------------------------
+ * lra_bam_depth turns the records of a coordinate-sorted BAM file into coverage on the device.  It reads the file as lra_bam_view does -- the same
+ * windows, the same plan and chunk rules for a region, the same refusals (bam_pass.h is the one code of both) -- and owns its device memory; one
+ * object serves one context.  A pass covers the whole file (all) or [beg, end) of one reference (region: lra_bam_view_region's conventions -- 0-based,
+ * half-open, end clamped to the reference's length, beg == end an empty pass, no index or a bad ref_id LRA_ERR_INVALID).
+ * Which records count.  refID >= 0, (flag & require) == require && (flag & exclude) == 0 (exclude ~0u: 0x704 -- unmapped, secondary, QC fail,
+ * duplicate) and mapq >= min_mapq.
+ * How ops count.  The core CIGAR's ops; those of the CG:B:I tag when the core CIGAR is <l_seq>S<n>N and the record has the tag (wherever it stands in
+ * the aux block).  M = X add 1 to every reference position they cover; D advances and adds only with count_deletions; N advances and never adds;
+ * I S H P neither advance nor add; a record of 0 ops adds nothing.  Depth is uint32.  Positions outside the reference (or the region) are dropped.
+ * Per-base text (bin == 0): RNAME \t POS (1-based) \t DEPTH \n for the positions with depth > 0; all_positions: for every position of the pass's range,
+ * in a whole-file pass every position of every reference in header order.
+ * Binned text (bin > 0): RNAME \t START (0-based) \t END \t MEAN \n for every bin [b0 + k bin, min(b0 + (k + 1) bin, range end)), b0 = the pass's beg
+ * (0 for whole references), empty bins too.  MEAN in integers: h = (100 sum + len / 2) / len in 64 bits, printed as h / 100 '.' and two digits of h % 100.
+ * Values (want_values): uint32 depth[count] per position from `first` on (bin == 0; without all_positions stretches no record reaches are left out
+ * and `first` jumps), or uint64 sum[count] per bin from the bin that starts at `first` on (bin > 0).  want_text and want_values may both be set; one
+ * of them must be.
+ * Pieces come in reference order, then position order.  A delivered piece is final: nothing delivered later changes it, no position or bin comes
+ * twice.  A piece's memory is page-locked, owned by the object and valid until the next call on it; count == 0 && text_len == 0: the pass is over.
+ * (count is set with or without want_values; a piece may have count > 0 and no text.)
+ * Refusals (LRA_ERR_INVALID, the view's texts under this object's name): a BGZF fault, a block_size below 32, a record the view's arithmetic
+ * refuses, a refID outside [-1, n_ref), a CIGAR op code above 8, an aux block that ends inside a tag while the CG tag of a counted <l_seq>S<n>N record
+ * is looked for, a file that ends inside a record -- and a record whose (refID, pos), refID -1 last, sorts in front of its predecessor's, across
+ * window edges too: "not coordinate-sorted at record N".  The pieces the records in front of the fault made final are delivered first, the next call
+ * refuses, and the object takes another pass.
+ * Memory.  The position window: int32 diff[span_bases + 2], twice, holds [base, base + span) of the current reference; positions below the next
+ * window's first record are final, finished (scanned, delivered) and the base slides; a window whose records reach beyond it is taken in prefixes,
+ * and a single record longer than it doubles span_bases.  window_bytes as the view's; span_bases 0: 4 Mi positions, below 65536: raised.
+ * Stats, summed over the object's life: windows, records read / counted / filtered, slides, positions with depth > 0, the sum and the maximum of the
+ * depth delivered (a pass adds these three when it is over), bytes read / inflated / delivered, ms per stage (read + inflate: wall; the rest HIP
+ * events). */
+typedef struct lra_bam_depth lra_bam_depth;
+struct lra_bam_depth_opts {
+  uint32_t require, exclude, min_mapq, count_deletions, bin, all_positions, want_text, want_values;
+  uint64_t window_bytes, span_bases;
+};
+struct lra_bam_depth_piece {
+  int32_t ref_id; int64_t first; uint64_t count;
+  const uint32_t* depth; const uint64_t* sum; const char* text; uint64_t text_len;
+};
+struct lra_bam_depth_stats {
+  uint64_t windows, records_read, records_counted, records_filtered, slides, covered, depth_sum, depth_max, bytes_read, bytes_inflated, bytes_delivered;
+  double ms_read_inflate, ms_frame_select, ms_ops, ms_accumulate, ms_finish, ms_text, ms_copy;
+};
+int lra_bam_depth_create(lra_ctx* ctx, const char* bam_path, const char* bai_path, const struct lra_bam_depth_opts* opts, lra_bam_depth** out);
+int lra_bam_depth_header(lra_bam_depth* d, int* n_ref, const char* const** names, const uint64_t** ref_len);
+int lra_bam_depth_all(lra_bam_depth* d);
+int lra_bam_depth_region(lra_bam_depth* d, int32_t ref_id, int64_t beg, int64_t end);
+int lra_bam_depth_next(lra_bam_depth* d, struct lra_bam_depth_piece* piece);
+int lra_bam_depth_stats(lra_bam_depth* d, struct lra_bam_depth_stats* out);
+void lra_bam_depth_destroy(lra_bam_depth* d);
 /* the reads of a snapshot whose status word is non-zero: their number; *status (optional) = the snapshot's status array [n_reads], owned by the snapshot */
 uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status);
 /* The record buffer of a batch as ONE device buffer -- what a rank sends to rank 0 in the single exchange step of the multi-GPU path (the

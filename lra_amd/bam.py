@@ -301,6 +301,92 @@ class BamView:
             pass
 
 
+class DepthOpts(C.Structure):
+    """struct lra_bam_depth_opts (include/lra_hip.h)"""
+    _fields_ = [(k, C.c_uint32) for k in ("require", "exclude", "min_mapq", "count_deletions", "bin", "all_positions", "want_text", "want_values")] + \
+               [("window_bytes", C.c_uint64), ("span_bases", C.c_uint64)]
+
+
+class DepthPiece(C.Structure):
+    """struct lra_bam_depth_piece (include/lra_hip.h)"""
+    _fields_ = [("ref_id", C.c_int32), ("first", C.c_int64), ("count", C.c_uint64), ("depth", C.c_void_p), ("sum", C.c_void_p), ("text", C.c_void_p),
+                ("text_len", C.c_uint64)]
+
+
+class DepthStats(C.Structure):
+    """struct lra_bam_depth_stats (include/lra_hip.h)"""
+    _fields_ = [(k, C.c_uint64) for k in ("windows", "records_read", "records_counted", "records_filtered", "slides", "covered", "depth_sum", "depth_max",
+                                          "bytes_read", "bytes_inflated", "bytes_delivered")] + \
+               [(k, C.c_double) for k in ("ms_read_inflate", "ms_frame_select", "ms_ops", "ms_accumulate", "ms_finish", "ms_text", "ms_copy")]
+
+
+class BamDepth:
+    """lra_bam_depth: the coverage of a coordinate-sorted BAM file, computed on the device, per base (bin 0) or per bin; bai: the path of its .bai index
+    (None: whole-file passes only).  exclude None: 0x704, what samtools depth drops.  text / values: what a pass hands back."""
+
+    def __init__(self, ctx: Context, path, bai=None, require=0, exclude=None, min_mapq=0, count_deletions=False, bin=0, all_positions=False, text=True,
+                 values=False, window_bytes=0, span_bases=0):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        self.bin = int(bin)
+        o = DepthOpts(int(require), 0xffffffff if exclude is None else int(exclude), int(min_mapq), int(bool(count_deletions)), self.bin,
+                      int(bool(all_positions)), int(bool(text)), int(bool(values)), int(window_bytes), int(span_bases))
+        ctx.check(ctx.lib.lra_bam_depth_create(ctx.h, os.fsencode(path), os.fsencode(bai) if bai is not None else None, C.byref(o), C.byref(self.h)))
+
+    def header(self):
+        """-> (the reference names as bytes, their lengths)"""
+        n_ref, nm, rl = C.c_int(0), C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.ctx.lib.lra_bam_depth_header(self.h, C.byref(n_ref), C.byref(nm), C.byref(rl)))
+        k = n_ref.value
+        names = [C.string_at(q) for q in (C.c_char_p * k).from_address(nm.value)] if k else []
+        lens = list((C.c_uint64 * k).from_address(rl.value)) if k else []
+        return names, lens
+
+    def fetch(self, ref=None, beg=0, end=None):
+        """yields the pieces of a pass as (ref_id, first, count, values, text): ref None: the whole file; ref: a reference's index or name, [beg, end)
+        0-based half-open (end None: the reference's end).  values: a numpy array (uint32 depths from position `first` on, or uint64 bin sums from the
+        bin that starts at `first` on; None when the object was made without values) -- a view of the object's memory, valid until the next piece;
+        text: bytes (b"" without text)."""
+        lib = self.ctx.lib
+        if ref is None:
+            self.ctx.check(lib.lra_bam_depth_all(self.h))
+        else:
+            names, lens = self.header()
+            if not isinstance(ref, int):
+                key = ref.encode() if isinstance(ref, str) else ref
+                if key not in names:
+                    raise ValueError("no reference %r in the file" % ref)
+                ref = names.index(key)
+            if end is None:
+                end = lens[ref] if 0 <= ref < len(lens) else 0
+            self.ctx.check(lib.lra_bam_depth_region(self.h, C.c_int32(ref), C.c_int64(int(beg)), C.c_int64(int(end))))
+        while True:
+            p = DepthPiece()
+            self.ctx.check(lib.lra_bam_depth_next(self.h, C.byref(p)))
+            if not p.count and not p.text_len:
+                return
+            at, dt = (p.sum, np.uint64) if self.bin else (p.depth, np.uint32)
+            vals = np.ctypeslib.as_array(C.cast(at, C.POINTER(C.c_uint64 if self.bin else C.c_uint32)), shape=(p.count,)).view(dt) if at and p.count else None
+            yield p.ref_id, p.first, p.count, vals, (C.string_at(p.text, p.text_len) if p.text_len else b"")
+
+    def stats(self):
+        s = DepthStats()
+        self.ctx.check(self.ctx.lib.lra_bam_depth_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in DepthStats._fields_}
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:
+                self.ctx.lib.lra_bam_depth_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def bai_query(bai, n_ref, ref_id, beg, end, lib=None):
     """lra_bai_query_host (no GPU): the chunks [(beg, end)] of virtual offsets a region pass reads, from the .bai bytes.  n_ref: the BAM header's
     reference count (-1: not compared).  ValueError for LRA_ERR_INVALID (an index the reader refuses, ref_id outside it, beg > end)."""

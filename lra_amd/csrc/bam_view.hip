@@ -1,5 +1,7 @@
 // lra_amd/csrc/bam_view.hip -- lra_bam_view: a BAM file printed as SAM text on the device, whole or for a region reached through its .bai index (gfx950).
-// include/lra_hip.h has the interface, the text's rules and what a window allocates; bam_view_host.h reads the index and plans a region's chunks.
+// include/lra_hip.h has the interface, the text's rules and what a window allocates; bam_view_host.h reads the index and plans a region's chunks;
+// bam_pass.h runs the pass (the window loop below, shared with bam_depth.hip) and hands each window's records to window_text; bam_rec.h has the
+// record's core fields and the aux walk.
 //
 // window.  One lra_bgzf_step (zsource.h) reads `window_bytes` compressed bytes, inflates their whole members on the device behind the carried tail and
 // lra_bam_launch_frame chains the block_size fields.  A region's chunk [vb, ve) seeks to vb >> 16, resets the step and frames from vb & 0xffff; the
@@ -19,22 +21,14 @@
 #include "common.h"
 #include "chunk_copy.h"
 #include "scan.h"
-#include "bam_view_host.h"
-#include "bam_merge_host.h"
+#include "bam_pass.h"
 #include "bam_keys.h"
-#include "zsource.h"
-#include <fcntl.h>
-#include <unistd.h>
-#include <stdarg.h>
 #include <algorithm>
-#include <chrono>
 #include <vector>
 
 namespace {
 
-constexpr uint64_t MIN_WINDOW = 65536, DEFAULT_WINDOW = 16ull << 20;
 constexpr int CHUNK = 4096;
-constexpr unsigned long long NONE = ~0ull;
 enum { K_NONE = 0, K_COPY = 1, K_SEQ = 2, K_QUAL = 3, K_ELEM = 4 };
 
 struct Item {                                                 // one printed tag
@@ -64,27 +58,6 @@ struct View {                                                 // what the kernel
   unsigned long long* bad;                                    // [0] bv_check, [1] bv_tags, [2] bv_oplen: the lowest bad record; [3] the first record at or behind the region's end
 };
 
-__device__ __forceinline__ uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
-__device__ __forceinline__ int ndig(uint64_t v) { int d = 1; while (v >= 10) { v /= 10; d++; } return d; }
-__device__ __forceinline__ int slen(int64_t v) { return v < 0 ? 1 + ndig((uint64_t)(-v)) : ndig((uint64_t)v); }
-__device__ __forceinline__ unsigned char* put_u(unsigned char* d, uint64_t v) {
-  const int k = ndig(v);
-  for (int i = k - 1; i >= 0; i--) { d[i] = (unsigned char)('0' + v % 10); v /= 10; }
-  return d + k;
-}
-__device__ __forceinline__ unsigned char* put_s(unsigned char* d, int64_t v) {
-  if (v < 0) { *d++ = '-'; return put_u(d, (uint64_t)(-v)); }
-  return put_u(d, (uint64_t)v);
-}
-// the last index i < n with a[i] <= x (a ascends, a[0] <= x)
-__device__ __forceinline__ uint64_t last_le(const uint64_t* __restrict__ a, uint64_t n, uint64_t x) {
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (a[mid] <= x) lo = mid + 1; else hi = mid; }
-  return lo - 1;
-}
-__device__ __forceinline__ int type_size(uint8_t t) {
-  switch (t) { case 'c': case 'C': case 'A': return 1; case 's': case 'S': return 2; case 'i': case 'I': case 'f': return 4; default: return 0; }
-}
 __device__ __forceinline__ int64_t int_value(const uint8_t* p, uint8_t t) {
   switch (t) {
     case 'c': return (int8_t)p[0];
@@ -96,22 +69,12 @@ __device__ __forceinline__ int64_t int_value(const uint8_t* p, uint8_t t) {
   }
 }
 
-struct Core { int32_t ref, pos, next_ref, next_pos, tlen; uint32_t bs, l_name, mapq, n_cig, flag, l_seq; uint64_t fixed; };
-__device__ __forceinline__ Core core_of(const uint8_t* p) {
-  Core c;
-  c.bs = le32(p); c.ref = (int32_t)le32(p + 4); c.pos = (int32_t)le32(p + 8); c.l_name = p[12]; c.mapq = p[13]; c.n_cig = le16(p + 16); c.flag = le16(p + 18);
-  c.l_seq = le32(p + 20); c.next_ref = (int32_t)le32(p + 24); c.next_pos = (int32_t)le32(p + 28); c.tlen = (int32_t)le32(p + 32);
-  c.fixed = 32 + (uint64_t)c.l_name + 4ull * c.n_cig + ((uint64_t)c.l_seq + 1) / 2 + (uint64_t)c.l_seq;
-  return c;
-}
-
 __global__ void __launch_bounds__(256) bv_check(View V) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= V.n) return;
   const uint8_t* p = V.data + V.pos[i];
   const Core c = core_of(p);
-  const bool ok = (uint64_t)c.bs + 4 == V.pos[i + 1] - V.pos[i] && c.l_name >= 1 && c.fixed <= c.bs && p[36 + c.l_name - 1] == 0 && c.ref >= -1 && c.ref < V.n_ref;
-  if (!ok) atomicMin(&V.bad[0], (unsigned long long)i);
+  if (!core_ok(p, c, V.pos[i + 1] - V.pos[i], V.n_ref)) atomicMin(&V.bad[0], (unsigned long long)i);
 }
 
 __global__ void __launch_bounds__(256) bv_select(View V) {
@@ -134,38 +97,6 @@ __global__ void __launch_bounds__(256) bv_cut(View V) {
   if (i < V.n && i >= V.bad[3]) V.keep[i] = 0;
 }
 
-// The tag at data[at, end): false when it ends behind `end` or names an unknown type.  *val = its value's offset (B: the first element), *count = elements (B),
-// bytes in front of the NUL (Z, H) or 1; *next = the byte behind it.
-__device__ __forceinline__ bool tag_at(const uint8_t* d, uint64_t at, uint64_t end, uint8_t* type, uint8_t* sub, uint64_t* val, uint32_t* count, uint64_t* next) {
-  if (end - at < 3) return false;
-  const uint8_t t = d[at + 2];
-  *type = t; *sub = 0; *val = at + 3; *count = 1;
-  const int sz = type_size(t);
-  if (sz) {
-    if (end - at < 3 + (uint64_t)sz) return false;
-    *next = at + 3 + sz;
-    return true;
-  }
-  if (t == 'Z' || t == 'H') {
-    uint64_t e = at + 3;
-    while (e < end && d[e]) e++;
-    if (e >= end) return false;
-    *count = (uint32_t)(e - (at + 3)); *next = e + 1;
-    return true;
-  }
-  if (t == 'B') {
-    if (end - at < 8) return false;
-    const uint8_t s = d[at + 3];
-    const int es = s == 'A' ? 0 : type_size(s);
-    if (!es) return false;
-    const uint32_t n = le32(d + at + 4);
-    if ((uint64_t)n * es > end - at - 8) return false;
-    *sub = s; *val = at + 8; *count = n; *next = at + 8 + (uint64_t)n * es;
-    return true;
-  }
-  return false;
-}
-
 __global__ void __launch_bounds__(256) bv_tags(View V) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= V.n) return;
@@ -176,7 +107,7 @@ __global__ void __launch_bounds__(256) bv_tags(View V) {
     const uint8_t* p = V.data + at0;
     const Core c = core_of(p);
     ops = at0 + 36 + c.l_name; n_op = c.n_cig;
-    const bool cg_form = c.n_cig == 2 && le32(V.data + ops) == ((c.l_seq << 4) | 4u) && (le32(V.data + ops + 4) & 15u) == 3u;
+    const bool cg_form = cg_form_at(V.data + ops, c);
     const uint64_t end = V.pos[i + 1];
     uint64_t at = at0 + 4 + c.fixed;
     bool ok = true;
@@ -418,121 +349,33 @@ __global__ void __launch_bounds__(256) bv_bulk(View V) {
   });
 }
 
-struct Timer {
-  hipEvent_t a = nullptr, b = nullptr; hipStream_t st;
-  explicit Timer(hipStream_t s) : st(s) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, st); }
-  double stop() { float ms = 0; (void)hipEventRecord(b, st); (void)hipEventSynchronize(b); (void)hipEventElapsedTime(&ms, a, b); return ms; }
-  ~Timer() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-};
-unsigned blocks_of(uint64_t lanes) { return (unsigned)((lanes + 255) / 256); }
-unsigned wave_blocks(lra_ctx* ctx, uint64_t waves) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((waves + 3) / 4, (uint64_t)ctx->num_cu * 32)); }
-// the view's own arrays: an eighth of slack so that windows of about one size do not allocate anew; contents are not kept
-template <typename T> struct Buf {
-  T* p = nullptr; size_t n = 0;
-  bool ensure(size_t want) {
-    if (want <= n) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr; n = 0;
-    const size_t m = want + want / 8 + 16;
-    if (hipMalloc((void**)&p, m * sizeof(T)) != hipSuccess) return false;
-    n = m;
-    return true;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-double wall_ms(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-
-bool read_header(const std::string& path, uint64_t hdr, std::vector<uint8_t>& out, std::string& why) {
-  lra_bgzf_source src;
-  src.fd = open(path.c_str(), O_RDONLY);
-  if (src.fd < 0) { why = "cannot open it"; return false; }
-  out.clear();
-  bool ok = true;
-  while (ok && out.size() < hdr) {
-    uint32_t isize = 0;
-    if (!src.peek(&isize)) { why = src.err.empty() ? "the file ends inside the header" : src.err; ok = false; break; }
-    const size_t at = out.size();
-    out.resize(at + isize);
-    if (!src.take(out.data() + at)) { why = src.err; ok = false; }
-  }
-  close(src.fd);
-  if (ok) out.resize(hdr);
-  return ok;
-}
-
 }  // namespace
 
-struct lra_bam_view {
-  lra_ctx* ctx = nullptr;
-  std::string path, bai_path;
-  int fd = -1;
-  uint64_t window = 0, hdr = 0;
-  std::vector<uint8_t> header; lra_merge_refs refs; std::vector<const char*> name_ptr;
-  bool has_index = false; lra_bai_file bai;
+struct lra_bam_view : lra_bam_pass {                           // (bam_pass.h: the file, the step, the plan, the window loop)
   uint32_t req = 0, excl = 0;
-  lra_bgzf_step z;
-  // the pass
-  int mode = 0;                                               // 0: none, 1: the whole file, 2: a region
-  int32_t ref_id = 0; int64_t beg = 0, end = 0;
-  std::vector<lra_bai_chunk> plan; size_t ci = 0; bool chunk_open = false, over = true;
-  uint64_t skip = 0, want = 0, rec_base = 0, carry_voff = 0;
-  std::string pend_err;
   // the window
-  Buf<uint8_t> rname, pkind, ppre, text, ftext; Buf<uint64_t> rname_off, pos, misc, item_off, elem_off, float_off, op_off, ops_src, cg_at, eoff, ooff, felem, poff, psrc;
+  Buf<uint8_t> pkind, ppre, text, ftext; Buf<uint64_t> item_off, elem_off, float_off, op_off, ops_src, cg_at, eoff, ooff, felem, poff, psrc;
   Buf<uint32_t> keep, mspan, mbf, c_item, c_elem, c_float, c_op, elen, oplen, ftoff, plen; Buf<int32_t> mref, mpos; Buf<Item> item; Buf<float> fval;
   PinBuf<char> h_text;
-  struct lra_bam_view_stats S{};
+  struct lra_bam_view_stats S{};                              // (windows, bytes read / inflated, read + inflate and the frame's share are the pass's)
+  uint64_t w_len = 0, w_rec = 0;                              // the text of the window in hand
 
   void release_all() {
-    z.release();
-    rname.release(); pkind.release(); ppre.release(); text.release(); ftext.release(); rname_off.release(); pos.release(); misc.release(); item_off.release();
+    release_pass();
+    pkind.release(); ppre.release(); text.release(); ftext.release(); item_off.release();
     elem_off.release(); float_off.release(); op_off.release(); ops_src.release(); cg_at.release(); eoff.release(); ooff.release(); felem.release(); poff.release();
     psrc.release(); keep.release(); mspan.release(); mbf.release(); c_item.release(); c_elem.release(); c_float.release(); c_op.release(); elen.release();
     oplen.release(); ftoff.release(); plen.release(); mref.release(); mpos.release(); item.release(); fval.release(); h_text.release();
   }
-  // a refusal ends the pass; the view takes another
-  int fail(int code, const char* fmt, ...) __attribute__((format(printf, 3, 4))) {
-    char buf[1024];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    (void)hipStreamSynchronize(ctx->stream);
-    over = true; chunk_open = false; pend_err.clear();
-    return lra_set_err(ctx, code, "%s", buf);
-  }
-  template <class T> bool grab(Buf<T>& b, size_t want_items) { if (b.ensure(want_items)) return true; (void)hipGetLastError(); return false; }
-  std::string where(uint64_t idx) const {                     // a record of the window, for a refusal's text
-    if (mode == 1) return "record " + std::to_string(rec_base + idx);
-    return "record " + std::to_string(idx) + " of the records read from compressed offset " + std::to_string(z.file_off);
-  }
-  uint64_t voff(uint64_t p) const {                           // the virtual offset of decoded position p (at or behind the carry) of the step's data
-    const std::vector<uint64_t>& o = z.out_off;
-    const size_t m = (size_t)(std::upper_bound(o.begin(), o.end(), p) - o.begin()) - 1;
-    return ((z.file_off + z.in_off[m]) << 16) | (p - o[m]);
-  }
-  uint64_t limit_of(uint64_t ve) const;
-  int start_pass();
   int window_text(uint64_t n, uint64_t limit, uint64_t* len, uint64_t* n_rec, uint64_t* bad_idx, uint64_t* bad_pos, std::string* bad_why, uint64_t* stop_idx);
+  // the pass's consumer
+  int window(uint64_t n, uint64_t limit, uint64_t* bad_idx, uint64_t* bad_pos, std::string* bad_why, uint64_t* stop_idx) {
+    return window_text(n, limit, &w_len, &w_rec, bad_idx, bad_pos, bad_why, stop_idx);
+  }
+  void forget() { w_len = w_rec = 0; }
+  bool deliver() { S.records += w_rec; S.bytes_text += w_len; return w_len != 0; }
   int next(const char** h_text_out, uint64_t* len, uint64_t* n_records);
 };
-
-// the decoded position in front of which the records of a chunk that ends at virtual offset ve start
-uint64_t lra_bam_view::limit_of(uint64_t ve) const {
-  const uint64_t ce = ve >> 16, ue = ve & 0xffff, base = z.file_off, carry = z.out_off[0];
-  if (ce < base) return carry && carry_voff < ve ? 1 : 0;      // the chunk ends in the members before: only the carried record can start inside it
-  const std::vector<uint64_t>& in = z.in_off;
-  const size_t m = (size_t)(std::lower_bound(in.begin(), in.end(), ce - base) - in.begin());
-  if (m == in.size()) return ~0ull;
-  return in[m] == ce - base ? z.out_off[m] + ue : z.out_off[m];
-}
-
-int lra_bam_view::start_pass() {
-  (void)hipStreamSynchronize(ctx->stream);
-  over = false; chunk_open = false; ci = 0; pend_err.clear(); rec_base = 0; carry_voff = 0;
-  if (mode == 1) {
-    if (lseek(fd, 0, SEEK_SET) != 0) return fail(LRA_ERR_INVALID, "lra_bam_view: cannot seek in %s", path.c_str());
-    z.reset(); skip = hdr; want = window; chunk_open = true;
-  }
-  return LRA_OK;
-}
 
 // The text of the window's records [0, n): the first n of the framed ones.  *bad_idx < n: that record is refused (*bad_why) and nothing was printed.
 int lra_bam_view::window_text(uint64_t n, uint64_t limit, uint64_t* len, uint64_t* n_rec, uint64_t* bad_idx, uint64_t* bad_pos, std::string* bad_why, uint64_t* stop_idx) {
@@ -666,82 +509,12 @@ int lra_bam_view::window_text(uint64_t n, uint64_t limit, uint64_t* len, uint64_
 }
 
 int lra_bam_view::next(const char** out, uint64_t* len, uint64_t* n_records) {
-  hipStream_t st = ctx->stream;
   *out = nullptr; *len = 0; if (n_records) *n_records = 0;
   for (;;) {
-    if (over) return LRA_OK;
-    if (!pend_err.empty()) { const std::string e = pend_err; return fail(LRA_ERR_INVALID, "%s", e.c_str()); }
-    if (!chunk_open) {
-      if (mode != 2 || ci >= plan.size()) { over = true; return LRA_OK; }
-      const uint64_t vb = plan[ci].beg;
-      if (lseek(fd, (off_t)(vb >> 16), SEEK_SET) < 0) return fail(LRA_ERR_INVALID, "lra_bam_view: cannot seek in %s", path.c_str());
-      z.reset(); z.file_off = vb >> 16; skip = vb & 0xffff; carry_voff = 0; chunk_open = true;
-      want = std::min(window, (plan[ci].end >> 16) - (vb >> 16) + 65536);   // the chunk's members and the one its end lies in: a short chunk is a short read
-    }
-    // the window
-    const auto t0 = std::chrono::steady_clock::now();
-    const off_t f0 = lseek(fd, 0, SEEK_CUR);
-    const uint64_t carry = z.dec_len - z.dec_used;
-    uint64_t w = want;
-    const int rc = z.fill(ctx, fd, &w, lra_bgzf_launch_inflate_lut, "view_h2d", "view_inflate");
-    want = w;
-    if (rc == LRA_ERR_NOMEM) return fail(rc, "lra_bam_view: %s failed for a window of %s", z.nomem_pinned ? "hipHostMalloc" : "hipMalloc", path.c_str());
-    if (rc == LRA_ERR_INVALID) return fail(rc, "lra_bam_view: read of %s failed", path.c_str());
-    if (rc) { over = true; return rc; }
-    S.ms_read_inflate += wall_ms(t0);
-    S.windows++;
-    S.bytes_read += (uint64_t)std::max<off_t>(lseek(fd, 0, SEEK_CUR) - f0, 0);
-    S.bytes_inflated += z.dlen - std::min(carry, z.dlen);
-    const uint64_t dlen = z.dlen, start = std::min(skip, dlen);
-    const bool fault = !z.err.empty();
-    if (dlen == start && !z.at_end) { z.commit(dlen); skip -= start; continue; }   // nothing but the header (or the bytes in front of the chunk) so far
-    const uint64_t limit = mode == 2 ? limit_of(plan[ci].end) : ~0ull;
-    const uint64_t cap = (dlen - start) / 36 + 1;
-    if (!grab(pos, cap + 1) || !grab(misc, 64)) return fail(LRA_ERR_NOMEM, "lra_bam_view: hipMalloc failed for the record starts of a window");
-    uint64_t fr[4] = {0, start, 0, 0};
-    if (dlen > start) {
-      Timer T(st);
-      lra_bam_launch_frame(st, z.data, start, dlen, pos.p, cap, misc.p);
-      LRA_HIP_CHECK(ctx, hipGetLastError());
-      LRA_HIP_CHECK(ctx, hipMemcpyAsync(fr, misc.p, 32, hipMemcpyDeviceToHost, st));
-      LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-      S.ms_frame_select += T.stop();
-    }
-    uint64_t n = fr[0];
-    const uint64_t used = fr[1];
-    const bool more_in_chunk = limit > used;                   // the record that starts at `used`, if there is one, belongs to the chunk
-    if (n == 0 && !fr[2] && !z.at_end && more_in_chunk) { want = std::max(want, z.comp_len) * 2; continue; }   // a record larger than the window: read on, twice as much
-    bool last = z.at_end;
-    std::string tail_err, rec_err;                             // what is wrong behind the window's whole records; a record among them that is refused
-    if (more_in_chunk) {
-      if (fr[2]) tail_err = "lra_bam_view: " + path + ": " + where(n) + " is a bad record (block_size " + std::to_string(fr[3]) + ")";
-      else if (fault) tail_err = "lra_bam_view: " + path + ": " + z.err;
-      else if (z.at_end && used < dlen) tail_err = "lra_bam_view: " + path + ": " + where(n) + " is cut by the end of the file";
-    }
-    uint64_t tlen = 0, nrec = 0, stop_idx = NONE;
-    if (n) {
-      LRA_HIP_CHECK(ctx, hipMemcpyAsync(pos.p + n, misc.p + 1, 8, hipMemcpyDeviceToDevice, st));
-      for (;;) {
-        uint64_t bad_idx = NONE, bad_pos = 0; std::string why;
-        if (int r2 = window_text(n, limit, &tlen, &nrec, &bad_idx, &bad_pos, &why, &stop_idx)) return r2;
-        if (bad_idx >= n) break;
-        if (!(mode == 2 && bad_pos >= limit)) rec_err = "lra_bam_view: " + path + ": " + where(bad_idx) + " " + why;   // (a record behind the chunk's end is not this pass's to refuse)
-        n = bad_idx; tlen = nrec = 0;                          // the records in front of it go first
-        if (!n) break;
-      }
-    }
-    if (stop_idx != NONE) { tail_err.clear(); rec_err.clear(); }   // the pass ends in front of both
-    pend_err = !rec_err.empty() ? rec_err : tail_err;
-    const bool ended = mode == 2 && (stop_idx != NONE || !more_in_chunk);
-    if (ended || last || fr[2] || !pend_err.empty()) {
-      chunk_open = false;
-      if (mode == 2) ci++; else if (pend_err.empty()) over = true;
-    } else {
-      carry_voff = voff(used);
-      z.commit(used); rec_base += n; skip = 0; want = window;
-    }
-    S.records += nrec; S.bytes_text += tlen;
-    if (tlen) { *out = h_text.p; *len = tlen; if (n_records) *n_records = nrec; return LRA_OK; }
+    int state = 0;
+    if (int rc = step(*this, &state)) return rc;
+    if (state == 2) return LRA_OK;
+    if (state == 1) { *out = h_text.p; *len = w_len; if (n_records) *n_records = w_rec; return LRA_OK; }
   }
 }
 
@@ -749,41 +522,11 @@ extern "C" int lra_bam_view_create(lra_ctx* ctx, const char* bam_path, const cha
   if (!ctx || !bam_path || !out) return LRA_ERR_INVALID;
   *out = nullptr;
   std::unique_ptr<lra_bam_view> v(new lra_bam_view());
-  v->ctx = ctx; v->path = bam_path;
-  v->window = window_bytes ? std::max(window_bytes, MIN_WINDOW) : DEFAULT_WINDOW;
-  if (lra_hts_sniff(v->path, &v->hdr) != LRA_IN_BAM) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: %s is not a BAM file", bam_path);
-  std::string why;
-  if (!read_header(v->path, v->hdr, v->header, why)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: %s: %s", bam_path, why.c_str());
-  if (!lra_merge_parse_refs(v->header.data(), v->header.size(), v->refs)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: %s: not a valid BAM header", bam_path);
-  for (const std::string& s : v->refs.name) v->name_ptr.push_back(s.c_str());
-  if (bai_path) {
-    v->bai_path = bai_path;
-    const int fd = open(bai_path, O_RDONLY);
-    if (fd < 0) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: cannot open %s", bai_path);
-    std::vector<uint8_t> b;
-    const off_t sz = lseek(fd, 0, SEEK_END);
-    bool ok = sz >= 0 && lseek(fd, 0, SEEK_SET) == 0;
-    uint64_t got = 0;
-    if (ok) { b.resize((size_t)sz); ok = lra_read_all(fd, b.data(), (uint64_t)sz, &got) && got == (uint64_t)sz; }
-    close(fd);
-    if (!ok) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: read of %s failed", bai_path);
-    if (!lra_bai_read(b.data(), b.size(), v->refs.n_ref, v->bai, why)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: %s: %s", bai_path, why.c_str());
-    v->has_index = true;
+  if (int rc = v->open_files(ctx, "lra_bam_view", bam_path, bai_path, window_bytes)) {
+    if (v->fd >= 0) close(v->fd);
+    v->release_all();
+    return rc;
   }
-  v->fd = open(bam_path, O_RDONLY);
-  if (v->fd < 0) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_create: cannot open %s", bam_path);
-  // the reference names, on the device: RNAME and RNEXT are copies of them
-  LRA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  std::string names; std::vector<uint64_t> off(1, 0);
-  for (const std::string& s : v->refs.name) { names += s; off.push_back(names.size()); }
-  if (!v->rname.ensure(names.size() + 1) || !v->rname_off.ensure(off.size())) {
-    (void)hipGetLastError(); close(v->fd); v->release_all();
-    return lra_set_err(ctx, LRA_ERR_NOMEM, "lra_bam_view_create: hipMalloc failed for the reference names");
-  }
-  hipError_t e = hipMemcpyAsync(v->rname_off.p, off.data(), 8 * off.size(), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && !names.empty()) e = hipMemcpyAsync(v->rname.p, names.data(), names.size(), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) { close(v->fd); v->release_all(); return lra_set_err(ctx, LRA_ERR_HIP, "lra_bam_view_create: %s", hipGetErrorString(e)); }
   *out = v.release();
   return LRA_OK;
 }
@@ -815,31 +558,12 @@ extern "C" int lra_bam_view_set_flags(lra_bam_view* v, uint32_t require, uint32_
 
 extern "C" int lra_bam_view_all(lra_bam_view* v) {
   if (!v) return LRA_ERR_INVALID;
-  LRA_HIP_CHECK(v->ctx, hipSetDevice(v->ctx->device));
-  v->mode = 1; v->plan.clear();
-  return v->start_pass();
+  return v->pass_all();
 }
 
 extern "C" int lra_bam_view_region(lra_bam_view* v, int32_t ref_id, int64_t beg, int64_t end) {
   if (!v) return LRA_ERR_INVALID;
-  lra_ctx* ctx = v->ctx;
-  LRA_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  v->over = true;
-  if (!v->has_index) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_region: %s was opened without an index", v->path.c_str());
-  std::string why;
-  if (ref_id >= 0 && ref_id < v->refs.n_ref && end > (int64_t)v->refs.len[(size_t)ref_id]) end = std::max<int64_t>((int64_t)v->refs.len[(size_t)ref_id], std::min(beg, end));
-  std::vector<lra_bai_chunk> plan;
-  if (!lra_bai_plan(v->bai, ref_id, beg, end, plan, why)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_view_region: %s: %s", v->path.c_str(), why.c_str());
-  // Chunks that lie less than a window of compressed bytes apart are read as one: a member inflates in about 10 ms whatever else the device does, so a
-  // step per chunk costs more than the bytes between two chunks.  The records between them are in file order like the rest and fail the overlap test.
-  size_t o = 0;
-  for (size_t i = 0; i < plan.size(); i++) {
-    if (o && (plan[i].beg >> 16) - (plan[o - 1].end >> 16) < v->window) plan[o - 1].end = plan[i].end;
-    else plan[o++] = plan[i];
-  }
-  plan.resize(o);
-  v->mode = 2; v->ref_id = ref_id; v->beg = beg; v->end = end; v->plan.swap(plan);
-  return v->start_pass();
+  return v->pass_region(ref_id, beg, end);
 }
 
 extern "C" int lra_bam_view_next(lra_bam_view* v, const char** h_text, uint64_t* len, uint64_t* n_records) {
@@ -851,6 +575,8 @@ extern "C" int lra_bam_view_next(lra_bam_view* v, const char** h_text, uint64_t*
 extern "C" int lra_bam_view_stats(lra_bam_view* v, struct lra_bam_view_stats* out) {
   if (!v || !out) return LRA_ERR_INVALID;
   *out = v->S;
+  out->windows = v->windows; out->bytes_read = v->bytes_read; out->bytes_inflated = v->bytes_inflated;
+  out->ms_read_inflate = v->ms_read_inflate; out->ms_frame_select += v->ms_frame;
   return LRA_OK;
 }
 

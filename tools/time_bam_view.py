@@ -1,12 +1,12 @@
 """The device BAM view on the sorted BAM of one bench-like batch (needs the GPU):
 
-    python tools/time_bam_view.py [n_reads=2048] [read_len=30000] [repeats=3] [window_bytes=0]
+    python tools/time_bam_view.py [n_reads=2048] [read_len=30000] [repeats=3] [window_bytes=0] [keep=PATH]
 
 The batch's BAM records (lra_map_records_device_bam) are sorted by the device sorter and written, with their .bai, to a temporary directory: the file
 tools/time_bam_sorted.py times the writing of.  Then lra_bam_view, `repeats` times after one warm-up: the whole file as SAM text -- wall time, the view's
 own split (lra_bam_view_stats: read + inflate, frame + select, tags + lengths, the floats' round trip, emit, the copy to the host) and the MB/s of text
 -- and the latency of a region of 1 kb and of 1 Mb in the middle of the reference (region call to the last piece, on an open view).  Median and
-range, and one JSON line."""
+range, and one JSON line.  keep: the sorted file and its index are also written to PATH and PATH.bai (tools/time_bam_depth.py reads them)."""
 import json
 import os
 import sys
@@ -33,6 +33,7 @@ def main():
     rlen = int(sys.argv[2]) if len(sys.argv) > 2 else 30000
     reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
     window = int(sys.argv[4]) if len(sys.argv) > 4 else 0
+    keep = sys.argv[5] if len(sys.argv) > 5 else None
     dev = torch.device("cuda", 0)
     ctx = Context(0)
     genome = st.make_genome(16_000_000, 1, dev)
@@ -78,6 +79,10 @@ def main():
             f.write(head + data + bgzf.EOF_BLOCK)
         with open(path + ".bai", "wb") as f:
             f.write(bai)
+        if keep:
+            for suffix, blob in (("", head + data + bgzf.EOF_BLOCK), (".bai", bai)):
+                with open(keep + suffix, "wb") as f:
+                    f.write(blob)
         out["file_bytes"] = os.path.getsize(path)
         runs = {s: [] for s in ("wall",) + STAGES}
         text_bytes = 0
