@@ -1771,6 +1771,83 @@ int lra_bam_depth_region(lra_bam_depth* d, int32_t ref_id, int64_t beg, int64_t 
 int lra_bam_depth_next(lra_bam_depth* d, struct lra_bam_depth_piece* piece);
 int lra_bam_depth_stats(lra_bam_depth* d, struct lra_bam_depth_stats* out);
 void lra_bam_depth_destroy(lra_bam_depth* d);
+/* ---- BAM to VCF: the insertions and deletions of every alignment, whole or by region through the .bai (additive to ABI 9) ---------------------------
+ * lra_bam_vcf prints one VCF line per insertion and deletion of the alignments of a BAM file, on the device: the step behind the aligner in the
+ * reference's "call SVs from lra alignments" pipeline (call_assembly_SVs/SamToVCF.py).  It reads the file as lra_bam_view and lra_bam_depth do -- the
+ * same windows, the same plan and chunk rules for a region, the same refusals (bam_pass.h is the one code of the three) -- and owns its device memory;
+ * one object serves one context.  No base of SEQ is compared with the genome: mismatches are not variants (the script never prints one).
+ *   create    the context must hold a genome and a chromosome table (lra_ctx_load_genome[_device], lra_ctx_load_chromosomes; upper case, as the
+ *             script's ref.fetch(...).upper()).  n_chrom == n_ref and every chromosome's length against the BAM header's: no genome, or any
+ *             difference, is LRA_ERR_INVALID naming the first reference that differs.  Chromosomes are matched to references by index, not by name:
+ *             the context holds no names.  The test is repeated when a pass starts and at every next.
+ *   opts      require / exclude as lra_bam_depth's; exclude ~0u means 0x4 (pysam's fetch yields every mapped record, secondary and supplementary
+ *             included).  min_mapq.  min_length: a variant is kept if |len(ALT) - len(REF)| >= min_length; 0 is raised to 1.  pos_one_based 0: POS is
+ *             the 0-based position of the anchor base, as the script prints it; 1: that + 1, as VCF means it.  want_text, want_values (one of them
+ *             must be set), window_bytes as the view's.  NULL opts: the defaults, text only.
+ * Which records are walked.  refID >= 0, (flag & require) == require && (flag & exclude) == 0, mapq >= min_mapq, at least one op, l_seq > 0 and at
+ * least one M = X base.  The ops are the core CIGAR's, or those of the CG:B:I tag when the core CIGAR is <l_seq>S<n>N and the record has the tag
+ * (lra_bam_depth's rule and code).  A record that passes the filters and has no op, l_seq = 0 or no M = X base is skipped and counted (the script
+ * raises IndexError / TypeError on these); the others that are not walked count as filtered.
+ * The walk, over the ops in order with two counters, q in SEQ (from 0) and r on the reference (from pos).  Ops of length 0 and H and P yield nothing
+ * and do not part a run.  M = X advance both; aq = q - 1 behind them is the SEQ index of the last aligned base.  Everything in front of the first M = X
+ * base is skipped (it only advances the counters).  Behind it, consecutive I / S ops form one insertion run (they advance q) and consecutive D / N ops
+ * one deletion run (they advance r): I P I and I I are one run, D N D is one run.  With r0 the value of r where the run begins, its anchor is the
+ * reference base r0 - 1: the last base in front of the run, aligned or -- behind a deletion run -- deleted.  aq does not move in either run.  A run that
+ * is followed by another entry (an M = X base or a run of the other kind) is a variant; a run that reaches the end of the CIGAR is none.
+ *   INS   POS = r0 - 1, REF = the genome base there, ALT = SEQ[aq, q) with q behind the run: from the anchor through the last inserted base
+ *   DEL   POS = r0 - 1, REF = the genome [r0 - 1, r) with r behind the run: from the anchor through the last deleted base, ALT = SEQ[aq]
+ * QSTART = aq + 1.  REF's first base comes from the genome and ALT's first from the read: they differ when the anchor is a mismatch.  SEQ is decoded
+ * through "=ACMGRSVTWYHKDBN"; genome bytes are copied as loaded, from chrom_pos[refID] + position.  SVLEN = len(ALT) - len(REF); SVTYPE is DEL if it is
+ * negative, else INS.
+ * Where the script is not followed.  (1) An insertion run directly followed by a deletion run: the script takes the rest of the read as ALT; here ALT
+ * ends with the run's last inserted base, which is the script's rule wherever the next entry has a query position.  (2) The records the script would
+ * crash on (above) are skipped and counted.  (3) Chromosomes are matched to the genome by index, not by name.
+ * The line:  RNAME \t POS \t . \t REF \t ALT \t 60 \t PASS \t SVTYPE=%s;SVLEN=%d;QNAME=%s;QSTART=%d;QSTRAND=%c \t GT \t 1/1 \n, QSTRAND '-' for flag
+ * 0x10.  Lines come in the file's order of the records and within a record in CIGAR order; nothing is sorted.
+ * Region (lra_bam_view_region's conventions: 0-based, half-open, end clamped, beg == end an empty pass, no index or a bad ref_id LRA_ERR_INVALID): the
+ * pass reads the records that overlap [beg, end) and prints the variants whose anchor position, 0-based, lies in [beg, end).  Over a whole reference
+ * this is the script's --chrom.
+ * Values (want_values): one lra_bam_vcf_variant per line, in the lines' order: ref_id, the anchor's 0-based position (whatever pos_one_based says),
+ * qstart, svlen, kind (0 INS, 1 DEL), strand (1 for flag 0x10), record = the record's 0-based ordinal among the records the pass has read (in a pass
+ * over the whole file: in the file), text_off = where its line begins in the piece's text (0 without text).
+ * Pieces: whole lines, one piece per window that has variants, in page-locked memory of the object, valid until the next call on it; n_variants == 0
+ * && text_len == 0: the pass is over.
+ * Refusals (LRA_ERR_INVALID, the pass's own under this object's name -- a BGZF fault, a bad block_size or record, an aux block that ends inside a tag
+ * while a CG tag is looked for, a file that ends inside a record -- and): a record that passes the filters with an op code above 8; a walked record
+ * whose query-consuming ops (M I S = X) do not sum to l_seq; a walked record with pos < 0 or whose reference span ends beyond its reference.  The
+ * lowest record of a window is refused, for the first of these reasons that holds.  The records in front of the fault are delivered first, the next
+ * call refuses, and the object takes another pass.
+ * Memory.  Beside the step's and the frame's arrays (lra_bam_view's formula: C + 1 + 2 (D + 4096 + 64) + 20 (M + 1) + 8 (D / 36 + 2)), a window of N
+ * framed records with O ops in G runs and V variants whose lines take X bytes allocates on the device
+ *     32 N (region passes: + 16 N) + 42 O + 40 G + 176 V + X + 64
+ * each array an eighth larger than asked and never shrunk; X + 1 + 40 V bytes of page-locked host memory take the text and the values.  X has no
+ * bound a priori -- a deletion's REF is as long as the deletion --: it is the total of the scanned line lengths, in 64 bits, and a text that cannot
+ * be allocated is LRA_ERR_NOMEM, never a cut line.
+ * Stats, summed over the object's life: windows, records read / walked / filtered / skipped, INS and DEL lines, bytes read / inflated / printed, ms
+ * per stage (read + inflate: wall; frame + select, ops, walk, lengths, emit, copy: HIP events). */
+typedef struct lra_bam_vcf lra_bam_vcf;
+struct lra_bam_vcf_opts {
+  uint32_t require, exclude, min_mapq, min_length, pos_one_based, want_text, want_values, reserved;
+  uint64_t window_bytes;
+};
+struct lra_bam_vcf_variant {
+  uint64_t record, text_off; int64_t svlen;
+  int32_t ref_id, pos; uint32_t qstart; uint8_t kind, strand; uint16_t pad;
+};
+struct lra_bam_vcf_piece {
+  uint64_t n_variants; const struct lra_bam_vcf_variant* variants; const char* text; uint64_t text_len;
+};
+struct lra_bam_vcf_stats {
+  uint64_t windows, records_read, records_walked, records_filtered, records_skipped, n_ins, n_del, bytes_read, bytes_inflated, bytes_text;
+  double ms_read_inflate, ms_frame_select, ms_ops, ms_walk, ms_lengths, ms_emit, ms_copy;
+};
+int lra_bam_vcf_create(lra_ctx* ctx, const char* bam_path, const char* bai_path, const struct lra_bam_vcf_opts* opts, lra_bam_vcf** out);
+int lra_bam_vcf_header(lra_bam_vcf* d, int* n_ref, const char* const** names, const uint64_t** ref_len);
+int lra_bam_vcf_all(lra_bam_vcf* d);
+int lra_bam_vcf_region(lra_bam_vcf* d, int32_t ref_id, int64_t beg, int64_t end);
+int lra_bam_vcf_next(lra_bam_vcf* d, struct lra_bam_vcf_piece* piece);
+int lra_bam_vcf_stats(lra_bam_vcf* d, struct lra_bam_vcf_stats* out);
+void lra_bam_vcf_destroy(lra_bam_vcf* d);
 /* the reads of a snapshot whose status word is non-zero: their number; *status (optional) = the snapshot's status array [n_reads], owned by the snapshot */
 uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status);
 /* The record buffer of a batch as ONE device buffer -- what a rank sends to rank 0 in the single exchange step of the multi-GPU path (the

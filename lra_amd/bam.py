@@ -387,6 +387,116 @@ class BamDepth:
             pass
 
 
+class VcfOpts(C.Structure):
+    """struct lra_bam_vcf_opts (include/lra_hip.h)"""
+    _fields_ = [(k, C.c_uint32) for k in ("require", "exclude", "min_mapq", "min_length", "pos_one_based", "want_text", "want_values", "reserved")] + \
+               [("window_bytes", C.c_uint64)]
+
+
+# struct lra_bam_vcf_variant (include/lra_hip.h), 40 bytes
+VCF_VARIANT_DTYPE = np.dtype([("record", "<u8"), ("text_off", "<u8"), ("svlen", "<i8"), ("ref_id", "<i4"), ("pos", "<i4"), ("qstart", "<u4"), ("kind", "u1"),
+                              ("strand", "u1"), ("pad", "<u2")])
+
+
+class VcfPiece(C.Structure):
+    """struct lra_bam_vcf_piece (include/lra_hip.h)"""
+    _fields_ = [("n_variants", C.c_uint64), ("variants", C.c_void_p), ("text", C.c_void_p), ("text_len", C.c_uint64)]
+
+
+class VcfStats(C.Structure):
+    """struct lra_bam_vcf_stats (include/lra_hip.h)"""
+    _fields_ = [(k, C.c_uint64) for k in ("windows", "records_read", "records_walked", "records_filtered", "records_skipped", "n_ins", "n_del", "bytes_read",
+                                          "bytes_inflated", "bytes_text")] + \
+               [(k, C.c_double) for k in ("ms_read_inflate", "ms_frame_select", "ms_ops", "ms_walk", "ms_lengths", "ms_emit", "ms_copy")]
+
+
+VCF_INFO_LINES = (
+    '##INFO=<ID=QNAME,Number=1,Type=String,Description="Name of query sequence">\n'
+    '##INFO=<ID=QSTART,Number=1,Type=Integer,Description="Position of query sequence">\n'
+    '##INFO=<ID=QSTRAND,Number=1,Type=String,Description="Contig strand">\n'
+    '##INFO=<ID=SVLEN,Number=.,Type=Integer,Description="Difference in length between REF and ALT alleles">\n'
+    '##INFO=<ID=SVTYPE,Number=1,Type=String,Description="Type of structural variant">\n'
+    '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">\n')
+
+
+def vcf_header(reference, names, lens, sample="unknown"):
+    """the header in front of BamVcf's lines (no GPU): the file format, date and source lines of the reference's script, ##reference=<the path given>, one
+    ##contig line per entry of the BAM header's reference table (names as bytes or str), the five INFO lines, the FORMAT line and the column line with
+    the sample's name -> bytes"""
+    text = lambda x: x.decode() if isinstance(x, bytes) else str(x)
+    out = "##fileformat=VCFv4.2\n##fileDate=20190102\n##source=SamToVCF\n##reference=%s\n" % text(reference)
+    out += "".join("##contig=<ID=%s,length=%d>\n" % (text(n), int(k)) for n, k in zip(names, lens))
+    out += VCF_INFO_LINES + "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n" % text(sample)
+    return out.encode()
+
+
+class BamVcf:
+    """lra_bam_vcf: one VCF line per insertion and deletion of a BAM file's alignments, walked and printed on the device.  ctx must hold the genome and its
+    chromosome table (lra_amd.genome_io.GenomeFile(...).install(ctx), or lra_ctx_load_genome + lra_ctx_load_chromosomes), in the order of the file's
+    reference table.  bai: the path of its .bai index (None: whole-file passes only).  exclude None: 0x4.  text / values: what a pass hands back."""
+
+    def __init__(self, ctx: Context, path, bai=None, require=0, exclude=None, min_mapq=0, min_length=1, pos_one_based=False, text=True, values=False,
+                 window_bytes=0):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        o = VcfOpts(int(require), 0xffffffff if exclude is None else int(exclude), int(min_mapq), int(min_length), int(bool(pos_one_based)), int(bool(text)),
+                    int(bool(values)), 0, int(window_bytes))
+        ctx.check(ctx.lib.lra_bam_vcf_create(ctx.h, os.fsencode(path), os.fsencode(bai) if bai is not None else None, C.byref(o), C.byref(self.h)))
+
+    def header(self):
+        """-> (the reference names as bytes, their lengths)"""
+        n_ref, nm, rl = C.c_int(0), C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.ctx.lib.lra_bam_vcf_header(self.h, C.byref(n_ref), C.byref(nm), C.byref(rl)))
+        k = n_ref.value
+        names = [C.string_at(q) for q in (C.c_char_p * k).from_address(nm.value)] if k else []
+        lens = list((C.c_uint64 * k).from_address(rl.value)) if k else []
+        return names, lens
+
+    def fetch(self, ref=None, beg=0, end=None):
+        """yields the pieces of a pass as (n_variants, values, text): ref None: the whole file; ref: a reference's index or name, [beg, end) 0-based
+        half-open (end None: the reference's end).  values: a numpy record array of VCF_VARIANT_DTYPE (None when the object was made without values) -- a
+        view of the object's memory, valid until the next piece; text: bytes (b"" without text)."""
+        lib = self.ctx.lib
+        if ref is None:
+            self.ctx.check(lib.lra_bam_vcf_all(self.h))
+        else:
+            names, lens = self.header()
+            if not isinstance(ref, int):
+                key = ref.encode() if isinstance(ref, str) else ref
+                if key not in names:
+                    raise ValueError("no reference %r in the file" % ref)
+                ref = names.index(key)
+            if end is None:
+                end = lens[ref] if 0 <= ref < len(lens) else 0
+            self.ctx.check(lib.lra_bam_vcf_region(self.h, C.c_int32(ref), C.c_int64(int(beg)), C.c_int64(int(end))))
+        while True:
+            p = VcfPiece()
+            self.ctx.check(lib.lra_bam_vcf_next(self.h, C.byref(p)))
+            if not p.n_variants and not p.text_len:
+                return
+            vals = None
+            if p.variants and p.n_variants:
+                vals = np.ctypeslib.as_array(C.cast(p.variants, C.POINTER(C.c_uint8)), shape=(p.n_variants * VCF_VARIANT_DTYPE.itemsize,)).view(VCF_VARIANT_DTYPE)
+            yield p.n_variants, vals, (C.string_at(p.text, p.text_len) if p.text_len else b"")
+
+    def stats(self):
+        s = VcfStats()
+        self.ctx.check(self.ctx.lib.lra_bam_vcf_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in VcfStats._fields_}
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:
+                self.ctx.lib.lra_bam_vcf_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def bai_query(bai, n_ref, ref_id, beg, end, lib=None):
     """lra_bai_query_host (no GPU): the chunks [(beg, end)] of virtual offsets a region pass reads, from the .bai bytes.  n_ref: the BAM header's
     reference count (-1: not compared).  ValueError for LRA_ERR_INVALID (an index the reader refuses, ref_id outside it, beg > end)."""

@@ -73,16 +73,7 @@ __global__ void __launch_bounds__(256) dp_select(Dp V) {
     if (inside && ((uint32_t)c.ref > (uint32_t)V.ref_id || (c.ref == V.ref_id && (int64_t)c.pos >= V.end))) atomicMin(&V.bad[3], (unsigned long long)i);
   }
   uint64_t ops = at0 + 36 + c.l_name; uint32_t n_op = c.n_cig;
-  if (keep && cg_form_at(V.data + ops, c)) {                   // the ops are the CG:B:I tag's, if the record has one
-    const uint64_t end = V.pos[i + 1];
-    uint64_t at = at0 + 4 + c.fixed;
-    while (at < end) {
-      uint8_t t, s; uint64_t val, next; uint32_t cnt;
-      if (!tag_at(V.data, at, end, &t, &s, &val, &cnt, &next)) { atomicMin(&V.bad[2], (unsigned long long)i); keep = false; break; }
-      if (V.data[at] == 'C' && V.data[at + 1] == 'G' && t == 'B' && s == 'I') { ops = val; n_op = cnt; break; }
-      at = next;
-    }
-  }
+  if (keep && !ops_of(V.data, at0, V.pos[i + 1], c, &ops, &n_op)) { atomicMin(&V.bad[2], (unsigned long long)i); keep = false; }   // (the CG:B:I tag's, if the record has one)
   V.keep[i] = keep ? 1u : 0u; V.c_op[i] = keep ? n_op : 0u; V.ops_src[i] = ops;
   V.r_ref[i] = c.ref; V.r_pos[i] = c.pos;
 }

@@ -1,6 +1,7 @@
 // lra_amd/csrc/bam_pass.h -- lra_bam_pass: one pass over the records of a BAM file in windows, whole or for a region reached through its .bai index.
-// What lra_bam_view (bam_view.hip: the records as SAM text) and lra_bam_depth (bam_depth.hip: the records as coverage) share: the file, its header and
-// index, the BGZF step, a region's plan and chunk rules, the window loop with its carry and virtual-offset bookkeeping, and the refusal texts.
+// What lra_bam_view (bam_view.hip: the records as SAM text), lra_bam_depth (bam_depth.hip: the records as coverage) and lra_bam_vcf (bam_vcf.hip: their
+// insertions and deletions as VCF lines) share: the file, its header and index, the BGZF step, a region's plan and chunk rules, the window loop with its
+// carry and virtual-offset bookkeeping, and the refusal texts.
 // include/lra_hip.h states the rules under lra_bam_view.
 //
 // window.  One lra_bgzf_step (zsource.h) reads `window` compressed bytes, inflates their whole members on the device behind the carried tail and

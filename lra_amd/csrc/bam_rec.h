@@ -1,6 +1,6 @@
-// lra_amd/csrc/bam_rec.h -- what the readers of raw BAM records on the device share (bam_view.hip, bam_depth.hip): a record's core fields, the walk over
-// its aux block, the test for the CG:B:I form of a long CIGAR, decimal digits, and the small host helpers of a windowed pass (event timer, grid sizes,
-// the growable device array).  The kernels and helpers are TU-local, as scan.h's and bam_keys.h's are.
+// lra_amd/csrc/bam_rec.h -- what the readers of raw BAM records on the device share (bam_view.hip, bam_depth.hip, bam_vcf.hip): a record's core fields, the
+// walk over its aux block, the test for the CG:B:I form of a long CIGAR and where a record's ops are, the packed SEQ as bases by one wave, decimal digits,
+// and the small host helpers of a windowed pass (event timer, grid sizes, the growable device array).  The kernels and helpers are TU-local, as scan.h's and bam_keys.h's are.
 #pragma once
 #include "common.h"
 #include "bam_keys.h"
@@ -78,6 +78,48 @@ __device__ __forceinline__ bool tag_at(const uint8_t* d, uint64_t at, uint64_t e
     return true;
   }
   return false;
+}
+
+// Where record at0's ops are (depth and the variant walk count the same ones): the core CIGAR, or the elements of the CG:B:I tag, wherever it stands in the
+// aux block, when the core CIGAR is <l_seq>S<n>N and the record has the tag.  false: the aux block ends inside a tag or names an unknown type in front of it.
+__device__ __forceinline__ bool ops_of(const uint8_t* data, uint64_t at0, uint64_t end, const Core& c, uint64_t* ops, uint32_t* n_op) {
+  *ops = at0 + 36 + c.l_name; *n_op = c.n_cig;
+  if (!cg_form_at(data + *ops, c)) return true;
+  uint64_t at = at0 + 4 + c.fixed;
+  while (at < end) {
+    uint8_t t, s; uint64_t val, next; uint32_t cnt;
+    if (!tag_at(data, at, end, &t, &s, &val, &cnt, &next)) return false;
+    if (data[at] == 'C' && data[at + 1] == 'G' && t == 'B' && s == 'I') { *ops = val; *n_op = cnt; return true; }
+    at = next;
+  }
+  return true;
+}
+
+// n bases of the packed sequence `seq` from base j0 on to dst, by one wave: dst in aligned dwords, each lane two of them (eight bases) from one source
+// dword (and the byte behind it when the eight start in a byte's low nibble); bytes in front of the first aligned dword and behind the last whole eight.
+// A byte holds its first base in the high nibble: with the nibbles of every byte swapped, nibble m of the source is base m.
+__device__ __forceinline__ uint32_t four_bases(uint32_t v) {   // the four nibbles of v's low 16 bits, the first base lowest
+  const char* T = "=ACMGRSVTWYHKDBN";
+  return (uint32_t)(uint8_t)T[v & 15] | ((uint32_t)(uint8_t)T[(v >> 4) & 15] << 8) | ((uint32_t)(uint8_t)T[(v >> 8) & 15] << 16) | ((uint32_t)(uint8_t)T[(v >> 12) & 15] << 24);
+}
+__device__ __forceinline__ unsigned char base_at(const uint8_t* seq, uint64_t j) { return (unsigned char)"=ACMGRSVTWYHKDBN"[(seq[j >> 1] >> ((~j & 1) << 2)) & 15]; }
+__device__ __forceinline__ void wave_seq(unsigned char* dst, const uint8_t* seq, uint64_t j0, uint64_t n, int lane) {
+  const uint64_t head = min(n, (uint64_t)((4 - ((uintptr_t)dst & 3)) & 3));
+  if ((uint64_t)lane < head) dst[lane] = base_at(seq, j0 + lane);
+  dst += head; j0 += head; n -= head;
+  const uint64_t n8 = n >> 3;
+  uint32_t* d32 = (uint32_t*)dst;
+  for (uint64_t i = lane; i < n8; i += 64) {
+    const uint64_t j = j0 + 8 * i;
+    const uint8_t* s = seq + (j >> 1);
+    uint64_t w = ld32(s);
+    if (j & 1) w |= (uint64_t)s[4] << 32;                      // (base j + 7 is the high nibble of s[4]: inside the sequence)
+    uint64_t x = ((w & 0x0f0f0f0f0full) << 4) | ((w >> 4) & 0x0f0f0f0f0full);
+    if (j & 1) x >>= 4;
+    d32[2 * i] = four_bases((uint32_t)x & 0xffffu); d32[2 * i + 1] = four_bases((uint32_t)(x >> 16) & 0xffffu);
+  }
+  const uint64_t done = 8 * n8, tail = n - done;              // at most 7 bases
+  if ((uint64_t)lane < tail) dst[done + lane] = base_at(seq, j0 + done + lane);
 }
 
 struct Timer {

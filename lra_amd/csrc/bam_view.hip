@@ -17,7 +17,7 @@
 // printed there with "%.6g" and come back as text (one copy each way per window).  bv_pieces, a lane per record, sizes the pieces; one scan places them.
 // emit.  bv_small, a lane per record: the fields a lane prints (numbers, RNAME, tag prefixes, scalars).  bv_ops / bv_elems, a lane per op / element at
 // its scanned offset.  bv_bulk, chunk_copy.h's walk: the output cut into 4 KiB chunks, a wave each, aligned dword stores; names and Z / H strings are
-// copies, SEQ is expanded eight bases per source dword through the 16-entry table, QUAL is + 33.  The text is one device buffer, one copy to the host.
+// copies, SEQ is expanded eight bases per source dword through the 16-entry table (wave_seq, bam_rec.h), QUAL is + 33.  The text is one device buffer, one copy to the host.
 #include "common.h"
 #include "chunk_copy.h"
 #include "scan.h"
@@ -290,33 +290,6 @@ __global__ void __launch_bounds__(256) bv_elems(View V) {
     const uint64_t f = I.f0 + k;
     for (uint32_t q = V.ftoff[f]; q < V.ftoff[f + 1]; q++) *d++ = (unsigned char)V.ftext[q];
   } else put_s(d, int_value(V.data + I.src + k * type_size(t), t));
-}
-
-// n bases of the packed sequence `seq` from base j0 on to dst, by one wave: dst in aligned dwords, each lane two of them (eight bases) from one source
-// dword (and the byte behind it when the eight start in a byte's low nibble); bytes in front of the first aligned dword and behind the last whole eight.
-// A byte holds its first base in the high nibble: with the nibbles of every byte swapped, nibble m of the source is base m.
-__device__ __forceinline__ uint32_t four_bases(uint32_t v) {   // the four nibbles of v's low 16 bits, the first base lowest
-  const char* T = "=ACMGRSVTWYHKDBN";
-  return (uint32_t)(uint8_t)T[v & 15] | ((uint32_t)(uint8_t)T[(v >> 4) & 15] << 8) | ((uint32_t)(uint8_t)T[(v >> 8) & 15] << 16) | ((uint32_t)(uint8_t)T[(v >> 12) & 15] << 24);
-}
-__device__ __forceinline__ unsigned char base_at(const uint8_t* seq, uint64_t j) { return (unsigned char)"=ACMGRSVTWYHKDBN"[(seq[j >> 1] >> ((~j & 1) << 2)) & 15]; }
-__device__ __forceinline__ void wave_seq(unsigned char* dst, const uint8_t* seq, uint64_t j0, uint64_t n, int lane) {
-  const uint64_t head = min(n, (uint64_t)((4 - ((uintptr_t)dst & 3)) & 3));
-  if ((uint64_t)lane < head) dst[lane] = base_at(seq, j0 + lane);
-  dst += head; j0 += head; n -= head;
-  const uint64_t n8 = n >> 3;
-  uint32_t* d32 = (uint32_t*)dst;
-  for (uint64_t i = lane; i < n8; i += 64) {
-    const uint64_t j = j0 + 8 * i;
-    const uint8_t* s = seq + (j >> 1);
-    uint64_t w = ld32(s);
-    if (j & 1) w |= (uint64_t)s[4] << 32;                      // (base j + 7 is the high nibble of s[4]: inside the sequence)
-    uint64_t x = ((w & 0x0f0f0f0f0full) << 4) | ((w >> 4) & 0x0f0f0f0f0full);
-    if (j & 1) x >>= 4;
-    d32[2 * i] = four_bases((uint32_t)x & 0xffffu); d32[2 * i + 1] = four_bases((uint32_t)(x >> 16) & 0xffffu);
-  }
-  const uint64_t done = 8 * n8, tail = n - done;              // at most 7 bases
-  if ((uint64_t)lane < tail) dst[done + lane] = base_at(seq, j0 + done + lane);
 }
 
 // n qualities from src to dst, + 33, by one wave (wave_copy's shape)
