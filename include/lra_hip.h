@@ -489,7 +489,9 @@ int lra_filter_chains_ex_batch(lra_ctx* ctx, uint64_t n_chains, const uint64_t* 
  * given as index ranges into two tuple arrays; max_freq = opts.localMaxFreq; per-task diagonal bounds
  * (NULL = unbounded; the filter applies only when both are non-zero, CompareLists.h:87).  Output: the
  * emitted pairs as absolute indices into the two tuple arrays, CSR by task, in the reference's order
- * (context-owned, valid until the next call).  Synchronous.                                        */
+ * (context-owned, valid until the next call).  Synchronous.  Both tuple arrays must be 16-byte aligned
+ * and readable up to the next 32-byte boundary beyond their last tuple (the walk of large tasks fetches
+ * whole 8-word lines); the d_tuples of the library's own index results satisfy this.               */
 typedef struct lra_local_index_result {
   int32_t n_seqs;
   uint64_t n_windows, n_tuples, bytes;

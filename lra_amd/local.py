@@ -20,11 +20,16 @@ class LocalPairsResult(C.Structure):
 class LocalIndex:
     """Device-resident local index of a set of sequences (owns its buffer)."""
 
-    def __init__(self, ctx: Context, seq_dev, off_dev, k=10, w=5, window=256, max_freq=15):
+    def __init__(self, ctx: Context, seq_dev, off_dev, k=10, w=5, window=256, max_freq=15, active=None):
+        """active: a device uint8 tensor, one byte per sequence; a sequence whose byte is 0 keeps its windows but gets no tuples (lra_local_index_masked_batch)."""
         self.ctx, self.k, self.w, self.window, self.max_freq = ctx, k, w, window, max_freq
         n = int(off_dev.numel()) - 1
         res = LocalIndexResult()
-        ctx.check(ctx.lib.lra_local_index_batch(ctx.h, n, ptr(seq_dev), ptr(off_dev), k, w, window, max_freq, C.byref(res)))
+        if active is None:
+            ctx.check(ctx.lib.lra_local_index_batch(ctx.h, n, ptr(seq_dev), ptr(off_dev), k, w, window, max_freq, C.byref(res)))
+        else:
+            assert active.dtype == torch.uint8 and int(active.numel()) == n
+            ctx.check(ctx.lib.lra_local_index_masked_batch(ctx.h, n, ptr(seq_dev), ptr(off_dev), ptr(active), k, w, window, max_freq, C.byref(res)))
         # keep it: copy out of the context-owned buffer and re-base the three pointers
         self.buf = ctx.to_tensor(res.d_base, int(res.bytes), torch.uint8)
         base_old, base_new = int(res.d_base), self.buf.data_ptr()
