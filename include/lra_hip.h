@@ -1785,7 +1785,19 @@ void lra_bam_depth_destroy(lra_bam_depth* d);
  *   opts      require / exclude as lra_bam_depth's; exclude ~0u means 0x4 (pysam's fetch yields every mapped record, secondary and supplementary
  *             included).  min_mapq.  min_length: a variant is kept if |len(ALT) - len(REF)| >= min_length; 0 is raised to 1.  pos_one_based 0: POS is
  *             the 0-based position of the anchor base, as the script prints it; 1: that + 1, as VCF means it.  want_text, want_values (one of them
- *             must be set), window_bytes as the view's.  NULL opts: the defaults, text only.
+ *             must be set), window_bytes as the view's.  drop_contained (the field that was `reserved`; 0: off, today's output): see below.  NULL
+ *             opts: the defaults, text only.
+ * drop_contained: the reference's ParseAlignment.py, the step in front of SamToVCF.py in call_assembly_SVs, which drops every alignment that lies inside
+ * an earlier one so that a nested contig alignment does not call the same indel again.  The filter runs over the records with refID >= 0 in file order,
+ * in front of the flag and MAPQ filters (the script sees every line).  e(i) = pos + 1 + tlen in 64 bits, tlen the stored field (lra writes
+ * tEnd - tStart: Alignment.h says the script depends on it; the field may be negative).  The first record of each run of equal refID is kept; record i
+ * is dropped when e(i) <= the largest e(j) of the earlier records j of its run -- equal ends drop.  (The script compares with the end of the last kept
+ * record, which is that maximum: a dropped record never exceeds it.)  On the device: a segmented max-scan over the window's records
+ * (bam_contained.h), the last refID and its running maximum carried from window to window and moved on only when a window is delivered, so a window
+ * run again in front of a refused record starts from the same carry.  It holds for a pass over the whole file and for a region pass with beg == 0,
+ * which reads every record of the reference with pos < end in order; lra_bam_vcf_region with beg > 0 and the filter on is LRA_ERR_INVALID and says
+ * why.  Dropped records are not walked, count in records_contained and not in records_filtered; `record` still counts every record read.  The filter
+ * adds 4 N + 24 (N / 2048 + 3) device bytes to a window of N records.
  * Which records are walked.  refID >= 0, (flag & require) == require && (flag & exclude) == 0, mapq >= min_mapq, at least one op, l_seq > 0 and at
  * least one M = X base.  The ops are the core CIGAR's, or those of the CG:B:I tag when the core CIGAR is <l_seq>S<n>N and the record has the tag
  * (lra_bam_depth's rule and code).  A record that passes the filters and has no op, l_seq = 0 or no M = X base is skipped and counted (the script
@@ -1829,7 +1841,7 @@ void lra_bam_depth_destroy(lra_bam_depth* d);
  * per stage (read + inflate: wall; frame + select, ops, walk, lengths, emit, copy: HIP events). */
 typedef struct lra_bam_vcf lra_bam_vcf;
 struct lra_bam_vcf_opts {
-  uint32_t require, exclude, min_mapq, min_length, pos_one_based, want_text, want_values, reserved;
+  uint32_t require, exclude, min_mapq, min_length, pos_one_based, want_text, want_values, drop_contained;
   uint64_t window_bytes;
 };
 struct lra_bam_vcf_variant {
@@ -1842,6 +1854,7 @@ struct lra_bam_vcf_piece {
 struct lra_bam_vcf_stats {
   uint64_t windows, records_read, records_walked, records_filtered, records_skipped, n_ins, n_del, bytes_read, bytes_inflated, bytes_text;
   double ms_read_inflate, ms_frame_select, ms_ops, ms_walk, ms_lengths, ms_emit, ms_copy;
+  uint64_t records_contained;                                  /* appended: what drop_contained dropped */
 };
 int lra_bam_vcf_create(lra_ctx* ctx, const char* bam_path, const char* bai_path, const struct lra_bam_vcf_opts* opts, lra_bam_vcf** out);
 int lra_bam_vcf_header(lra_bam_vcf* d, int* n_ref, const char* const** names, const uint64_t** ref_len);
@@ -1850,6 +1863,86 @@ int lra_bam_vcf_region(lra_bam_vcf* d, int32_t ref_id, int64_t beg, int64_t end)
 int lra_bam_vcf_next(lra_bam_vcf* d, struct lra_bam_vcf_piece* piece);
 int lra_bam_vcf_stats(lra_bam_vcf* d, struct lra_bam_vcf_stats* out);
 void lra_bam_vcf_destroy(lra_bam_vcf* d);
+/* ---- Assembly SV calls from a coordinate-sorted BAM: filter, call, size, mask, number, merge (additive to ABI 9) ---------------------------------------
+ * lra_bam_svcalls is the one-haplotype half of the reference's call_assembly_SVs/callassemblysv.snakefile on the device: the rules parseAlignment
+ * (ParseAlignment.py), CallSV (SamToVCF.py), FilterBySizeAndSVTYPE, FilterByCentromereAndAltChromAndAddID and mergeCalls (bedtools, awk, mergeSV.py).
+ * Input is a coordinate-sorted BAM of one haplotype's contig alignments, output the merged DEL and INS tables; the variant table stays on the device
+ * from the records to the printed lines.  Combining two haplotypes (Homcalls, Hetcalls, combineHet) is not done.  It is the fourth consumer of the pass
+ * (bam_pass.h), and shares the contained filter and the walk with lra_bam_vcf (bam_contained.h, bam_vcf_walk.h); one object serves one context.
+ *   create    as lra_bam_vcf_create: the context must hold the genome and its chromosome table, compared with the BAM header's reference table.
+ *   opts      require / exclude / min_mapq / window_bytes as lra_bam_vcf's.  drop_contained: lra_bam_vcf's filter (NULL opts: 1).  min_size: a
+ *             candidate needs |SVLEN| >= min_size; 0 is raised to 1 (NULL opts: 40).  aligner, hap: the ID's words, printable and without blanks; NULL:
+ *             "aligner" and "maternal".  pos_one_based: the text's START and END are printed + 1 (the values never).  vcf_columns: the line has no END
+ *             column -- ten columns with the ID third, as a VCF line.  want_text, want_values: one of them must be set (NULL opts: text only).
+ * A pass covers the whole file (lra_bam_svcalls_all) or a whole reference (lra_bam_svcalls_region with beg == 0 and end >= the reference's length; it
+ * needs the index): anything narrower is LRA_ERR_INVALID, because the merge and the numbering need every row.
+ * Per reference, in file order:
+ *   candidates  the variants of lra_bam_vcf's walk over the records the contained filter kept, with |SVLEN| >= min_size; the kind is SVLEN's sign.  A row
+ *               is START = the anchor's 0-based position (the POS the script prints), END = START + |SVLEN|: FilterBySizeAndSVTYPE's awk, where
+ *               len(REF) - len(ALT) = |SVLEN| for a DEL and the converse for an INS.  DEL and INS rows are two independent tables from here on.
+ *   mask        lra_bam_svcalls_set_mask(n, ref_id[], beg[], end[]): half-open 0-based intervals in any order, overlapping or not; n = 0 is no mask
+ *               (the state after create).  A row is dropped when START < m.end && m.beg < END for an interval m of its reference: bedtools
+ *               intersect -v -- one shared base drops, touching does not.  An interval with ref_id outside the header's table, beg < 0 or end < beg is
+ *               LRA_ERR_INVALID.  The call ends a pass in hand.  The snakefile's alt-chromosome awk, $1!~/^GL/ || $1!~/^hs37d5/ || $1!~/^NC/, is
+ *               always true (no name begins with all three): it drops nothing, and neither is anything dropped here.
+ *   numbering   NR counts the rows of a kind that survive the mask from 1, over the pass, in row order: the file's order of the records, then CIGAR
+ *               order.  The ID is <aligner>.<DEL|INS>.<hap>.<NR>.  (The snakefile passes -v aln=aligner to awk, so the files it writes carry the
+ *               literal word "aligner", not "lra": the default here.)
+ *   merge       for rows i, j of one kind and one reference, ov = min(END) - max(START); R(i, j) holds when ov > 0 && 10 ov >= len_i && 10 ov > len_j
+ *               with len = END - START: mergeCalls' awk over bedtools intersect -wao, $23 / ($3 - $2) >= 0.1 && $23 / ($14 - $13) > 0.1 (the asymmetry
+ *               is the snakefile's; the integer form is the double test exactly: a quotient that is not 1 / 10 differs from it by at least
+ *               1 / (10 len), far above an ulp).  In NR order row i is kept unless an earlier KEPT row k has R(k, i): mergeSV.py.  A dropped row
+ *               spreads nothing: of A ~ B ~ C with A and C unrelated, A and C are kept.  NR order is not position order (a long record's late
+ *               variant precedes the next record's early one).  On the device: every row's earlier related rows as an edge list, then rounds -- a
+ *               row is kept once all of them are dropped, dropped once one is kept -- until a round decides nothing; no cap, the result is the serial
+ *               walk's for every input.  The pairs are found among the earlier rows of the reference and kind, by tiles of 256 rows in NR order: a tile
+ *               whose rows' interval shares no base with the row is passed over, which in a sorted file leaves the tiles near the row.
+ *   delivery    a reference's rows are final when a record of a later reference has been delivered or the pass ends.  They come as its DEL piece, then
+ *               its INS piece (piece.kind 1, 0; piece.ref_id); a kind without rows has no piece.  One line per kept row, in NR order:
+ *                 RNAME \t START \t END \t ID \t REF \t ALT \t 60 \t PASS \t INFO \t GT \t 1/1 \n
+ *               REF, ALT and INFO byte for byte lra_bam_vcf's.  Between windows the table keeps, beside its numbers, only what cannot be had again: QNAME
+ *               and ALT; REF is read from the resident genome when the line is printed, and only kept rows are printed.
+ * Values (want_values): one lra_bam_svcalls_row per kept row: ref_id, start, end (0-based), nr, svlen, qstart, kind (0 INS, 1 DEL), strand, record (the
+ * record's ordinal among the records the pass has read), text_off.
+ * Pieces live in page-locked memory of the object, valid until the next call on it; n_rows == 0 && text_len == 0: the pass is over.
+ * Refusals (LRA_ERR_INVALID): lra_bam_vcf's, under this object's name, and a record that sorts in front of its predecessor by (refID, pos), refID -1
+ * last ("the file is not coordinate-sorted at record N"): the filter and the delivery by reference rely on the order.  The pieces of the references
+ * that were final in front of the fault -- those with a later reference's record delivered -- come first, then the call refuses; what the unfinished
+ * reference had gathered is dropped, and the object takes another pass.
+ * Memory.  Beside the step's and the walk's arrays (lra_bam_vcf's formula, the text apart: 32 N (+ 16 N) + 42 O + 40 G + 88 V, + 4 N + 24 (N / 2048 + 3)
+ * with the filter), a window with V candidates allocates 24 V + 32; the tables hold 88 bytes per row plus its QNAME and ALT, for the reference in hand
+ * and what a window has read of the next, twice at most while rows move to the front; a reference's M rows of a kind with E related pairs and K kept
+ * rows whose lines take X bytes allocate 36 M + 16 (M / 256 + 1) + 4 E + 32 K + X + 64 K (values) + 64, each array an eighth larger than asked and never shrunk; X + 1 +
+ * 64 K bytes of page-locked host memory take a piece.
+ * Stats, summed over the object's life: windows, records read / contained / walked; rows too small, masked, merged away and kept, each for INS and DEL;
+ * the merge's deciding rounds; bytes read / inflated / printed; ms per stage (read + inflate: wall; frame + select, ops, walk, lengths -- the walk's --
+ * rows, merge, emit, copy: HIP events). */
+typedef struct lra_bam_svcalls lra_bam_svcalls;
+struct lra_bam_svcalls_opts {
+  uint32_t require, exclude, min_mapq, min_size, drop_contained, pos_one_based, vcf_columns, want_text, want_values, reserved;
+  uint64_t window_bytes;
+  const char* aligner; const char* hap;
+};
+struct lra_bam_svcalls_row {
+  uint64_t record, text_off, nr; int64_t start, end, svlen;
+  int32_t ref_id; uint32_t qstart; uint8_t kind, strand; uint16_t pad; uint32_t pad2;
+};
+struct lra_bam_svcalls_piece {
+  uint64_t n_rows; const struct lra_bam_svcalls_row* rows; const char* text; uint64_t text_len; int32_t ref_id; uint32_t kind;
+};
+struct lra_bam_svcalls_stats {
+  uint64_t windows, records_read, records_contained, records_walked, small_ins, small_del, masked_ins, masked_del, merged_ins, merged_del, kept_ins, kept_del,
+           merge_rounds, bytes_read, bytes_inflated, bytes_text;
+  double ms_read_inflate, ms_frame_select, ms_ops, ms_walk, ms_lengths, ms_rows, ms_merge, ms_emit, ms_copy;
+};
+int lra_bam_svcalls_create(lra_ctx* ctx, const char* bam_path, const char* bai_path, const struct lra_bam_svcalls_opts* opts, lra_bam_svcalls** out);
+int lra_bam_svcalls_header(lra_bam_svcalls* d, int* n_ref, const char* const** names, const uint64_t** ref_len);
+int lra_bam_svcalls_set_mask(lra_bam_svcalls* d, uint64_t n, const int32_t* ref_id, const int64_t* beg, const int64_t* end);
+int lra_bam_svcalls_all(lra_bam_svcalls* d);
+int lra_bam_svcalls_region(lra_bam_svcalls* d, int32_t ref_id, int64_t beg, int64_t end);
+int lra_bam_svcalls_next(lra_bam_svcalls* d, struct lra_bam_svcalls_piece* piece);
+int lra_bam_svcalls_stats(lra_bam_svcalls* d, struct lra_bam_svcalls_stats* out);
+void lra_bam_svcalls_destroy(lra_bam_svcalls* d);
 /* the reads of a snapshot whose status word is non-zero: their number; *status (optional) = the snapshot's status array [n_reads], owned by the snapshot */
 uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status);
 /* The record buffer of a batch as ONE device buffer -- what a rank sends to rank 0 in the single exchange step of the multi-GPU path (the

@@ -389,7 +389,7 @@ class BamDepth:
 
 class VcfOpts(C.Structure):
     """struct lra_bam_vcf_opts (include/lra_hip.h)"""
-    _fields_ = [(k, C.c_uint32) for k in ("require", "exclude", "min_mapq", "min_length", "pos_one_based", "want_text", "want_values", "reserved")] + \
+    _fields_ = [(k, C.c_uint32) for k in ("require", "exclude", "min_mapq", "min_length", "pos_one_based", "want_text", "want_values", "drop_contained")] + \
                [("window_bytes", C.c_uint64)]
 
 
@@ -407,7 +407,8 @@ class VcfStats(C.Structure):
     """struct lra_bam_vcf_stats (include/lra_hip.h)"""
     _fields_ = [(k, C.c_uint64) for k in ("windows", "records_read", "records_walked", "records_filtered", "records_skipped", "n_ins", "n_del", "bytes_read",
                                           "bytes_inflated", "bytes_text")] + \
-               [(k, C.c_double) for k in ("ms_read_inflate", "ms_frame_select", "ms_ops", "ms_walk", "ms_lengths", "ms_emit", "ms_copy")]
+               [(k, C.c_double) for k in ("ms_read_inflate", "ms_frame_select", "ms_ops", "ms_walk", "ms_lengths", "ms_emit", "ms_copy")] + \
+               [("records_contained", C.c_uint64)]
 
 
 VCF_INFO_LINES = (
@@ -433,14 +434,16 @@ def vcf_header(reference, names, lens, sample="unknown"):
 class BamVcf:
     """lra_bam_vcf: one VCF line per insertion and deletion of a BAM file's alignments, walked and printed on the device.  ctx must hold the genome and its
     chromosome table (lra_amd.genome_io.GenomeFile(...).install(ctx), or lra_ctx_load_genome + lra_ctx_load_chromosomes), in the order of the file's
-    reference table.  bai: the path of its .bai index (None: whole-file passes only).  exclude None: 0x4.  text / values: what a pass hands back."""
+    reference table.  bai: the path of its .bai index (None: whole-file passes only).  exclude None: 0x4.  text / values: what a pass hands back.
+    drop_contained: records that lie inside an earlier record of their reference are not walked (the reference's ParseAlignment.py; the file must be
+    coordinate-sorted, and a region pass must begin at 0)."""
 
     def __init__(self, ctx: Context, path, bai=None, require=0, exclude=None, min_mapq=0, min_length=1, pos_one_based=False, text=True, values=False,
-                 window_bytes=0):
+                 window_bytes=0, drop_contained=False):
         self.ctx = ctx
         self.h = C.c_void_p()
         o = VcfOpts(int(require), 0xffffffff if exclude is None else int(exclude), int(min_mapq), int(min_length), int(bool(pos_one_based)), int(bool(text)),
-                    int(bool(values)), 0, int(window_bytes))
+                    int(bool(values)), int(bool(drop_contained)), int(window_bytes))
         ctx.check(ctx.lib.lra_bam_vcf_create(ctx.h, os.fsencode(path), os.fsencode(bai) if bai is not None else None, C.byref(o), C.byref(self.h)))
 
     def header(self):
@@ -488,6 +491,119 @@ class BamVcf:
         if self.h:
             if self.ctx.h:
                 self.ctx.lib.lra_bam_vcf_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SvCallsOpts(C.Structure):
+    """struct lra_bam_svcalls_opts (include/lra_hip.h)"""
+    _fields_ = [(k, C.c_uint32) for k in ("require", "exclude", "min_mapq", "min_size", "drop_contained", "pos_one_based", "vcf_columns", "want_text", "want_values",
+                                          "reserved")] + [("window_bytes", C.c_uint64), ("aligner", C.c_char_p), ("hap", C.c_char_p)]
+
+
+# struct lra_bam_svcalls_row (include/lra_hip.h), 64 bytes
+SVCALLS_ROW_DTYPE = np.dtype([("record", "<u8"), ("text_off", "<u8"), ("nr", "<u8"), ("start", "<i8"), ("end", "<i8"), ("svlen", "<i8"), ("ref_id", "<i4"),
+                              ("qstart", "<u4"), ("kind", "u1"), ("strand", "u1"), ("pad", "<u2"), ("pad2", "<u4")])
+
+
+class SvCallsPiece(C.Structure):
+    """struct lra_bam_svcalls_piece (include/lra_hip.h)"""
+    _fields_ = [("n_rows", C.c_uint64), ("rows", C.c_void_p), ("text", C.c_void_p), ("text_len", C.c_uint64), ("ref_id", C.c_int32), ("kind", C.c_uint32)]
+
+
+class SvCallsStats(C.Structure):
+    """struct lra_bam_svcalls_stats (include/lra_hip.h)"""
+    _fields_ = [(k, C.c_uint64) for k in ("windows", "records_read", "records_contained", "records_walked", "small_ins", "small_del", "masked_ins", "masked_del",
+                                          "merged_ins", "merged_del", "kept_ins", "kept_del", "merge_rounds", "bytes_read", "bytes_inflated", "bytes_text")] + \
+               [(k, C.c_double) for k in ("ms_read_inflate", "ms_frame_select", "ms_ops", "ms_walk", "ms_lengths", "ms_rows", "ms_merge", "ms_emit", "ms_copy")]
+
+
+def parse_bed(lines, names):
+    """the intervals of a BED file's lines (bytes or str; 0-based, half-open; track, browser and comment lines skipped) whose name is one of `names` -- the
+    BAM header's -- -> [(ref_id, beg, end)]; other names are ignored (no GPU)"""
+    idx = {(n.decode() if isinstance(n, bytes) else n): k for k, n in enumerate(names)}
+    out = []
+    for ln in lines:
+        ln = ln.decode() if isinstance(ln, bytes) else ln
+        f = ln.split()
+        if len(f) < 3 or f[0].startswith("#") or f[0] in ("track", "browser"):
+            continue
+        if f[0] in idx:
+            out.append((idx[f[0]], int(f[1]), int(f[2])))
+    return out
+
+
+class BamSvCalls:
+    """lra_bam_svcalls: the merged DEL and INS tables of one haplotype's assembly alignments, from a coordinate-sorted BAM -- the contained filter, the calls,
+    the size and mask filters, the numbering and the merge of the reference's call_assembly_SVs pipeline, on the device (include/lra_hip.h has the rules).
+    ctx must hold the genome and its chromosome table, as for BamVcf.  vcf_columns: lines without the END column."""
+
+    def __init__(self, ctx: Context, path, bai=None, require=0, exclude=None, min_mapq=0, min_size=40, drop_contained=True, aligner="aligner", hap="maternal",
+                 pos_one_based=False, vcf_columns=False, text=True, values=False, window_bytes=0):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
+        o = SvCallsOpts(int(require), 0xffffffff if exclude is None else int(exclude), int(min_mapq), int(min_size), int(bool(drop_contained)), int(bool(pos_one_based)),
+                        int(bool(vcf_columns)), int(bool(text)), int(bool(values)), 0, int(window_bytes), enc(aligner), enc(hap))
+        ctx.check(ctx.lib.lra_bam_svcalls_create(ctx.h, os.fsencode(path), os.fsencode(bai) if bai is not None else None, C.byref(o), C.byref(self.h)))
+
+    def header(self):
+        """-> (the reference names as bytes, their lengths)"""
+        n_ref, nm, rl = C.c_int(0), C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.ctx.lib.lra_bam_svcalls_header(self.h, C.byref(n_ref), C.byref(nm), C.byref(rl)))
+        k = n_ref.value
+        names = [C.string_at(q) for q in (C.c_char_p * k).from_address(nm.value)] if k else []
+        lens = list((C.c_uint64 * k).from_address(rl.value)) if k else []
+        return names, lens
+
+    def set_mask(self, intervals):
+        """intervals: [(ref_id, beg, end)], 0-based and half-open, in any order; [] takes the mask away"""
+        iv = list(intervals)
+        r = np.ascontiguousarray([x[0] for x in iv], np.int32)
+        b = np.ascontiguousarray([x[1] for x in iv], np.int64)
+        e = np.ascontiguousarray([x[2] for x in iv], np.int64)
+        q = lambda a: C.c_void_p(a.ctypes.data) if len(a) else None
+        self.ctx.check(self.ctx.lib.lra_bam_svcalls_set_mask(self.h, C.c_uint64(len(iv)), q(r), q(b), q(e)))
+
+    def fetch(self, ref=None):
+        """yields the pieces of a pass as (ref_id, kind "DEL" / "INS", n_rows, values, text): ref None: the whole file; ref: a reference's index or name.  A
+        reference's DEL piece comes in front of its INS piece.  values: a numpy record array of SVCALLS_ROW_DTYPE (None when the object was made without
+        values) -- a view of the object's memory, valid until the next piece; text: bytes (b"" without text)."""
+        lib = self.ctx.lib
+        if ref is None:
+            self.ctx.check(lib.lra_bam_svcalls_all(self.h))
+        else:
+            names, lens = self.header()
+            if not isinstance(ref, int):
+                key = ref.encode() if isinstance(ref, str) else ref
+                if key not in names:
+                    raise ValueError("no reference %r in the file" % ref)
+                ref = names.index(key)
+            self.ctx.check(lib.lra_bam_svcalls_region(self.h, C.c_int32(ref), C.c_int64(0), C.c_int64(lens[ref] if 0 <= ref < len(lens) else 0)))
+        while True:
+            p = SvCallsPiece()
+            self.ctx.check(lib.lra_bam_svcalls_next(self.h, C.byref(p)))
+            if not p.n_rows and not p.text_len:
+                return
+            vals = None
+            if p.rows and p.n_rows:
+                vals = np.ctypeslib.as_array(C.cast(p.rows, C.POINTER(C.c_uint8)), shape=(p.n_rows * SVCALLS_ROW_DTYPE.itemsize,)).view(SVCALLS_ROW_DTYPE)
+            yield p.ref_id, "DEL" if p.kind else "INS", p.n_rows, vals, (C.string_at(p.text, p.text_len) if p.text_len else b"")
+
+    def stats(self):
+        s = SvCallsStats()
+        self.ctx.check(self.ctx.lib.lra_bam_svcalls_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in SvCallsStats._fields_}
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:
+                self.ctx.lib.lra_bam_svcalls_destroy(self.h)
             self.h = None
 
     def __del__(self):
