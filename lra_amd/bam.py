@@ -207,6 +207,73 @@ class BamMerger:
             pass
 
 
+class _BamPass:
+    """What the wrappers of the windowed passes over a BAM file share (BamView, BamDepth, BamVcf, BamSvCalls; bam_pass.h behind them): the handle, made
+    and reached through the C functions <_prefix>_create, _header, _all, _region, _next, _stats and _destroy; the file's reference names and lengths,
+    decoded once; a pass's start from ref / beg / end; stats() from the class's _Stats structure."""
+    _prefix = None
+    _Stats = None
+    _header_front = 0                                                           # pointer arguments of <_prefix>_header in front of n_ref (BamView: the text, its length)
+
+    def _fn(self, name):
+        return getattr(self.ctx.lib, "%s_%s" % (self._prefix, name))
+
+    def _create(self, ctx, path, bai, *args):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        self._refs = None
+        ctx.check(self._fn("create")(ctx.h, os.fsencode(path), os.fsencode(bai) if bai is not None else None, *args, C.byref(self.h)))
+
+    def _references(self):
+        """-> (the reference names as bytes, their lengths): new lists"""
+        if self._refs is None:
+            n_ref, nm, rl = C.c_int(0), C.c_void_p(), C.c_void_p()
+            self.ctx.check(self._fn("header")(self.h, *([None] * self._header_front), C.byref(n_ref), C.byref(nm), C.byref(rl)))
+            k = n_ref.value
+            self._refs = ([C.string_at(q) for q in (C.c_char_p * k).from_address(nm.value)] if k else [],
+                          list((C.c_uint64 * k).from_address(rl.value)) if k else [])
+        return list(self._refs[0]), list(self._refs[1])
+
+    def _start(self, ref, beg=0, end=None):
+        """starts a pass: ref None: the whole file; ref: a reference's index or name, [beg, end) 0-based half-open (end None: the reference's end)"""
+        if ref is None:
+            self.ctx.check(self._fn("all")(self.h))
+            return
+        names, lens = self._references()
+        if not isinstance(ref, int):
+            key = ref.encode() if isinstance(ref, str) else ref
+            if key not in names:
+                raise ValueError("no reference %r in the file" % ref)
+            ref = names.index(key)
+        if end is None:
+            end = lens[ref] if 0 <= ref < len(lens) else 0
+        self.ctx.check(self._fn("region")(self.h, C.c_int32(ref), C.c_int64(int(beg)), C.c_int64(int(end))))
+
+    def _next(self, *out):
+        self.ctx.check(self._fn("next")(self.h, *[C.byref(x) for x in out]))
+
+    def header(self):
+        """-> (the reference names as bytes, their lengths)"""
+        return self._references()
+
+    def stats(self):
+        s = self._Stats()
+        self.ctx.check(self._fn("stats")(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in self._Stats._fields_}
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:                                                      # (an object that outlives its context is left alone: destroy needs the context's device)
+                self._fn("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ViewStats(C.Structure):
     """struct lra_bam_view_stats (include/lra_hip.h)"""
     _fields_ = [("windows", C.c_uint64), ("records", C.c_uint64), ("bytes_read", C.c_uint64), ("bytes_inflated", C.c_uint64), ("bytes_text", C.c_uint64),
@@ -236,24 +303,19 @@ def parse_region(text, names, ref_len):
     return r, beg, end
 
 
-class BamView:
+class BamView(_BamPass):
     """lra_bam_view: the records of a BAM file as SAM text, printed on the device; bai: the path of its .bai index (None: whole-file passes only);
     window_bytes: compressed bytes per step (0: the library's default)."""
+    _prefix, _Stats, _header_front = "lra_bam_view", ViewStats, 2
 
     def __init__(self, ctx: Context, path, bai=None, window_bytes=0):
-        self.ctx = ctx
-        self.h = C.c_void_p()
-        ctx.check(ctx.lib.lra_bam_view_create(ctx.h, os.fsencode(path), os.fsencode(bai) if bai is not None else None, C.c_uint64(int(window_bytes)),
-                                              C.byref(self.h)))
+        self._create(ctx, path, bai, C.c_uint64(int(window_bytes)))
 
     def header(self):
         """-> (header text as bytes, the reference names as bytes, their lengths)"""
-        t, n, n_ref, nm, rl = C.c_void_p(), C.c_uint64(0), C.c_int(0), C.c_void_p(), C.c_void_p()
-        self.ctx.check(self.ctx.lib.lra_bam_view_header(self.h, C.byref(t), C.byref(n), C.byref(n_ref), C.byref(nm), C.byref(rl)))
-        k = n_ref.value
-        names = [C.string_at(q) for q in (C.c_char_p * k).from_address(nm.value)] if k else []
-        lens = list((C.c_uint64 * k).from_address(rl.value)) if k else []
-        return (C.string_at(t, n.value) if n.value else b""), names, lens
+        t, n = C.c_void_p(), C.c_uint64(0)
+        self.ctx.check(self.ctx.lib.lra_bam_view_header(self.h, C.byref(t), C.byref(n), None, None, None))
+        return ((C.string_at(t, n.value) if n.value else b""),) + self._references()
 
     def set_flags(self, require=0, exclude=0):
         self.ctx.check(self.ctx.lib.lra_bam_view_set_flags(self.h, C.c_uint32(int(require)), C.c_uint32(int(exclude))))
@@ -261,44 +323,15 @@ class BamView:
     def fetch(self, ref=None, beg=0, end=None):
         """yields the pieces (bytes: whole SAM lines) of a pass: ref None: every record; ref: a reference's index or name, [beg, end) 0-based half-open
         (end None: the reference's end).  self.last_records counts the pass's lines."""
-        lib = self.ctx.lib
-        if ref is None:
-            self.ctx.check(lib.lra_bam_view_all(self.h))
-        else:
-            _, names, lens = self.header()
-            if not isinstance(ref, int):
-                key = ref.encode() if isinstance(ref, str) else ref
-                if key not in names:
-                    raise ValueError("no reference %r in the file" % ref)
-                ref = names.index(key)
-            if end is None:
-                end = lens[ref] if 0 <= ref < len(lens) else 0
-            self.ctx.check(lib.lra_bam_view_region(self.h, C.c_int32(ref), C.c_int64(int(beg)), C.c_int64(int(end))))
+        self._start(ref, beg, end)
         self.last_records = 0
         while True:
             p, n, k = C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
-            self.ctx.check(lib.lra_bam_view_next(self.h, C.byref(p), C.byref(n), C.byref(k)))
+            self._next(p, n, k)
             if not n.value:
                 return
             self.last_records += k.value
             yield C.string_at(p, n.value)
-
-    def stats(self):
-        s = ViewStats()
-        self.ctx.check(self.ctx.lib.lra_bam_view_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in ViewStats._fields_}
-
-    def close(self):
-        if self.h:
-            if self.ctx.h:
-                self.ctx.lib.lra_bam_view_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class DepthOpts(C.Structure):
@@ -320,71 +353,32 @@ class DepthStats(C.Structure):
                [(k, C.c_double) for k in ("ms_read_inflate", "ms_frame_select", "ms_ops", "ms_accumulate", "ms_finish", "ms_text", "ms_copy")]
 
 
-class BamDepth:
+class BamDepth(_BamPass):
     """lra_bam_depth: the coverage of a coordinate-sorted BAM file, computed on the device, per base (bin 0) or per bin; bai: the path of its .bai index
     (None: whole-file passes only).  exclude None: 0x704, what samtools depth drops.  text / values: what a pass hands back."""
+    _prefix, _Stats = "lra_bam_depth", DepthStats
 
     def __init__(self, ctx: Context, path, bai=None, require=0, exclude=None, min_mapq=0, count_deletions=False, bin=0, all_positions=False, text=True,
                  values=False, window_bytes=0, span_bases=0):
-        self.ctx = ctx
-        self.h = C.c_void_p()
         self.bin = int(bin)
         o = DepthOpts(int(require), 0xffffffff if exclude is None else int(exclude), int(min_mapq), int(bool(count_deletions)), self.bin,
                       int(bool(all_positions)), int(bool(text)), int(bool(values)), int(window_bytes), int(span_bases))
-        ctx.check(ctx.lib.lra_bam_depth_create(ctx.h, os.fsencode(path), os.fsencode(bai) if bai is not None else None, C.byref(o), C.byref(self.h)))
-
-    def header(self):
-        """-> (the reference names as bytes, their lengths)"""
-        n_ref, nm, rl = C.c_int(0), C.c_void_p(), C.c_void_p()
-        self.ctx.check(self.ctx.lib.lra_bam_depth_header(self.h, C.byref(n_ref), C.byref(nm), C.byref(rl)))
-        k = n_ref.value
-        names = [C.string_at(q) for q in (C.c_char_p * k).from_address(nm.value)] if k else []
-        lens = list((C.c_uint64 * k).from_address(rl.value)) if k else []
-        return names, lens
+        self._create(ctx, path, bai, C.byref(o))
 
     def fetch(self, ref=None, beg=0, end=None):
         """yields the pieces of a pass as (ref_id, first, count, values, text): ref None: the whole file; ref: a reference's index or name, [beg, end)
         0-based half-open (end None: the reference's end).  values: a numpy array (uint32 depths from position `first` on, or uint64 bin sums from the
         bin that starts at `first` on; None when the object was made without values) -- a view of the object's memory, valid until the next piece;
         text: bytes (b"" without text)."""
-        lib = self.ctx.lib
-        if ref is None:
-            self.ctx.check(lib.lra_bam_depth_all(self.h))
-        else:
-            names, lens = self.header()
-            if not isinstance(ref, int):
-                key = ref.encode() if isinstance(ref, str) else ref
-                if key not in names:
-                    raise ValueError("no reference %r in the file" % ref)
-                ref = names.index(key)
-            if end is None:
-                end = lens[ref] if 0 <= ref < len(lens) else 0
-            self.ctx.check(lib.lra_bam_depth_region(self.h, C.c_int32(ref), C.c_int64(int(beg)), C.c_int64(int(end))))
+        self._start(ref, beg, end)
         while True:
             p = DepthPiece()
-            self.ctx.check(lib.lra_bam_depth_next(self.h, C.byref(p)))
+            self._next(p)
             if not p.count and not p.text_len:
                 return
             at, dt = (p.sum, np.uint64) if self.bin else (p.depth, np.uint32)
             vals = np.ctypeslib.as_array(C.cast(at, C.POINTER(C.c_uint64 if self.bin else C.c_uint32)), shape=(p.count,)).view(dt) if at and p.count else None
             yield p.ref_id, p.first, p.count, vals, (C.string_at(p.text, p.text_len) if p.text_len else b"")
-
-    def stats(self):
-        s = DepthStats()
-        self.ctx.check(self.ctx.lib.lra_bam_depth_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in DepthStats._fields_}
-
-    def close(self):
-        if self.h:
-            if self.ctx.h:
-                self.ctx.lib.lra_bam_depth_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class VcfOpts(C.Structure):
@@ -431,73 +425,34 @@ def vcf_header(reference, names, lens, sample="unknown"):
     return out.encode()
 
 
-class BamVcf:
+class BamVcf(_BamPass):
     """lra_bam_vcf: one VCF line per insertion and deletion of a BAM file's alignments, walked and printed on the device.  ctx must hold the genome and its
     chromosome table (lra_amd.genome_io.GenomeFile(...).install(ctx), or lra_ctx_load_genome + lra_ctx_load_chromosomes), in the order of the file's
     reference table.  bai: the path of its .bai index (None: whole-file passes only).  exclude None: 0x4.  text / values: what a pass hands back.
     drop_contained: records that lie inside an earlier record of their reference are not walked (the reference's ParseAlignment.py; the file must be
     coordinate-sorted, and a region pass must begin at 0)."""
+    _prefix, _Stats = "lra_bam_vcf", VcfStats
 
     def __init__(self, ctx: Context, path, bai=None, require=0, exclude=None, min_mapq=0, min_length=1, pos_one_based=False, text=True, values=False,
                  window_bytes=0, drop_contained=False):
-        self.ctx = ctx
-        self.h = C.c_void_p()
         o = VcfOpts(int(require), 0xffffffff if exclude is None else int(exclude), int(min_mapq), int(min_length), int(bool(pos_one_based)), int(bool(text)),
                     int(bool(values)), int(bool(drop_contained)), int(window_bytes))
-        ctx.check(ctx.lib.lra_bam_vcf_create(ctx.h, os.fsencode(path), os.fsencode(bai) if bai is not None else None, C.byref(o), C.byref(self.h)))
-
-    def header(self):
-        """-> (the reference names as bytes, their lengths)"""
-        n_ref, nm, rl = C.c_int(0), C.c_void_p(), C.c_void_p()
-        self.ctx.check(self.ctx.lib.lra_bam_vcf_header(self.h, C.byref(n_ref), C.byref(nm), C.byref(rl)))
-        k = n_ref.value
-        names = [C.string_at(q) for q in (C.c_char_p * k).from_address(nm.value)] if k else []
-        lens = list((C.c_uint64 * k).from_address(rl.value)) if k else []
-        return names, lens
+        self._create(ctx, path, bai, C.byref(o))
 
     def fetch(self, ref=None, beg=0, end=None):
         """yields the pieces of a pass as (n_variants, values, text): ref None: the whole file; ref: a reference's index or name, [beg, end) 0-based
         half-open (end None: the reference's end).  values: a numpy record array of VCF_VARIANT_DTYPE (None when the object was made without values) -- a
         view of the object's memory, valid until the next piece; text: bytes (b"" without text)."""
-        lib = self.ctx.lib
-        if ref is None:
-            self.ctx.check(lib.lra_bam_vcf_all(self.h))
-        else:
-            names, lens = self.header()
-            if not isinstance(ref, int):
-                key = ref.encode() if isinstance(ref, str) else ref
-                if key not in names:
-                    raise ValueError("no reference %r in the file" % ref)
-                ref = names.index(key)
-            if end is None:
-                end = lens[ref] if 0 <= ref < len(lens) else 0
-            self.ctx.check(lib.lra_bam_vcf_region(self.h, C.c_int32(ref), C.c_int64(int(beg)), C.c_int64(int(end))))
+        self._start(ref, beg, end)
         while True:
             p = VcfPiece()
-            self.ctx.check(lib.lra_bam_vcf_next(self.h, C.byref(p)))
+            self._next(p)
             if not p.n_variants and not p.text_len:
                 return
             vals = None
             if p.variants and p.n_variants:
                 vals = np.ctypeslib.as_array(C.cast(p.variants, C.POINTER(C.c_uint8)), shape=(p.n_variants * VCF_VARIANT_DTYPE.itemsize,)).view(VCF_VARIANT_DTYPE)
             yield p.n_variants, vals, (C.string_at(p.text, p.text_len) if p.text_len else b"")
-
-    def stats(self):
-        s = VcfStats()
-        self.ctx.check(self.ctx.lib.lra_bam_vcf_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in VcfStats._fields_}
-
-    def close(self):
-        if self.h:
-            if self.ctx.h:
-                self.ctx.lib.lra_bam_vcf_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class SvCallsOpts(C.Structure):
@@ -538,28 +493,18 @@ def parse_bed(lines, names):
     return out
 
 
-class BamSvCalls:
+class BamSvCalls(_BamPass):
     """lra_bam_svcalls: the merged DEL and INS tables of one haplotype's assembly alignments, from a coordinate-sorted BAM -- the contained filter, the calls,
     the size and mask filters, the numbering and the merge of the reference's call_assembly_SVs pipeline, on the device (include/lra_hip.h has the rules).
     ctx must hold the genome and its chromosome table, as for BamVcf.  vcf_columns: lines without the END column."""
+    _prefix, _Stats = "lra_bam_svcalls", SvCallsStats
 
     def __init__(self, ctx: Context, path, bai=None, require=0, exclude=None, min_mapq=0, min_size=40, drop_contained=True, aligner="aligner", hap="maternal",
                  pos_one_based=False, vcf_columns=False, text=True, values=False, window_bytes=0):
-        self.ctx = ctx
-        self.h = C.c_void_p()
         enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
         o = SvCallsOpts(int(require), 0xffffffff if exclude is None else int(exclude), int(min_mapq), int(min_size), int(bool(drop_contained)), int(bool(pos_one_based)),
                         int(bool(vcf_columns)), int(bool(text)), int(bool(values)), 0, int(window_bytes), enc(aligner), enc(hap))
-        ctx.check(ctx.lib.lra_bam_svcalls_create(ctx.h, os.fsencode(path), os.fsencode(bai) if bai is not None else None, C.byref(o), C.byref(self.h)))
-
-    def header(self):
-        """-> (the reference names as bytes, their lengths)"""
-        n_ref, nm, rl = C.c_int(0), C.c_void_p(), C.c_void_p()
-        self.ctx.check(self.ctx.lib.lra_bam_svcalls_header(self.h, C.byref(n_ref), C.byref(nm), C.byref(rl)))
-        k = n_ref.value
-        names = [C.string_at(q) for q in (C.c_char_p * k).from_address(nm.value)] if k else []
-        lens = list((C.c_uint64 * k).from_address(rl.value)) if k else []
-        return names, lens
+        self._create(ctx, path, bai, C.byref(o))
 
     def set_mask(self, intervals):
         """intervals: [(ref_id, beg, end)], 0-based and half-open, in any order; [] takes the mask away"""
@@ -574,43 +519,16 @@ class BamSvCalls:
         """yields the pieces of a pass as (ref_id, kind "DEL" / "INS", n_rows, values, text): ref None: the whole file; ref: a reference's index or name.  A
         reference's DEL piece comes in front of its INS piece.  values: a numpy record array of SVCALLS_ROW_DTYPE (None when the object was made without
         values) -- a view of the object's memory, valid until the next piece; text: bytes (b"" without text)."""
-        lib = self.ctx.lib
-        if ref is None:
-            self.ctx.check(lib.lra_bam_svcalls_all(self.h))
-        else:
-            names, lens = self.header()
-            if not isinstance(ref, int):
-                key = ref.encode() if isinstance(ref, str) else ref
-                if key not in names:
-                    raise ValueError("no reference %r in the file" % ref)
-                ref = names.index(key)
-            self.ctx.check(lib.lra_bam_svcalls_region(self.h, C.c_int32(ref), C.c_int64(0), C.c_int64(lens[ref] if 0 <= ref < len(lens) else 0)))
+        self._start(ref)
         while True:
             p = SvCallsPiece()
-            self.ctx.check(lib.lra_bam_svcalls_next(self.h, C.byref(p)))
+            self._next(p)
             if not p.n_rows and not p.text_len:
                 return
             vals = None
             if p.rows and p.n_rows:
                 vals = np.ctypeslib.as_array(C.cast(p.rows, C.POINTER(C.c_uint8)), shape=(p.n_rows * SVCALLS_ROW_DTYPE.itemsize,)).view(SVCALLS_ROW_DTYPE)
             yield p.ref_id, "DEL" if p.kind else "INS", p.n_rows, vals, (C.string_at(p.text, p.text_len) if p.text_len else b"")
-
-    def stats(self):
-        s = SvCallsStats()
-        self.ctx.check(self.ctx.lib.lra_bam_svcalls_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in SvCallsStats._fields_}
-
-    def close(self):
-        if self.h:
-            if self.ctx.h:
-                self.ctx.lib.lra_bam_svcalls_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def bai_query(bai, n_ref, ref_id, beg, end, lib=None):

@@ -1,10 +1,11 @@
 // lra_amd/csrc/bam_depth.hip -- lra_bam_depth: the coverage of a coordinate-sorted BAM file, per base or per bin, whole or for a region (gfx950).
-// include/lra_hip.h has the interface and the rules; bam_pass.h is the pass it shares with lra_bam_view (the windows, a region's plan, the refusals).
+// include/lra_hip.h has the interface and the rules; bam_pass.h is the pass it shares with lra_bam_view (the windows, a region's plan, the refusals) and
+// the record front in front of dp_select (Front, rec_check, rec_in_region, rec_cut) with the handle shell.
 //
-// records.  dp_check, a lane per framed record: the record's arithmetic (bam_rec.h, the view's rule).  bs_span (bam_keys.h) gives a region pass every
-// record's span for the overlap test.  dp_select, a lane per record: the order against the record in front (the carried key for the first), the filter
-// (refID, flag, mapq, the overlap), the first record at or behind the region's end, and where the ops are: the core CIGAR, or the CG:B:I tag found by the
-// aux walk when the core CIGAR is <l_seq>S<n>N.  One scan of the op counts.
+// records.  The pass's front: rec_check, a lane per framed record: the record's arithmetic; bs_span gives a region pass every record's span for the overlap
+// test.  dp_select, a lane per record: the order against the record in front (the carried key for the first), the filter (refID, flag, mapq, and
+// rec_in_region's overlap and first record at or behind the region's end; rec_cut behind it), and where the ops are: the core CIGAR, or the CG:B:I tag
+// found by the aux walk when the core CIGAR is <l_seq>S<n>N.  One scan of the op counts.
 // ops.  dp_oplen, a lane per op: its reference length (M D N = X), the op code against 8.  One scan over the ops; less its value at the record's first
 // op it is the op's offset from the record's pos.  dp_ends, a lane per record: pos + the reference length of its ops.
 // accumulate.  dp_accum, a lane per op, adds to the difference array diff[] of the position window [dbase, dbase + span): + 1 where a maximal run of
@@ -32,72 +33,54 @@ constexpr uint64_t PIECE_POS = 4ull << 20;                    // positions (or b
 constexpr uint64_t PIECE_TEXT = 64ull << 20;                  // and the bytes of its text
 constexpr uint32_t DEFAULT_EXCLUDE = 0x704;
 
+enum { B_ORDER = B_OWN, B_AUX, B_OP };                         // bad[] behind the pass's words: the lowest record out of order, with a bad aux block, with a bad op code
+
 struct Dp {                                                   // what the kernels of a window see
-  const uint8_t* data; const uint64_t* pos; uint64_t n;       // record i is data[pos[i], pos[i + 1])
-  int n_ref; uint32_t req, excl, min_mapq, count_del;
-  int region; int32_t ref_id; int64_t beg, end; uint64_t limit;
+  Front F;                                                    // (bam_pass.h) record i is F.data[F.pos[i], F.pos[i + 1])
+  uint32_t req, excl, min_mapq, count_del;
   uint32_t last_ref; int32_t last_pos; int has_last;          // the key of the record in front of the window's first
-  uint32_t* keep; Meta M;
+  uint32_t* keep;
   int32_t* r_ref; int32_t* r_pos; int64_t* r_end;
   uint32_t* c_op; uint64_t* op_off; uint64_t* ops_src;
   uint32_t* oplen; uint64_t* ostart; uint64_t n_op;
-  unsigned long long* bad;                                    // the lowest bad record: [0] dp_check, [1] the order, [2] the aux walk, [4] an op code; [3] the first record at or behind the region's end
 };
 
 __device__ __forceinline__ bool consumes_ref(uint32_t code) { return (0x18du >> code) & 1u; }            // M D N = X
 __device__ __forceinline__ bool covers(uint32_t code, uint32_t count_del) { return code == 0 || code == 7 || code == 8 || (code == 2 && count_del); }
 
-__global__ void __launch_bounds__(256) dp_check(Dp V) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V.n) return;
-  const uint8_t* p = V.data + V.pos[i];
-  const Core c = core_of(p);
-  if (!core_ok(p, c, V.pos[i + 1] - V.pos[i], V.n_ref)) atomicMin(&V.bad[0], (unsigned long long)i);
-}
-
 __global__ void __launch_bounds__(256) dp_select(Dp V) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V.n) return;
-  const uint64_t at0 = V.pos[i];
-  const uint8_t* p = V.data + at0;
+  if (i >= V.F.n) return;
+  const uint64_t at0 = V.F.pos[i];
+  const uint8_t* p = V.F.data + at0;
   const Core c = core_of(p);
   // the order: (refID, pos) with refID -1 last
   uint32_t pr = 0; int32_t pp = 0; bool has = false;
-  if (i) { const uint8_t* q = V.data + V.pos[i - 1]; pr = le32(q + 4); pp = (int32_t)le32(q + 8); has = true; }
+  if (i) { const uint8_t* q = V.F.data + V.F.pos[i - 1]; pr = le32(q + 4); pp = (int32_t)le32(q + 8); has = true; }
   else if (V.has_last) { pr = V.last_ref; pp = V.last_pos; has = true; }
-  if (has && ((uint32_t)c.ref < pr || ((uint32_t)c.ref == pr && c.pos < pp))) atomicMin(&V.bad[1], (unsigned long long)i);
+  if (has && ((uint32_t)c.ref < pr || ((uint32_t)c.ref == pr && c.pos < pp))) atomicMin(&V.F.bad[B_ORDER], (unsigned long long)i);
   bool keep = c.ref >= 0 && (c.flag & V.req) == V.req && (c.flag & V.excl) == 0 && c.mapq >= V.min_mapq;
-  if (V.region) {
-    const bool inside = at0 < V.limit;
-    keep = keep && inside && c.ref == V.ref_id && (int64_t)c.pos < V.end && (int64_t)c.pos + (int64_t)V.M.span[i] > V.beg;
-    if (inside && ((uint32_t)c.ref > (uint32_t)V.ref_id || (c.ref == V.ref_id && (int64_t)c.pos >= V.end))) atomicMin(&V.bad[3], (unsigned long long)i);
-  }
+  if (V.F.region) keep = rec_in_region(V.F, i, c.ref, c.pos) && keep;
   uint64_t ops = at0 + 36 + c.l_name; uint32_t n_op = c.n_cig;
-  if (keep && !ops_of(V.data, at0, V.pos[i + 1], c, &ops, &n_op)) { atomicMin(&V.bad[2], (unsigned long long)i); keep = false; }   // (the CG:B:I tag's, if the record has one)
+  if (keep && !ops_of(V.F.data, at0, V.F.pos[i + 1], c, &ops, &n_op)) { atomicMin(&V.F.bad[B_AUX], (unsigned long long)i); keep = false; }   // (the CG:B:I tag's, if the record has one)
   V.keep[i] = keep ? 1u : 0u; V.c_op[i] = keep ? n_op : 0u; V.ops_src[i] = ops;
   V.r_ref[i] = c.ref; V.r_pos[i] = c.pos;
-}
-
-// nothing at or behind the first record at or behind the region's end is taken
-__global__ void __launch_bounds__(256) dp_cut(Dp V) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < V.n && i >= V.bad[3]) { V.keep[i] = 0; V.c_op[i] = 0; }
 }
 
 __global__ void __launch_bounds__(256) dp_oplen(Dp V) {
   const uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= V.n_op) return;
-  const uint64_t r = last_le(V.op_off, V.n, o);
-  const uint32_t op = le32(V.data + V.ops_src[r] + 4 * (o - V.op_off[r]));
+  const uint64_t r = last_le(V.op_off, V.F.n, o);
+  const uint32_t op = le32(V.F.data + V.ops_src[r] + 4 * (o - V.op_off[r]));
   const uint32_t code = op & 15u;
-  if (code > 8u) atomicMin(&V.bad[4], (unsigned long long)r);
+  if (code > 8u) atomicMin(&V.F.bad[B_OP], (unsigned long long)r);
   V.oplen[o] = code <= 8u && consumes_ref(code) ? op >> 4 : 0u;
 }
 
 // a lane per record: the end of its ops on the reference
 __global__ void __launch_bounds__(256) dp_ends(Dp V) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V.n) return;
+  if (i >= V.F.n) return;
   int64_t e = (int64_t)V.r_pos[i];
   if (V.keep[i]) e += (int64_t)(V.ostart[V.op_off[i + 1]] - V.ostart[V.op_off[i]]);
   V.r_end[i] = e;
@@ -115,8 +98,8 @@ __global__ void __launch_bounds__(256) dp_accum(Dp V, Acc A) {
   if (o >= A.o_hi) return;
   const uint32_t len = V.oplen[o];
   if (!len) return;                                            // (consumes no reference base)
-  const uint64_t r = last_le(V.op_off, V.n, o), o0 = V.op_off[r], o1 = V.op_off[r + 1];
-  const uint8_t* src = V.data + V.ops_src[r];
+  const uint64_t r = last_le(V.op_off, V.F.n, o), o0 = V.op_off[r], o1 = V.op_off[r + 1];
+  const uint8_t* src = V.F.data + V.ops_src[r];
   if (!covers(le32(src + 4 * (o - o0)) & 15u, V.count_del)) return;
   // the reference-consuming neighbours: the ops of no reference length in between are the short look
   bool left = false, right = false;
@@ -252,7 +235,7 @@ struct lra_bam_depth : lra_bam_pass {
   bool dirty = false, flushed = false, done = true;           // diff holds adds; the last tasks are queued; the pass delivers nothing more
   Dp V{};
   // the window's arrays, the position window, the piece
-  Buf<uint32_t> keep, mspan, mbf, c_op, oplen, depth, llen; Buf<int32_t> mref, mpos, r_ref, r_pos, dbuf[2]; Buf<int64_t> r_end;
+  Buf<uint32_t> keep, c_op, oplen, depth, llen; Buf<int32_t> r_ref, r_pos, dbuf[2]; Buf<int64_t> r_end;
   Buf<uint64_t> op_off, ops_src, ostart, doff, psum, loff; Buf<unsigned long long> sum; Buf<uint8_t> text;
   int dcur = 0;
   PinBuf<char> h_meta, h_text; PinBuf<uint32_t> h_depth; PinBuf<uint64_t> h_sum;
@@ -260,7 +243,7 @@ struct lra_bam_depth : lra_bam_pass {
 
   void release_all() {
     release_pass();
-    keep.release(); mspan.release(); mbf.release(); c_op.release(); oplen.release(); depth.release(); llen.release(); mref.release(); mpos.release();
+    keep.release(); c_op.release(); oplen.release(); depth.release(); llen.release();
     r_ref.release(); r_pos.release(); dbuf[0].release(); dbuf[1].release(); r_end.release(); op_off.release(); ops_src.release(); ostart.release();
     doff.release(); psum.release(); loff.release(); sum.release(); text.release();
     h_meta.release(); h_text.release(); h_depth.release(); h_sum.release();
@@ -298,7 +281,7 @@ int lra_bam_depth::begin_pass() {
   hipStream_t st = ctx->stream;
   tasks.clear(); w_tasks.clear(); have_last = false; w_have = false; flushed = false; done = false;
   cur_ref = pl_ref = -1; base = dbase = live = pl_base = pl_dbase = pl_live = 0; carry = 0; bin_part = 0; pl_span = span;
-  LRA_HIP_CHECK(ctx, hipMemsetAsync(misc.p + 16, 0, 32, st));
+  LRA_HIP_CHECK(ctx, hipMemsetAsync(misc.p + MISC_CNT, 0, 32, st));
   if (dirty || dbuf[0].n < span + 2 || dbuf[1].n < span + 2) {   // a pass that was left, or the first one: both arrays are cleared
     dirty = true;
     if (!clear_diff(dbuf[0], span + 2) || !clear_diff(dbuf[1], span + 2)) return fail(LRA_ERR_NOMEM, "lra_bam_depth: hipMalloc failed for a position window of %llu bases", (unsigned long long)span);
@@ -331,35 +314,21 @@ int lra_bam_depth::window(uint64_t n, uint64_t limit, uint64_t* bad_idx, uint64_
   *bad_idx = NONE; *stop_idx = NONE;
   forget();
   memset(&V, 0, sizeof V);
-  V.data = z.data; V.pos = pos.p; V.n = n; V.n_ref = refs.n_ref; V.req = O.require; V.excl = O.exclude; V.min_mapq = O.min_mapq; V.count_del = O.count_deletions;
-  V.region = mode == 2; V.ref_id = ref_id; V.beg = beg; V.end = end; V.limit = limit;
+  V.req = O.require; V.excl = O.exclude; V.min_mapq = O.min_mapq; V.count_del = O.count_deletions;
   V.last_ref = last_ref; V.last_pos = last_pos; V.has_last = have_last;
-  bool ok = grab(keep, n) && grab(c_op, n) && grab(op_off, n + 1) && grab(ops_src, n) && grab(r_ref, n) && grab(r_pos, n) && grab(r_end, n);
-  if (ok && V.region) ok = grab(mref, n) && grab(mpos, n) && grab(mspan, n) && grab(mbf, n);
-  if (!ok) return fail(LRA_ERR_NOMEM, "lra_bam_depth: hipMalloc failed for the arrays of %llu records", (unsigned long long)n);
-  V.keep = keep.p; V.M = Meta{mref.p, mpos.p, mspan.p, mbf.p}; V.r_ref = r_ref.p; V.r_pos = r_pos.p; V.r_end = r_end.p;
+  if (!(grab(keep, n) && grab(c_op, n) && grab(op_off, n + 1) && grab(ops_src, n) && grab(r_ref, n) && grab(r_pos, n) && grab(r_end, n)))
+    return fail(LRA_ERR_NOMEM, "lra_bam_depth: hipMalloc failed for the arrays of %llu records", (unsigned long long)n);
+  V.keep = keep.p; V.r_ref = r_ref.p; V.r_pos = r_pos.p; V.r_end = r_end.p;
   V.c_op = c_op.p; V.op_off = op_off.p; V.ops_src = ops_src.p;
-  V.bad = (unsigned long long*)(misc.p + 8);
-  unsigned long long res[5];
+  unsigned long long res[B_WORDS];
   uint64_t n_op = 0;
   {
     Timer T(st);
-    LRA_HIP_CHECK(ctx, hipMemsetAsync(V.bad, 0xff, 40, st));
-    hipLaunchKernelGGL(dp_check, dim3(blocks_of(n)), dim3(256), 0, st, V);
-    LRA_HIP_CHECK(ctx, hipGetLastError());
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.bad, 40, hipMemcpyDeviceToHost, st));
-    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    if (res[0] < n) {
-      S.ms_frame_select += T.stop();
-      *bad_idx = res[0];
-      LRA_HIP_CHECK(ctx, hipMemcpyAsync(bad_pos, pos.p + res[0], 8, hipMemcpyDeviceToHost, st));
-      LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-      *bad_why = "is shorter than its fields say, has no NUL behind its name, or names a reference outside [-1, " + std::to_string(refs.n_ref) + ")";
-      return LRA_OK;
-    }
-    if (V.region) hipLaunchKernelGGL(bs_span, dim3(wave_blocks(ctx, n)), dim3(256), 0, st, n, V.data, V.pos, V.M);
+    const int rc = front_check(V.F, n, limit, bad_idx, bad_pos, bad_why);
+    if (rc || *bad_idx != NONE) { S.ms_frame_select += T.stop(); return rc; }
+    front_span(V.F);
     hipLaunchKernelGGL(dp_select, dim3(blocks_of(n)), dim3(256), 0, st, V);
-    if (V.region) hipLaunchKernelGGL(dp_cut, dim3(blocks_of(n)), dim3(256), 0, st, V);
+    front_cut(V.F, V.keep, V.c_op);
     LRA_HIP_CHECK(ctx, hipGetLastError());
     if (lra_exclusive_scan<uint32_t>(ctx, (long)n, c_op.p, op_off.p)) return fail(LRA_ERR_HIP, "lra_bam_depth: a scan failed");
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(&n_op, op_off.p + n, 8, hipMemcpyDeviceToHost, st));
@@ -382,24 +351,16 @@ int lra_bam_depth::window(uint64_t n, uint64_t limit, uint64_t* bad_idx, uint64_
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(h_keep, keep.p, 4 * n, hipMemcpyDeviceToHost, st));
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(h_ref, r_ref.p, 4 * n, hipMemcpyDeviceToHost, st));
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(h_pos, r_pos.p, 4 * n, hipMemcpyDeviceToHost, st));
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.bad, 40, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.F.bad, sizeof res, hipMemcpyDeviceToHost, st));
     LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     S.ms_ops += T.stop();
-    *stop_idx = res[3];
-    const uint64_t lim = std::min<uint64_t>(n, res[3]);        // (what stands behind the region's end is not this pass's to refuse)
+    *stop_idx = res[B_STOP];
+    const uint64_t lim = std::min<uint64_t>(n, res[B_STOP]);   // (what stands behind the region's end is not this pass's to refuse)
     uint64_t b = NONE; int kind = 0;
-    if (res[1] < lim) { b = res[1]; kind = 1; }
-    if (res[2] < lim && res[2] < b) { b = res[2]; kind = 2; }
-    if (res[4] < lim && res[4] < b) { b = res[4]; kind = 4; }
-    if (kind) {
-      *bad_idx = b;
-      LRA_HIP_CHECK(ctx, hipMemcpyAsync(bad_pos, pos.p + b, 8, hipMemcpyDeviceToHost, st));
-      LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-      if (kind == 1) *bad_why = "sorts in front of its predecessor: the file is not coordinate-sorted at " + where(b);
-      else if (kind == 2) *bad_why = "has an aux block that ends inside a tag or names an unknown type";
-      else *bad_why = "has a CIGAR op code above 8";
-      return LRA_OK;
-    }
+    for (int k : {B_ORDER, B_AUX, B_OP}) if (res[k] < lim && res[k] < b) { b = res[k]; kind = k; }   // (the lowest record; of two kinds at one record, the first)
+    if (kind == B_ORDER) return refuse(b, "sorts in front of its predecessor: the file is not coordinate-sorted at " + where(b), bad_idx, bad_pos, bad_why);
+    if (kind == B_AUX) return refuse(b, "has an aux block that ends inside a tag or names an unknown type", bad_idx, bad_pos, bad_why);
+    if (kind == B_OP) return refuse(b, "has a CIGAR op code above 8", bad_idx, bad_pos, bad_why);
     // the plan: finish what lies below the next record, slide or grow when it reaches beyond the array, take the records that fit, and again
     std::vector<uint64_t> h_opoff;                             // (the op ranges of the prefixes: read where a prefix ends)
     const uint64_t n_take = lim;
@@ -461,7 +422,7 @@ int lra_bam_depth::finish_piece(int64_t to, struct lra_bam_depth_piece* piece, b
   const uint64_t per = std::max<uint64_t>(1, std::min(PIECE_POS, PIECE_TEXT / max_line));   // positions or bins of a piece
   Fin F; memset(&F, 0, sizeof F);
   F.first = base; F.ref = cur_ref; F.all = (int)O.all_positions; F.rname = (const char*)rname.p; F.rname_off = rname_off.p; F.carry = carry;
-  F.red = (unsigned long long*)(misc.p + 16);
+  F.red = (unsigned long long*)(misc.p + MISC_CNT);
   if (O.bin) m = std::min<uint64_t>(m, zeros ? per * O.bin : std::min<uint64_t>(PIECE_POS, per * O.bin)); else m = std::min(m, per);
   F.m = m;
   {
@@ -575,7 +536,7 @@ int lra_bam_depth::run_task(struct lra_bam_depth_piece* piece, bool* made) {
     default: {
       Timer T(st);
       Acc A; A.diff = dbuf[dcur].p; A.dbase = dbase; A.cells = std::min<uint64_t>(span + 1, dbuf[dcur].n); A.lo_c = range_lo(cur_ref); A.hi_c = range_hi(cur_ref);
-      A.o_lo = (uint64_t)t.a; A.o_hi = (uint64_t)t.b; A.outside = (unsigned int*)(misc.p + 19);
+      A.o_lo = (uint64_t)t.a; A.o_hi = (uint64_t)t.b; A.outside = (unsigned int*)(misc.p + MISC_CNT + 3);
       if (A.o_hi > A.o_lo) {
         hipLaunchKernelGGL(dp_accum, dim3(blocks_of(A.o_hi - A.o_lo)), dim3(256), 0, st, V, A);
         LRA_HIP_CHECK(ctx, hipGetLastError());
@@ -602,8 +563,8 @@ int lra_bam_depth::next(struct lra_bam_depth_piece* piece) {
     if (flushed) {                                             // the pass is over and everything is out: the stats' reductions come back
       unsigned long long red[4] = {0, 0, 0, 0};
       if (misc.p) {
-        LRA_HIP_CHECK(ctx, hipMemcpyAsync(red, misc.p + 16, 32, hipMemcpyDeviceToHost, st));
-        LRA_HIP_CHECK(ctx, hipMemsetAsync(misc.p + 16, 0, 32, st));
+        LRA_HIP_CHECK(ctx, hipMemcpyAsync(red, misc.p + MISC_CNT, 32, hipMemcpyDeviceToHost, st));
+        LRA_HIP_CHECK(ctx, hipMemsetAsync(misc.p + MISC_CNT, 0, 32, st));
         LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
         S.covered += red[0]; S.depth_sum += red[1]; S.depth_max = std::max<uint64_t>(S.depth_max, red[2]);
         if ((unsigned int)red[3]) return fail(LRA_ERR_HIP, "lra_bam_depth: %u adds fell outside the position window", (unsigned int)red[3]);
@@ -630,38 +591,20 @@ extern "C" int lra_bam_depth_create(lra_ctx* ctx, const char* bam_path, const ch
   if (d->O.exclude == ~0u) d->O.exclude = DEFAULT_EXCLUDE;
   if (!d->O.want_text && !d->O.want_values) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_depth_create: neither text nor values are wanted");
   d->span = d->O.span_bases ? std::max(d->O.span_bases, MIN_SPAN) : DEFAULT_SPAN;
-  if (int rc = d->open_files(ctx, "lra_bam_depth", bam_path, bai_path, d->O.window_bytes)) {
-    if (d->fd >= 0) close(d->fd);
-    d->release_all();
-    return rc;
-  }
+  if (int rc = d->open_files(ctx, "lra_bam_depth", bam_path, bai_path, d->O.window_bytes)) return pass_create_failed(d.get(), rc);
   uint64_t longest = 1;
   for (const std::string& s : d->refs.name) longest = std::max<uint64_t>(longest, s.size());
   d->max_line = longest + 48;                                  // a name, three numbers of at most 10, 10 and 23 bytes, the separators
-  // the frame's words [0, 8), the lowest bad records [8, 16), the stats' reductions [16, 19), the adds outside the array [19]
-  if (!d->misc.ensure(64) || hipMemsetAsync(d->misc.p, 0, 64 * 8, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-    (void)hipGetLastError(); close(d->fd); d->release_all();
-    return lra_set_err(ctx, LRA_ERR_NOMEM, "lra_bam_depth_create: hipMalloc failed");
-  }
+  // misc behind the pass's words: the stats' reductions [MISC_CNT, MISC_CNT + 3), the adds outside the array [MISC_CNT + 3]
+  if (!d->zero_misc()) return pass_create_failed(d.get(), lra_set_err(ctx, LRA_ERR_NOMEM, "lra_bam_depth_create: hipMalloc failed"));
   *out = d.release();
   return LRA_OK;
 }
 
-extern "C" void lra_bam_depth_destroy(lra_bam_depth* d) {
-  if (!d) return;
-  (void)hipSetDevice(d->ctx->device);
-  (void)hipStreamSynchronize(d->ctx->stream);
-  d->release_all();
-  if (d->fd >= 0) close(d->fd);
-  delete d;
-}
+extern "C" void lra_bam_depth_destroy(lra_bam_depth* d) { pass_destroy(d); }
 
 extern "C" int lra_bam_depth_header(lra_bam_depth* d, int* n_ref, const char* const** names, const uint64_t** ref_len) {
-  if (!d) return LRA_ERR_INVALID;
-  if (n_ref) *n_ref = d->refs.n_ref;
-  if (names) *names = d->name_ptr.data();
-  if (ref_len) *ref_len = d->refs.len.data();
-  return LRA_OK;
+  return d ? d->header_refs(n_ref, names, ref_len) : LRA_ERR_INVALID;
 }
 
 extern "C" int lra_bam_depth_all(lra_bam_depth* d) {
@@ -687,7 +630,6 @@ extern "C" int lra_bam_depth_next(lra_bam_depth* d, struct lra_bam_depth_piece* 
 extern "C" int lra_bam_depth_stats(lra_bam_depth* d, struct lra_bam_depth_stats* out) {
   if (!d || !out) return LRA_ERR_INVALID;
   *out = d->S;
-  out->windows = d->windows; out->bytes_read = d->bytes_read; out->bytes_inflated = d->bytes_inflated;
-  out->ms_read_inflate = d->ms_read_inflate; out->ms_frame_select += d->ms_frame;
+  d->add_stats(out);
   return LRA_OK;
 }

@@ -21,6 +21,7 @@
 #include "bam_index_host.h"
 #include "bam_merge_host.h"
 #include "bam_keys.h"
+#include "bam_rec.h"
 #include "zsource.h"
 #include <rocprim/rocprim.hpp>
 #include <fcntl.h>
@@ -144,18 +145,11 @@ __global__ void __launch_bounds__(256) mi_windows(MIdx A) {
   }
 }
 
-struct Timer {
-  hipEvent_t a = nullptr, b = nullptr; hipStream_t st;
-  explicit Timer(hipStream_t s) : st(s) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, st); }
-  double stop() { float ms = 0; (void)hipEventRecord(b, st); (void)hipEventSynchronize(b); (void)hipEventElapsedTime(&ms, a, b); return ms; }
-  ~Timer() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-};
-unsigned blocks_of(uint64_t lanes) { return (unsigned)((lanes + 255) / 256); }
-unsigned wave_blocks(lra_ctx* ctx, uint64_t waves) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((waves + 3) / 4, (uint64_t)ctx->num_cu * 32)); }
 inline size_t grown(size_t have, size_t want) { return want <= have ? 0 : std::max(want, (size_t)4096) - have; }   // what DevBuf::ensure adds, in items
 // The merger's own arrays: DevBuf without its floor of 4096 items (two runs of a few records merge in the budget that sorted them), an eighth of slack
-// so that windows of about one size do not allocate anew each time.  Contents are not kept.
-template <typename T> struct Buf {
+// so that windows of about one size do not allocate anew each time.  Contents are not kept.  Not bam_rec.h's Buf, whose slack has 16 items more: the
+// budget arithmetic of grown() below counts by room().  (Timer, blocks_of, wave_blocks and wall_ms are bam_rec.h's.)
+template <typename T> struct MergeBuf {
   T* p = nullptr; size_t n = 0;
   static size_t room(size_t want) { return want + want / 8; }
   bool ensure(size_t want) {
@@ -168,15 +162,14 @@ template <typename T> struct Buf {
   }
   void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
-template <typename T> size_t grown(const Buf<T>& b, size_t want) { return want <= b.n ? 0 : Buf<T>::room(want) - b.n; }
-double wall_ms(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+template <typename T> size_t grown(const MergeBuf<T>& b, size_t want) { return want <= b.n ? 0 : MergeBuf<T>::room(want) - b.n; }
 
 struct Run {
   std::string path;
   int fd = -1;
   lra_bgzf_step z;
   uint64_t skip = 0, want = 0; off_t size = 0;                // header bytes still in front of the records; compressed bytes per refill; the file's size
-  Buf<uint64_t> start, key, addr; Buf<uint32_t> ord, len;
+  MergeBuf<uint64_t> start, key, addr; MergeBuf<uint32_t> ord, len;
   bool filled = false;
   uint64_t n = 0, e = 0;                                      // the window's whole records; how many of them are emitted
   uint64_t first = 0, used = 0;                               // the first record's offset in the window's data; the byte behind the last
@@ -190,25 +183,6 @@ struct Run {
 typedef lra_merge_chunk Chunk;
 typedef lra_merge_refs RefTable;
 
-// the uncompressed header's first `hdr` bytes, member by member on the host
-bool read_header(const std::string& path, uint64_t hdr, std::vector<uint8_t>& out, std::string& why) {
-  lra_bgzf_source src;
-  src.fd = open(path.c_str(), O_RDONLY);
-  if (src.fd < 0) { why = "cannot open it"; return false; }
-  out.clear();
-  bool ok = true;
-  while (ok && out.size() < hdr) {
-    uint32_t isize = 0;
-    if (!src.peek(&isize)) { why = src.err.empty() ? "the file ends inside the header" : src.err; ok = false; break; }
-    const size_t at = out.size();
-    out.resize(at + isize);
-    if (!src.take(out.data() + at)) { why = src.err; ok = false; }
-  }
-  close(src.fd);
-  if (ok) out.resize(hdr);
-  return ok;
-}
-
 }  // namespace
 
 struct lra_bam_merger {
@@ -218,10 +192,10 @@ struct lra_bam_merger {
   std::vector<uint8_t> header; RefTable refs; bool long_ref = false;
   std::vector<uint64_t> lin_off;
   // the round
-  Buf<uint8_t> small, pend, tail;                             // small: the runs' table (64 per run), the counts (16 per run), 16 words of results
-  Buf<uint64_t> at, spos, hoff, rkey, rbeg, rend; Buf<uint32_t> slen, head, mspan, mbf; Buf<int32_t> mref, mpos;
-  Buf<unsigned long long> stat, lin; Buf<uint64_t> d_lin_off;
-  Buf<uint64_t> skey[2]; Buf<uint32_t> sord[2]; Buf<uint8_t> stemp;   // index: a reference's chunks by bin
+  MergeBuf<uint8_t> small, pend, tail;                        // small: the runs' table (64 per run), the counts (16 per run), 16 words of results
+  MergeBuf<uint64_t> at, spos, hoff, rkey, rbeg, rend; MergeBuf<uint32_t> slen, head, mspan, mbf; MergeBuf<int32_t> mref, mpos;
+  MergeBuf<unsigned long long> stat, lin; MergeBuf<uint64_t> d_lin_off;
+  MergeBuf<uint64_t> skey[2]; MergeBuf<uint32_t> sord[2]; MergeBuf<uint8_t> stemp;   // index: a reference's chunks by bin
   bool index_ready = false;
   uint64_t pend_len = 0, cursor = 0, cut = 0, u_total = 0;
   int32_t c_ref = -1; uint32_t c_bin = 0;
@@ -256,8 +230,8 @@ struct lra_bam_merger {
     release_all();                                             // (a merger that failed only refuses: nothing stays on the device)
     return lra_set_err(ctx, code, "%s", buf);
   }
-  // Buf::ensure under the budget
-  template <class T> int grab(Buf<T>& b, size_t want, const char* what) {
+  // MergeBuf::ensure under the budget
+  template <class T> int grab(MergeBuf<T>& b, size_t want, const char* what) {
     const size_t add = grown(b, want) * sizeof(T);
     if (add && dev_bytes() + add > max_bytes)
       return fail(LRA_ERR_NOMEM, "lra_bam_merger: %s needs %zu bytes of device memory, the budget is %llu", what, dev_bytes() + add, (unsigned long long)max_bytes);
@@ -533,7 +507,7 @@ extern "C" int lra_bam_merger_create(lra_ctx* ctx, uint64_t max_bytes, uint64_t 
     uint64_t hdr = 0;
     if (lra_hts_sniff(R.path, &hdr) != LRA_IN_BAM) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_merger_create: %s is not a BAM file", R.path.c_str());
     std::vector<uint8_t> h; std::string why; RefTable T;
-    if (!read_header(R.path, hdr, h, why)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_merger_create: %s: %s", R.path.c_str(), why.c_str());
+    if (!lra_bam_read_header(R.path, hdr, h, why)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_merger_create: %s: %s", R.path.c_str(), why.c_str());
     if (!lra_merge_parse_refs(h.data(), h.size(), T)) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_merger_create: %s: not a valid BAM header", R.path.c_str());
     R.skip = hdr;
     if (r == 0) { m->header.swap(h); m->refs = T; continue; }

@@ -1,7 +1,8 @@
 // lra_amd/csrc/bam_pass.h -- lra_bam_pass: one pass over the records of a BAM file in windows, whole or for a region reached through its .bai index.
-// What lra_bam_view (bam_view.hip: the records as SAM text), lra_bam_depth (bam_depth.hip: the records as coverage) and lra_bam_vcf (bam_vcf.hip: their
-// insertions and deletions as VCF lines) share: the file, its header and index, the BGZF step, a region's plan and chunk rules, the window loop with its
-// carry and virtual-offset bookkeeping, and the refusal texts.
+// What lra_bam_view (bam_view.hip: the records as SAM text), lra_bam_depth (bam_depth.hip: the records as coverage), lra_bam_vcf (bam_vcf.hip: their
+// insertions and deletions as VCF lines) and lra_bam_svcalls (bam_svcalls.hip: the assembly SV tables) share: the file, its header and index, the BGZF
+// step, a region's plan and chunk rules, the window loop with its carry and virtual-offset bookkeeping, the refusal texts, the record front of a window
+// and the shell of the C handle functions.
 // include/lra_hip.h states the rules under lra_bam_view.
 //
 // window.  One lra_bgzf_step (zsource.h) reads `window` compressed bytes, inflates their whole members on the device behind the carried tail and
@@ -11,6 +12,14 @@
 // consumer.  step(c) hands the window's framed records [0, n) to c.window(): it refuses one (the lowest bad index: the step calls again with the
 // records in front of it, after c.forget()), names the first record at or behind a region's end, or takes them all; c.deliver() closes the window and
 // says whether the consumer has something for its caller.  The window's data (z.data, pos) stays as it is until the next step.
+// front.  What stands between "the records are framed" and a consumer's own work, once for all consumers.  Front: the fields every consumer's kernels
+// need for selection; a consumer's argument struct holds one as its member F.  rec_check, a lane per framed record: the record's arithmetic (core_ok,
+// bam_rec.h), the lowest bad index through atomicMin.  bs_span (bam_keys.h, the index's own code) gives a region pass every record's reference span.
+// rec_in_region, called by every consumer's select kernel: the overlap of [pos, pos + span) with [beg, end), records behind the chunk's limit left out,
+// and the first record at or behind the region's end marked (refID -1 sorts last); the flag, mapq and refID tests stay the consumer's.  rec_cut: nothing
+// at or behind that record is taken.  bad[]: B_CHECK and B_STOP are every consumer's, its own kinds are numbered from B_OWN on.  On the host
+// front_check / front_span / front_cut / refuse run them; a consumer's stats timer runs around the calls.
+// handle shell.  pass_create_failed, pass_destroy, header_refs and add_stats are what the extern "C" functions of every consumer repeat.
 #pragma once
 #include "common.h"
 #include "scan.h"
@@ -30,22 +39,37 @@ namespace {
 constexpr uint64_t PASS_MIN_WINDOW = 65536, PASS_DEFAULT_WINDOW = 16ull << 20;
 constexpr unsigned long long NONE = ~0ull;
 
-inline bool read_header(const std::string& path, uint64_t hdr, std::vector<uint8_t>& out, std::string& why) {
-  lra_bgzf_source src;
-  src.fd = open(path.c_str(), O_RDONLY);
-  if (src.fd < 0) { why = "cannot open it"; return false; }
-  out.clear();
-  bool ok = true;
-  while (ok && out.size() < hdr) {
-    uint32_t isize = 0;
-    if (!src.peek(&isize)) { why = src.err.empty() ? "the file ends inside the header" : src.err; ok = false; break; }
-    const size_t at = out.size();
-    out.resize(at + isize);
-    if (!src.take(out.data() + at)) { why = src.err; ok = false; }
-  }
-  close(src.fd);
-  if (ok) out.resize(hdr);
-  return ok;
+// misc: the frame's words [MISC_FRAME, MISC_BAD), the lowest bad records bad[] [MISC_BAD, MISC_CNT), the consumer's counts from MISC_CNT on
+enum { MISC_FRAME = 0, MISC_BAD = 8, MISC_CNT = 16, MISC_WORDS = 64 };
+enum { B_CHECK = 0, B_STOP = 1, B_OWN = 2, B_WORDS = MISC_CNT - MISC_BAD };   // bad[]: rec_check's lowest record, the first record at or behind the region's end, then the consumer's kinds
+
+struct Front {                                                // what every consumer's kernels see of a window
+  const uint8_t* data; const uint64_t* pos; uint64_t n;       // record i is data[pos[i], pos[i + 1])
+  int n_ref;
+  int region; int32_t ref_id; int64_t beg, end; uint64_t limit;
+  Meta M; unsigned long long* bad;
+};
+
+__global__ void __launch_bounds__(256) rec_check(Front F) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= F.n) return;
+  const uint8_t* p = F.data + F.pos[i];
+  const Core c = core_of(p);
+  if (!core_ok(p, c, F.pos[i + 1] - F.pos[i], F.n_ref)) atomicMin(&F.bad[B_CHECK], (unsigned long long)i);
+}
+
+// A region pass's verdict on record i at (ref, pos): it starts in front of the chunk's limit and shares a base with [beg, end).  The first record at or
+// behind the region's end is marked whatever the verdict (refID -1 sorts last).
+__device__ __forceinline__ bool rec_in_region(const Front& F, uint64_t i, int32_t ref, int32_t pos) {
+  const bool inside = F.pos[i] < F.limit;
+  if (inside && ((uint32_t)ref > (uint32_t)F.ref_id || (ref == F.ref_id && (int64_t)pos >= F.end))) atomicMin(&F.bad[B_STOP], (unsigned long long)i);
+  return inside && ref == F.ref_id && (int64_t)pos < F.end && (int64_t)pos + (int64_t)F.M.span[i] > F.beg;
+}
+
+// nothing at or behind the first record at or behind the region's end is taken: its flag, and its count where the consumer has one, are cleared
+__global__ void __launch_bounds__(256) rec_cut(Front F, uint32_t* __restrict__ flag, uint32_t* __restrict__ count) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < F.n && i >= F.bad[B_STOP]) { flag[i] = 0; if (count) count[i] = 0; }
 }
 
 struct lra_bam_pass {
@@ -65,9 +89,10 @@ struct lra_bam_pass {
   std::string pend_err;
   // the window
   Buf<uint8_t> rname; Buf<uint64_t> rname_off, pos, misc;     // the reference names on the device; the framed records' starts; the frame's words and the consumer's
+  Buf<int32_t> mref, mpos; Buf<uint32_t> mspan, mbf;          // bs_span's fields of a region pass's records
   uint64_t windows = 0, bytes_read = 0, bytes_inflated = 0; double ms_read_inflate = 0, ms_frame = 0;
 
-  void release_pass() { z.release(); rname.release(); rname_off.release(); pos.release(); misc.release(); }
+  void release_pass() { z.release(); rname.release(); rname_off.release(); pos.release(); misc.release(); mref.release(); mpos.release(); mspan.release(); mbf.release(); }
   // a refusal ends the pass; the object takes another
   int fail(int code, const char* fmt, ...) __attribute__((format(printf, 3, 4))) {
     char buf[1024];
@@ -111,7 +136,7 @@ struct lra_bam_pass {
     window = window_bytes ? std::max(window_bytes, PASS_MIN_WINDOW) : PASS_DEFAULT_WINDOW;
     if (lra_hts_sniff(path, &hdr) != LRA_IN_BAM) return lra_set_err(ctx, LRA_ERR_INVALID, "%s_create: %s is not a BAM file", who, bam_path);
     std::string why;
-    if (!read_header(path, hdr, header, why)) return lra_set_err(ctx, LRA_ERR_INVALID, "%s_create: %s: %s", who, bam_path, why.c_str());
+    if (!lra_bam_read_header(path, hdr, header, why)) return lra_set_err(ctx, LRA_ERR_INVALID, "%s_create: %s: %s", who, bam_path, why.c_str());
     if (!lra_merge_parse_refs(header.data(), header.size(), refs)) return lra_set_err(ctx, LRA_ERR_INVALID, "%s_create: %s: not a valid BAM header", who, bam_path);
     for (const std::string& s : refs.name) name_ptr.push_back(s.c_str());
     if (bai_path_) {
@@ -170,6 +195,56 @@ struct lra_bam_pass {
     return start_pass();
   }
 
+  // ---- the record front of a window ----
+  // record idx is refused: where it starts, for the step's test against the chunk's limit
+  int refuse(uint64_t idx, const std::string& why, uint64_t* bad_idx, uint64_t* bad_pos, std::string* bad_why) {
+    hipStream_t st = ctx->stream;
+    *bad_idx = idx; *bad_why = why;
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(bad_pos, pos.p + idx, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    return LRA_OK;
+  }
+  // F from the pass for the window's records [0, n); bs_span's arrays for a region pass; bad[] cleared; the records' arithmetic.  *bad_idx < n: the lowest
+  // record that is refused.
+  int front_check(Front& F, uint64_t n, uint64_t limit, uint64_t* bad_idx, uint64_t* bad_pos, std::string* bad_why) {
+    hipStream_t st = ctx->stream;
+    *bad_idx = NONE;
+    F.data = z.data; F.pos = pos.p; F.n = n; F.n_ref = refs.n_ref;
+    F.region = mode == 2; F.ref_id = ref_id; F.beg = beg; F.end = end; F.limit = limit;
+    if (F.region && !(grab(mref, n) && grab(mpos, n) && grab(mspan, n) && grab(mbf, n)))
+      return fail(LRA_ERR_NOMEM, "%s: hipMalloc failed for the arrays of %llu records", who, (unsigned long long)n);
+    F.M = Meta{mref.p, mpos.p, mspan.p, mbf.p}; F.bad = (unsigned long long*)(misc.p + MISC_BAD);
+    unsigned long long lowest = NONE;
+    LRA_HIP_CHECK(ctx, hipMemsetAsync(F.bad, 0xff, 8 * B_WORDS, st));
+    hipLaunchKernelGGL(rec_check, dim3(blocks_of(n)), dim3(256), 0, st, F);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&lowest, F.bad + B_CHECK, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (lowest < n)
+      return refuse(lowest, "is shorter than its fields say, has no NUL behind its name, or names a reference outside [-1, " + std::to_string(refs.n_ref) + ")", bad_idx, bad_pos, bad_why);
+    return LRA_OK;
+  }
+  // in front of a region pass's select kernel, and behind it (flag, count: rec_cut's)
+  void front_span(const Front& F) { if (F.region) hipLaunchKernelGGL(bs_span, dim3(wave_blocks(ctx, F.n)), dim3(256), 0, ctx->stream, F.n, F.data, F.pos, F.M); }
+  void front_cut(const Front& F, uint32_t* flag, uint32_t* count) { if (F.region) hipLaunchKernelGGL(rec_cut, dim3(blocks_of(F.n)), dim3(256), 0, ctx->stream, F, flag, count); }
+
+  // ---- the handle shell: with pass_create_failed and pass_destroy below, what the extern "C" functions of every consumer repeat ----
+  bool zero_misc() {
+    if (misc.ensure(MISC_WORDS) && hipMemsetAsync(misc.p, 0, 8 * MISC_WORDS, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+  }
+  int header_refs(int* n_ref, const char* const** names, const uint64_t** ref_len) const {
+    if (n_ref) *n_ref = refs.n_ref;
+    if (names) *names = name_ptr.data();
+    if (ref_len) *ref_len = refs.len.data();
+    return LRA_OK;
+  }
+  template <class St> void add_stats(St* out) const {         // the fields of a consumer's stats that the pass owns
+    out->windows = windows; out->bytes_read = bytes_read; out->bytes_inflated = bytes_inflated;
+    out->ms_read_inflate = ms_read_inflate; out->ms_frame_select += ms_frame;
+  }
+
   // One turn of the window loop.  *state: 0 go on, 1 the consumer has something to deliver, 2 the pass is over.
   template <class C> int step(C& c, int* state) {
     hipStream_t st = ctx->stream;
@@ -202,7 +277,7 @@ struct lra_bam_pass {
     if (dlen == start && !z.at_end) { z.commit(dlen); skip -= start; return LRA_OK; }   // nothing but the header (or the bytes in front of the chunk) so far
     const uint64_t limit = mode == 2 ? limit_of(plan[ci].end) : ~0ull;
     const uint64_t cap = (dlen - start) / 36 + 1;
-    if (!grab(pos, cap + 1) || !grab(misc, 64)) return fail(LRA_ERR_NOMEM, "%s: hipMalloc failed for the record starts of a window", who);
+    if (!grab(pos, cap + 1) || !grab(misc, MISC_WORDS)) return fail(LRA_ERR_NOMEM, "%s: hipMalloc failed for the record starts of a window", who);
     uint64_t fr[4] = {0, start, 0, 0};
     if (dlen > start) {
       Timer T(st);
@@ -227,7 +302,7 @@ struct lra_bam_pass {
     uint64_t stop_idx = NONE;
     c.forget();
     if (n) {
-      LRA_HIP_CHECK(ctx, hipMemcpyAsync(pos.p + n, misc.p + 1, 8, hipMemcpyDeviceToDevice, st));
+      LRA_HIP_CHECK(ctx, hipMemcpyAsync(pos.p + n, misc.p + MISC_FRAME + 1, 8, hipMemcpyDeviceToDevice, st));
       for (;;) {
         uint64_t bad_idx = NONE, bad_pos = 0; std::string why;
         if (int r2 = c.window(n, limit, &bad_idx, &bad_pos, &why, &stop_idx)) return r2;
@@ -251,5 +326,20 @@ struct lra_bam_pass {
     return LRA_OK;
   }
 };
+
+// a consumer H : lra_bam_pass whose create failed with rc; one that is destroyed
+template <class H> int pass_create_failed(H* h, int rc) {
+  if (h->fd >= 0) close(h->fd);
+  h->release_all();
+  return rc;
+}
+template <class H> void pass_destroy(H* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->ctx->device);
+  (void)hipStreamSynchronize(h->ctx->stream);
+  h->release_all();
+  if (h->fd >= 0) close(h->fd);
+  delete h;
+}
 
 }  // namespace

@@ -1,6 +1,8 @@
-// lra_amd/csrc/bam_rec.h -- what the readers of raw BAM records on the device share (bam_view.hip, bam_depth.hip, bam_vcf.hip): a record's core fields, the
-// walk over its aux block, the test for the CG:B:I form of a long CIGAR and where a record's ops are, the packed SEQ as bases by one wave, decimal digits,
-// and the small host helpers of a windowed pass (event timer, grid sizes, the growable device array).  The kernels and helpers are TU-local, as scan.h's and bam_keys.h's are.
+// lra_amd/csrc/bam_rec.h -- what the readers of raw BAM records on the device share (bam_view.hip, bam_depth.hip, bam_vcf.hip, bam_svcalls.hip): a record's
+// core fields, the walk over its aux block, the test for the CG:B:I form of a long CIGAR and where a record's ops are, the packed SEQ as bases by one wave,
+// decimal digits, and the small host helpers of every windowed BAM object, the sorter and the merger with them (event timer, grid sizes, wall clock, the
+// growable device array).  The kernels over a window's records that every pass runs -- the check, the region test, the cut -- are bam_pass.h's front.
+// The kernels and helpers are TU-local, as scan.h's and bam_keys.h's are.
 #pragma once
 #include "common.h"
 #include "bam_keys.h"

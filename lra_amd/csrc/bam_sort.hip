@@ -18,6 +18,7 @@
 #include "bgzf_deflate.h"
 #include "bam_index_host.h"
 #include "bam_keys.h"
+#include "bam_rec.h"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <vector>
@@ -150,17 +151,6 @@ struct lra_bam_sorter {
     return keep_bytes(N, B) + std::max(sort_arena(N), index_arena(N, B, per_ref)) + round_bytes(std::min(round(), members_of(B)));
   }
 };
-
-namespace {
-struct Timer {
-  hipEvent_t a = nullptr, b = nullptr; hipStream_t st;
-  explicit Timer(hipStream_t s) : st(s) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, st); }
-  double stop() { float ms = 0; (void)hipEventRecord(b, st); (void)hipEventSynchronize(b); (void)hipEventElapsedTime(&ms, a, b); return ms; }
-  ~Timer() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-};
-unsigned blocks_of(uint64_t lanes) { return (unsigned)((lanes + 255) / 256); }
-unsigned wave_blocks(lra_ctx* ctx, uint64_t waves) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((waves + 3) / 4, (uint64_t)ctx->num_cu * 32)); }
-}  // namespace
 
 extern "C" int lra_bam_sorter_create(lra_ctx* ctx, uint64_t max_bytes, lra_bam_sorter** out) {
   if (!ctx || !out || !max_bytes) return LRA_ERR_INVALID;

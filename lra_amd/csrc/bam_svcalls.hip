@@ -351,7 +351,7 @@ int lra_bam_svcalls::window(uint64_t n, uint64_t limit, uint64_t* bad_idx, uint6
     S.ms_frame_select += T.stop();
   }
   if (mres[M_UNSORTED] < n)                                   // the records in front of it go first; what the walk refuses among them is refused then
-    return W.refuse(*this, mres[M_UNSORTED], "sorts in front of its predecessor: the file is not coordinate-sorted at " + where(mres[M_UNSORTED]), bad_idx, bad_pos, bad_why);
+    return refuse(mres[M_UNSORTED], "sorts in front of its predecessor: the file is not coordinate-sorted at " + where(mres[M_UNSORTED]), bad_idx, bad_pos, bad_why);
   uint64_t nv = 0, total = 0;
   if (int rc = W.walk(*this, V, O.drop_contained != 0, false, bad_idx, bad_pos, bad_why, stop_idx, &nv, &total, w_cnt)) return rc;
   if (*bad_idx != NONE) return LRA_OK;
@@ -568,35 +568,22 @@ extern "C" int lra_bam_svcalls_create(lra_ctx* ctx, const char* bam_path, const 
   int rc = d->open_files(ctx, "lra_bam_svcalls", bam_path, bai_path, d->O.window_bytes);
   if (!rc) rc = d->take_genome("lra_bam_svcalls_create");
   if (!rc) rc = d->set_mask(0, nullptr, nullptr, nullptr);
-  bool ok = !rc && d->misc.ensure(64) && d->sv_misc.ensure(M_WORDS) && hipMemsetAsync(d->misc.p, 0, 64 * 8, ctx->stream) == hipSuccess;
+  bool ok = !rc && d->zero_misc() && d->sv_misc.ensure(M_WORDS);
   for (int k = 0; ok && k < 2; k++)
     ok = d->d_stem[k].ensure(d->stem[k].size() + 1) && hipMemcpyAsync(d->d_stem[k].p, d->stem[k].data(), d->stem[k].size(), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
   ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
-    if (d->fd >= 0) close(d->fd);
-    d->release_all();
-    return rc ? rc : lra_set_err(ctx, LRA_ERR_NOMEM, "lra_bam_svcalls_create: hipMalloc failed");
+    return pass_create_failed(d.get(), rc ? rc : lra_set_err(ctx, LRA_ERR_NOMEM, "lra_bam_svcalls_create: hipMalloc failed"));
   }
   *out = d.release();
   return LRA_OK;
 }
 
-extern "C" void lra_bam_svcalls_destroy(lra_bam_svcalls* d) {
-  if (!d) return;
-  (void)hipSetDevice(d->ctx->device);
-  (void)hipStreamSynchronize(d->ctx->stream);
-  d->release_all();
-  if (d->fd >= 0) close(d->fd);
-  delete d;
-}
+extern "C" void lra_bam_svcalls_destroy(lra_bam_svcalls* d) { pass_destroy(d); }
 
 extern "C" int lra_bam_svcalls_header(lra_bam_svcalls* d, int* n_ref, const char* const** names, const uint64_t** ref_len) {
-  if (!d) return LRA_ERR_INVALID;
-  if (n_ref) *n_ref = d->refs.n_ref;
-  if (names) *names = d->name_ptr.data();
-  if (ref_len) *ref_len = d->refs.len.data();
-  return LRA_OK;
+  return d ? d->header_refs(n_ref, names, ref_len) : LRA_ERR_INVALID;
 }
 
 extern "C" int lra_bam_svcalls_set_mask(lra_bam_svcalls* d, uint64_t n, const int32_t* ref_id, const int64_t* beg, const int64_t* end) {
@@ -634,7 +621,6 @@ extern "C" int lra_bam_svcalls_next(lra_bam_svcalls* d, struct lra_bam_svcalls_p
 extern "C" int lra_bam_svcalls_stats(lra_bam_svcalls* d, struct lra_bam_svcalls_stats* out) {
   if (!d || !out) return LRA_ERR_INVALID;
   *out = d->S;
-  out->windows = d->windows; out->bytes_read = d->bytes_read; out->bytes_inflated = d->bytes_inflated;
-  out->ms_read_inflate = d->ms_read_inflate; out->ms_frame_select += d->ms_frame;
+  d->add_stats(out);
   return LRA_OK;
 }

@@ -38,7 +38,7 @@ __global__ void __launch_bounds__(256) vc_small(Vc V) {
       *d++ = '\t'; d = put_u(d, (uint64_t)v.anchor + V.rules.pos_one_based);
       *d++ = '\t'; *d++ = '.'; *d++ = '\t';
       V.text[V.poff[4 * j + 2]] = '\t';
-      put_info(V.text + V.poff[4 * j + 3], v.del != 0, v.svlen, V.data + v.name_at, v.l_name, v.aq + 1, (v.flag & 16u) != 0);
+      put_info(V.text + V.poff[4 * j + 3], v.del != 0, v.svlen, V.F.data + v.name_at, v.l_name, v.aq + 1, (v.flag & 16u) != 0);
     }
     if (V.vals) {
       struct lra_bam_vcf_variant x;
@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(256) vc_bulk(Vc V) {
     if (to <= from) return;
     const Var& v = V.var[q >> 2];
     if (part == 1) wave_copy(V.text + from, V.genome + v.g_at + (from - wb), to - from, lane);
-    else wave_seq(V.text + from, V.data + v.seq_at, v.aq + (from - wb), to - from, lane);
+    else wave_seq(V.text + from, V.F.data + v.seq_at, v.aq + (from - wb), to - from, lane);
   });
 }
 
@@ -167,35 +167,17 @@ extern "C" int lra_bam_vcf_create(lra_ctx* ctx, const char* bam_path, const char
   if (!d->O.want_text && !d->O.want_values) return lra_set_err(ctx, LRA_ERR_INVALID, "lra_bam_vcf_create: neither text nor values are wanted");
   int rc = d->open_files(ctx, "lra_bam_vcf", bam_path, bai_path, d->O.window_bytes);
   if (!rc) rc = d->take_genome("lra_bam_vcf_create");
-  if (rc) {
-    if (d->fd >= 0) close(d->fd);
-    d->release_all();
-    return rc;
-  }
-  // the frame's words [0, 8), the lowest bad records [8, 16), the window's counts [16, 16 + N_CNT)
-  if (!d->misc.ensure(64) || hipMemsetAsync(d->misc.p, 0, 64 * 8, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-    (void)hipGetLastError(); close(d->fd); d->release_all();
-    return lra_set_err(ctx, LRA_ERR_NOMEM, "lra_bam_vcf_create: hipMalloc failed");
-  }
+  if (rc) return pass_create_failed(d.get(), rc);
+  // misc behind the pass's words: the window's counts [MISC_CNT, MISC_CNT + N_CNT)
+  if (!d->zero_misc()) return pass_create_failed(d.get(), lra_set_err(ctx, LRA_ERR_NOMEM, "lra_bam_vcf_create: hipMalloc failed"));
   *out = d.release();
   return LRA_OK;
 }
 
-extern "C" void lra_bam_vcf_destroy(lra_bam_vcf* d) {
-  if (!d) return;
-  (void)hipSetDevice(d->ctx->device);
-  (void)hipStreamSynchronize(d->ctx->stream);
-  d->release_all();
-  if (d->fd >= 0) close(d->fd);
-  delete d;
-}
+extern "C" void lra_bam_vcf_destroy(lra_bam_vcf* d) { pass_destroy(d); }
 
 extern "C" int lra_bam_vcf_header(lra_bam_vcf* d, int* n_ref, const char* const** names, const uint64_t** ref_len) {
-  if (!d) return LRA_ERR_INVALID;
-  if (n_ref) *n_ref = d->refs.n_ref;
-  if (names) *names = d->name_ptr.data();
-  if (ref_len) *ref_len = d->refs.len.data();
-  return LRA_OK;
+  return d ? d->header_refs(n_ref, names, ref_len) : LRA_ERR_INVALID;
 }
 
 extern "C" int lra_bam_vcf_all(lra_bam_vcf* d) {
@@ -226,7 +208,6 @@ extern "C" int lra_bam_vcf_next(lra_bam_vcf* d, struct lra_bam_vcf_piece* piece)
 extern "C" int lra_bam_vcf_stats(lra_bam_vcf* d, struct lra_bam_vcf_stats* out) {
   if (!d || !out) return LRA_ERR_INVALID;
   *out = d->S;
-  out->windows = d->windows; out->bytes_read = d->bytes_read; out->bytes_inflated = d->bytes_inflated;
-  out->ms_read_inflate = d->ms_read_inflate; out->ms_frame_select += d->ms_frame;
+  d->add_stats(out);
   return LRA_OK;
 }

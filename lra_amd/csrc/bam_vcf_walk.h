@@ -3,9 +3,10 @@
 // the arrays they run on and the stages in order.  include/lra_hip.h has the rules under lra_bam_vcf; bam_vcf_host.h the arithmetic host and kernels share;
 // bam_contained.h the filter in front of the walk.  The kernels are TU-local, as scan.h's and bam_rec.h's are.
 //
-// records.  vc_check, a lane per framed record: the record's arithmetic (bam_rec.h, the view's rule).  bs_span (bam_keys.h) gives a region pass every
-// record's span for the overlap test.  vc_select, a lane per record: the contained filter's flag, the filters, the first record at or behind the region's
-// end, and where the ops are (ops_of, bam_rec.h: depth's rule).  One scan of the op counts.
+// records.  The pass's front (bam_pass.h: Front, rec_check, rec_in_region, rec_cut; its refuse): rec_check, a lane per framed record: the record's
+// arithmetic; bs_span gives a region pass every record's span for the overlap test.  vc_select, a lane per record: the contained filter's flag, the filters
+// (rec_in_region: the overlap and the first record at or behind the region's end; rec_cut behind it), and where the ops are (ops_of, bam_rec.h: depth's
+// rule).  One scan of the op counts.
 // the walk.  A lane per op, never a lane or a wave per record: one record of millions of ops is as many lanes as a thousand records of three.
 // vc_opinfo: the op's advance in SEQ (M I S = X) and on the reference (M D N = X) and its class -- match, ins (I S), del (D N), none (H P, length 0).
 // Two scans over all ops of the window give (q, r) in front of every op; less their values at the record's first op they are the record's counters: the
@@ -31,7 +32,8 @@ namespace {
 
 enum { C_NONE = 0, C_MATCH = 1, C_INS = 2, C_DEL = 3 };
 enum { S_FILTERED = 0, S_SKIPPED = 1, S_CAND = 2 };
-enum { B_CHECK = 0, B_STOP = 1, B_KINDS = 2 };                 // bad[]: vc_check's lowest record, the first record at or behind the region's end, then bam_vcf_host.h's kinds
+enum { B_KINDS = B_OWN };                                      // bad[] behind the pass's words: bam_vcf_host.h's kinds
+static_assert(S_FILTERED == 0, "rec_cut clears state[] to S_FILTERED");
 enum { N_WALKED = 0, N_SKIPPED = 1, N_INS = 2, N_DEL = 3, N_CONTAINED = 4, N_SMALL_INS = 5, N_SMALL_DEL = 6, N_CNT = 7 };    // cnt[]
 
 struct Var {                                                  // a kept variant
@@ -40,19 +42,18 @@ struct Var {                                                  // a kept variant
 };
 
 struct Vc {                                                   // what the kernels of a window see
-  const uint8_t* data; const uint64_t* pos; uint64_t n;       // record i is data[pos[i], pos[i + 1])
-  int n_ref; lra_vcf_rules rules; int count_small;
-  int region; int32_t ref_id; int64_t beg, end; uint64_t limit;
+  Front F;                                                    // (bam_pass.h) record i is F.data[F.pos[i], F.pos[i + 1])
+  lra_vcf_rules rules; int count_small;
   const char* rname; const uint64_t* rname_off;
   const unsigned char* genome; const uint64_t* chrom_pos;
-  uint32_t* state; Meta M; const uint32_t* drop;               // drop: bam_contained.h's flags, or null
+  uint32_t* state; const uint32_t* drop;               // drop: bam_contained.h's flags, or null
   uint32_t* c_op; uint64_t* op_off; uint64_t* ops_src; uint32_t* has_m; uint32_t* walked;
   uint32_t* qadv; uint32_t* radv; uint8_t* cls; uint8_t* lcls; uint32_t* orec; uint32_t* head; uint64_t* Q; uint64_t* R; uint64_t* hoff; uint64_t n_op;
   uint64_t* g_op; uint32_t* g_m; uint64_t* mcnt; uint64_t* m_end; uint32_t* vkeep; uint64_t* voff; uint64_t n_grp;
   Var* var; uint32_t* plen; uint64_t* poff; uint64_t n_var;
   struct lra_bam_vcf_variant* vals; uint64_t ord_base;
   unsigned char* text; uint64_t n_text;
-  unsigned long long* bad; unsigned long long* cnt;
+  unsigned long long* cnt;
 };
 
 __device__ __forceinline__ uint32_t class_of(uint32_t code, uint32_t len) {
@@ -60,46 +61,28 @@ __device__ __forceinline__ uint32_t class_of(uint32_t code, uint32_t len) {
   return code == 0 || code == 7 || code == 8 ? C_MATCH : code == 1 || code == 4 ? C_INS : code == 2 || code == 3 ? C_DEL : C_NONE;
 }
 
-__global__ void __launch_bounds__(256) vc_check(Vc V) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V.n) return;
-  const uint8_t* p = V.data + V.pos[i];
-  const Core c = core_of(p);
-  if (!core_ok(p, c, V.pos[i + 1] - V.pos[i], V.n_ref)) atomicMin(&V.bad[B_CHECK], (unsigned long long)i);
-}
-
 __global__ void __launch_bounds__(256) vc_select(Vc V) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V.n) return;
-  const uint64_t at0 = V.pos[i];
-  const Core c = core_of(V.data + at0);
+  if (i >= V.F.n) return;
+  const uint64_t at0 = V.F.pos[i];
+  const Core c = core_of(V.F.data + at0);
   bool pass = c.ref >= 0 && !(V.drop && V.drop[i]) && (c.flag & V.rules.require) == V.rules.require && (c.flag & V.rules.exclude) == 0 && c.mapq >= V.rules.min_mapq;
-  if (V.region) {
-    const bool inside = at0 < V.limit;
-    pass = pass && inside && c.ref == V.ref_id && (int64_t)c.pos < V.end && (int64_t)c.pos + (int64_t)V.M.span[i] > V.beg;
-    if (inside && ((uint32_t)c.ref > (uint32_t)V.ref_id || (c.ref == V.ref_id && (int64_t)c.pos >= V.end))) atomicMin(&V.bad[B_STOP], (unsigned long long)i);
-  }
+  if (V.F.region) pass = rec_in_region(V.F, i, c.ref, c.pos) && pass;
   bool cand = pass && c.n_cig >= 1 && c.l_seq > 0;
   uint64_t ops = at0 + 36 + c.l_name; uint32_t n_op = c.n_cig;
-  if (cand && !ops_of(V.data, at0, V.pos[i + 1], c, &ops, &n_op)) { atomicMin(&V.bad[B_KINDS + LRA_VCF_BAD_AUX], (unsigned long long)i); cand = false; }
+  if (cand && !ops_of(V.F.data, at0, V.F.pos[i + 1], c, &ops, &n_op)) { atomicMin(&V.F.bad[B_KINDS + LRA_VCF_BAD_AUX], (unsigned long long)i); cand = false; }
   cand = cand && n_op >= 1;
   V.state[i] = !pass ? S_FILTERED : cand ? S_CAND : S_SKIPPED;
   V.c_op[i] = cand ? n_op : 0u; V.ops_src[i] = ops; V.has_m[i] = 0u;
 }
 
-// nothing at or behind the first record at or behind the region's end is taken
-__global__ void __launch_bounds__(256) vc_cut(Vc V) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < V.n && i >= V.bad[B_STOP]) { V.state[i] = S_FILTERED; V.c_op[i] = 0; }
-}
-
 __global__ void __launch_bounds__(256) vc_opinfo(Vc V) {
   const uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= V.n_op) return;
-  const uint64_t r = last_le(V.op_off, V.n, o);
-  const uint32_t op = le32(V.data + V.ops_src[r] + 4 * (o - V.op_off[r]));
+  const uint64_t r = last_le(V.op_off, V.F.n, o);
+  const uint32_t op = le32(V.F.data + V.ops_src[r] + 4 * (o - V.op_off[r]));
   const uint32_t code = op & 15u, len = op >> 4;
-  if (code > 8u) atomicMin(&V.bad[B_KINDS + LRA_VCF_BAD_OP], (unsigned long long)r);
+  if (code > 8u) atomicMin(&V.F.bad[B_KINDS + LRA_VCF_BAD_OP], (unsigned long long)r);
   const uint32_t c = code > 8u ? (uint32_t)C_NONE : class_of(code, len);
   V.cls[o] = (uint8_t)c; V.orec[o] = (uint32_t)r; V.head[o] = c != C_NONE ? 1u : 0u;   // (head: until vc_heads, "has a class")
   V.qadv[o] = c == C_MATCH || c == C_INS ? len : 0u;
@@ -130,18 +113,18 @@ __global__ void __launch_bounds__(256) vc_heads(Vc V) {
 __global__ void __launch_bounds__(256) vc_rec(Vc V) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   bool walked = false, skipped = false, contained = false;
-  if (i < V.n) {
+  if (i < V.F.n) {
     const uint32_t st = V.state[i];
-    if (V.drop && V.drop[i]) contained = !V.region || (i < V.bad[B_STOP] && (int32_t)le32(V.data + V.pos[i] + 4) == V.ref_id);
+    if (V.drop && V.drop[i]) contained = !V.F.region || (i < V.F.bad[B_STOP] && (int32_t)le32(V.F.data + V.F.pos[i] + 4) == V.F.ref_id);
     walked = st == S_CAND && V.has_m[i];
     skipped = st == S_SKIPPED || (st == S_CAND && !walked);
     V.walked[i] = walked ? 1u : 0u;
     if (walked) {
-      const Core c = core_of(V.data + V.pos[i]);
+      const Core c = core_of(V.F.data + V.F.pos[i]);
       const uint64_t o0 = V.op_off[i], o1 = V.op_off[i + 1];
-      if (V.Q[o1] - V.Q[o0] != (uint64_t)c.l_seq) atomicMin(&V.bad[B_KINDS + LRA_VCF_BAD_SEQ], (unsigned long long)i);
+      if (V.Q[o1] - V.Q[o0] != (uint64_t)c.l_seq) atomicMin(&V.F.bad[B_KINDS + LRA_VCF_BAD_SEQ], (unsigned long long)i);
       const uint64_t len = V.chrom_pos[c.ref + 1] - V.chrom_pos[c.ref];
-      if (c.pos < 0 || (uint64_t)c.pos + (V.R[o1] - V.R[o0]) > len) atomicMin(&V.bad[B_KINDS + LRA_VCF_BAD_SPAN], (unsigned long long)i);
+      if (c.pos < 0 || (uint64_t)c.pos + (V.R[o1] - V.R[o0]) > len) atomicMin(&V.F.bad[B_KINDS + LRA_VCF_BAD_SPAN], (unsigned long long)i);
     }
   }
   const unsigned long long bw = __ballot(walked), bs = __ballot(skipped), bc = __ballot(contained);
@@ -179,13 +162,13 @@ __device__ __forceinline__ bool variant_of(const Vc& V, uint64_t g, Var* out, in
   if (V.orec[o2] != r) return false;                           // the run reaches the end of the CIGAR
   const uint64_t o0 = V.op_off[r];
   if (V.mcnt[g] == V.mcnt[V.hoff[o0]]) return false;           // no M = X base in front of it
-  const uint64_t at0 = V.pos[r];
-  const Core k = core_of(V.data + at0);
+  const uint64_t at0 = V.F.pos[r];
+  const Core k = core_of(V.F.data + at0);
   const uint64_t qb = V.Q[o0], rb = V.R[o0];
   const uint64_t aq = V.m_end[V.mcnt[g] - 1] - 1 - qb, q1 = V.Q[o2] - qb;
   const int64_t r0 = (int64_t)k.pos + (int64_t)(V.R[o] - rb), r1 = (int64_t)k.pos + (int64_t)(V.R[o2] - rb);
   const lra_vcf_shape s = lra_vcf_shape_of(c == C_DEL, aq, r0, q1, r1);
-  if (!lra_vcf_anchor_in(V.region, r0 - 1, V.beg, V.end)) return false;
+  if (!lra_vcf_anchor_in(V.F.region, r0 - 1, V.F.beg, V.F.end)) return false;
   if (!lra_vcf_long_enough(s.svlen, V.rules.min_length)) { if (small) *small = c == C_DEL ? 2 : 1; return false; }
   if (out) {
     out->rec = r; out->name_at = at0 + 36; out->seq_at = at0 + 36 + k.l_name + 4ull * k.n_cig; out->aq = aq;
@@ -274,14 +257,14 @@ inline int lra_vcf_take_genome(lra_bam_pass& P, const char* fn, const unsigned c
 
 // The walk's arrays and its stages for a consumer `P` of the pass.  The times go where the consumer's stats point.
 struct lra_vcf_walk {
-  Buf<uint32_t> state, mspan, mbf, c_op, has_m, walked, qadv, radv, orec, head, g_m, vkeep, plen; Buf<int32_t> mref, mpos; Buf<uint8_t> cls, lcls;
+  Buf<uint32_t> state, c_op, has_m, walked, qadv, radv, orec, head, g_m, vkeep, plen; Buf<uint8_t> cls, lcls;
   Buf<uint64_t> op_off, ops_src, Q, R, hoff, g_op, mcnt, m_end, voff, poff; Buf<Var> var;
   lra_contained CT; bool ct_fault = false;
   double* ms_frame_select = nullptr; double* ms_ops = nullptr; double* ms_walk = nullptr; double* ms_lengths = nullptr;
 
   void release() {
-    state.release(); mspan.release(); mbf.release(); c_op.release(); has_m.release(); walked.release(); qadv.release(); radv.release(); orec.release(); head.release();
-    g_m.release(); vkeep.release(); plen.release(); mref.release(); mpos.release(); cls.release(); lcls.release(); op_off.release(); ops_src.release(); Q.release();
+    state.release(); c_op.release(); has_m.release(); walked.release(); qadv.release(); radv.release(); orec.release(); head.release();
+    g_m.release(); vkeep.release(); plen.release(); cls.release(); lcls.release(); op_off.release(); ops_src.release(); Q.release();
     R.release(); hoff.release(); g_op.release(); mcnt.release(); m_end.release(); voff.release(); poff.release(); var.release(); CT.release();
   }
   // a pass begins
@@ -294,41 +277,22 @@ struct lra_vcf_walk {
   // the window is delivered
   void commit(lra_bam_pass& P) { if (!CT.commit(P.ctx->stream)) ct_fault = true; }   // (the next window refuses)
 
-  int refuse(lra_bam_pass& P, uint64_t idx, const std::string& why, uint64_t* bad_idx, uint64_t* bad_pos, std::string* bad_why) {
-    hipStream_t st = P.ctx->stream;
-    *bad_idx = idx; *bad_why = why;
-    LRA_HIP_CHECK(P.ctx, hipMemcpyAsync(bad_pos, P.pos.p + idx, 8, hipMemcpyDeviceToHost, st));
-    LRA_HIP_CHECK(P.ctx, hipStreamSynchronize(st));
-    return LRA_OK;
-  }
-
-  // The records' arithmetic.  V: the caller has zeroed it and set what is its own (rules, count_small, genome, chrom_pos, ord_base); the pass's fields and the
-  // arrays are set here.  *bad_idx < n: the lowest record that is refused.
+  // The records' arithmetic (the pass's front_check).  V: the caller has zeroed it and set what is its own (rules, count_small, genome, chrom_pos, ord_base); the
+  // pass's fields and the arrays are set here.  *bad_idx < n: the lowest record that is refused.
   int check(lra_bam_pass& P, Vc& V, uint64_t n, uint64_t limit, uint64_t* bad_idx, uint64_t* bad_pos, std::string* bad_why) {
     lra_ctx* ctx = P.ctx; hipStream_t st = ctx->stream;
     *bad_idx = NONE;
     if (ct_fault) return P.fail(LRA_ERR_HIP, "%s: the contained filter's carry could not be kept", P.who);
-    V.data = P.z.data; V.pos = P.pos.p; V.n = n; V.n_ref = P.refs.n_ref;
-    V.region = P.mode == 2; V.ref_id = P.ref_id; V.beg = P.beg; V.end = P.end; V.limit = limit;
     V.rname = (const char*)P.rname.p; V.rname_off = P.rname_off.p;
-    bool ok = P.grab(state, n) && P.grab(c_op, n) && P.grab(op_off, n + 1) && P.grab(ops_src, n) && P.grab(has_m, n) && P.grab(walked, n);
-    if (ok && V.region) ok = P.grab(mref, n) && P.grab(mpos, n) && P.grab(mspan, n) && P.grab(mbf, n);
-    if (!ok) return P.fail(LRA_ERR_NOMEM, "%s: hipMalloc failed for the arrays of %llu records", P.who, (unsigned long long)n);
-    V.state = state.p; V.M = Meta{mref.p, mpos.p, mspan.p, mbf.p}; V.c_op = c_op.p; V.op_off = op_off.p; V.ops_src = ops_src.p; V.has_m = has_m.p; V.walked = walked.p;
-    V.bad = (unsigned long long*)(P.misc.p + 8); V.cnt = (unsigned long long*)(P.misc.p + 16);
-    unsigned long long res[8];
+    if (!(P.grab(state, n) && P.grab(c_op, n) && P.grab(op_off, n + 1) && P.grab(ops_src, n) && P.grab(has_m, n) && P.grab(walked, n)))
+      return P.fail(LRA_ERR_NOMEM, "%s: hipMalloc failed for the arrays of %llu records", P.who, (unsigned long long)n);
+    V.state = state.p; V.c_op = c_op.p; V.op_off = op_off.p; V.ops_src = ops_src.p; V.has_m = has_m.p; V.walked = walked.p;
+    V.cnt = (unsigned long long*)(P.misc.p + MISC_CNT);
     Timer T(st);
-    LRA_HIP_CHECK(ctx, hipMemsetAsync(V.bad, 0xff, 64, st));
     LRA_HIP_CHECK(ctx, hipMemsetAsync(V.cnt, 0, 8 * N_CNT, st));
-    hipLaunchKernelGGL(vc_check, dim3(blocks_of(n)), dim3(256), 0, st, V);
-    LRA_HIP_CHECK(ctx, hipGetLastError());
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.bad, 64, hipMemcpyDeviceToHost, st));
-    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    const int rc = P.front_check(V.F, n, limit, bad_idx, bad_pos, bad_why);
     *ms_frame_select += T.stop();
-    if (res[B_CHECK] < n)
-      return refuse(P, res[B_CHECK], "is shorter than its fields say, has no NUL behind its name, or names a reference outside [-1, " + std::to_string(P.refs.n_ref) + ")", bad_idx, bad_pos,
-                    bad_why);
-    return LRA_OK;
+    return rc;
   }
 
   // Behind check(): the filter, the select, the ops, the runs, the variants.  *nv variants stand in var.p; with want_plen their lines' pieces are placed (poff.p) and
@@ -336,19 +300,19 @@ struct lra_vcf_walk {
   int walk(lra_bam_pass& P, Vc& V, bool drop_contained, bool want_plen, uint64_t* bad_idx, uint64_t* bad_pos, std::string* bad_why, uint64_t* stop_idx, uint64_t* nv, uint64_t* total,
            uint64_t* cnt) {
     lra_ctx* ctx = P.ctx; hipStream_t st = ctx->stream;
-    const uint64_t n = V.n;
+    const uint64_t n = V.F.n;
     *stop_idx = NONE; *nv = 0; *total = 0;
-    unsigned long long res[8];
+    unsigned long long res[B_WORDS];
     uint64_t n_op = 0;
     {
       Timer T(st);
       if (drop_contained) {
-        if (!CT.window(st, V.data, V.pos, n, V.region ? V.limit : ~0ull)) return P.fail(LRA_ERR_NOMEM, "%s: the contained filter of %llu records failed", P.who, (unsigned long long)n);
+        if (!CT.window(st, V.F.data, V.F.pos, n, V.F.region ? V.F.limit : ~0ull)) return P.fail(LRA_ERR_NOMEM, "%s: the contained filter of %llu records failed", P.who, (unsigned long long)n);
         V.drop = CT.drop.p;
       }
-      if (V.region) hipLaunchKernelGGL(bs_span, dim3(wave_blocks(ctx, n)), dim3(256), 0, st, n, V.data, V.pos, V.M);
+      P.front_span(V.F);
       hipLaunchKernelGGL(vc_select, dim3(blocks_of(n)), dim3(256), 0, st, V);
-      if (V.region) hipLaunchKernelGGL(vc_cut, dim3(blocks_of(n)), dim3(256), 0, st, V);
+      P.front_cut(V.F, V.state, V.c_op);
       LRA_HIP_CHECK(ctx, hipGetLastError());
       if (lra_exclusive_scan<uint32_t>(ctx, (long)n, c_op.p, op_off.p)) return P.fail(LRA_ERR_HIP, "%s: a scan failed", P.who);
       LRA_HIP_CHECK(ctx, hipMemcpyAsync(&n_op, op_off.p + n, 8, hipMemcpyDeviceToHost, st));
@@ -374,14 +338,14 @@ struct lra_vcf_walk {
       LRA_HIP_CHECK(ctx, hipGetLastError());
       if (lra_exclusive_scan<uint32_t>(ctx, (long)n_op, head.p, hoff.p)) return P.fail(LRA_ERR_HIP, "%s: a scan failed", P.who);
       LRA_HIP_CHECK(ctx, hipMemcpyAsync(&n_grp, hoff.p + n_op, 8, hipMemcpyDeviceToHost, st));
-      LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.bad, 64, hipMemcpyDeviceToHost, st));
+      LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.F.bad, sizeof res, hipMemcpyDeviceToHost, st));
       LRA_HIP_CHECK(ctx, hipMemcpyAsync(cnt, V.cnt, 8 * N_CNT, hipMemcpyDeviceToHost, st));
       LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
       *ms_ops += T.stop();
       *stop_idx = res[B_STOP];
       const uint64_t lim = std::min<uint64_t>(n, res[B_STOP]);    // (what stands behind the region's end is not this pass's to refuse)
       uint64_t b = NONE; int kind = 0;
-      if (lra_vcf_first_bad(res + B_KINDS, lim, &b, &kind)) { memset(cnt, 0, 8 * N_CNT); return refuse(P, b, lra_vcf_bad_text(kind), bad_idx, bad_pos, bad_why); }
+      if (lra_vcf_first_bad(res + B_KINDS, lim, &b, &kind)) { memset(cnt, 0, 8 * N_CNT); return P.refuse(b, lra_vcf_bad_text(kind), bad_idx, bad_pos, bad_why); }
     }
     {
       Timer T(st);

@@ -1,15 +1,15 @@
 // lra_amd/csrc/bam_view.hip -- lra_bam_view: a BAM file printed as SAM text on the device, whole or for a region reached through its .bai index (gfx950).
 // include/lra_hip.h has the interface, the text's rules and what a window allocates; bam_view_host.h reads the index and plans a region's chunks;
-// bam_pass.h runs the pass (the window loop below, shared with bam_depth.hip) and hands each window's records to window_text; bam_rec.h has the
-// record's core fields and the aux walk.
+// bam_pass.h runs the pass (the window loop below, shared with the other consumers) and hands each window's records to window_text; it also has the
+// record front -- Front, rec_check, rec_in_region, rec_cut and the handle shell; bam_rec.h has the record's core fields and the aux walk.
 //
 // window.  One lra_bgzf_step (zsource.h) reads `window_bytes` compressed bytes, inflates their whole members on the device behind the carried tail and
 // lra_bam_launch_frame chains the block_size fields.  A region's chunk [vb, ve) seeks to vb >> 16, resets the step and frames from vb & 0xffff; the
 // step's member table turns ve into a decoded position, the limit behind which no record of the chunk starts.  Planned chunks less than a window
 // apart in the file are read as one (the overlap test drops what lies between them): a step costs a member's inflate latency, about 10 ms.
-// records.  bv_check, a lane per framed record: the record's arithmetic, the lowest bad index through atomicMin.  bs_span (bam_keys.h, the index's own
-// code) gives a region pass every record's reference span; bv_select, a lane per record: the flag filter, the overlap test, the first record at or behind
-// the region's end (nothing behind it is taken: bv_cut).  bv_tags, a lane per kept record, walks the aux block: every type and length against the
+// records.  The pass's front (bam_pass.h): rec_check, a lane per framed record: the record's arithmetic, the lowest bad index through atomicMin; bs_span
+// gives a region pass every record's reference span; bv_select, a lane per record: the flag filter, and rec_in_region's overlap test and first record at
+// or behind the region's end (nothing behind it is taken: rec_cut).  bv_tags, a lane per kept record, walks the aux block: every type and length against the
 // record's end, the counts of tags, array elements, floats and CIGAR ops (those of a CG:B:I tag when the core CIGAR is <l_seq>S<n>N); after the scans
 // bv_items writes one item per printed tag.
 // lengths.  A line is a row of pieces: name | flag .. MAPQ | CIGAR | RNEXT .. TLEN | SEQ | QUAL | one per tag | newline.  bv_oplen, a lane per CIGAR op,
@@ -40,12 +40,13 @@ struct Item {                                                 // one printed tag
 };
 static_assert(sizeof(Item) == 40, "Item");
 
+enum { B_TAGS = B_OWN, B_OP };                                 // bad[] behind the pass's words: the lowest bad record of bv_tags, of bv_oplen
+
 struct View {                                                 // what the kernels of a window see
-  const uint8_t* data; const uint64_t* pos; uint64_t n;       // record i is data[pos[i], pos[i + 1])
-  int n_ref; uint32_t req, excl;
-  int region; int32_t ref_id; int64_t beg, end; uint64_t limit;
+  Front F;                                                    // (bam_pass.h) record i is F.data[F.pos[i], F.pos[i + 1])
+  uint32_t req, excl;
   const char* rname; const uint64_t* rname_off;
-  uint32_t* keep; Meta M;
+  uint32_t* keep;
   uint32_t* c_item; uint32_t* c_elem; uint32_t* c_float; uint32_t* c_op;
   uint64_t* item_off; uint64_t* elem_off; uint64_t* float_off; uint64_t* op_off;
   uint64_t* ops_src; uint64_t* cg_at;                         // where the record's ops are; the CG:B:I tag that is not printed (NONE: none)
@@ -55,7 +56,6 @@ struct View {                                                 // what the kernel
   float* fval; uint64_t* felem; uint64_t n_float; const uint32_t* ftoff; const char* ftext;
   uint32_t* plen; uint64_t* poff; uint8_t* pkind; uint8_t* ppre; uint64_t* psrc; uint64_t n_piece;
   unsigned char* text; uint64_t n_text;
-  unsigned long long* bad;                                    // [0] bv_check, [1] bv_tags, [2] bv_oplen: the lowest bad record; [3] the first record at or behind the region's end
 };
 
 __device__ __forceinline__ int64_t int_value(const uint8_t* p, uint8_t t) {
@@ -69,52 +69,34 @@ __device__ __forceinline__ int64_t int_value(const uint8_t* p, uint8_t t) {
   }
 }
 
-__global__ void __launch_bounds__(256) bv_check(View V) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V.n) return;
-  const uint8_t* p = V.data + V.pos[i];
-  const Core c = core_of(p);
-  if (!core_ok(p, c, V.pos[i + 1] - V.pos[i], V.n_ref)) atomicMin(&V.bad[0], (unsigned long long)i);
-}
-
 __global__ void __launch_bounds__(256) bv_select(View V) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V.n) return;
-  const uint8_t* p = V.data + V.pos[i];
+  if (i >= V.F.n) return;
+  const uint8_t* p = V.F.data + V.F.pos[i];
   const uint32_t flag = le16(p + 18);
   bool keep = (flag & V.req) == V.req && (flag & V.excl) == 0;
-  if (V.region) {
-    const int32_t ref = V.M.ref[i], pos = V.M.pos[i];
-    const bool inside = V.pos[i] < V.limit;
-    keep = keep && inside && ref == V.ref_id && (int64_t)pos < V.end && (int64_t)pos + (int64_t)V.M.span[i] > V.beg;
-    if (inside && ((uint32_t)ref > (uint32_t)V.ref_id || (ref == V.ref_id && (int64_t)pos >= V.end))) atomicMin(&V.bad[3], (unsigned long long)i);   // (refID -1 sorts last)
-  }
+  if (V.F.region) keep = rec_in_region(V.F, i, V.F.M.ref[i], V.F.M.pos[i]) && keep;
   V.keep[i] = keep ? 1u : 0u;
-}
-
-__global__ void __launch_bounds__(256) bv_cut(View V) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < V.n && i >= V.bad[3]) V.keep[i] = 0;
 }
 
 __global__ void __launch_bounds__(256) bv_tags(View V) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V.n) return;
+  if (i >= V.F.n) return;
   uint32_t n_item = 0, n_elem = 0, n_float = 0, n_op = 0;
   uint64_t ops = 0, cg = NONE;
   if (V.keep[i]) {
-    const uint64_t at0 = V.pos[i];
-    const uint8_t* p = V.data + at0;
+    const uint64_t at0 = V.F.pos[i];
+    const uint8_t* p = V.F.data + at0;
     const Core c = core_of(p);
     ops = at0 + 36 + c.l_name; n_op = c.n_cig;
-    const bool cg_form = cg_form_at(V.data + ops, c);
-    const uint64_t end = V.pos[i + 1];
+    const bool cg_form = cg_form_at(V.F.data + ops, c);
+    const uint64_t end = V.F.pos[i + 1];
     uint64_t at = at0 + 4 + c.fixed;
     bool ok = true;
     while (at < end) {
       uint8_t t, s; uint64_t val, next; uint32_t cnt;
-      if (!tag_at(V.data, at, end, &t, &s, &val, &cnt, &next)) { ok = false; break; }
-      if (cg_form && cg == NONE && V.data[at] == 'C' && V.data[at + 1] == 'G' && t == 'B' && s == 'I') { cg = at; ops = val; n_op = cnt; }
+      if (!tag_at(V.F.data, at, end, &t, &s, &val, &cnt, &next)) { ok = false; break; }
+      if (cg_form && cg == NONE && V.F.data[at] == 'C' && V.F.data[at + 1] == 'G' && t == 'B' && s == 'I') { cg = at; ops = val; n_op = cnt; }
       else {
         n_item++;
         if (t == 'f') { n_elem++; n_float++; }
@@ -122,7 +104,7 @@ __global__ void __launch_bounds__(256) bv_tags(View V) {
       }
       at = next;
     }
-    if (!ok) { atomicMin(&V.bad[1], (unsigned long long)i); n_item = n_elem = n_float = n_op = 0; }
+    if (!ok) { atomicMin(&V.F.bad[B_TAGS], (unsigned long long)i); n_item = n_elem = n_float = n_op = 0; }
   }
   V.c_item[i] = n_item; V.c_elem[i] = n_elem; V.c_float[i] = n_float; V.c_op[i] = n_op;
   V.ops_src[i] = ops; V.cg_at[i] = cg;
@@ -130,16 +112,16 @@ __global__ void __launch_bounds__(256) bv_tags(View V) {
 
 __global__ void __launch_bounds__(256) bv_items(View V) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V.n || !V.keep[i] || V.item_off[i + 1] == V.item_off[i]) return;
-  const uint64_t at0 = V.pos[i], end = V.pos[i + 1], cg = V.cg_at[i];
-  const Core c = core_of(V.data + at0);
+  if (i >= V.F.n || !V.keep[i] || V.item_off[i + 1] == V.item_off[i]) return;
+  const uint64_t at0 = V.F.pos[i], end = V.F.pos[i + 1], cg = V.cg_at[i];
+  const Core c = core_of(V.F.data + at0);
   uint64_t at = at0 + 4 + c.fixed, j = V.item_off[i], e = V.elem_off[i], f = V.float_off[i];
   while (at < end) {
     uint8_t t, s; uint64_t val, next; uint32_t cnt;
-    if (!tag_at(V.data, at, end, &t, &s, &val, &cnt, &next)) break;   // (bv_tags walked the same bytes)
+    if (!tag_at(V.F.data, at, end, &t, &s, &val, &cnt, &next)) break;   // (bv_tags walked the same bytes)
     if (at != cg) {
       Item I;
-      I.src = val; I.e0 = e; I.f0 = f; I.count = cnt; I.rec = (uint32_t)i; I.type = t; I.sub = s; I.t0 = V.data[at]; I.t1 = V.data[at + 1]; I.pad = 0;
+      I.src = val; I.e0 = e; I.f0 = f; I.count = cnt; I.rec = (uint32_t)i; I.type = t; I.sub = s; I.t0 = V.F.data[at]; I.t1 = V.F.data[at + 1]; I.pad = 0;
       V.item[j++] = I;
       if (t == 'f') { e++; f++; }
       else if (t == 'B') { e += cnt; if (s == 'f') f += cnt; }
@@ -151,9 +133,9 @@ __global__ void __launch_bounds__(256) bv_items(View V) {
 __global__ void __launch_bounds__(256) bv_oplen(View V) {
   const uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= V.n_op) return;
-  const uint64_t r = last_le(V.op_off, V.n, o);
-  const uint32_t op = le32(V.data + V.ops_src[r] + 4 * (o - V.op_off[r]));
-  if ((op & 15u) > 8u) atomicMin(&V.bad[2], (unsigned long long)r);
+  const uint64_t r = last_le(V.op_off, V.F.n, o);
+  const uint32_t op = le32(V.F.data + V.ops_src[r] + 4 * (o - V.op_off[r]));
+  if ((op & 15u) > 8u) atomicMin(&V.F.bad[B_OP], (unsigned long long)r);
   V.oplen[o] = (uint32_t)ndig(op >> 4) + 1u;
 }
 
@@ -166,7 +148,7 @@ __global__ void __launch_bounds__(256) bv_elemlen(View V) {
   const Item I = V.item[lo - 1];
   const uint64_t k = e - I.e0;
   const uint8_t t = I.type == 'B' ? I.sub : I.type;
-  const uint8_t* p = V.data + I.src + k * type_size(t);
+  const uint8_t* p = V.F.data + I.src + k * type_size(t);
   if (t == 'f') {
     V.fval[I.f0 + k] = __uint_as_float(le32(p));
     V.felem[I.f0 + k] = e | (I.type == 'B' ? 1ull << 63 : 0);
@@ -189,19 +171,19 @@ __device__ __forceinline__ unsigned char* put_name(const View& V, unsigned char*
   return d;
 }
 // RNEXT: a reference outside the table prints as '*' (only refID is checked: a mate's reference is not this record's to refuse)
-__device__ __forceinline__ int32_t next_ref_of(const View& V, const Core& c) { return c.next_ref >= V.n_ref ? -1 : c.next_ref; }
+__device__ __forceinline__ int32_t next_ref_of(const View& V, const Core& c) { return c.next_ref >= V.F.n_ref ? -1 : c.next_ref; }
 
 // a lane per record: the lengths and kinds of its pieces
 __global__ void __launch_bounds__(256) bv_pieces(View V) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V.n) return;
+  if (i >= V.F.n) return;
   const uint64_t pb = 7 * i + V.item_off[i];
   if (!V.keep[i]) {
     for (int k = 0; k < 7; k++) { V.plen[pb + k] = 0; V.pkind[pb + k] = K_NONE; V.ppre[pb + k] = 0; V.psrc[pb + k] = 0; }
     return;
   }
-  const uint64_t at0 = V.pos[i];
-  const uint8_t* p = V.data + at0;
+  const uint64_t at0 = V.F.pos[i];
+  const uint8_t* p = V.F.data + at0;
   const Core c = core_of(p);
   auto set = [&](uint64_t q, uint32_t len, uint8_t kind, uint8_t pre, uint64_t src) { V.plen[q] = len; V.pkind[q] = kind; V.ppre[q] = pre; V.psrc[q] = src; };
   set(pb, c.l_name - 1, K_COPY, 0, at0 + 36);
@@ -212,7 +194,7 @@ __global__ void __launch_bounds__(256) bv_pieces(View V) {
   set(pb + 3, 4u + (nr >= 0 && nr == c.ref ? 1u : name_len(V, nr)) + slen((int64_t)c.next_pos + 1) + slen(c.tlen), K_NONE, 0, 0);
   const uint64_t sq = at0 + 36 + c.l_name + 4ull * c.n_cig, ql = sq + ((uint64_t)c.l_seq + 1) / 2;
   set(pb + 4, c.l_seq ? c.l_seq : 1u, c.l_seq ? K_SEQ : K_NONE, 0, sq);
-  const bool has_q = c.l_seq && V.data[ql] != 0xff;
+  const bool has_q = c.l_seq && V.F.data[ql] != 0xff;
   set(pb + 5, 1u + (has_q ? c.l_seq : 1u), has_q ? K_QUAL : K_NONE, 1, ql);
   const uint64_t j0 = V.item_off[i], j1 = V.item_off[i + 1];
   for (uint64_t j = j0; j < j1; j++) {
@@ -222,7 +204,7 @@ __global__ void __launch_bounds__(256) bv_pieces(View V) {
     else if (I.type == 'Z' || I.type == 'H') set(q, 6u + I.count, K_COPY, 6, I.src);
     else if (I.type == 'f') set(q, 6u + (uint32_t)(V.eoff[I.e0 + 1] - V.eoff[I.e0]), K_ELEM, 6, 0);
     else if (I.type == 'B') set(q, 7u + (uint32_t)(V.eoff[I.e0 + I.count] - V.eoff[I.e0]), K_ELEM, 7, 0);
-    else set(q, 6u + (uint32_t)slen(int_value(V.data + I.src, I.type)), K_NONE, 6, 0);
+    else set(q, 6u + (uint32_t)slen(int_value(V.F.data + I.src, I.type)), K_NONE, 6, 0);
   }
   set(pb + 6 + (j1 - j0), 1, K_NONE, 1, 0);
 }
@@ -230,9 +212,9 @@ __global__ void __launch_bounds__(256) bv_pieces(View V) {
 // a lane per record: everything a lane prints
 __global__ void __launch_bounds__(256) bv_small(View V) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V.n || !V.keep[i]) return;
+  if (i >= V.F.n || !V.keep[i]) return;
   const uint64_t pb = 7 * i + V.item_off[i];
-  const uint8_t* p = V.data + V.pos[i];
+  const uint8_t* p = V.F.data + V.F.pos[i];
   const Core c = core_of(p);
   unsigned char* d = V.text + V.poff[pb + 1];
   *d++ = '\t'; d = put_u(d, c.flag);
@@ -258,9 +240,9 @@ __global__ void __launch_bounds__(256) bv_small(View V) {
     d = V.text + V.poff[pb + 6 + (j - j0)];
     const bool integer = I.type != 'A' && I.type != 'Z' && I.type != 'H' && I.type != 'f' && I.type != 'B';
     *d++ = '\t'; *d++ = I.t0; *d++ = I.t1; *d++ = ':'; *d++ = integer ? 'i' : I.type; *d++ = ':';
-    if (I.type == 'A') *d = V.data[I.src];
+    if (I.type == 'A') *d = V.F.data[I.src];
     else if (I.type == 'B') *d = I.sub;
-    else if (integer) put_s(d, int_value(V.data + I.src, I.type));
+    else if (integer) put_s(d, int_value(V.F.data + I.src, I.type));
   }
   V.text[V.poff[pb + 6 + (j1 - j0)]] = '\n';
 }
@@ -268,8 +250,8 @@ __global__ void __launch_bounds__(256) bv_small(View V) {
 __global__ void __launch_bounds__(256) bv_ops(View V) {
   const uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= V.n_op) return;
-  const uint64_t r = last_le(V.op_off, V.n, o), o0 = V.op_off[r];
-  const uint32_t op = le32(V.data + V.ops_src[r] + 4 * (o - o0));
+  const uint64_t r = last_le(V.op_off, V.F.n, o), o0 = V.op_off[r];
+  const uint32_t op = le32(V.F.data + V.ops_src[r] + 4 * (o - o0));
   unsigned char* d = put_u(V.text + V.poff[7 * r + V.item_off[r] + 2] + (V.ooff[o] - V.ooff[o0]), op >> 4);
   *d = (unsigned char)"MIDNSHP=X???????"[op & 15u];
 }
@@ -289,7 +271,7 @@ __global__ void __launch_bounds__(256) bv_elems(View V) {
   if (t == 'f') {
     const uint64_t f = I.f0 + k;
     for (uint32_t q = V.ftoff[f]; q < V.ftoff[f + 1]; q++) *d++ = (unsigned char)V.ftext[q];
-  } else put_s(d, int_value(V.data + I.src + k * type_size(t), t));
+  } else put_s(d, int_value(V.F.data + I.src + k * type_size(t), t));
 }
 
 // n qualities from src to dst, + 33, by one wave (wave_copy's shape)
@@ -315,7 +297,7 @@ __global__ void __launch_bounds__(256) bv_bulk(View V) {
     if (kind == K_NONE || kind == K_ELEM) return;
     const uint64_t wb = b + V.ppre[q], from = max(lo, wb), to = min(hi, end);
     if (to <= from) return;
-    const uint8_t* src = V.data + V.psrc[q];
+    const uint8_t* src = V.F.data + V.psrc[q];
     if (kind == K_COPY) wave_copy(V.text + from, src + (from - wb), to - from, lane);
     else if (kind == K_QUAL) wave_qual(V.text + from, src + (from - wb), to - from, lane);
     else wave_seq(V.text + from, src, from - wb, to - from, lane);
@@ -328,7 +310,7 @@ struct lra_bam_view : lra_bam_pass {                           // (bam_pass.h: t
   uint32_t req = 0, excl = 0;
   // the window
   Buf<uint8_t> pkind, ppre, text, ftext; Buf<uint64_t> item_off, elem_off, float_off, op_off, ops_src, cg_at, eoff, ooff, felem, poff, psrc;
-  Buf<uint32_t> keep, mspan, mbf, c_item, c_elem, c_float, c_op, elen, oplen, ftoff, plen; Buf<int32_t> mref, mpos; Buf<Item> item; Buf<float> fval;
+  Buf<uint32_t> keep, c_item, c_elem, c_float, c_op, elen, oplen, ftoff, plen; Buf<Item> item; Buf<float> fval;
   PinBuf<char> h_text;
   struct lra_bam_view_stats S{};                              // (windows, bytes read / inflated, read + inflate and the frame's share are the pass's)
   uint64_t w_len = 0, w_rec = 0;                              // the text of the window in hand
@@ -337,8 +319,8 @@ struct lra_bam_view : lra_bam_pass {                           // (bam_pass.h: t
     release_pass();
     pkind.release(); ppre.release(); text.release(); ftext.release(); item_off.release();
     elem_off.release(); float_off.release(); op_off.release(); ops_src.release(); cg_at.release(); eoff.release(); ooff.release(); felem.release(); poff.release();
-    psrc.release(); keep.release(); mspan.release(); mbf.release(); c_item.release(); c_elem.release(); c_float.release(); c_op.release(); elen.release();
-    oplen.release(); ftoff.release(); plen.release(); mref.release(); mpos.release(); item.release(); fval.release(); h_text.release();
+    psrc.release(); keep.release(); c_item.release(); c_elem.release(); c_float.release(); c_op.release(); elen.release();
+    oplen.release(); ftoff.release(); plen.release(); item.release(); fval.release(); h_text.release();
   }
   int window_text(uint64_t n, uint64_t limit, uint64_t* len, uint64_t* n_rec, uint64_t* bad_idx, uint64_t* bad_pos, std::string* bad_why, uint64_t* stop_idx);
   // the pass's consumer
@@ -354,38 +336,23 @@ struct lra_bam_view : lra_bam_pass {                           // (bam_pass.h: t
 int lra_bam_view::window_text(uint64_t n, uint64_t limit, uint64_t* len, uint64_t* n_rec, uint64_t* bad_idx, uint64_t* bad_pos, std::string* bad_why, uint64_t* stop_idx) {
   hipStream_t st = ctx->stream;
   *len = 0; *n_rec = 0; *bad_idx = NONE; *stop_idx = NONE;
-  const int n_ref = refs.n_ref;
   View V; memset(&V, 0, sizeof V);
-  V.data = z.data; V.pos = pos.p; V.n = n; V.n_ref = n_ref; V.req = req; V.excl = excl;
-  V.region = mode == 2; V.ref_id = ref_id; V.beg = beg; V.end = end; V.limit = limit;
+  V.req = req; V.excl = excl;
   V.rname = (const char*)rname.p; V.rname_off = rname_off.p;
-  bool ok = grab(keep, n) && grab(c_item, n) && grab(c_elem, n) && grab(c_float, n) && grab(c_op, n) && grab(item_off, n + 1) && grab(elem_off, n + 1) &&
-            grab(float_off, n + 1) && grab(op_off, n + 1) && grab(ops_src, n) && grab(cg_at, n);
-  if (ok && V.region) ok = grab(mref, n) && grab(mpos, n) && grab(mspan, n) && grab(mbf, n);
-  if (!ok) return fail(LRA_ERR_NOMEM, "lra_bam_view: hipMalloc failed for the arrays of %llu records", (unsigned long long)n);
-  V.keep = keep.p; V.M = Meta{mref.p, mpos.p, mspan.p, mbf.p};
+  if (!(grab(keep, n) && grab(c_item, n) && grab(c_elem, n) && grab(c_float, n) && grab(c_op, n) && grab(item_off, n + 1) && grab(elem_off, n + 1) &&
+        grab(float_off, n + 1) && grab(op_off, n + 1) && grab(ops_src, n) && grab(cg_at, n)))
+    return fail(LRA_ERR_NOMEM, "lra_bam_view: hipMalloc failed for the arrays of %llu records", (unsigned long long)n);
+  V.keep = keep.p;
   V.c_item = c_item.p; V.c_elem = c_elem.p; V.c_float = c_float.p; V.c_op = c_op.p;
   V.item_off = item_off.p; V.elem_off = elem_off.p; V.float_off = float_off.p; V.op_off = op_off.p; V.ops_src = ops_src.p; V.cg_at = cg_at.p;
-  V.bad = (unsigned long long*)(misc.p + 8);
-  unsigned long long res[4];
+  unsigned long long res[B_WORDS];
   {
     Timer T(st);
-    LRA_HIP_CHECK(ctx, hipMemsetAsync(V.bad, 0xff, 32, st));
-    hipLaunchKernelGGL(bv_check, dim3(blocks_of(n)), dim3(256), 0, st, V);
-    LRA_HIP_CHECK(ctx, hipGetLastError());
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.bad, 32, hipMemcpyDeviceToHost, st));
-    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    if (res[0] < n) {
-      S.ms_frame_select += T.stop();
-      *bad_idx = res[0];
-      LRA_HIP_CHECK(ctx, hipMemcpyAsync(bad_pos, pos.p + res[0], 8, hipMemcpyDeviceToHost, st));
-      LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-      *bad_why = "is shorter than its fields say, has no NUL behind its name, or names a reference outside [-1, " + std::to_string(n_ref) + ")";
-      return LRA_OK;
-    }
-    if (V.region) hipLaunchKernelGGL(bs_span, dim3(wave_blocks(ctx, n)), dim3(256), 0, st, n, V.data, V.pos, V.M);
+    const int rc = front_check(V.F, n, limit, bad_idx, bad_pos, bad_why);
+    if (rc || *bad_idx != NONE) { S.ms_frame_select += T.stop(); return rc; }
+    front_span(V.F);
     hipLaunchKernelGGL(bv_select, dim3(blocks_of(n)), dim3(256), 0, st, V);
-    if (V.region) hipLaunchKernelGGL(bv_cut, dim3(blocks_of(n)), dim3(256), 0, st, V);
+    front_cut(V.F, V.keep, nullptr);
     LRA_HIP_CHECK(ctx, hipGetLastError());
     S.ms_frame_select += T.stop();
   }
@@ -401,12 +368,12 @@ int lra_bam_view::window_text(uint64_t n, uint64_t limit, uint64_t* len, uint64_
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(&tot[1], elem_off.p + n, 8, hipMemcpyDeviceToHost, st));
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(&tot[2], float_off.p + n, 8, hipMemcpyDeviceToHost, st));
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(&tot[3], op_off.p + n, 8, hipMemcpyDeviceToHost, st));
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.bad, 32, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.F.bad, sizeof res, hipMemcpyDeviceToHost, st));
     LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    *stop_idx = res[3];
-    if (res[1] < n) {
+    *stop_idx = res[B_STOP];
+    if (res[B_TAGS] < n) {
       S.ms_tags_lengths += T.stop();
-      *bad_idx = res[1]; *bad_why = "has an aux block that ends inside a tag or names an unknown type";
+      *bad_idx = res[B_TAGS]; *bad_why = "has an aux block that ends inside a tag or names an unknown type";
       return LRA_OK;
     }
     V.n_item = tot[0]; V.n_elem = tot[1]; V.n_float = tot[2]; V.n_op = tot[3];
@@ -453,10 +420,10 @@ int lra_bam_view::window_text(uint64_t n, uint64_t limit, uint64_t* len, uint64_
     if (lra_exclusive_scan<uint32_t>(ctx, (long)n, keep.p, float_off.p)) return fail(LRA_ERR_HIP, "lra_bam_view: a scan failed");   // (float_off is done with: the kept records)
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(&total, poff.p + V.n_piece, 8, hipMemcpyDeviceToHost, st));
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(&kept, float_off.p + n, 8, hipMemcpyDeviceToHost, st));
-    LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.bad, 32, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(res, V.F.bad, sizeof res, hipMemcpyDeviceToHost, st));
     LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
     S.ms_tags_lengths += T.stop();
-    if (res[2] < n) { *bad_idx = res[2]; *bad_why = "has a CIGAR op code above 8"; return LRA_OK; }
+    if (res[B_OP] < n) { *bad_idx = res[B_OP]; *bad_why = "has a CIGAR op code above 8"; return LRA_OK; }
   }
   if (!total) return LRA_OK;
   if (!grab(text, total + 64)) return fail(LRA_ERR_NOMEM, "lra_bam_view: hipMalloc of %llu bytes for a window's text failed", (unsigned long long)total);
@@ -495,32 +462,18 @@ extern "C" int lra_bam_view_create(lra_ctx* ctx, const char* bam_path, const cha
   if (!ctx || !bam_path || !out) return LRA_ERR_INVALID;
   *out = nullptr;
   std::unique_ptr<lra_bam_view> v(new lra_bam_view());
-  if (int rc = v->open_files(ctx, "lra_bam_view", bam_path, bai_path, window_bytes)) {
-    if (v->fd >= 0) close(v->fd);
-    v->release_all();
-    return rc;
-  }
+  if (int rc = v->open_files(ctx, "lra_bam_view", bam_path, bai_path, window_bytes)) return pass_create_failed(v.get(), rc);
   *out = v.release();
   return LRA_OK;
 }
 
-extern "C" void lra_bam_view_destroy(lra_bam_view* v) {
-  if (!v) return;
-  (void)hipSetDevice(v->ctx->device);
-  (void)hipStreamSynchronize(v->ctx->stream);
-  v->release_all();
-  if (v->fd >= 0) close(v->fd);
-  delete v;
-}
+extern "C" void lra_bam_view_destroy(lra_bam_view* v) { pass_destroy(v); }
 
 extern "C" int lra_bam_view_header(lra_bam_view* v, const char** text, uint64_t* text_len, int* n_ref, const char* const** names, const uint64_t** ref_len) {
   if (!v) return LRA_ERR_INVALID;
   if (text) *text = (const char*)v->header.data() + 8;
   if (text_len) *text_len = lra_bai_le32(v->header.data() + 4);
-  if (n_ref) *n_ref = v->refs.n_ref;
-  if (names) *names = v->name_ptr.data();
-  if (ref_len) *ref_len = v->refs.len.data();
-  return LRA_OK;
+  return v->header_refs(n_ref, names, ref_len);
 }
 
 extern "C" int lra_bam_view_set_flags(lra_bam_view* v, uint32_t require, uint32_t exclude) {
@@ -548,8 +501,7 @@ extern "C" int lra_bam_view_next(lra_bam_view* v, const char** h_text, uint64_t*
 extern "C" int lra_bam_view_stats(lra_bam_view* v, struct lra_bam_view_stats* out) {
   if (!v || !out) return LRA_ERR_INVALID;
   *out = v->S;
-  out->windows = v->windows; out->bytes_read = v->bytes_read; out->bytes_inflated = v->bytes_inflated;
-  out->ms_read_inflate = v->ms_read_inflate; out->ms_frame_select += v->ms_frame;
+  v->add_stats(out);
   return LRA_OK;
 }
 

@@ -72,6 +72,10 @@ struct lra_bgzf_source {
   bool take(uint8_t* out);                         // that member inflated into out[0, isize) and consumed; false: a fault (err)
 };
 
+// The first `hdr` bytes of the BGZF file at `path`, uncompressed -- a BAM file's header, as lra_hts_sniff sized it -- member by member on the host.
+// false: *why says what is wrong with the file, without its name.
+bool lra_bam_read_header(const std::string& path, uint64_t hdr, std::vector<uint8_t>& out, std::string& why);
+
 // gzip that is not BGZF: one serial bit stream over the whole compressed file as one array (lra_gz_stream), inflated a step at a time on the host
 struct lra_gzip_source {
   std::vector<uint8_t> comp;

@@ -1,6 +1,7 @@
 // lra_amd/csrc/zsource.hip -- the BGZF / gzip source layer of the readers (zsource.h): the file-read loop, the BGZF member walk, a step of members inflated
 // on the device, the next member inflated on the host, a whole-file gzip stream.  Host code; the inflate kernels are input_bam.hip's and inflate_lut.hip's.
 #include "zsource.h"
+#include <fcntl.h>
 #include <unistd.h>
 #include <algorithm>
 
@@ -164,6 +165,24 @@ bool lra_bgzf_source::take(uint8_t* out) {
   if (st) { err = block_error(file_off + pos, lra_bgzf_reason(st)); return false; }
   pos += member_len;
   return true;
+}
+
+bool lra_bam_read_header(const std::string& path, uint64_t hdr, std::vector<uint8_t>& out, std::string& why) {
+  lra_bgzf_source src;
+  src.fd = open(path.c_str(), O_RDONLY);
+  if (src.fd < 0) { why = "cannot open it"; return false; }
+  out.clear();
+  bool ok = true;
+  while (ok && out.size() < hdr) {
+    uint32_t isize = 0;
+    if (!src.peek(&isize)) { why = src.err.empty() ? "the file ends inside the header" : src.err; ok = false; break; }
+    const size_t at = out.size();
+    out.resize(at + isize);
+    if (!src.take(out.data() + at)) { why = src.err; ok = false; }
+  }
+  close(src.fd);
+  if (ok) out.resize(hdr);
+  return ok;
 }
 
 bool lra_gzip_source::load(int fd) {
