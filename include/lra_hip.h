@@ -1867,7 +1867,7 @@ void lra_bam_vcf_destroy(lra_bam_vcf* d);
  * lra_bam_svcalls is the one-haplotype half of the reference's call_assembly_SVs/callassemblysv.snakefile on the device: the rules parseAlignment
  * (ParseAlignment.py), CallSV (SamToVCF.py), FilterBySizeAndSVTYPE, FilterByCentromereAndAltChromAndAddID and mergeCalls (bedtools, awk, mergeSV.py).
  * Input is a coordinate-sorted BAM of one haplotype's contig alignments, output the merged DEL and INS tables; the variant table stays on the device
- * from the records to the printed lines.  Combining two haplotypes (Homcalls, Hetcalls, combineHet) is not done.  It is the fourth consumer of the pass
+ * from the records to the printed lines.  Combining two haplotypes (Homcalls, Hetcalls, combineHet) is lra_sv_combine's, below.  It is the fourth consumer of the pass
  * (bam_pass.h), and shares the contained filter and the walk with lra_bam_vcf (bam_contained.h, bam_vcf_walk.h); one object serves one context.
  *   create    as lra_bam_vcf_create: the context must hold the genome and its chromosome table, compared with the BAM header's reference table.
  *   opts      require / exclude / min_mapq / window_bytes as lra_bam_vcf's.  drop_contained: lra_bam_vcf's filter (NULL opts: 1).  min_size: a
@@ -1943,6 +1943,77 @@ int lra_bam_svcalls_region(lra_bam_svcalls* d, int32_t ref_id, int64_t beg, int6
 int lra_bam_svcalls_next(lra_bam_svcalls* d, struct lra_bam_svcalls_piece* piece);
 int lra_bam_svcalls_stats(lra_bam_svcalls* d, struct lra_bam_svcalls_stats* out);
 void lra_bam_svcalls_destroy(lra_bam_svcalls* d);
+/* ---- Two haplotypes' assembly SV calls as hom / het VCF lines (additive to ABI 9) -----------------------------------------------------------------------
+ * lra_sv_combine is the two-haplotype half of call_assembly_SVs/callassemblysv.snakefile on the device: the rules Homcalls, Hetcalls and combineHet.  It
+ * owns two lra_bam_svcalls passes -- the maternal BAM's, then the paternal one's, hap words "maternal" and "paternal" -- whose kept rows stay on the device
+ * (an internal sink of the pass; such a pass builds no text), classifies every row against the other haplotype's table and prints the six classes.
+ *   create    both files as lra_bam_svcalls_create takes one.  The two headers' reference tables must equal the context's (the passes' own test) and each
+ *             other, name by name: LRA_ERR_INVALID naming the first difference otherwise.
+ *   opts      require / exclude / min_mapq / min_size / drop_contained / window_bytes / aligner / pos_one_based / want_text / want_values as
+ *             lra_bam_svcalls'.  frac_num / frac_den: the fraction F of the partner test; 0 / 0 is 3 / 10; den == 0, num == 0 or num > den is
+ *             LRA_ERR_INVALID.  filter_pass: the line's FILTER column (below).  NULL opts: the defaults, text only.
+ *   inputs    for each kind K in {INS, DEL}: M_K and P_K, the maternal and the paternal pass's kept rows after its own merge, in delivery order (by
+ *             reference, then NR), each row with the NR and ID its own pass gave it (<aligner>.<K>.maternal.<NR>, <aligner>.<K>.paternal.<NR>).
+ *   partner   rows a, b of one kind and one reference, ov = min(a.end, b.end) - max(a.start, b.start): ov > 0 && den ov >= num (a.end - a.start) &&
+ *             den ov >= num (b.end - b.start), in 64 bits.  This is bedtools intersect -f F -r over the .merge.vcf files, whose columns 2 and 3 (START,
+ *             END) bedtools reads as BED, half-open -- the reading mergeCalls already relies on.  Symmetric; touching rows are no partners; INS and DEL
+ *             rows never meet.  bedtools makes the test in single precision, (float)ov / (float)len >= 0.3f (its source as remembered: bedtools is not
+ *             run anywhere here).  For len <= 2^24 = 16777216 the integer form is that test exactly, for 3 / 10 and for 1 / 10: both operands are exact
+ *             floats, the quotient is correctly rounded, 0.3f lies above 3 / 10 so equality and everything above it pass, and a quotient below 3 / 10
+ *             is below by at least 1 / (10 len), more than the 0.1 * 2^-25 between 3 / 10 and the midpoint under 0.3f (0.3 * 2^-27 for 0.1f).
+ *             bam_svcombine_host.h has the numbers, tools/micro/bam_svcombine_host_check.cpp checks them.
+ *   classes   hom_K: the rows of M_K with a partner in P_K, each once however many partners it has (-u), with its maternal ID.  het_m_K: the rows of M_K
+ *             without one; het_p_K: the rows of P_K without a partner in M_K (-v, both ways round).  A paternal row with a partner is printed nowhere.
+ *             Every class keeps its table's order.
+ *   line      RNAME \t START \t ID \t REF \t ALT \t 60 \t INFO \t INFO \t GT \t 1/1 \n -- the snakefile's awk prints $9,$9: the FILTER column carries
+ *             INFO a second time, and the genotype stays 1/1 in the het files too; what the reference prints is printed.  filter_pass: 60 \t PASS \t
+ *             INFO, combinehapSV.snakefile's line (with frac 1 / 10 its whole rule), byte for byte lra_bam_svcalls' line with vcf_columns.  START is
+ *             printed + 1 with pos_one_based.
+ *   delivery  lra_sv_combine_all / _region (a whole reference only, as lra_bam_svcalls_region) start a run; the first lra_sv_combine_next makes both
+ *             passes to their ends -- a row's class needs both tables, and the order is by class, not by reference, so nothing is delivered before --
+ *             and then the pieces come in combineHet's order: maternal INS het, maternal DEL het, paternal INS het, paternal DEL het, INS hom, DEL hom
+ *             (piece.hap 0 maternal / 1 paternal, kind 0 INS / 1 DEL, cls 0 het / 1 hom; a hom piece has hap 0).  A class without rows has no piece;
+ *             n_rows == 0 && text_len == 0: the run is over.  The snakefile cats the SAM header in front of lra.vcf; that slip is not reproduced.
+ *   mask      lra_sv_combine_set_mask goes to both passes and ends a run in hand.
+ * Values (want_values): one lra_sv_combine_row per printed row: lra_bam_svcalls_row's fields, hap and cls (in that struct's pad bytes).
+ * Refusals: a refusal of either pass (lra_bam_svcalls': an unsorted file, a bad record) refuses the lra_sv_combine_next that met it, with that pass's
+ * message behind "the maternal pass: " / "the paternal pass: "; nothing is delivered, and the object takes another run.
+ * On the device: per pairing (A, B) of M_K against P_K and P_K against M_K, B's rows of a reference are one contiguous range, found by binary search on
+ * ref and tiled by 256 rows with each tile's [lowest START, highest END); a lane per row of A passes over the tiles it shares no base with and tests the
+ * rows of the others.  B is in NR order, not START order, so there is no early exit on START.  The flag is a function of the two tables alone.
+ * Memory.  Beside the two passes' own (lra_bam_svcalls' formula, no text), both haplotypes' kept rows live until the next run: 88 bytes per kept row
+ * plus its QNAME and ALT, half as much again while a table grows; 4 bytes per row for the flags; 12 (n_ref + 2) + 16 (K / 256 + n_ref + 1) for a
+ * pairing against K rows; a class of C rows out of a table of M whose lines take X bytes allocates 16 M + 32 C + X + 64 C (values) + 64, and X + 1 + 64 C
+ * bytes of page-locked host memory take a piece.
+ * Stats, summed over the object's life: runs; printed rows per class, kind and haplotype; the paternal rows with a partner; bytes printed; ms of the two
+ * passes (wall), of classify, emit and copy (HIP events); pass[0], pass[1]: the two passes' own stats. */
+typedef struct lra_sv_combine lra_sv_combine;
+struct lra_sv_combine_opts {
+  uint32_t require, exclude, min_mapq, min_size, drop_contained, pos_one_based, frac_num, frac_den, filter_pass, want_text, want_values, reserved;
+  uint64_t window_bytes;
+  const char* aligner;
+};
+struct lra_sv_combine_row {
+  uint64_t record, text_off, nr; int64_t start, end, svlen;
+  int32_t ref_id; uint32_t qstart; uint8_t kind, strand, hap, cls; uint32_t pad;
+};
+struct lra_sv_combine_piece {
+  uint64_t n_rows; const struct lra_sv_combine_row* rows; const char* text; uint64_t text_len; uint32_t hap, kind, cls, pad;
+};
+struct lra_sv_combine_stats {
+  uint64_t runs, het_m_ins, het_m_del, het_p_ins, het_p_del, hom_ins, hom_del, partnered_p_ins, partnered_p_del, bytes_text;
+  double ms_pass_m, ms_pass_p, ms_classify, ms_emit, ms_copy;
+  struct lra_bam_svcalls_stats pass[2];
+};
+int lra_sv_combine_create(lra_ctx* ctx, const char* bam_m, const char* bai_m, const char* bam_p, const char* bai_p, const struct lra_sv_combine_opts* opts,
+                          lra_sv_combine** out);
+int lra_sv_combine_header(lra_sv_combine* d, int* n_ref, const char* const** names, const uint64_t** ref_len);
+int lra_sv_combine_set_mask(lra_sv_combine* d, uint64_t n, const int32_t* ref_id, const int64_t* beg, const int64_t* end);
+int lra_sv_combine_all(lra_sv_combine* d);
+int lra_sv_combine_region(lra_sv_combine* d, int32_t ref_id, int64_t beg, int64_t end);
+int lra_sv_combine_next(lra_sv_combine* d, struct lra_sv_combine_piece* piece);
+int lra_sv_combine_stats(lra_sv_combine* d, struct lra_sv_combine_stats* out);
+void lra_sv_combine_destroy(lra_sv_combine* d);
 /* the reads of a snapshot whose status word is non-zero: their number; *status (optional) = the snapshot's status array [n_reads], owned by the snapshot */
 uint64_t lra_map_host_flagged(const lra_map_host* snap, const uint32_t** status);
 /* The record buffer of a batch as ONE device buffer -- what a rank sends to rank 0 in the single exchange step of the multi-GPU path (the

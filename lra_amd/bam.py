@@ -513,7 +513,7 @@ class BamSvCalls(_BamPass):
         b = np.ascontiguousarray([x[1] for x in iv], np.int64)
         e = np.ascontiguousarray([x[2] for x in iv], np.int64)
         q = lambda a: C.c_void_p(a.ctypes.data) if len(a) else None
-        self.ctx.check(self.ctx.lib.lra_bam_svcalls_set_mask(self.h, C.c_uint64(len(iv)), q(r), q(b), q(e)))
+        self.ctx.check(self._fn("set_mask")(self.h, C.c_uint64(len(iv)), q(r), q(b), q(e)))
 
     def fetch(self, ref=None):
         """yields the pieces of a pass as (ref_id, kind "DEL" / "INS", n_rows, values, text): ref None: the whole file; ref: a reference's index or name.  A
@@ -529,6 +529,86 @@ class BamSvCalls(_BamPass):
             if p.rows and p.n_rows:
                 vals = np.ctypeslib.as_array(C.cast(p.rows, C.POINTER(C.c_uint8)), shape=(p.n_rows * SVCALLS_ROW_DTYPE.itemsize,)).view(SVCALLS_ROW_DTYPE)
             yield p.ref_id, "DEL" if p.kind else "INS", p.n_rows, vals, (C.string_at(p.text, p.text_len) if p.text_len else b"")
+
+
+class SvCombineOpts(C.Structure):
+    """struct lra_sv_combine_opts (include/lra_hip.h)"""
+    _fields_ = [(k, C.c_uint32) for k in ("require", "exclude", "min_mapq", "min_size", "drop_contained", "pos_one_based", "frac_num", "frac_den", "filter_pass",
+                                          "want_text", "want_values", "reserved")] + [("window_bytes", C.c_uint64), ("aligner", C.c_char_p)]
+
+
+# struct lra_sv_combine_row (include/lra_hip.h), 64 bytes: SVCALLS_ROW_DTYPE with hap and cls in its pad
+SVCOMBINE_ROW_DTYPE = np.dtype([("record", "<u8"), ("text_off", "<u8"), ("nr", "<u8"), ("start", "<i8"), ("end", "<i8"), ("svlen", "<i8"), ("ref_id", "<i4"),
+                                ("qstart", "<u4"), ("kind", "u1"), ("strand", "u1"), ("hap", "u1"), ("cls", "u1"), ("pad", "<u4")])
+
+
+class SvCombinePiece(C.Structure):
+    """struct lra_sv_combine_piece (include/lra_hip.h)"""
+    _fields_ = [("n_rows", C.c_uint64), ("rows", C.c_void_p), ("text", C.c_void_p), ("text_len", C.c_uint64), ("hap", C.c_uint32), ("kind", C.c_uint32),
+                ("cls", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class SvCombineStats(C.Structure):
+    """struct lra_sv_combine_stats (include/lra_hip.h)"""
+    _fields_ = [(k, C.c_uint64) for k in ("runs", "het_m_ins", "het_m_del", "het_p_ins", "het_p_del", "hom_ins", "hom_del", "partnered_p_ins", "partnered_p_del",
+                                          "bytes_text")] + \
+               [(k, C.c_double) for k in ("ms_pass_m", "ms_pass_p", "ms_classify", "ms_emit", "ms_copy")] + [("passes", SvCallsStats * 2)]
+
+
+# the seven files of tools/svcombine_bam.py in delivery order: (hap, kind, cls) -> the file's suffix behind PREFIX
+SVCOMBINE_FILES = ((("maternal", "INS", "het"), ".maternal.INS.het.vcf"), (("maternal", "DEL", "het"), ".maternal.DEL.het.vcf"),
+                   (("paternal", "INS", "het"), ".paternal.INS.het.vcf"), (("paternal", "DEL", "het"), ".paternal.DEL.het.vcf"),
+                   (("maternal", "INS", "hom"), ".INS.hom.vcf"), (("maternal", "DEL", "hom"), ".DEL.hom.vcf"))
+
+
+def parse_frac(text):
+    """"3/10" -> (3, 10); ValueError unless it is NUM/DEN with 0 < NUM <= DEN (no GPU)"""
+    num, sep, den = str(text).partition("/")
+    if not sep or not num.strip().isdigit() or not den.strip().isdigit() or not 0 < int(num) <= int(den) < 2 ** 32:
+        raise ValueError("fraction %r: not NUM/DEN with 0 < NUM <= DEN" % (text,))
+    return int(num), int(den)
+
+
+class SvCombine(_BamPass):
+    """lra_sv_combine: two haplotypes' assembly SV calls as the diploid call set -- the rules Homcalls, Hetcalls and combineHet of the reference's
+    call_assembly_SVs pipeline on the device (include/lra_hip.h has the rules).  path_m / path_p: the maternal and the paternal haplotype's coordinate-sorted
+    BAM; ctx must hold the genome and its chromosome table, as for BamSvCalls.  frac: (num, den) of the partner test, None: 3 / 10.  filter_pass: the FILTER
+    column is PASS, not INFO a second time."""
+    _prefix, _Stats = "lra_sv_combine", SvCombineStats
+
+    def __init__(self, ctx: Context, path_m, path_p, bai_m=None, bai_p=None, require=0, exclude=None, min_mapq=0, min_size=40, drop_contained=True,
+                 aligner="aligner", pos_one_based=False, frac=None, filter_pass=False, text=True, values=False, window_bytes=0):
+        enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
+        num, den = (0, 0) if frac is None else frac
+        o = SvCombineOpts(int(require), 0xffffffff if exclude is None else int(exclude), int(min_mapq), int(min_size), int(bool(drop_contained)),
+                          int(bool(pos_one_based)), int(num), int(den), int(bool(filter_pass)), int(bool(text)), int(bool(values)), 0, int(window_bytes), enc(aligner))
+        self._create(ctx, path_m, bai_m, os.fsencode(path_p), os.fsencode(bai_p) if bai_p is not None else None, C.byref(o))
+
+    set_mask = BamSvCalls.set_mask
+
+    def stats(self):
+        """-> the object's counts and times; "passes": the two lra_bam_svcalls passes' own stats, maternal first"""
+        s = SvCombineStats()
+        self.ctx.check(self.ctx.lib.lra_sv_combine_stats(self.h, C.byref(s)))
+        out = {k: getattr(s, k) for k, _ in SvCombineStats._fields_ if k != "passes"}
+        out["passes"] = [{k: getattr(p, k) for k, _ in SvCallsStats._fields_} for p in s.passes]
+        return out
+
+    def fetch(self, ref=None):
+        """yields the pieces of a run as (hap "maternal" / "paternal", kind "INS" / "DEL", cls "het" / "hom", n_rows, values, text) in combineHet's order:
+        the maternal het pieces (INS, DEL), the paternal ones, then the hom pieces (hap "maternal": their IDs).  ref None: the whole files; ref: a
+        reference's index or name.  values: a numpy record array of SVCOMBINE_ROW_DTYPE (None without values), valid until the next piece."""
+        self._start(ref)
+        while True:
+            p = SvCombinePiece()
+            self._next(p)
+            if not p.n_rows and not p.text_len:
+                return
+            vals = None
+            if p.rows and p.n_rows:
+                vals = np.ctypeslib.as_array(C.cast(p.rows, C.POINTER(C.c_uint8)), shape=(p.n_rows * SVCOMBINE_ROW_DTYPE.itemsize,)).view(SVCOMBINE_ROW_DTYPE)
+            yield ("paternal" if p.hap else "maternal", "DEL" if p.kind else "INS", "hom" if p.cls else "het", p.n_rows, vals,
+                   (C.string_at(p.text, p.text_len) if p.text_len else b""))
 
 
 def bai_query(bai, n_ref, ref_id, beg, end, lib=None):

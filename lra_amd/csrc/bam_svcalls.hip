@@ -19,11 +19,14 @@
 //   RNAME \t START \t [END \t] ID \t | REF | \t ALT | \t 60 \t PASS \t SVTYPE= .. QSTRAND= . \t GT \t 1/1 \n
 // sv_small prints the first and the last and the value record, sv_bulk (chunk_copy.h's walk) copies REF from the genome and ALT from the kept bytes.
 // sv_pop moves the rows behind the head, and their bytes, to the front.
+// sink (bam_sv_table.h; lra_sv_combine's, no part of the ABI).  With one set, the kept rows are not printed: sv_sink_len, one scan and sv_sink_copy, a wave
+// per kept row, append them and their bytes to the sink's table of the kind, b_off rebased, in front of sv_pop.  Without one nothing here differs.
 #include "common.h"
 #include "chunk_copy.h"
 #include "scan.h"
 #include "bam_pass.h"
 #include "bam_vcf_walk.h"
+#include "bam_sv_table.h"
 #include "bam_svcalls_host.h"
 #include <stddef.h>
 #include <algorithm>
@@ -32,29 +35,8 @@
 
 namespace {
 
-constexpr int SV_CHUNK = 4096, SV_BATCH = 8, SV_TILE = 256;
+constexpr int SV_BATCH = 8, SV_TILE = 256;
 enum { M_UNSORTED = 0, M_LAST = 1, M_HAS_LAST = 2, M_MASKED_INS = 3, M_MASKED_DEL = 4, M_PREFIX = 5, M_BASE = 6, M_CHANGED = 8, M_WORDS = 16 };   // sv_misc[]
-
-struct SvRow {                                                 // a row of a kind's table
-  int64_t start, end, svlen; uint64_t nr, record, g_at, ref_len, alt_len, b_off;   // b_off: QNAME then ALT in the kind's bytes
-  int32_t ref; uint32_t qstart, l_name, reverse;
-};
-
-// an array whose first items survive its growth
-template <typename T> struct KeepBuf {
-  T* p = nullptr; size_t n = 0;
-  bool ensure(size_t want, size_t keep, hipStream_t st) {
-    if (want <= n) return true;
-    const size_t m = want + want / 2 + 64;
-    T* q = nullptr;
-    if (hipMalloc((void**)&q, m * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (keep && (hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) { (void)hipFree(q); return false; }
-    if (p) { (void)hipStreamSynchronize(st); (void)hipFree(p); }
-    p = q; n = m;
-    return true;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
 
 // ---- the window ------------------------------------------------------------------------------------------------------------------------------------------------
 struct SvW {
@@ -125,20 +107,7 @@ __global__ void __launch_bounds__(256) sv_bytes(SvW W, int k) {
   }
 }
 
-// ---- a reference's rows of one kind ------------------------------------------------------------------------------------------------------------------------------
-struct SvF {
-  const SvRow* rows; uint64_t m;                              // the table's head: rows [0, m), one reference, NR order
-  unsigned long long* misc;
-  int64_t* t_lo; int64_t* t_hi;                               // per SV_TILE rows in NR order: the lowest START and the highest END
-  uint32_t* deg; uint64_t* eoff; uint32_t* in;
-  uint32_t* st_a; uint32_t* st_b;
-  uint32_t* kept; uint64_t* koff; uint32_t* kidx; uint64_t nk;
-  uint32_t* plen; uint64_t* poff;
-  const char* rname; const uint64_t* rname_off; const unsigned char* genome; const uint8_t* bytes;
-  const char* stem; uint32_t stem_len; int del; uint32_t one_based, vcf_columns;
-  unsigned char* text; uint64_t n_text; struct lra_bam_svcalls_row* vals;
-};
-
+// ---- a reference's rows of one kind (SvF and the line emitter: bam_sv_table.h) -----------------------------------------------------------------------------------
 // rows [0, n) are sorted by reference: how many lie at or below r
 __global__ void __launch_bounds__(256) sv_prefix(const SvRow* rows, uint64_t n, int32_t r, unsigned long long* out) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -199,56 +168,25 @@ __global__ void __launch_bounds__(256) sv_kept(SvF F, const uint32_t* state) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < F.m) F.kept[i] = state[i] == LRA_SV_KEPT ? 1u : 0u;
 }
-__device__ __forceinline__ uint32_t sv_head_len(const SvF& F, const SvRow& r) {
-  const uint32_t name = (uint32_t)(F.rname_off[r.ref + 1] - F.rname_off[r.ref]);
-  return name + 1u + (uint32_t)ndig((uint64_t)r.start + F.one_based) + 1u + (F.vcf_columns ? 0u : (uint32_t)ndig((uint64_t)r.end + F.one_based) + 1u) + F.stem_len + (uint32_t)ndig(r.nr) + 1u;
-}
-__global__ void __launch_bounds__(256) sv_plen(SvF F) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= F.m || !F.kept[i]) return;
-  const uint64_t j = F.koff[i];
-  F.kidx[j] = (uint32_t)i;
-  if (!F.plen) return;
-  const SvRow& r = F.rows[i];
-  F.plen[4 * j] = sv_head_len(F, r); F.plen[4 * j + 1] = (uint32_t)r.ref_len; F.plen[4 * j + 2] = 1u + (uint32_t)r.alt_len;   // (32 bits: bam_vcf_walk.h's vc_compact says why)
-  F.plen[4 * j + 3] = info_len(r.svlen, r.l_name, r.qstart);
-}
-__global__ void __launch_bounds__(256) sv_small(SvF F) {
+// ---- the sink: the kept rows of a reference, appended to another object's table ------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) sv_sink_len(SvF F, uint32_t* blen) {
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= F.nk) return;
   const SvRow& r = F.rows[F.kidx[j]];
-  if (F.text) {
-    unsigned char* d = F.text + F.poff[4 * j];
-    const uint64_t a = F.rname_off[r.ref], b = F.rname_off[r.ref + 1];
-    for (uint64_t k = a; k < b; k++) *d++ = (unsigned char)F.rname[k];
-    *d++ = '\t'; d = put_u(d, (uint64_t)r.start + F.one_based);
-    if (!F.vcf_columns) { *d++ = '\t'; d = put_u(d, (uint64_t)r.end + F.one_based); }
-    *d++ = '\t';
-    for (uint32_t k = 0; k < F.stem_len; k++) *d++ = (unsigned char)F.stem[k];
-    d = put_u(d, r.nr); *d++ = '\t';
-    F.text[F.poff[4 * j + 2]] = '\t';
-    put_info(F.text + F.poff[4 * j + 3], F.del != 0, r.svlen, F.bytes + r.b_off, r.l_name, r.qstart, r.reverse != 0);
-  }
-  if (F.vals) {
-    struct lra_bam_svcalls_row x;
-    x.record = r.record; x.text_off = F.text ? F.poff[4 * j] : 0; x.nr = r.nr; x.start = r.start; x.end = r.end; x.svlen = r.svlen; x.ref_id = r.ref; x.qstart = r.qstart;
-    x.kind = F.del ? 1 : 0; x.strand = (uint8_t)r.reverse; x.pad = 0; x.pad2 = 0;
-    F.vals[j] = x;
-  }
+  blen[j] = r.l_name + (uint32_t)r.alt_len;
 }
-__global__ void __launch_bounds__(256) sv_bulk(SvF F) {
+// a wave per kept row: the row behind out[0, at_row) with b_off rebased, its bytes behind out_bytes[0, at_byte)
+__global__ void __launch_bounds__(256) sv_sink_copy(SvF F, const uint64_t* boff, SvRow* out, uint64_t at_row, uint8_t* out_bytes, uint64_t at_byte) {
   const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
   const int lane = threadIdx.x & 63;
-  chunk_walk<SV_CHUNK>(F.n_text, 4 * F.nk, F.poff, wave, n_waves, [&](uint64_t q, uint64_t b, uint64_t end, uint64_t lo, uint64_t hi) {
-    const int part = (int)(q & 3);
-    if (part != 1 && part != 2) return;
-    const uint64_t wb = b + (part == 2 ? 1 : 0), from = max(lo, wb), to = min(hi, end);
-    if (to <= from) return;
-    const SvRow& r = F.rows[F.kidx[q >> 2]];
-    const unsigned char* src = part == 1 ? F.genome + r.g_at : F.bytes + r.b_off + r.l_name;
-    wave_copy(F.text + from, src + (from - wb), to - from, lane);
-  });
+  for (uint64_t j = wave; j < F.nk; j += n_waves) {
+    const SvRow& r = F.rows[F.kidx[j]];
+    const uint64_t to = at_byte + boff[j], n = (uint64_t)r.l_name + r.alt_len;
+    for (uint64_t c = lane; c < n; c += 64) out_bytes[to + c] = F.bytes[r.b_off + c];
+    if (lane == 0) { SvRow* o = out + at_row + j; *o = r; o->b_off = to; }
+  }
 }
+
 // the rows [from, n) move to the front of `out`, their bytes' offsets less the first one's (*base, for the host's copy of the bytes)
 __global__ void __launch_bounds__(256) sv_pop(const SvRow* rows, SvRow* out, uint64_t from, uint64_t n, unsigned long long* base) {
   const uint64_t i = from + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -279,6 +217,7 @@ struct lra_bam_svcalls : lra_bam_pass {
   // a reference's rows
   Buf<uint32_t> deg, in, st_a, st_b, kept, kidx, plen; Buf<uint64_t> eoff, koff, poff; Buf<int64_t> t_lo, t_hi; Buf<uint8_t> text; Buf<struct lra_bam_svcalls_row> vals;
   PinBuf<char> h_text; PinBuf<struct lra_bam_svcalls_row> h_vals;
+  lra_sv_sink* sink = nullptr; Buf<uint32_t> s_len; Buf<uint64_t> s_off;   // set: a reference's kept rows go there and nothing is printed
 
   lra_bam_svcalls() { W.ms_frame_select = &S.ms_frame_select; W.ms_ops = &S.ms_ops; W.ms_walk = &S.ms_walk; W.ms_lengths = &S.ms_lengths; }
   void release_all() {
@@ -288,7 +227,7 @@ struct lra_bam_svcalls : lra_bam_pass {
       for (int b = 0; b < 2; b++) { rows[k][b].release(); bytes[k][b].release(); }
     }
     t_lo.release(); t_hi.release(); deg.release(); in.release(); st_a.release(); st_b.release(); kept.release(); kidx.release(); plen.release(); eoff.release(); koff.release(); poff.release(); text.release(); vals.release();
-    h_text.release(); h_vals.release();
+    h_text.release(); h_vals.release(); s_len.release(); s_off.release();
   }
   int take_genome(const char* fn) { return lra_vcf_take_genome(*this, fn, &d_genome, &d_chrom_pos); }
   int set_mask(uint64_t n, const int32_t* ref_id, const int64_t* b, const int64_t* e);
@@ -311,6 +250,7 @@ struct lra_bam_svcalls : lra_bam_pass {
     return false;                                              // (next() looks at the tables itself)
   }
   int finish_kind(int k, uint64_t m, struct lra_bam_svcalls_piece* piece);
+  int to_sink(int k, SvF& F, uint64_t nk, struct lra_bam_svcalls_piece* piece);
   int pop(int k, uint64_t m);
   int next(struct lra_bam_svcalls_piece* piece);
 };
@@ -441,6 +381,7 @@ int lra_bam_svcalls::finish_kind(int k, uint64_t m, struct lra_bam_svcalls_piece
   }
   S.merge_rounds += rounds;
   (k ? S.merged_del : S.merged_ins) += m - nk; (k ? S.kept_del : S.kept_ins) += nk;
+  if (sink) return to_sink(k, F, nk, piece);
   uint64_t total = 0, dev_text = 0, host_text = 0, value_bytes = 0;
   {
     Timer T(st);
@@ -485,6 +426,34 @@ int lra_bam_svcalls::finish_kind(int k, uint64_t m, struct lra_bam_svcalls_piece
   return LRA_OK;
 }
 
+// The kept rows of finish_kind's F go behind the sink's table of kind k, device to device, with their bytes; the piece says only how many.
+int lra_bam_svcalls::to_sink(int k, SvF& F, uint64_t nk, struct lra_bam_svcalls_piece* piece) {
+  hipStream_t st = ctx->stream;
+  lra_sv_sink& K = *sink;
+  Timer T(st);
+  F.nk = nk; F.plen = nullptr; F.bytes = bytes[k][cur[k]].p;
+  hipLaunchKernelGGL(sv_plen, dim3(blocks_of(F.m)), dim3(256), 0, st, F);   // (kidx: the kept rows in NR order)
+  LRA_HIP_CHECK(ctx, hipGetLastError());
+  if (nk) {
+    uint64_t nb = 0;
+    if (!grab(s_len, nk) || !grab(s_off, nk + 1)) return fail(LRA_ERR_NOMEM, "lra_bam_svcalls: hipMalloc failed for %llu rows", (unsigned long long)nk);
+    hipLaunchKernelGGL(sv_sink_len, dim3(blocks_of(nk)), dim3(256), 0, st, F, s_len.p);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    if (lra_exclusive_scan<uint32_t>(ctx, (long)nk, s_len.p, s_off.p)) return fail(LRA_ERR_HIP, "lra_bam_svcalls: a scan failed");
+    LRA_HIP_CHECK(ctx, hipMemcpyAsync(&nb, s_off.p + nk, 8, hipMemcpyDeviceToHost, st));
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    if (!K.rows[k].ensure(K.n_rows[k] + nk, K.n_rows[k], st) || !K.bytes[k].ensure(K.n_bytes[k] + nb + 8, K.n_bytes[k], st))
+      return fail(LRA_ERR_NOMEM, "lra_bam_svcalls: hipMalloc failed for %llu kept rows and %llu bytes of names and ALT", (unsigned long long)(K.n_rows[k] + nk), (unsigned long long)(K.n_bytes[k] + nb));
+    hipLaunchKernelGGL(sv_sink_copy, dim3(wave_blocks(ctx, nk)), dim3(256), 0, st, F, (const uint64_t*)s_off.p, K.rows[k].p, K.n_rows[k], K.bytes[k].p, K.n_bytes[k]);
+    LRA_HIP_CHECK(ctx, hipGetLastError());
+    LRA_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    K.n_rows[k] += nk; K.n_bytes[k] += nb;
+  }
+  S.ms_copy += T.stop();
+  piece->n_rows = nk; piece->kind = (uint32_t)k;
+  return LRA_OK;
+}
+
 // the rows [0, m) of kind k leave the table
 int lra_bam_svcalls::pop(int k, uint64_t m) {
   hipStream_t st = ctx->stream;
@@ -510,6 +479,7 @@ int lra_bam_svcalls::next(struct lra_bam_svcalls_piece* piece) {
   hipStream_t st = ctx->stream;
   memset(piece, 0, sizeof *piece);
   if (!over) if (int rc = take_genome("lra_bam_svcalls_next")) { over = true; faulted = true; return rc; }   // (the context may have taken another genome since)
+  if (sink) { sink->rname = (const char*)rname.p; sink->rname_off = rname_off.p; sink->genome = d_genome; }
   for (;;) {
     if (fin_stage == 0 && !faulted && (n_rows[0] || n_rows[1])) {
       // the lowest reference in the tables; it is final when a record of a later one has been delivered, or the pass is over
@@ -579,6 +549,8 @@ extern "C" int lra_bam_svcalls_create(lra_ctx* ctx, const char* bam_path, const 
   *out = d.release();
   return LRA_OK;
 }
+
+__attribute__((visibility("hidden"))) void lra_bam_svcalls_set_sink(lra_bam_svcalls* d, lra_sv_sink* sink) { d->sink = sink; }
 
 extern "C" void lra_bam_svcalls_destroy(lra_bam_svcalls* d) { pass_destroy(d); }
 

@@ -197,7 +197,9 @@ __global__ void __launch_bounds__(256) vc_vkeep(Vc V) {
 }
 
 #define LIT_LEN(s) ((uint32_t)sizeof(s) - 1u)
-#define T_INFO "\t60\tPASS\tSVTYPE="
+#define T_QUAL "\t60\t"
+#define T_PASS "PASS\t"
+#define T_SVTYPE "SVTYPE="
 #define T_SVLEN ";SVLEN="
 #define T_QNAME ";QNAME="
 #define T_QSTART ";QSTART="
@@ -207,18 +209,27 @@ template <size_t N> __device__ __forceinline__ unsigned char* put_lit(unsigned c
   for (size_t k = 0; k + 1 < N; k++) d[k] = (unsigned char)s[k];
   return d + (N - 1);
 }
-// the bytes of a line from "\t60\tPASS\t" through the newline, which both consumers print alike
-__device__ __forceinline__ uint32_t info_len(int64_t svlen, uint32_t l_name, uint64_t qstart) {
-  return LIT_LEN(T_INFO) + 3u + LIT_LEN(T_SVLEN) + (uint32_t)slen(svlen) + LIT_LEN(T_QNAME) + l_name + LIT_LEN(T_QSTART) + (uint32_t)ndig(qstart) + LIT_LEN(T_QSTRAND) + 1u + LIT_LEN(T_END);
+// the INFO column, SVTYPE= through QSTRAND's sign
+__device__ __forceinline__ uint32_t info_body_len(int64_t svlen, uint32_t l_name, uint64_t qstart) {
+  return LIT_LEN(T_SVTYPE) + 3u + LIT_LEN(T_SVLEN) + (uint32_t)slen(svlen) + LIT_LEN(T_QNAME) + l_name + LIT_LEN(T_QSTART) + (uint32_t)ndig(qstart) + LIT_LEN(T_QSTRAND) + 1u;
 }
-__device__ __forceinline__ void put_info(unsigned char* d, bool del, int64_t svlen, const uint8_t* name, uint32_t l_name, uint64_t qstart, bool reverse) {
-  d = put_lit(d, T_INFO);
+__device__ __forceinline__ unsigned char* put_info_body(unsigned char* d, bool del, int64_t svlen, const uint8_t* name, uint32_t l_name, uint64_t qstart, bool reverse) {
+  d = put_lit(d, T_SVTYPE);
   if (del) d = put_lit(d, "DEL"); else d = put_lit(d, "INS");
   d = put_lit(d, T_SVLEN); d = put_s(d, svlen);
   d = put_lit(d, T_QNAME);
   for (uint32_t k = 0; k < l_name; k++) *d++ = name[k];
   d = put_lit(d, T_QSTART); d = put_u(d, qstart);
   d = put_lit(d, T_QSTRAND); *d++ = reverse ? '-' : '+';
+  return d;
+}
+// the bytes of a line from "\t60\tPASS\t" through the newline, which both consumers print alike
+__device__ __forceinline__ uint32_t info_len(int64_t svlen, uint32_t l_name, uint64_t qstart) {
+  return LIT_LEN(T_QUAL) + LIT_LEN(T_PASS) + info_body_len(svlen, l_name, qstart) + LIT_LEN(T_END);
+}
+__device__ __forceinline__ void put_info(unsigned char* d, bool del, int64_t svlen, const uint8_t* name, uint32_t l_name, uint64_t qstart, bool reverse) {
+  d = put_lit(d, T_QUAL); d = put_lit(d, T_PASS);
+  d = put_info_body(d, del, svlen, name, l_name, qstart, reverse);
   put_lit(d, T_END);
 }
 
