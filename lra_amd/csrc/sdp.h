@@ -35,7 +35,10 @@ struct Node {            // one full sub-problem (SubProblem.h:15-37), 48 bytes
 
 // Everything ProcessPoint touches for one read lies in one contiguous block (sections 256-byte aligned): a wave's working set is a
 // couple of megabytes in one place instead of six arrays gigabytes apart (TLB reach).
-struct ReadArena { uint64_t base; uint32_t entOff, apOff, stkOff, visOff, blkPair, poolPair, poolPairs, edOff; };   // base: device address; byte offsets; nodes at 0
+struct ReadArena { uint64_t base; uint32_t entOff, apOff, stkOff, visOff, blkPair, poolPair, poolPairs, edOff, visPl; };   // base: device address; byte offsets; nodes at 0
+// visOff: the visit records (sub-problem id, index in Di / Ei), one PLANE of P records per (family pair, level) the read can have: the row family's visPl & 0xff planes, then
+// the column family's visPl >> 8 -- record of point p on plane k at vis[k * P + p].  A family of n distinct rows / columns uses the levels 0 .. ceil(log2 n) (vis_planes);
+// the layout kernels bound n by the read's points, or take the exact rows / columns where a launch before them has counted them (Chunk::lines).
 // edOff: one 64-bit word per entry -- for a D entry d the diagonal Ei[Db[d]] (static), which Maximization compares every candidate at (SubRountine.h:292): stored
 // beside the entry, the candidate scan is ONE round of independent loads instead of two dependent ones
 // The pair area at stkOff holds the candidate stacks, then (from pair index blkPair) the Block lists, then (from poolPair) a pool of
@@ -61,6 +64,7 @@ struct BuildArgs {
   const uint32_t* hq; const uint32_t* ht; const uint8_t* hfl; const uint32_t* h2; const uint64_t* key3; const uint32_t* pay3;
   uint32_t* scratch;                         // 34 words per point + 64 per read
   uint32_t* cntEntries; uint32_t* cntNodes; uint32_t* cntD; uint32_t* cntV; uint32_t* cntRC;   // [n] (count pass out; cntRC: max(distinct rows, distinct columns))
+  uint32_t* lines;                           // [2 n] count pass out: the read's distinct rows, distinct columns (Chunk::lines)
   const ReadArena* ra;                       // emit pass: per-read blocks
   uint32_t* status;
   unsigned long long* stat;                  // LRA_SDP_BUILD_STAT: cycles per pass (set-up, A, C, D, E, F, G, family set-up) summed over the launch's reads; null = off
@@ -117,6 +121,20 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
   return v;
 }
 __device__ __host__ inline uint32_t al256(uint64_t x) { return (uint32_t)((x + 255) & ~(uint64_t)255); }
+// Levels of a decomposition over n distinct lines: a node halves its lines (floor / ceil) until one is left, so level k holds at most ceil(n / 2^k) lines per node and
+// the leaves are at level ceil(log2 n) at the latest.  Never more than LV: sdp_build gives a read up (LRA_ST_RANGE) at the first level without a plane.
+__device__ __host__ inline uint32_t vis_planes(uint64_t n) {
+  uint32_t d = 1;
+  while (d < (uint32_t)LV && (uint64_t(1) << (d - 1)) < n) d++;
+  return d;
+}
+// The plane of slot (family pair, level) = fam2 * LV + level among a read's planes (ReadArena::visPl), NONE where the read has no such level
+__device__ __forceinline__ uint32_t vis_plane(uint32_t visPl, int slot) {
+  const uint32_t plR = visPl & 0xffu, plC = visPl >> 8;
+  if (slot < LV) return (uint32_t)slot < plR ? (uint32_t)slot : NONE;
+  const uint32_t lv = (uint32_t)(slot - LV);
+  return lv < plC ? plR + lv : NONE;
+}
 // A read's block is found through an address kept in a table (ReadArena::base).  A pointer made from an integer is a FLAT pointer to the compiler: every access through
 // it is a flat_load / flat_store, which counts on the LDS counter as well as on the vector-memory one -- so every LDS read (the gap-cost table inside w(), the slot state)
 // waits for all the stores in flight (a stack / Block push is followed by exactly that).  Saying that the address is in global memory gives global_load / global_store.
@@ -162,6 +180,7 @@ struct Chunk {                                 // reads [r0, r1) of the call: on
   int r0, r1, nr; uint64_t cp;                 // cp: its points
   // slot 10
   uint32_t* scratch; uint32_t* cntE; uint32_t* cntN; uint32_t* cntD; uint32_t* cntV; uint32_t* cntRC; uint32_t* order; uint32_t* order2; uint32_t* poolUsed;
+  uint32_t* lines;                             // per read its distinct rows and columns where a launch has counted them (the count pass, k_big_lines), else 0, 0: the visit planes' bound
   uint64_t* bytes; uint64_t* byteOff; ReadArena* ra;
   std::vector<uint32_t> h_orderAll, h_prev;    // the reads largest first; the reads of the attempt before this one
   BuildArgs ba; StatBuf buildStat;             // (ba.stat = buildStat.d)
@@ -197,11 +216,12 @@ void launch_reset_frags(hipStream_t st, int n, int r0, const uint32_t* order, co
                         uint32_t* fprevNode, uint32_t* fprevInd, uint8_t* fflags, uint32_t* status);
 void launch_pen_table(hipStream_t st, const PwlTab& pw, short* tab, int* bad);   // PEN_TAB_WG entries
 void launch_arena_estimate(hipStream_t st, int n, int r0, const uint64_t* ptOff, float fE, float fN, uint32_t* cntE, uint32_t* cntN, uint32_t* cntD);
-void launch_arena_sizes(hipStream_t st, int n, int r0, const uint64_t* ptOff, const uint32_t* cntE, const uint32_t* cntN, const uint32_t* cntD, ReadArena* ra, uint64_t* bytes,
-                        const uint32_t* order, int shift);
+void launch_arena_sizes(hipStream_t st, int n, int r0, const uint64_t* ptOff, const uint32_t* cntE, const uint32_t* cntN, const uint32_t* cntD, const uint32_t* lines, ReadArena* ra,
+                        uint64_t* bytes, const uint32_t* order, int shift);
 void launch_arena_bases(hipStream_t st, int n, const uint64_t* byteOff, ReadArena* ra, const uint32_t* order, char* arena);
 void launch_visit_clear(hipStream_t st, int n, const ReadArena* ra, const uint64_t* byteOff, const uint32_t* order);
-void launch_big_lines(hipStream_t st, int n, int r0, const uint32_t* order, const uint64_t* ptOff, const uint32_t* hq, const uint32_t* ht, const uint32_t* h2, uint32_t* maxLines);
+void launch_big_lines(hipStream_t st, int n, int r0, const uint32_t* order, const uint64_t* ptOff, const uint32_t* hq, const uint32_t* ht, const uint32_t* h2, uint32_t* maxLines,
+                      uint32_t* lines);
 // ---- sdp_build.hip: the count (emit = false) or emit pass; a 1024-thread workgroup per read for ba.order[0, n), a wave per read for reads [from, to) of d_order / h_order
 void launch_wg_builds(bool emit, hipStream_t st, const BuildArgs& ba, int n);
 void launch_small_builds(bool emit, lra_ctx* ctx, const BuildArgs& ba, const uint32_t* d_order, const std::vector<uint32_t>& h_order, const uint64_t* h_pt, int from, int to);

@@ -19,7 +19,9 @@
 //    are built level by level instead of depth first: per family the points are kept sorted by diagonal and stably
 //    partitioned by half at every level (prefix sums), which yields every node's sorted distinct Di/Ei at once;
 //    Db/Eb have closed forms (counts of smaller diagonals), and every (point, level) gets its sub-problem and its
-//    index in Di/Ei recorded -- the Lower_Bound searches of ProcessPoint/PassValueToD* disappear;
+//    index in Di/Ei recorded -- the Lower_Bound searches of ProcessPoint/PassValueToD* disappear.  The records are kept
+//    level by level: per read one plane of P records for every (family pair, level) it can have, vis[plane][point]
+//    (sdp.h, ReadArena) -- a level of the build writes one plane, a lane of ProcessPoint streams along its own;
 //  * ProcessPoint: one wave per read; lane (family pair, level) < 2 * LV owns the sub-problems of that level, so the sub-problems a
 //    point touches advance concurrently and none is ever touched by two lanes; short candidate insertions run per lane, long ones
 //    wave-cooperatively (prefetched candidates, iterations that change nothing skipped with a ballot, six-level probes in the
@@ -27,8 +29,8 @@
 //    fill up double out of a per-read pool;
 //  * TraceBack / DecidePrimaryChains: one lane per read after the exact sort of the values.
 //
-// Roofline: integer/float bookkeeping with dependent loads, HBM-nominal; algorithmic bytes = 44 B per sub-problem entry + 269 B per
-// point (visit row + coordinates).  A launch lasts as long as its largest reads: one chunk per batch, largest first.
+// Roofline: integer/float bookkeeping with dependent loads, HBM-nominal; algorithmic bytes = 44 B per sub-problem entry + 8 B per level of the read
+// and family pair + 13 B per point (visit records + coordinates).  A launch lasts as long as its largest reads: one chunk per batch, largest first.
 //
 // This file is the driver: sdp_run, a sequence of named stages over the state of one call (lra_sdp::Call, sdp.h), and the two entry points.  The kernels and their
 // launch functions are in sdp_points.hip, sdp_build.hip, sdp_process.hip, sdp_process_wg.hip and sdp_trace.hip, the analysis hooks in sdp_diag.hip (sdp.h lists them).
@@ -200,12 +202,14 @@ int chunk_begin(const Call& c, Chunk& k) {
   lra_ctx* ctx = c.ctx; hipStream_t st = c.st; const std::vector<uint64_t>& h_pt = c.h_pt;
   const int r0 = k.r0, nr = k.nr; const uint64_t cp = k.cp;
   const size_t nr1 = (size_t)nr + 1;
-  size_t needS = sz(34 * cp + 64 * (size_t)nr + 64, 4) + sz(nr1, 4) * 8 + sz(nr1 + 1, 8) * 3 + sz(nr1, sizeof(ReadArena)) + 4096;
+  size_t needS = sz(34 * cp + 64 * (size_t)nr + 64, 4) + sz(nr1, 4) * 8 + sz(2 * nr1, 4) + sz(nr1 + 1, 8) * 3 + sz(nr1, sizeof(ReadArena)) + 4096;
   char* ws = (char*)lra_ensure(ctx, 10, needS);
   if (!ws) return LRA_ERR_NOMEM;
   k.scratch = (uint32_t*)take(ws, 34 * cp + 64 * (size_t)nr + 64, 4);
   k.cntE = (uint32_t*)take(ws, nr1, 4); k.cntN = (uint32_t*)take(ws, nr1, 4); k.cntD = (uint32_t*)take(ws, nr1, 4);
   k.cntV = (uint32_t*)take(ws, nr1, 4); k.cntRC = (uint32_t*)take(ws, nr1, 4); k.order = (uint32_t*)take(ws, nr1, 4); k.order2 = (uint32_t*)take(ws, nr1, 4); k.poolUsed = (uint32_t*)take(ws, nr1, 4);
+  k.lines = (uint32_t*)take(ws, 2 * nr1, 4);
+  LRA_HIP_CHECK(ctx, hipMemsetAsync(k.lines, 0, 2 * nr1 * 4, st));             // (no read's rows / columns counted yet)
   {
     // largest first, equal sizes in read order: a counting sort by size (a13's inner sparse DP orders 170 k jobs: 11 ms of std::sort with the device idle)
     std::vector<uint32_t> h_order(nr);
@@ -233,7 +237,7 @@ int chunk_begin(const Call& c, Chunk& k) {
   BuildArgs& ba = k.ba;
   memset(&ba, 0, sizeof ba);
   ba.r0 = r0; ba.n = nr; ba.ptOff = c.ptOff; ba.hq = c.hq; ba.ht = c.ht; ba.hfl = c.hfl; ba.h2 = c.pay2; ba.key3 = c.key1; ba.pay3 = c.pay1; ba.scratch = k.scratch;
-  ba.cntEntries = k.cntE; ba.cntNodes = k.cntN; ba.cntD = k.cntD; ba.cntV = k.cntV; ba.cntRC = k.cntRC; ba.status = c.status; ba.order = k.order; ba.stat = nullptr;
+  ba.cntEntries = k.cntE; ba.cntNodes = k.cntN; ba.cntD = k.cntD; ba.cntV = k.cntV; ba.cntRC = k.cntRC; ba.lines = k.lines; ba.status = c.status; ba.order = k.order; ba.stat = nullptr;
   if (diag_build_stat()) { k.buildStat.alloc(16, st); ba.stat = k.buildStat.d; }
   k.h_status.assign(nr, 0);
   k.subOrder = k.order; k.nsub = nr;
@@ -331,10 +335,10 @@ int arena_layout(const Call& c, Chunk& k, Attempt& a) {
     LRA_HIP_CHECK(ctx, hipMemcpyAsync(a.dwoff, woff.data(), ((size_t)nbig + 1) * 8, hipMemcpyHostToDevice, st));
     if (a.early) {
       LRA_HIP_CHECK(ctx, hipMemsetAsync(a.d_maxLines, 0, 4, st));
-      launch_big_lines(st, nbig, r0, k.subOrder, c.ptOff, c.hq, c.ht, c.pay2, a.d_maxLines);
+      launch_big_lines(st, nbig, r0, k.subOrder, c.ptOff, c.hq, c.ht, c.pay2, a.d_maxLines, k.lines);
     }
   }
-  launch_arena_sizes(st, nsub, r0, c.ptOff, k.cntE, k.cntN, k.cntD, k.ra, k.bytes, k.subOrder, a.shift);
+  launch_arena_sizes(st, nsub, r0, c.ptOff, k.cntE, k.cntN, k.cntD, k.lines, k.ra, k.bytes, k.subOrder, a.shift);
   SDP_TRY(lra_exclusive_scan<uint64_t>(ctx, nsub, k.bytes, k.byteOff));
   LRA_HIP_CHECK(ctx, hipMemcpyAsync(&a.totB, k.byteOff + nsub, 8, hipMemcpyDeviceToHost, st));
   if (a.early) LRA_HIP_CHECK(ctx, hipMemcpyAsync(&a.bigLines, a.d_maxLines, 4, hipMemcpyDeviceToHost, st));

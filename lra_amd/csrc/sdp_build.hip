@@ -1,5 +1,8 @@
 // lra_amd/csrc/sdp_build.hip -- the sparse DP's decompositions (sdp.h lists the files; the design is described in sdp.hip): sdp_build, the count pass and the emit pass
 // of the four divide-and-conquer trees of every read, a wave per read or a 1024-thread workgroup per large read.  gfx950 only.
+// The visit records (sub-problem id, index in Di / Ei of a point on a level) go to the read's visit PLANES (sdp.h, ReadArena): pass F of a level writes the one plane of
+// its (family pair, level), vis[plane * P + point] -- one contiguous 8 P bytes within the level instead of one 8-byte slot in every point's own row -- and never a level the
+// read has no plane for: that read is given up with LRA_ST_RANGE, as one beyond LV levels is.
 #include "sdp.h"
 #include <type_traits>
 
@@ -104,11 +107,11 @@ __global__ void __launch_bounds__(64 * NW, NW == 1 ? OCC : 1) sdp_build(BuildArg
   BTICK(0);
   uint32_t nEntries = 0, nNodesTot = 0, sumD = 0, nVisits = 0;
   Node* nodesR = nullptr; Ent* entR = nullptr; uint32_t* apR = nullptr; int2* stkR = nullptr; uint2* visR = nullptr; long long* edR = nullptr;
-  uint32_t blkPair = 0;
+  uint32_t blkPair = 0, visPl = 0;
   if (EMIT) {
     const ReadArena A = a.ra[rr];
     char* b = arena_ptr(A.base);
-    blkPair = A.blkPair;
+    blkPair = A.blkPair; visPl = A.visPl;
     nodesR = (Node*)b; entR = (Ent*)(b + A.entOff); apR = (uint32_t*)(b + A.apOff); stkR = (int2*)(b + A.stkOff); visR = (uint2*)(b + A.visOff);
     edR = (long long*)(b + A.edOff);
   }
@@ -123,6 +126,9 @@ __global__ void __launch_bounds__(64 * NW, NW == 1 ? OCC : 1) sdp_build(BuildArg
     const int nS = cOff[sc + 1] - cOff[sc], nEn = cOff[sc + 2] - cOff[sc + 1], Pf = nS + nEn;
     if (nS == 0 || nEn == 0) continue;
     const int fam2 = fam & 1;
+    // the family pair's visit planes: one per level the read was laid out for (ReadArena::visPl), the column family's behind the row family's
+    const int nPl = EMIT ? (int)(fam2 ? visPl >> 8 : visPl & 0xffu) : LV;
+    uint2* visF = EMIT ? visR + (size_t)(fam2 ? visPl & 0xffu : 0u) * P : nullptr;
     const int dSide = swapped ? 1 : 0, eSide = swapped ? 0 : 1;
     for (int i = tid; i < Pf; i += NT) {
       const uint32_t pos = pay3[cOff[sc] + i];
@@ -134,7 +140,9 @@ __global__ void __launch_bounds__(64 * NW, NW == 1 ? OCC : 1) sdp_build(BuildArg
     SYNC();
     BTICK(7);
     for (int level = 0; nNodes > 0 && !outgrown; level++) {
-      if (level >= LV) { overflow = true; break; }
+      if (level >= nPl) { overflow = true; break; }                        // (a level without a plane is never written.  Laid out from the read's rows / columns
+                                                                            // or from its points, the planes fall short only beyond LV levels)
+      uint2* visL = EMIT ? visF + (size_t)level * P : nullptr;
       const int nxt = cur ^ 1;
       IT* lpc = lp + cur * P; IT* lpn = lp + nxt * P;
       IT* llc = ll + cur * P; IT* lln = ll + nxt * P;
@@ -315,7 +323,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 1 ? OCC : 1) sdp_build(BuildArg
       BTICK(4);
       // F: node index of every element for the next level; emit Di / Ei and the visit records
       {
-        // (the pass reads ln[P + .], the tables, ph, lpn and the points; it writes ln[.] below P, the entries and the visit rows: nothing it reads)
+        // (the pass reads ln[P + .], the tables, ph, lpn and the points; it writes ln[.] below P, the entries and the level's visit plane: nothing it reads)
         constexpr int UF = 2;
         for (int j0 = 0; j0 < Pf; j0 += UF * NT) {
           uint32_t k2v[UF], le[UF], ls[UF], ch[UF], gidv[UF], bg[UF], c1[UF], nNE[UF], nND[UF], bs[UF], p0v[UF], p1v[UF], pbg[UF], posv[UF], tq[UF], tt[UF];
@@ -377,7 +385,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 1 ? OCC : 1) sdp_build(BuildArg
                   entR[ent].val = dgv;
                   if (isS && idx == n - 1) nodesR[gid].eLast = dgv;
                 }
-                visR[(uint64_t)pos * (2 * LV) + fam2 * LV + level] = make_uint2(gid, idx);
+                visL[pos] = make_uint2(gid, idx);
               }
             }
           }
@@ -493,9 +501,9 @@ __global__ void __launch_bounds__(64 * NW, NW == 1 ? OCC : 1) sdp_build(BuildArg
     for (int w = 0; w < NW; w++) nVisits += (uint32_t)s_w[0][w];
   }
   if (tid == 0) {
-    if (!EMIT) { a.cntEntries[rr] = nEntries; a.cntNodes[rr] = nNodesTot; a.cntD[rr] = sumD; a.cntV[rr] = nVisits; a.cntRC[rr] = (uint32_t)max(R, C); }
+    if (!EMIT) { a.cntEntries[rr] = nEntries; a.cntNodes[rr] = nNodesTot; a.cntD[rr] = sumD; a.cntV[rr] = nVisits; a.cntRC[rr] = (uint32_t)max(R, C); a.lines[2 * rr] = (uint32_t)R; a.lines[2 * rr + 1] = (uint32_t)C; }
     else { a.cntV[rr] = nEntries; a.cntRC[rr] = (uint32_t)max(R, C); }      // (what the read really has; its rows / columns for the choice of the ProcessPoint kernel)
-    if (overflow) atomicOr(&a.status[r], (uint32_t)LRA_ST_RANGE);             // more than 2^(LV-1) distinct rows / columns
+    if (overflow) atomicOr(&a.status[r], (uint32_t)LRA_ST_RANGE);             // more than 2^(LV-1) distinct rows / columns (or a level beyond the read's visit planes)
     if (outgrown) atomicOr(&a.status[r], (uint32_t)LRA_ST_CAPACITY);
   }
 #undef TB

@@ -8,7 +8,8 @@ using namespace lra_sdp;
 namespace {
 
 __global__ void k_arena_sizes(int n, int r0, const uint64_t* __restrict__ ptOff, const uint32_t* __restrict__ cntE, const uint32_t* __restrict__ cntN,
-                              const uint32_t* __restrict__ cntD, ReadArena* ra, uint64_t* bytes, const uint32_t* __restrict__ order, int shift) {
+                              const uint32_t* __restrict__ cntD, const uint32_t* __restrict__ lines, ReadArena* ra, uint64_t* bytes,
+                              const uint32_t* __restrict__ order, int shift) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= n) return;
   const int rr = (int)order[b];
@@ -22,7 +23,11 @@ __global__ void k_arena_sizes(int n, int r0, const uint64_t* __restrict__ ptOff,
   const uint64_t stkPairs = 2 * D + 4 * N + 2, blkPairs = 2 * E + 8 * N + 2, poolPairs = (2 * E + 4096) << shift;
   a.stkOff = (uint32_t)o; a.blkPair = (uint32_t)stkPairs; a.poolPair = (uint32_t)(stkPairs + blkPairs); a.poolPairs = (uint32_t)poolPairs;
   o = al256(o + (stkPairs + blkPairs + poolPairs) * 8);
-  a.visOff = (uint32_t)o; o = al256(o + P * 2 * LV * sizeof(uint2));
+  // the visit planes: as many as the read's rows / columns give levels -- counted (k_big_lines, the count pass: lines[] != 0), else no more than its points
+  const uint32_t nR = lines[2 * rr], nC = lines[2 * rr + 1];
+  const uint32_t plR = vis_planes(nR ? nR : P), plC = vis_planes(nC ? nC : P);
+  a.visPl = plR | (plC << 8);
+  a.visOff = (uint32_t)o; o = al256(o + P * (plR + plC) * sizeof(uint2));
   ra[rr] = a;
   bytes[b] = o;
 }
@@ -51,8 +56,8 @@ __global__ void k_visit_clear(const ReadArena* __restrict__ ra, const uint64_t* 
 // The distinct rows and columns (GetRowInfo / GetColInfo) of the reads a launch gives a workgroup each, ahead of their build: the maximum picks the sdp_process_wg
 // variant, so that the workgroup ProcessPoint launch can follow the large reads' build on its side stream without a word from the host in between.
 __global__ void k_big_lines(int r0, const uint32_t* __restrict__ order, const uint64_t* __restrict__ ptOff, const uint32_t* __restrict__ hq, const uint32_t* __restrict__ ht,
-                            const uint32_t* __restrict__ h2, uint32_t* maxLines) {
-  const int r = r0 + (int)order[blockIdx.x];
+                            const uint32_t* __restrict__ h2, uint32_t* maxLines, uint32_t* lines) {
+  const int rr = (int)order[blockIdx.x], r = r0 + rr;
   const uint64_t p0 = ptOff[r];
   const int P = (int)(ptOff[r + 1] - p0);
   const uint32_t* q = hq + p0; const uint32_t* t = ht + p0; const uint32_t* c = h2 + p0;
@@ -64,7 +69,7 @@ __global__ void k_big_lines(int r0, const uint32_t* __restrict__ order, const ui
   __syncthreads();
   if ((threadIdx.x & 63) == 0) { atomicAdd(&sR, R); atomicAdd(&sC, C); }
   __syncthreads();
-  if (threadIdx.x == 0) atomicMax(maxLines, max(sR, sC));
+  if (threadIdx.x == 0) { atomicMax(maxLines, max(sR, sC)); lines[2 * rr] = sR; lines[2 * rr + 1] = sC; }   // (lines[]: k_arena_sizes lays out the read's visit planes from them)
 }
 
 // ---- counting / point generation ------------------------------------------------------------------------------------
@@ -230,9 +235,9 @@ void launch_pen_table(hipStream_t st, const PwlTab& pw, short* tab, int* bad) {
 void launch_arena_estimate(hipStream_t st, int n, int r0, const uint64_t* ptOff, float fE, float fN, uint32_t* cntE, uint32_t* cntN, uint32_t* cntD) {
   hipLaunchKernelGGL(k_arena_estimate, dim3((n + 255) / 256), dim3(256), 0, st, n, r0, ptOff, fE, fN, cntE, cntN, cntD);
 }
-void launch_arena_sizes(hipStream_t st, int n, int r0, const uint64_t* ptOff, const uint32_t* cntE, const uint32_t* cntN, const uint32_t* cntD, ReadArena* ra, uint64_t* bytes,
-                        const uint32_t* order, int shift) {
-  hipLaunchKernelGGL(k_arena_sizes, dim3((n + 255) / 256), dim3(256), 0, st, n, r0, ptOff, cntE, cntN, cntD, ra, bytes, order, shift);
+void launch_arena_sizes(hipStream_t st, int n, int r0, const uint64_t* ptOff, const uint32_t* cntE, const uint32_t* cntN, const uint32_t* cntD, const uint32_t* lines, ReadArena* ra,
+                        uint64_t* bytes, const uint32_t* order, int shift) {
+  hipLaunchKernelGGL(k_arena_sizes, dim3((n + 255) / 256), dim3(256), 0, st, n, r0, ptOff, cntE, cntN, cntD, lines, ra, bytes, order, shift);
 }
 void launch_arena_bases(hipStream_t st, int n, const uint64_t* byteOff, ReadArena* ra, const uint32_t* order, char* arena) {
   hipLaunchKernelGGL(k_arena_bases, dim3((n + 255) / 256), dim3(256), 0, st, n, byteOff, ra, order, arena);
@@ -240,8 +245,9 @@ void launch_arena_bases(hipStream_t st, int n, const uint64_t* byteOff, ReadAren
 void launch_visit_clear(hipStream_t st, int n, const ReadArena* ra, const uint64_t* byteOff, const uint32_t* order) {
   hipLaunchKernelGGL(k_visit_clear, dim3(n), dim3(256), 0, st, ra, byteOff, order);
 }
-void launch_big_lines(hipStream_t st, int n, int r0, const uint32_t* order, const uint64_t* ptOff, const uint32_t* hq, const uint32_t* ht, const uint32_t* h2, uint32_t* maxLines) {
-  hipLaunchKernelGGL(k_big_lines, dim3(n), dim3(256), 0, st, r0, order, ptOff, hq, ht, h2, maxLines);
+void launch_big_lines(hipStream_t st, int n, int r0, const uint32_t* order, const uint64_t* ptOff, const uint32_t* hq, const uint32_t* ht, const uint32_t* h2, uint32_t* maxLines,
+                      uint32_t* lines) {
+  hipLaunchKernelGGL(k_big_lines, dim3(n), dim3(256), 0, st, r0, order, ptOff, hq, ht, h2, maxLines, lines);
 }
 
 }  // namespace lra_sdp

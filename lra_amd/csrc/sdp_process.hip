@@ -45,6 +45,10 @@ __global__ void __launch_bounds__(64, 4) sdp_process(ProcArgs a) {
   uint32_t* poolUsed = a.poolUsed + rr;
   const uint2* visR = (const uint2*)(ab + A.visOff);
   const int fam2 = lane < LV ? 0 : 1, level = lane < LV ? lane : lane - LV;   // lanes >= 2 * LV have no visits
+  // The lane's visit plane (ReadArena: vis[plane * P + point]): it streams along its own plane, eight records a 64-byte line.  visAt: the plane's first record, NONE for a
+  // lane whose level the read has no plane for -- it loads nothing and holds NONE.
+  const uint32_t visPlane = vis_plane(A.visPl, lane);
+  const uint32_t visAt = visPlane != NONE ? visPlane * (uint32_t)P : NONE;
   uint32_t bad = 0;
   // per-lane cache of the sub-problem this lane touched last (descriptor, stack top, last Block pair): consecutive points mostly
   // stay in the same sub-problem on the upper levels
@@ -67,8 +71,8 @@ __global__ void __launch_bounds__(64, 4) sdp_process(ProcArgs a) {
   static_assert(sizeof(Node) == 48, "a descriptor is fetched as three 16-byte pieces");
   __shared__ uint4 s_node[2][3][2 * LV];
   uint2 vN = make_uint2(NONE, 0), vNN = make_uint2(NONE, 0);
-  if (P > 0 && lane < 2 * LV) vN = visR[lane];
-  if (P > 1 && lane < 2 * LV) vNN = visR[(uint64_t)(2 * LV) + lane];
+  if (P > 0 && visAt != NONE) vN = visR[visAt];
+  if (P > 1 && visAt != NONE) vNN = visR[visAt + 1u];
   // (the lane is in no sub-problem yet: the first point's descriptors, asked for here)
 #define NODE_FETCH(id_, buf_) do { const char* src__ = (const char*)(nodes + (id_)); _Pragma("unroll") for (int w__ = 0; w__ < 3; w__++) \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src__ + 16 * w__), (__attribute__((address_space(3))) void*)&s_node[(buf_)][w__][0], 16, 0, 0); } while (0)
@@ -95,7 +99,7 @@ __global__ void __launch_bounds__(64, 4) sdp_process(ProcArgs a) {
     }
     if (pi + 1 < P) {                                                    // the rows of the point after next, the next point's flags: in flight while this one is processed
       vNN = make_uint2(NONE, 0);
-      if (pi + 2 < P && lane < 2 * LV) vNN = visR[(uint64_t)(pi + 2) * (2 * LV) + lane];
+      if (pi + 2 < P && visAt != NONE) vNN = visR[visAt + (uint32_t)(pi + 2)];
       flN = a.hfl[p0 + pi + 1 + vz]; lfN = a.hfr[p0 + pi + 1 + vz];
     }
     if (vN.x != NONE && vN.x != cId) NODE_FETCH(vN.x, (pi + 1) & 1);      // (lanes >= 2 * LV never have a visit: nothing is written beyond a buffer's 36 slots)

@@ -81,7 +81,7 @@ __global__ void __launch_bounds__(64 * WG_NW) sdp_process_wg(ProcArgs a) {
   int2* pairs = (int2*)(ab + A.stkOff);
   const uint32_t poolPair = A.poolPair, poolPairs = A.poolPairs;
   uint32_t* poolUsed = a.poolUsed + rr;
-  const uint2* visR = (const uint2*)(ab + A.visOff);
+  const uint2* visR = (const uint2*)(ab + A.visOff);               // the visit planes (ReadArena): a wave reads the planes of its own slots only
   // ---- per anchor: best[2] (one word per start point: value bits << 32 | ~visit rank; 0 = no candidate), cnt[2] (waves counted in), nS, sPos[2];
   // per point: pm = how many start points of its anchor precede it (2 bits), and in window mode the anchor's ordinal and whether it has one start point only
   //
@@ -145,8 +145,14 @@ __global__ void __launch_bounds__(64 * WG_NW) sdp_process_wg(ProcArgs a) {
   // the rows of the point after next are in flight in vector registers.  Memory returns in order: what was asked for at the top of the previous point is there
   // by the time anything of this point has been waited for, so a point starts without a round trip of its own.
   uint2 vN[SPW]; uint32_t flN = P > 0 ? u_u(a.hfl[p0]) : 0, lfN = P > 0 ? u_u(a.hfr[p0]) : 0, rkN = P > 0 ? u_u(pm[0]) : 0;
+  uint32_t visAt[SPW];                                                   // first record of slot k's plane; NONE: no such slot, or a level the read has no plane for
 #pragma unroll
-  for (int k = 0; k < SPW; k++) { const int slot = wg_slot(wave, k); vN[k] = (P > 0 && slot < 2 * LV) ? u_u2(visR[slot]) : make_uint2(NONE, 0); }
+  for (int k = 0; k < SPW; k++) {
+    const int slot = wg_slot(wave, k);
+    const uint32_t pl = slot < 2 * LV ? vis_plane(A.visPl, slot) : NONE;
+    visAt[k] = pl != NONE ? pl * (uint32_t)P : NONE;
+    vN[k] = (P > 0 && visAt[k] != NONE) ? u_u2(visR[visAt[k]]) : make_uint2(NONE, 0);
+  }
   uint2 vV[SPW]; uint32_t lfV = 0, rkV = 0; uint8_t flV = 0;   // (a byte stays a byte until it is used: widening one waits for its load)
   //                    // raw (per-lane copies of) the rows of point pi + 1 at the top of point pi
 #pragma unroll
@@ -154,7 +160,7 @@ __global__ void __launch_bounds__(64 * WG_NW) sdp_process_wg(ProcArgs a) {
   if (P > 1) {
     flV = a.hfl[p0 + 1]; lfV = a.hfr[p0 + 1]; rkV = pm[1];
 #pragma unroll
-    for (int k = 0; k < SPW; k++) { const int slot = wg_slot(wave, k); if (slot < 2 * LV) vV[k] = visR[(uint64_t)(2 * LV) + slot]; }
+    for (int k = 0; k < SPW; k++) if (visAt[k] != NONE) vV[k] = visR[visAt[k] + 1u];
   }
   uint32_t ndV[SPW], pfId[SPW]; float fvV = 0.f;                          // asked for one point ahead: lane l < 12 holds word l of the descriptor pfId[k]; the anchor's value
 #pragma unroll
@@ -204,7 +210,7 @@ __global__ void __launch_bounds__(64 * WG_NW) sdp_process_wg(ProcArgs a) {
       if (pi + 2 < P) {
         flV = a.hfl[p0 + pi + 2]; lfV = a.hfr[p0 + pi + 2]; rkV = pm[pi + 2];
 #pragma unroll
-        for (int k = 0; k < SPW; k++) { const int slot = wg_slot(wave, k); if (slot < 2 * LV) vV[k] = visR[(uint64_t)(pi + 2) * (2 * LV) + slot]; }
+        for (int k = 0; k < SPW; k++) if (visAt[k] != NONE) vV[k] = visR[visAt[k] + (uint32_t)(pi + 2)];
       }
       // ... and what the next point will start with: the descriptors of the sub-problems its slots move to (never the ones the slots are in now: those are newer
       // here than in memory; one a slot has left was written back above or earlier, ahead of this load), and its anchor's value if it is an end point
@@ -466,7 +472,7 @@ __global__ void __launch_bounds__(64 * WG_NW) sdp_process_wg(ProcArgs a) {
         const int vr = (int)(0xFFFFFFFFu - (uint32_t)wkey);
         const int slot = (vr / LV) * LV + (LV - 1 - vr % LV);
         const uint32_t pi = sPos[2 * f + win];
-        const uint2 v = visR[(uint64_t)pi * (2 * LV) + slot];
+        const uint2 v = visR[(uint64_t)vis_plane(A.visPl, slot) * (uint32_t)P + pi];   // (the winner visited on that level: the plane exists)
         a.fval[f0 + f] = val; a.fprevNode[f0 + f] = v.x; a.fprevInd[f0 + f] = v.y;
         a.fflags[f0 + f] = (uint8_t)((slot < LV ? 1 : 0) | (((a.hfl[p0 + pi] >> 1) & 1) ? 2 : 0));
       }
